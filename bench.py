@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks, see launch_ranks)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (+ what the last timed step computed, DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -115,7 +116,12 @@ def main():
     ap.add_argument('--no-live-traffic', action='store_true',
                     help="N = 1 default workload: do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this launch "
                          "after the timed region; roofline.traffic then carries the last committed measurement, labelled as such")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'at most 64 MB): the shifts, and the fused canvases at a fixed, seeded sample of voxel positions (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has not touched the GPU (torch is not
@@ -350,6 +356,46 @@ def plane_digest(plane, rows_per_chunk=2048):
         s = int((chunk * weights[:chunk.numel()]).sum().item())
         d = (d * 1000003 + s) % mod
     return d
+
+
+DUMP_BYTES = 64 * 10 ** 6    # --dump-outputs: all arrays together stay below this (64 MB)
+DUMP_SEED = 20240611
+
+
+def dump_positions(hc, wc, n_planes):
+    """--dump-outputs: the canvas voxels sampled in every plane, (ys, xs) int64 in row-major order.  Drawn from a fixed seed,
+    so the same arguments give the same positions on every run and build; as many as fit the budget with the float32 samples
+    of all planes and the float64 positions themselves."""
+    per = max(1, (DUMP_BYTES - (1 << 20)) // (4 * n_planes + 16))
+    n = min(hc * wc, per)
+    flat = np.sort(np.random.default_rng(DUMP_SEED).choice(hc * wc, size=n, replace=False))
+    return flat // wc, flat % wc
+
+
+def sample_canvas(canvas, ys, xs):
+    """[n, hc, wc] uint16 device canvas (any plane stride) -> [n, len(ys)] int16 device samples at (ys, xs), enqueued only."""
+    import torch
+    yi = torch.as_tensor(ys, device=canvas.device)
+    xi = torch.as_tensor(xs, device=canvas.device)
+    return canvas.view(torch.int16)[:, yi, xi]
+
+
+def write_dump(out_dir, shifts, samples, ys, xs, extra=None):
+    """Write the dump: shifts [2, 2] float64 (h_shift, v_shift as (dy, dx)), canvas_sample [planes, S] float32 (the uint16
+    voxels), canvas_sample_yx [S, 2] float64, plus ``extra`` (name -> array).  Returns what the line says about it."""
+    import torch
+    arrays = {'shifts': np.array([shifts.h_shift, shifts.v_shift], dtype=np.float64),
+              'canvas_sample': (samples.to(torch.int32) & 0xFFFF).cpu().numpy().astype(np.float32),
+              'canvas_sample_yx': np.stack([ys, xs], axis=1).astype(np.float64)}
+    arrays.update(extra or {})
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, f'dump of {total} bytes exceeds {DUMP_BYTES}'
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(a))
+    return {'dir': out_dir, 'bytes': int(total), 'arrays': {k: [list(a.shape), str(a.dtype)] for k, a in arrays.items()},
+            'sample': f'canvas voxels of every plane of the last timed step at {len(ys)} positions (seed {DUMP_SEED}), '
+                      'planes in (c, z) order p = c * Z + z'}
 
 
 ARENAS = []      # the DeviceArenas of this process's canvases (alloc_planes): their probe results go into the line
@@ -596,6 +642,12 @@ def run_region(ctx):
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev or 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # the canvas as the last timed step left it (the feather leg below fuses into the same slots), planes in (c, z) order
+        at = dump_positions(hc, wc, n_planes)         # (not ys, xs: those are the stage positions the CPU baseline needs)
+        slots = torch.tensor([slot_of_plane[p] for p in range(n_planes)], device=dev)
+        dump = write_dump(args.dump_outputs, state['shifts'], sample_canvas(canvas, *at)[slots], *at)
 
     plan = state['plan']
     assert tuple(state['shifts'].h_shift) == truth.h_shift and tuple(state['shifts'].v_shift) == truth.v_shift, \
@@ -630,6 +682,8 @@ def run_region(ctx):
                      'algorithmic_bytes_per_launch': int(alg_bytes), 'launch_ms': round(fuse_ms, 4)},
     }
 
+    if dump is not None:
+        out['dump_outputs'] = dump
     if rank == 0 and os.environ.get('SQ_BENCH_BREAKDOWN'):
         n = args.steps + args.warmup
         print('[bench] host ms per step: ' + ', '.join(f'{k} {v / n * 1e3:.2f}' for k, v in lap.items()), file=sys.stderr)
@@ -657,7 +711,8 @@ def run_region(ctx):
         while ARENAS:      # the region's canvas arena goes back to the driver before the job builds its own
             ARENAS.pop().close()
         torch.cuda.empty_cache()
-        ref_args = argparse.Namespace(**dict(vars(args), steps=1, warmup=1, no_cpu_baseline=True, planes=0, batch=0, sha_out=None))
+        ref_args = argparse.Namespace(**dict(vars(args), steps=1, warmup=1, no_cpu_baseline=True, planes=0, batch=0, sha_out=None,
+                                                dump_outputs=None))
         job = run_job(dict(ctx, args=ref_args, wl=dict(WORKLOADS['cfg4'], name='cfg4')))
         out['headline_job_on_this_gpu'] = {
             'workload': job['config']['workload'], 'value': job['value'], 'unit': job['unit'], 'ms_per_step': job['ms_per_step'],
@@ -887,6 +942,8 @@ def run_job(ctx):
 
     plans = {}
     fuse_events, state, lap = [], {}, {}
+    # --dump-outputs: rank 0's planes of the last timed job, sampled batch by batch before the next batch overwrites the canvas
+    dump_at = dump_positions(hc, wc, len(mine)) if (args.dump_outputs and rank == 0 and mine) else None
 
     def plan_for(shifts):
         """Host geometry + span plan, kept across steps while the shifts do not change (the plan depends on
@@ -966,6 +1023,8 @@ def run_job(ctx):
             if args.sha_out and record == 'last':
                 for k, p in enumerate(b):
                     state.setdefault('sha', {})[int(p)] = plane_digest(canvas[k])
+            if dump_at is not None and record == 'last':      # enqueued after the closing event: not in the timed seconds
+                state.setdefault('dump', []).append(sample_canvas(canvas[:len(b)], *dump_at))
         torch.cuda.synchronize()
         timed = (t3 - t0) + sum(a.elapsed_time(c) for a, c, _ in events) * 1e-3
         if record:
@@ -988,6 +1047,12 @@ def run_job(ctx):
     if args.sha_out:
         with open(f'{args.sha_out}.rank{rank}', 'w') as fh:
             json.dump(state.get('sha', {}), fh)
+    dump = None
+    if dump_at is not None:
+        extra = {'planes': np.asarray(mine, dtype=np.float64)}
+        if 'pair_table' in state:
+            extra['pair_table'] = np.asarray(state['pair_table'], dtype=np.float64)
+        dump = write_dump(args.dump_outputs, state['shifts'], torch.cat(state.pop('dump')), *dump_at, extra=extra)
     mine_s = seconds
     first_job = per_job[0]
     steady = float(np.mean(per_job[1:])) if len(per_job) > 1 else None
@@ -1045,6 +1110,8 @@ def run_job(ctx):
                      'frac_per_rank': [round(f, 4) for f in fracs], 'of_rank': 0},
         'parity': shift_parity(shifts, truth),
     }
+    if dump is not None:
+        out['dump_outputs'] = dump
     if rank == 0 and os.environ.get('SQ_BENCH_BREAKDOWN'):
         print(f'[bench] rank 0 timed {mine_s / args.steps * 1e3:.2f} ms/job; host ms per job (every job, warm-up first): ' +
               '; '.join(f'{k} ' + ' '.join(f'{x * 1e3:.2f}' for x in v) for k, v in lap.items()), file=sys.stderr)

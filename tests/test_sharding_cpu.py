@@ -331,6 +331,33 @@ def test_bench_arena_layout_views_do_not_alias():
     assert bench.tile_pointer_table(t2, range(n), order, 'cpu').tolist() == [t2[k].data_ptr() for k in range(n)]
 
 
+def test_bench_dump_outputs_sample_the_canvas_the_same_way_every_run(tmp_path):
+    """bench.py --dump-outputs: the same seeded positions on every run, the uint16 voxels there read through any plane stride
+    (the 'arena' layout) and written as float32, and the dump of the real workloads within 64 MB."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_for_test3', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, hc, wc = 3, 70, 90
+    _, canvas = bench.alloc_planes(n, 1, hc, wc, 'cpu', 'arena')
+    voxels = torch.randint(0, 1 << 16, (n, hc, wc), generator=torch.Generator().manual_seed(5), dtype=torch.int32)
+    canvas.copy_(voxels.to(torch.uint16))
+    ys, xs = bench.dump_positions(hc, wc, n)
+    again = bench.dump_positions(hc, wc, n)
+    assert np.array_equal(ys, again[0]) and np.array_equal(xs, again[1]) and len(ys) == hc * wc     # small canvas: all of it
+    info = bench.write_dump(str(tmp_path), Shifts((3, -244), (-244, -2)), bench.sample_canvas(canvas, ys, xs)[[2, 0, 1]], ys, xs)
+    got = np.load(tmp_path / 'canvas_sample.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, voxels.numpy()[[2, 0, 1]][:, ys, xs])
+    assert np.array_equal(np.load(tmp_path / 'shifts.npy'), [[3, -244], [-244, -2]])
+    assert np.array_equal(np.load(tmp_path / 'canvas_sample_yx.npy'), np.stack([ys, xs], 1))
+    assert info['bytes'] == sum(os.path.getsize(tmp_path / f'{k}.npy') - 128 for k in info['arrays'])
+    for planes, g in ((40, 16), (200, 32)):         # cfg3, and the cfg4 job on one GPU
+        _, _, w, h, *_ = bench.grid_setup(g, 0)
+        ys, xs = bench.dump_positions(h, w, planes)
+        assert planes * len(ys) * 4 + len(ys) * 16 + (1 << 20) <= bench.DUMP_BYTES
+        assert len(np.unique(ys * w + xs)) == len(ys) and ys.max() < h and xs.max() < w
+
+
 def test_bench_live_traffic_reads_the_pmc_passes(monkeypatch, tmp_path):
     """bench.py's roofline.traffic: two child passes under `rocprofv3 --pmc` (one counter each, the program directly
     after `--`), bytes = (2 * FETCH_SIZE + WRITE_SIZE) KB averaged over the fusion launches.  Driven here with a stand-in
