@@ -71,6 +71,7 @@ __global__ __launch_bounds__(256) void arena_pair_fill_kernel(char *d0, char *d1
     }
 }
 
+// SQ_ARENA_TRACE is the only environment variable the library reads: a diagnostic that prints to stderr and changes nothing
 bool trace_on() { return getenv("SQ_ARENA_TRACE") != nullptr; }
 
 double now_s() {

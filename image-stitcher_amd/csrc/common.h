@@ -27,19 +27,10 @@ inline int fail(int code, const char *fmt, ...) {
 // whose every voxel is produced from the same ordered list of tiles ("refs"): none (zero
 // fill), one (overwrite mode: the last writer), or several (feather mode).
 constexpr uint32_t TABLE_MAGIC = 0x53514654u;  // "SQFT"
-#ifndef SQ_BLOCK_ROWS
-#define SQ_BLOCK_ROWS 8
-#endif
-#ifndef SQ_BLOCK_COLS
-#define SQ_BLOCK_COLS 2048
-#endif
-constexpr int BLOCK_ROWS = SQ_BLOCK_ROWS;      // rows of a span one workgroup takes (multiple of 4: one wave per row)
-constexpr int BLOCK_COLS = SQ_BLOCK_COLS;      // columns of a span one workgroup takes
+constexpr int BLOCK_ROWS = 8;                  // rows of a span one workgroup takes (multiple of 4: one wave per row)
+constexpr int BLOCK_COLS = 2048;               // columns of a span one workgroup takes
 constexpr int MAX_REFS = 8;                    // feather: most tiles blended in one span
-#ifndef SQ_FEATHER_BLEND_ROWS
-#define SQ_FEATHER_BLEND_ROWS 16
-#endif
-constexpr int FEATHER_BLEND_ROWS = SQ_FEATHER_BLEND_ROWS;   // feather: rows of an item of a span several tiles cover: a 244-pixel
+constexpr int FEATHER_BLEND_ROWS = 16;         // feather: rows of an item of a span several tiles cover: a 244-pixel
                                                // strip then gives every thread of the workgroup two (row, group) pairs
                                                // (measured 8 / 16 / 32 rows: 0.495 / 0.519 / 0.49 of peak, r02_exp9_feather.log)
 

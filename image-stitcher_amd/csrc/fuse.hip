@@ -58,21 +58,8 @@ template <typename S>
 __device__ __forceinline__ S ldg_s(const void *p) {
     return *(const SQ_GLOBAL S *)p;
 }
-#ifndef SQ_STORE_POLICY
-#define SQ_STORE_POLICY 0
-#endif
 __device__ __forceinline__ void stg_nt(void *p, u32x4 v) {
-#if SQ_STORE_POLICY == 0
     __builtin_nontemporal_store(v, (SQ_GLOBAL u32x4 *)p);
-#elif SQ_STORE_POLICY == 1
-    asm volatile("global_store_dwordx4 %0, %1, off nt sc1" ::"v"(p), "v"(v) : "memory");
-#elif SQ_STORE_POLICY == 2
-    asm volatile("global_store_dwordx4 %0, %1, off nt sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#elif SQ_STORE_POLICY == 3
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#else
-    *(SQ_GLOBAL u32x4 *)p = v;
-#endif
 }
 // 16-byte non-temporal store at scalar base + 32-bit lane offset (bytes): no 64-bit address pair in vector registers
 // (nt measured best here too: 0.623 against 0.599 plain, 0.622 "sc1 nt", 0.602 "sc0 sc1"; profiles/r02_exp21_store_policy.log)
@@ -109,10 +96,7 @@ struct FuseParams {
 // Planes that are divided by the SAME gain image (the z planes of a channel) and whose canvas rows sit at the same
 // phase inside a 128-byte line are carried through an item together: the gains and their reciprocals are loaded /
 // computed once per group instead of once per plane.  32 bytes.
-#ifndef SQ_ZB
-#define SQ_ZB 5
-#endif
-constexpr int ZB = SQ_ZB;            // most planes in a group
+constexpr int ZB = 5;                // most planes in a group
 static_assert(ZB >= 1 && ZB <= 7, "a PlaneGroup holds at most 7 planes");
 struct PlaneGroup {
     int32_t n;          // 1..ZB
@@ -120,10 +104,7 @@ struct PlaneGroup {
 };
 static_assert(sizeof(PlaneGroup) == 32, "PlaneGroup layout");
 constexpr int QUEUE_STRIDE = 32;   // uint32 words between the counters
-#ifndef SQ_QUEUE_CHUNK
-#define SQ_QUEUE_CHUNK 8
-#endif
-constexpr int QUEUE_CHUNK = SQ_QUEUE_CHUNK;   // most consecutive lane positions a workgroup takes per atomic
+constexpr int QUEUE_CHUNK = 8;     // most consecutive lane positions a workgroup takes per atomic
 
 template <typename T>
 __device__ __forceinline__ const T *tile_ptr(const FuseParams &P, int plane, int tile) {
@@ -151,7 +132,7 @@ __device__ __forceinline__ T flat_f32(T v, float g) {
 // n - g q is exact in one FMA, and q + rem r = (n/g)(1 - h e), i.e. wrong by < 2^-44 relative
 // before its single rounding, while a 16-bit numerator keeps n/g at least 2^-41 (relative) away
 // from every rounding boundary.  A Newton step on r (two more FMAs) is therefore not needed; it was
-// there in earlier versions and is kept behind SQ_DIV_NEWTON.  Below 2^-112 the first quotient
+// there in earlier versions.  Below 2^-112 the first quotient
 // would overflow and the correction turn into inf - inf; the guard leaves a wide margin.  None of
 // this is taken on faith: sq_selftest_flat_divide compares the final clipped integers with the
 // IEEE path for ALL 2^23 mantissas x 65536 numerators in every binade of the range, on the GPU the
@@ -161,15 +142,8 @@ __device__ __forceinline__ T flat_f32(T v, float g) {
 // 4 VALU slots + the reciprocal instead of the 11 of the IEEE sequence (two v_div_scale, v_div_fmas,
 // v_div_fixup, two refinements).  Doing two pixels per instruction on the packed-float32 pipe
 // (v_pk_mul_f32 / v_pk_fma_f32) was tried: it needs 86 VGPRs (5 waves) and measured no faster.
-#ifndef SQ_DIV_NEWTON
-#define SQ_DIV_NEWTON 0
-#endif
 __device__ __forceinline__ float div_u16_normal(float n, float g) {
-    float r = __builtin_amdgcn_rcpf(g);
-#if SQ_DIV_NEWTON
-    const float e = fmaf(-g, r, 1.0f);
-    r = fmaf(e, r, r);
-#endif
+    const float r = __builtin_amdgcn_rcpf(g);
     const float q = n * r;
     const float rem = fmaf(-g, q, n);
     return fmaf(rem, r, q);
@@ -449,15 +423,7 @@ __device__ __forceinline__ void row_zero(T *drow, int n, int lane, bool leave_ta
     if (J.tail_p >= 0) stg_s<T>(drow + J.tail_p, 0);
 }
 
-#ifndef SQ_DEPTH_PLAIN
-#define SQ_DEPTH_PLAIN 16
-#endif
-#ifndef SQ_DEPTH_F32
-#define SQ_DEPTH_F32 2
-#endif
-#ifndef SQ_DEPTH_F64
-#define SQ_DEPTH_F64 1
-#endif
+constexpr int DEPTH_PLAIN = 16, DEPTH_F32 = 2, DEPTH_F64 = 1;   // slot pipeline depth wanted without gains / with float32 / float64 gains
 
 // the software pipeline over the (row, slot) steps of RB rows (see the comment above Row)
 template <typename T, int FLAT, bool FAST, int RND, int RB, int SLOTS, int DEPTH>
@@ -476,17 +442,11 @@ __device__ __forceinline__ void pipeline_rows(const Row<T> (&J)[RB], int lane) {
 
 // minimum waves per SIMD asked of the register allocator: 6 caps the float32-gain kernel at 80 VGPRs
 // without spilling (86 otherwise: 5 waves), measured +3 %; 8 spills and loses 20 %
-#ifndef SQ_WAVES_PLAIN
-#define SQ_WAVES_PLAIN 1
-#endif
+constexpr int WAVES_PLAIN = 1;
 // (round 4: 5, not 6 -- at 80 VGPRs the per-plane kernels with gains kept spill code inside their item loops, which this build
 //  does not ship any more: tools/barrier_scan.py scan_spills, tests/test_isa_cpu.py; these kernels serve groups of one)
-#ifndef SQ_WAVES_F32
-#define SQ_WAVES_F32 5
-#endif
-#ifndef SQ_WAVES_F64
-#define SQ_WAVES_F64 1
-#endif
+constexpr int WAVES_F32 = 5;
+constexpr int WAVES_F64 = 1;
 // one edge pixel through the plane's flatfield divide (the slot pipeline's arithmetic, one pixel at a time)
 template <typename T, int FLAT, int RND>
 __device__ __forceinline__ T correct_edge(T t, const char *gain, bool fast) {
@@ -509,13 +469,11 @@ __device__ __forceinline__ void process_item(const FuseParams &P, int plane, con
     constexpr int VEC = Pix<T>::N;
     constexpr int FSZ = FLAT == 2 ? 8 : 4;
     constexpr int LINE = 128 / (int)sizeof(T);
-#ifndef SQ_RB_FLAT
-#define SQ_RB_FLAT 1   // with gains a wave pipelines one row at a time (measured 0.8 % faster than two: less row state)
-#endif
-    constexpr int RB = FLAT ? SQ_RB_FLAT : (BLOCK_ROWS >= 4 ? BLOCK_ROWS / 4 : 1);   // rows a wave pipelines together
+    constexpr int RB_FLAT = 1;   // with gains a wave pipelines one row at a time (measured 0.8 % faster than two: less row state)
+    constexpr int RB = FLAT ? RB_FLAT : (BLOCK_ROWS >= 4 ? BLOCK_ROWS / 4 : 1);   // rows a wave pipelines together
     constexpr int SLOTS = BLOCK_COLS / VEC / 64 + 1;         // vectors per lane per row (+1: alignment phase)
     constexpr int NSTEP = RB * SLOTS;
-    constexpr int WANT = FLAT == 0 ? SQ_DEPTH_PLAIN : (FLAT == 1 ? SQ_DEPTH_F32 : SQ_DEPTH_F64);
+    constexpr int WANT = FLAT == 0 ? DEPTH_PLAIN : (FLAT == 1 ? DEPTH_F32 : DEPTH_F64);
     constexpr int DEPTH = WANT < NSTEP ? WANT : NSTEP;
     static_assert(SLOTS >= 2, "the tail pixels ride on a row's second slot");
     const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
@@ -706,7 +664,7 @@ __device__ __forceinline__ Seam sgpr(Seam s) {
 }
 
 template <typename T, int FLAT, bool DYN>
-__global__ __launch_bounds__(256, (FLAT == 1 ? (sizeof(T) == 2 ? SQ_WAVES_F32 : 1) : (FLAT == 2 ? SQ_WAVES_F64 : SQ_WAVES_PLAIN)))
+__global__ __launch_bounds__(256, (FLAT == 1 ? (sizeof(T) == 2 ? WAVES_F32 : 1) : (FLAT == 2 ? WAVES_F64 : WAVES_PLAIN)))
 void fuse_overwrite_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -821,12 +779,9 @@ __device__ __forceinline__ f32x2 div_by_refined2(f32x2 n, f32x2 d, f32x2 r) {
     const f32x2 q = n * r;
     return pk_fma(pk_fma(-d, q, n), r, q);
 }
-#ifndef SQ_FEATHER_PACKED
-#define SQ_FEATHER_PACKED 1
-#endif
 template <int RND, typename G>
 __device__ __forceinline__ uint32_t quot_pair(uint32_t word, G g_lo, G g_hi, G r_lo, G r_hi) {
-    if constexpr (RND == 1 && std::is_same<G, float>::value && SQ_FEATHER_PACKED) {
+    if constexpr (RND == 1 && std::is_same<G, float>::value) {
         const f32x2 n = {(float)(word & 0xFFFFu), (float)(word >> 16)};
         const f32x2 q = div_by_refined2(n, f32x2{g_lo, g_hi}, f32x2{r_lo, r_hi});
         typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -1070,11 +1025,9 @@ __device__ __forceinline__ void process_item_zg(const FuseParams &P, const UnitA
     }
 }
 
-#ifndef SQ_WAVES_ZG
-#define SQ_WAVES_ZG 1
-#endif
+constexpr int WAVES_ZG = 1;
 template <typename G, bool DYN, typename T = uint16_t>
-__global__ __launch_bounds__(256, SQ_WAVES_ZG) void fuse_overwrite_zg_kernel(const FuseParams P, const int64_t n_items) {
+__global__ __launch_bounds__(256, WAVES_ZG) void fuse_overwrite_zg_kernel(const FuseParams P, const int64_t n_items) {
     constexpr int FLAT = std::is_same<G, NoGain>::value ? 0 : (sizeof(G) == 8 ? 2 : 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -1416,11 +1369,9 @@ __device__ __forceinline__ void feather_one_item(const FuseParams &P, int plane,
     else blend_item<T, OutT, FLAT, false>(P, plane, it, threadIdx.x);
 }
 
-#ifndef SQ_WAVES_FEATHER_F32
-#define SQ_WAVES_FEATHER_F32 4      // (5 until round 4: spill code inside the item loops, see SQ_WAVES_F32)
-#endif
+constexpr int WAVES_FEATHER_F32 = 4;      // (5 until round 4: spill code inside the item loops, see WAVES_F32)
 template <typename T, typename OutT, int FLAT, bool DYN>
-__global__ __launch_bounds__(256, (FLAT == 1 && sizeof(T) == 2 && sizeof(OutT) == 2 ? SQ_WAVES_FEATHER_F32 : 1))
+__global__ __launch_bounds__(256, (FLAT == 1 && sizeof(T) == 2 && sizeof(OutT) == 2 ? WAVES_FEATHER_F32 : 1))
 void fuse_feather_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -1936,11 +1887,9 @@ __device__ __forceinline__ void blend_item_zgn(const FuseParams &P, const Feathe
 
 // waves per SIMD asked of the register allocator: with gains 3 (168 VGPRs instead of 171: 0.555 against 0.532 for 2 waves,
 // 4 waves / 128 VGPRs 0.551); without gains the allocator's own choice measured best (0.588 against 0.574 / 0.581 at 3 / 4)
-#ifndef SQ_WAVES_FEATHER_ZG
-#define SQ_WAVES_FEATHER_ZG 3
-#endif
+constexpr int WAVES_FEATHER_ZG = 3;
 template <int FLAT, bool DYN, typename OutT = uint16_t>
-__global__ __launch_bounds__(256, FLAT ? SQ_WAVES_FEATHER_ZG : 1) void fuse_feather_zg_kernel(const FuseParams P, const int64_t n_items) {
+__global__ __launch_bounds__(256, FLAT ? WAVES_FEATHER_ZG : 1) void fuse_feather_zg_kernel(const FuseParams P, const int64_t n_items) {
     typedef uint16_t T;
     constexpr bool F32OUT = sizeof(OutT) == 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1982,9 +1931,6 @@ __global__ __launch_bounds__(256, FLAT ? SQ_WAVES_FEATHER_ZG : 1) void fuse_feat
     };
     auto body = [&](int, const Item &it, const FeatherAux &A) {
         const int gn = sgpr(A.g.n);
-#ifdef SQ_FEATHER_ONLY      // experiment builds (tools/build_variant.sh): only the items that 0 / 1 / 2 / 3-or-4 tiles cover
-        if ((it.nref > 3 ? 3 : it.nref) != SQ_FEATHER_ONLY) return;
-#endif
         if (gn == 1) {
             feather_one_item<T, OutT, FLAT>(P, sgpr(A.g.plane[0]), it, wave, lane);
         } else if (F32OUT && it.nref <= 1) {
@@ -2191,12 +2137,6 @@ __global__ __launch_bounds__(256) void selftest_divide_kernel(int exponent0, int
         // and the 8-slot sequence yields the IEEE quotient itself, bit for bit (the blend of several
         // tiles uses the quotient as a float)
         local += __fdiv_rn((float)v, g) != div_u16_normal_ieee((float)v, g);
-#ifdef SQ_SELFTEST_DEBUG
-        if (flat_f32<uint16_t, 1>((uint16_t)v, g) != flat_f32_fast<uint16_t, 1>((uint16_t)v, g) && atomicAdd(bad + 1, 1ull) < 8)
-            printf("rint mismatch v=%d g=%a (%08x): ieee q=%a -> %u, fast q=%a -> %u\n", v, g, bits, __fdiv_rn((float)v, g),
-                   (unsigned)flat_f32<uint16_t, 1>((uint16_t)v, g), quotient_u16_normal<1>((float)v, g),
-                   (unsigned)flat_f32_fast<uint16_t, 1>((uint16_t)v, g));
-#endif
     }
     for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off);
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(bad, local);
@@ -2401,6 +2341,19 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
             P.queue = reinterpret_cast<uint32_t *>(static_cast<char *>(a->scratch_dev) + SL.queue);
     }
     const bool u16 = a->tile_dtype == SQ_U16;
+    // plane groups in the scratch (build_groups_kernel): planes that share a gain image whose class has no bit of cls_mask
+    // set go through the items together; with gains NULL any planes may
+    const bool grouping = a->scratch_dev && a->n_planes > 1 && ZB > 1 && !(a->flags & SQ_FUSE_NO_PLANE_GROUPS);
+    auto build_groups = [&](const void *const *gains, uint32_t cls_mask) {
+        char *sc = static_cast<char *>(a->scratch_dev);
+        uint32_t *n_groups = reinterpret_cast<uint32_t *>(sc + SL.n_groups);
+        PlaneGroup *groups = reinterpret_cast<PlaneGroup *>(sc + SL.groups);
+        hipLaunchKernelGGL(build_groups_kernel, dim3(1), dim3(256), 0, stream, gains, P.flat_class, cls_mask, a->n_planes,
+                           a->canvas_plane_stride * (int64_t)esz, ZB, n_groups, groups,
+                           (a->flags & SQ_FUSE_CONSECUTIVE_GROUPS) != 0);
+        P.groups = groups;
+        P.n_groups = n_groups;
+    };
 
     if (a->mode == SQ_FUSE_OVERWRITE) {
         if (a->canvas_dtype != a->tile_dtype)
@@ -2411,17 +2364,9 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
         if (P.queue) return launch(fuse_overwrite_kernel<T, F, true>, P, h.n_items, a->n_planes, stream, a->grid_blocks);     \
         return launch(fuse_overwrite_kernel<T, F, false>, P, h.n_items, a->n_planes, stream, a->grid_blocks);                 \
     } while (0)
-        const int64_t esz = u16 ? 2 : 1;
-        if (flat && a->scratch_dev && a->n_planes > 1 && ZB > 1 && !(a->flags & SQ_FUSE_NO_PLANE_GROUPS)) {
+        if (flat && grouping) {
             // planes that share a gain image go through the items together (fuse_overwrite_zg_kernel)
-            char *sc = static_cast<char *>(a->scratch_dev);
-            uint32_t *n_groups = reinterpret_cast<uint32_t *>(sc + SL.n_groups);
-            PlaneGroup *groups = reinterpret_cast<PlaneGroup *>(sc + SL.groups);
-            hipLaunchKernelGGL(build_groups_kernel, dim3(1), dim3(256), 0, stream, a->flat_ptrs_dev, P.flat_class, 1u, a->n_planes,
-                               a->canvas_plane_stride * esz, ZB, n_groups, groups,
-                               (a->flags & SQ_FUSE_CONSECUTIVE_GROUPS) != 0);
-            P.groups = groups;
-            P.n_groups = n_groups;
+            build_groups(a->flat_ptrs_dev, 1u);
 #define SQ_ZG(G, T)                                                                                                                  \
     do {                                                                                                                              \
         if (P.queue) return launch_zg(fuse_overwrite_zg_kernel<G, true, T>, P, h.n_items, a->n_planes, stream, a->grid_blocks);       \
@@ -2436,17 +2381,10 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
         }
         // (uint8 planes without gains stay with the per-plane pipeline: 0.651 against 0.643 through the groups on the arena,
         //  profiles/r04_exp_uint8_plane_groups.log -- with gains the groups take them from 0.367 to 0.601)
-        if (u16 && !flat && a->scratch_dev && a->n_planes > 1 && ZB > 1 && !(a->flags & SQ_FUSE_NO_PLANE_GROUPS)) {
+        if (u16 && !flat && grouping) {
             // no flatfield: the planes still go through the items ZB at a time, dealt over the canvas allocation -- they
             // share nothing but the geometry, but a group's stores land in different stretches of device memory
-            char *sc = static_cast<char *>(a->scratch_dev);
-            uint32_t *n_groups = reinterpret_cast<uint32_t *>(sc + SL.n_groups);
-            PlaneGroup *groups = reinterpret_cast<PlaneGroup *>(sc + SL.groups);
-            hipLaunchKernelGGL(build_groups_kernel, dim3(1), dim3(256), 0, stream, (const void *const *)nullptr, (const uint32_t *)nullptr, 0u,
-                               a->n_planes, a->canvas_plane_stride * esz, ZB, n_groups, groups,
-                               (a->flags & SQ_FUSE_CONSECUTIVE_GROUPS) != 0);
-            P.groups = groups;
-            P.n_groups = n_groups;
+            build_groups(nullptr, 0u);
             SQ_ZG(NoGain, uint16_t);
 #undef SQ_ZG
         }
@@ -2475,21 +2413,14 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
         if (flat == 1) SQ_FEATHER_F(T, O, 1); \
         SQ_FEATHER_F(T, O, 2);           \
     } while (0)
-    if (u16 && a->scratch_dev && a->n_planes > 1 && ZB > 1 && !(a->flags & SQ_FUSE_NO_PLANE_GROUPS) &&
-        std::min(a->tile_h, a->tile_w) <= BLEND_WSUM_MAX) {   // a weight is at most half the shorter tile side, a weight sum twice that
+    // (BLEND_WSUM_MAX: a weight is at most half the shorter tile side, a weight sum twice that)
+    if (u16 && grouping && std::min(a->tile_h, a->tile_w) <= BLEND_WSUM_MAX) {
         // planes that share a gain image (every gain moderate), or that have none, go through the items together
         // (fuse_feather_zg_kernel)
-        char *sc = static_cast<char *>(a->scratch_dev);
-        uint32_t *n_groups = reinterpret_cast<uint32_t *>(sc + SL.n_groups);
-        PlaneGroup *groups = reinterpret_cast<PlaneGroup *>(sc + SL.groups);
         // class bits (flat_classify_kernel): 1 outside the fast divide's range, 2 not moderate, 4 not all positive.  A float32
         // canvas takes its grouped quotients as n * (1 / g) within the north star's 1e-5 relative (blend_item_zg) -- a bound
         // that holds for sums of same-signed terms, so planes with a non-positive gain stay with the exact per-plane blend
-        hipLaunchKernelGGL(build_groups_kernel, dim3(1), dim3(256), 0, stream, a->flat_ptrs_dev, P.flat_class, f32out ? 7u : 3u, a->n_planes,
-                           a->canvas_plane_stride * (int64_t)(f32out ? sizeof(float) : sizeof(uint16_t)), ZB, n_groups, groups,
-                               (a->flags & SQ_FUSE_CONSECUTIVE_GROUPS) != 0);
-        P.groups = groups;
-        P.n_groups = n_groups;
+        build_groups(a->flat_ptrs_dev, f32out ? 7u : 3u);
 #define SQ_FEATHER_ZG(F, O)                                                                                                      \
     do {                                                                                                                          \
         if (P.queue) return launch_zg(fuse_feather_zg_kernel<F, true, O>, P, h.n_items, a->n_planes, stream, a->grid_blocks);    \

@@ -9,7 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -53,10 +52,9 @@ void parallel_ranges(int nthreads, size_t n, F fn) {
             if (!failed) failed = std::current_exception();
         }
     };
-    size_t started = 0;
     try {
-        for (int t = 1; t < nthreads; ++t, ++started) pool.emplace_back(run, t);
-    } catch (...) {      // no more threads to be had: the ranges not started run here, below
+        for (int t = 1; t < nthreads; ++t) pool.emplace_back(run, t);
+    } catch (...) {      // no more threads to be had: planning fails with that error (the ranges not started are not run here)
         std::lock_guard<std::mutex> lock(failed_mutex);
         if (!failed) failed = std::current_exception();
     }
@@ -157,7 +155,6 @@ struct SpanStage {
     std::vector<Ref> refs;
     int max_refs = 0;
     int64_t covered = 0;
-    std::chrono::steady_clock::time_point t_begin, t_sweep;
 };
 
 bool make_spans(const sq_rect *rects, int32_t n_rects, int32_t tile_h, int32_t tile_w, int32_t canvas_h, int32_t canvas_w,
@@ -175,7 +172,6 @@ bool make_spans(const sq_rect *rects, int32_t n_rects, int32_t tile_h, int32_t t
         fail(SQ_ERR_INVALID, "%s: unknown mode %d", who, mode);
         return false;
     }
-    S.t_begin = std::chrono::steady_clock::now();
     // Canvas clip of stitcher.py:590-594 (python slice semantics) + validation of the source side.
     std::vector<Clipped> cl;
     cl.reserve(n_rects);
@@ -332,7 +328,6 @@ bool make_spans(const sq_rect *rects, int32_t n_rects, int32_t tile_h, int32_t t
                  overflow_x[t]);
             return false;
         }
-    const auto t_runs = std::chrono::steady_clock::now();
     // Phase 2, in band order: a run continues the span above it when interval and owners are the same (spans of the
     // previous band sorted by xa, the band's runs too: a two-pointer walk), else it opens a new span.
     struct Open {
@@ -378,17 +373,6 @@ bool make_spans(const sq_rect *rects, int32_t n_rects, int32_t tile_h, int32_t t
             open.swap(open_next);
         }
     }
-
-    S.t_sweep = std::chrono::steady_clock::now();
-#ifdef SQ_EXPERIMENTS
-    if (getenv("SQ_PLAN_TIMING")) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[spans] band runs %.3f ms (%d threads, %zu bands), merge %.3f ms (%zu spans)\n", ms(S.t_begin, t_runs), sweep_threads,
-                n_bands, ms(t_runs, S.t_sweep), spans.size());
-    }
-#else
-    (void)t_runs;
-#endif
     return true;
 }
 }   // namespace
@@ -403,7 +387,6 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
     std::vector<Ref> &refs = S.refs;
     const int max_refs = S.max_refs;
     const int64_t covered = S.covered;
-    const auto t_begin = S.t_begin, t_sweep = S.t_sweep;
 
     // ---- work items, generated straight into their final place in the table -----------------------
     // Order (overwrite mode): "one tile-row block per XCD".  Items are grouped by the block of
@@ -416,35 +399,14 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
     // [0, 8 * lane_items) are interleaved this way (header field); the lanes' leftovers and the zero-fill
     // items follow.  Every item still moves whole row segments, so HBM sees the same contiguous runs, in
     // a different order.
-    //   (experiment builds only, -DSQ_EXPERIMENTS: SQ_PLAN_ORDER=0 keeps span order, 1 = row blocks
-    //   without the XCD interleave; the product library reads no environment variable)
-#ifdef SQ_EXPERIMENTS
-    const char *order_env = getenv("SQ_PLAN_ORDER");
-#else
-    const char *order_env = nullptr;
-#endif
-    // Feather plans take the overwrite plans' order (2): buckets of BLOCK_ROWS TILE rows (the first reference's) dealt to the XCD
+    // Feather plans take the overwrite plans' order: buckets of BLOCK_ROWS TILE rows (the first reference's) dealt to the XCD
     // lanes, so that an XCD works on a few rows of the gain image at a time -- the gains of a feather launch were fetched into
     // the L2s 60 times over in span order (FETCH_SIZE 142 GB per 40-plane launch against 87 GB of pixels, profiles/
-    // r04_feather_counters.log).  Measured on 40 planes of config 3, uint16 canvas with gains: span order (0) 0.608, canvas
-    // raster (3: bands of 16 rows left to right, x-neighbours in one workgroup's chunk) 0.611, this 0.620 of the HBM peak
-    // (profiles/r04_exp_feather_order.log; experiment builds: SQ_FEATHER_ORDER).
-#ifdef SQ_EXPERIMENTS
-    const char *forder_env = getenv("SQ_FEATHER_ORDER");
-#else
-    const char *forder_env = nullptr;
-#endif
-    const int order_mode = mode == SQ_FUSE_OVERWRITE ? (order_env ? atoi(order_env) : 2) : (forder_env ? atoi(forder_env) : 2);
+    // r04_feather_counters.log).  Measured on 40 planes of config 3, uint16 canvas with gains: span order 0.608, canvas
+    // raster (bands of 16 rows left to right, x-neighbours in one workgroup's chunk) 0.611, this 0.620 of the HBM peak
+    // (profiles/r04_exp_feather_order.log).
     constexpr int NX = 8;
-    // order 4 ("canvas bands"): bucket = the band of BLOCK_ROWS canvas rows an item starts in, zero-fill items
-    // included; spans are visited left to right so that a band's items come out in ascending x
-    const bool bands = order_mode == 4;
-    const int nblk = (bands ? canvas_h : tile_h) / BLOCK_ROWS + 2;   // buckets, +1 slack, +1 for the zero-fill bucket
-    std::vector<size_t> span_order(spans.size());
-    for (size_t i = 0; i < spans.size(); ++i) span_order[i] = i;
-    if (bands)
-        std::stable_sort(span_order.begin(), span_order.end(),
-                         [&](size_t a, size_t b) { return spans[a].dst_x < spans[b].dst_x; });
+    const int nblk = tile_h / BLOCK_ROWS + 2;   // buckets, +1 slack, +1 for the zero-fill bucket
     // Overwrite plans cut rows on the canvas' own grid of BLOCK_ROWS rows (not from the top of each span), so that
     // the items either side of a vertical seam cover the same rows and the seam can be given one owner (Seam in
     // common.h); a column remainder narrower than a line is widened at the expense of the piece before it.
@@ -464,13 +426,13 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
         return n;
     };
     std::vector<size_t> span_first(spans.size() + 1, 0);
-    for (size_t so = 0; so < spans.size(); ++so) {
-        const Span &sp = spans[span_order[so]];
+    for (size_t si = 0; si < spans.size(); ++si) {
+        const Span &sp = spans[si];
         const int item_rows = rows_of(sp);
         const int64_t row_steps = sp.h <= 0 ? 0
                                   : (ow_mode ? ((int64_t)(sp.dst_y + sp.h - 1) / item_rows - sp.dst_y / item_rows + 1)
                                              : ((int64_t)sp.h + item_rows - 1) / item_rows);
-        span_first[so + 1] = span_first[so] + (size_t)(row_steps * col_pieces(sp));
+        span_first[si + 1] = span_first[si] + (size_t)(row_steps * col_pieces(sp));
     }
     // The big work lists live in per-thread scratch that keeps its capacity between calls: a 32x32 plan needs ~30 MB
     // of them, and fresh pages for that (mmap, first touch, munmap) cost more than filling them.
@@ -483,22 +445,16 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
     std::vector<int32_t> &by_band = by_band_tls;
     items.resize(span_first.back());
     const int hw_threads = (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-#ifdef SQ_EXPERIMENTS
-    const char *threads_env = getenv("SQ_PLAN_THREADS");
-    const int nthreads = threads_env ? std::max(1, atoi(threads_env)) : (items.size() >= 32768 ? hw_threads : 1);
-#else
     const int nthreads = items.size() >= 32768 ? hw_threads : 1;
-#endif
-    parallel_ranges(nthreads, spans.size(), [&](int, size_t so_lo, size_t so_hi) {
-        for (size_t so = so_lo; so < so_hi; ++so) {
-            const size_t si = span_order[so];
+    parallel_ranges(nthreads, spans.size(), [&](int, size_t si_lo, size_t si_hi) {
+        for (size_t si = si_lo; si < si_hi; ++si) {
             const Span &sp = spans[si];
             const bool ow = ow_mode;
             const Ref *rf = (ow && sp.nref) ? &refs[sp.ref0] : nullptr;
             // feather: spans that several tiles cover are blended (row, 8-pixel group) pair by pair by all threads of a
             // workgroup (fuse.hip blend_item): taller items there, two pairs per thread on a 244-pixel strip
             const int item_rows = rows_of(sp);
-            Item *out = items.data() + span_first[so];
+            Item *out = items.data() + span_first[si];
             for (int r0 = 0; r0 < sp.h;) {
                 const int rows = std::min(ow ? item_rows - (sp.dst_y + r0) % item_rows : item_rows, sp.h - r0);
                 for (int c0 = 0; c0 < sp.w;) {
@@ -528,11 +484,9 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
         }
     });
     const int64_t n_items = (int64_t)items.size();
-    const auto t_gen = std::chrono::steady_clock::now();
 
     // seam owners: item J takes the seam on its left when the item I that ends where J begins covers the same rows
     // and both are at least a line wide (tile or zero fill, either side)
-    auto t_band = t_gen, t_sort = t_gen;
     seams.clear();
     if (mode == SQ_FUSE_OVERWRITE) {
         seams.assign(items.size(), Seam{-1, 0, 0, 0});
@@ -547,7 +501,6 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
             std::vector<int32_t> at(first.begin(), first.end() - 1);
             for (size_t i = 0; i < items.size(); ++i) by_band[at[items[i].dst_y / BLOCK_ROWS]++] = (int32_t)i;
         }
-        t_band = std::chrono::steady_clock::now();
         // inside a band: by (first row, END column), so that the item ending where J begins is a binary search away
         // (a 100 x 100 grid has 100+ items per band and millions of items)
         auto end_key = [&](int32_t i) { return ((int64_t)items[i].dst_y << 32) | (uint32_t)(items[i].dst_x + (items[i].hw & 0xFFFF)); };
@@ -556,7 +509,6 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
                 std::sort(by_band.begin() + first[k], by_band.begin() + first[k + 1],
                           [&](int32_t a, int32_t b) { return end_key(a) < end_key(b); });
         });
-        t_sort = std::chrono::steady_clock::now();
         // J's record is written by the thread that owns j; the LEAVE_TAIL bit of its left neighbour I belongs to another
         // item's record (which its own thread may be flagging HAS_LEFT at this moment): both go in with atomic ORs
         parallel_ranges(nthreads, items.size(), [&](int, size_t j_lo, size_t j_hi) {
@@ -581,21 +533,16 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
     }
 
     auto key_of = [&](const Item &it) {
-        if (bands) return std::min(it.dst_y / BLOCK_ROWS, nblk - 2);
-        // (experiment builds, SQ_PLAN_ORDER=5: the zero-fill items dealt into the lanes by their canvas row block instead
-        // of following them -- fills running beside copies instead of after them)
-        if (order_mode == 5 && !it.nref) return (it.dst_y / BLOCK_ROWS) % (nblk - 1);
         // feather items carry their row inside the SPAN (b); the tile row is the first reference's
         if (!ow_mode) return it.nref ? std::min((refs[it.a].src_y + it.b) / BLOCK_ROWS, nblk - 2) : nblk - 1;
         return it.nref ? std::min(it.b / BLOCK_ROWS, nblk - 2) : nblk - 1;
     };
-    const bool bucketed = order_mode == 1 || order_mode == 2 || order_mode == 4 || order_mode == 5;
     // bucket sizes, kept per thread range: the k-th item of a bucket (in list order) then knows its rank without a
     // serial pass -- rank = items of the bucket in earlier ranges + its rank inside its own range
     std::vector<std::vector<int64_t>> hist(nthreads, std::vector<int64_t>(nblk, 0));
     parallel_ranges(nthreads, items.size(), [&](int t, size_t lo, size_t hi) {
         std::vector<int64_t> &h = hist[t];
-        for (size_t i = lo; i < hi; ++i) ++h[bucketed ? key_of(items[i]) : 0];
+        for (size_t i = lo; i < hi; ++i) ++h[key_of(items[i])];
     });
     std::vector<int64_t> count(nblk, 0);
     for (int t = 0; t < nthreads; ++t)
@@ -604,7 +551,22 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
             hist[t][k] = count[k];      // -> rank of the range's first item of bucket k
             count[k] += c;
         }
-    const auto t_items = std::chrono::steady_clock::now();
+    // position of the k-th item of bucket k: its rank inside its XCD lane (the lane's blocks in order) ...
+    std::vector<int64_t> lane_base(nblk, 0), lane_len(NX, 0);
+    for (int k = 0; k < nblk - 1; ++k) {
+        lane_base[k] = lane_len[k % NX];
+        lane_len[k % NX] += count[k];
+    }
+    int64_t common = lane_len[0];
+    for (int x = 1; x < NX; ++x) common = std::min(common, lane_len[x]);
+    // ... interleaved over the first `common` ranks of every lane; the lanes' leftovers follow, lane by lane, and then
+    // the zero-fill bucket
+    std::vector<int64_t> tail_at(NX, 0);
+    int64_t zero_at = common * NX;
+    for (int x = 0; x < NX; ++x) {
+        tail_at[x] = zero_at;
+        zero_at += lane_len[x] - common;
+    }
 
     auto *plan = new sq_fuse_plan;
     TableHeader hd{};
@@ -619,6 +581,7 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
     hd.n_spans = (int64_t)spans.size();
     hd.n_refs = (int64_t)refs.size();
     hd.n_items = n_items;
+    hd.lane_items = common;
     hd.off_spans = sizeof(TableHeader);
     hd.off_refs = hd.off_spans + hd.n_spans * (int64_t)sizeof(Span);
     hd.off_items = hd.off_refs + hd.n_refs * (int64_t)sizeof(Ref);
@@ -640,69 +603,22 @@ static sq_fuse_plan *plan_create_impl(const sq_rect *rects, int32_t n_rects, int
         dst[pos] = items[i];
         if (dst_seam) dst_seam[pos] = seams[i];
     };
-    if (order_mode == 0) {
-        for (size_t i = 0; i < items.size(); ++i) place((int64_t)i, i);
-    } else if (order_mode == 3) {
-        // canvas raster order: bands of BLOCK_ROWS canvas rows, left to right; zero-fill items in place
-        std::vector<size_t> idx(items.size());
-        for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
-        const int band_rows = mode == SQ_FUSE_OVERWRITE ? BLOCK_ROWS : FEATHER_BLEND_ROWS;
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) {
-            const int ba = items[a].dst_y / band_rows, bb = items[b].dst_y / band_rows;
-            return ba != bb ? ba < bb : items[a].dst_x < items[b].dst_x;
-        });
-        for (size_t i = 0; i < idx.size(); ++i) place((int64_t)i, idx[i]);
-    } else {
-        // position of the k-th item of bucket `key` in the row-block-sorted list ...
-        std::vector<int64_t> start(nblk + 1, 0);
-        for (int k = 0; k < nblk; ++k) start[k + 1] = start[k] + count[k];
-        // ... and, for the XCD interleave, its rank inside its lane (blocks of the lane in order)
-        std::vector<int64_t> lane_base(nblk, 0), lane_len(NX, 0);
-        for (int k = 0; k < nblk - 1; ++k) {
-            lane_base[k] = lane_len[k % NX];
-            lane_len[k % NX] += count[k];
-        }
-        int64_t common = lane_len[0];
-        for (int x = 1; x < NX; ++x) common = std::min(common, lane_len[x]);
-        std::vector<int64_t> tail_at(NX, 0);
-        int64_t tail = common * NX;   // the lanes' leftovers follow, lane by lane
-        for (int x = 0; x < NX; ++x) {
-            tail_at[x] = tail;
-            tail += lane_len[x] - common;
-        }
-        if (order_mode == 2 || order_mode == 4 || order_mode == 5) {   // the header is already in the table: patch the field
-            hd.lane_items = common;
-            std::memcpy(plan->table.ptr, &hd, sizeof hd);
-        }
-        parallel_ranges(nthreads, items.size(), [&](int th, size_t lo, size_t hi) {
-            std::vector<int64_t> seen = hist[th];
-            for (size_t i = lo; i < hi; ++i) {
-                const int k = key_of(items[i]);
-                const int64_t j = seen[k]++;
-                int64_t pos;
-                if (k == nblk - 1 || order_mode == 1) {
-                    pos = start[k] + j;
-                } else {
-                    const int x = k % NX;
-                    const int64_t t = lane_base[k] + j;
-                    pos = t < common ? t * NX + x : tail_at[x] + (t - common);
-                }
-                place(pos, i);
+    parallel_ranges(nthreads, items.size(), [&](int th, size_t lo, size_t hi) {
+        std::vector<int64_t> seen = hist[th];
+        for (size_t i = lo; i < hi; ++i) {
+            const int k = key_of(items[i]);
+            const int64_t j = seen[k]++;
+            int64_t pos;
+            if (k == nblk - 1) {
+                pos = zero_at + j;
+            } else {
+                const int x = k % NX;
+                const int64_t t = lane_base[k] + j;
+                pos = t < common ? t * NX + x : tail_at[x] + (t - common);
             }
-        });
-    }
-    const auto t_order = std::chrono::steady_clock::now();
-    const size_t n_spans_dbg = spans.size();
-#ifdef SQ_EXPERIMENTS
-    if (getenv("SQ_PLAN_TIMING")) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "[plan] sweep %.3f ms, items %.3f, seam bands %.3f, seam sort %.3f, seam lookup + counts %.3f, emit %.3f ms (%zu spans, %lld items, %d threads)\n",
-                ms(t_begin, t_sweep), ms(t_sweep, t_gen), ms(t_gen, t_band), ms(t_band, t_sort), ms(t_sort, t_items), ms(t_items, t_order), n_spans_dbg,
-                (long long)n_items, nthreads);
-    }
-#else
-    (void)t_begin; (void)t_sweep; (void)t_items; (void)t_order; (void)n_spans_dbg; (void)t_gen; (void)t_band; (void)t_sort;
-#endif
+            place(pos, i);
+        }
+    });
     // The per-thread work lists keep their capacity for the next plan of this thread (a 32 x 32 grid's ~30 MB are cheaper to keep
     // than to fault in again), but not without bound: past SCRATCH_KEEP_BYTES they go back, so a thread that once planned a
     // 100 x 100 grid does not hold a third of a GB for the rest of its life.

@@ -16,7 +16,7 @@
 //   bucket_scan_kernel    exclusive scan of the histograms over the workgroups (the STABLE rank of a workgroup's first
 //                         item of each bucket); bucket_tables_kernel: bucket starts, the lanes' lengths, header.lane_items
 //   place_items_kernel    rank of every item inside its bucket in list order (wave by wave, ballots), its final position
-//                         (lane-interleaved like plan.cpp's order 2), item and seam record written there
+//                         (lane-interleaved like plan.cpp's host plans), item and seam record written there
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

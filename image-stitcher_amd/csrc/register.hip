@@ -878,9 +878,7 @@ __global__ __launch_bounds__(LONG ? LONG_THREADS : 1024) void rows_forward_kerne
 // ---------------------------------------------------------------------------------------------
 // K2: columns -- FFT both spectra along axis 0, cross-power product, inverse along axis 0
 // ---------------------------------------------------------------------------------------------
-#ifndef SQ_COL_THREADS
-#define SQ_COL_THREADS 512
-#endif
+constexpr int COL_THREADS = 512;
 // Which columns a block of the column kernels takes.  A block's pieces of a spectrum row are tc * 16 bytes, so 8 / tc
 // neighbouring blocks read and write the same 128-byte lines.  Workgroups go to the 8 XCDs (each with its own L2)
 // round-robin by their linear index: the blocks that share lines are made the ones an XCD receives back to back --
@@ -903,13 +901,13 @@ __device__ __forceinline__ void column_block(int share, int &pair, int &cb) {
 }
 
 template <bool GEN>
-__global__ __launch_bounds__(SQ_COL_THREADS) void columns_kernel(RegParams P) {
+__global__ __launch_bounds__(COL_THREADS) void columns_kernel(RegParams P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Layout &L = P.L;
     const int n0 = L.n0, n1h = L.n1h, sp = L.sp, tc = P.tc;
     cplx *f = reinterpret_cast<cplx *>(smem);   // [tc][n0]
     cplx *g = f + (int64_t)tc * n0;             // [tc][n0]
-    __shared__ double red[2][SQ_COL_THREADS / 64];
+    __shared__ double red[2][COL_THREADS / 64];
     int pair, cb;
     column_block(P.share, pair, cb);
     const int c0 = cb * tc;
@@ -1600,11 +1598,7 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
         for (int i = 0; i < L.ax0.nf; ++i) rmax = std::max<int>(rmax, L.ax0.radix[i]);
         while (tc < 8 && 2 * (int64_t)tc * (L.n0 / rmax) < 256 && 2 * (int64_t)(2 * tc) * L.n0 * 16 <= 144 * 1024) tc *= 2;
     }
-    int col_threads = 2 * (int64_t)std::max(tc, 1) * L.n0 * 16 >= 64 * 1024 ? SQ_COL_THREADS : 256;   // a long column brings its own waves
-#ifdef SQ_EXPERIMENTS      // (the product library reads no environment variable)
-    if (const char *e = getenv("SQ_REG_TC")) tc = tc ? std::max(1, std::min(atoi(e), (int)((144 * 1024) / (2 * (int64_t)L.n0 * 16)))) : 0;
-    if (const char *e = getenv("SQ_REG_COL_THREADS")) col_threads = std::min(SQ_COL_THREADS, std::max(64, atoi(e)));
-#endif
+    const int col_threads = 2 * (int64_t)std::max(tc, 1) * L.n0 * 16 >= 64 * 1024 ? COL_THREADS : 256;   // a long column brings its own waves
     P.tc = tc;
     hipStream_t s = static_cast<hipStream_t>(stream_);
 
@@ -1622,19 +1616,14 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
     // (LDS FFT + a per-wave argmax) likes up to 8 lines within 64 KB.  Never more than keeps ~2 blocks
     // per CU busy when the batch is small (the bench's single centre pairs).
     const int64_t line_bytes = (int64_t)(L.m1 ? L.m1 : L.n1) * 16;   // a Bluestein line is m1 points long
-    const int64_t dft_scratch = 0;
     auto lines_per_block = [&](int cap, int n_lines) {
         if (L.long1) return 1;
-        int rl = (int)std::max<int64_t>(1, std::min<int64_t>(cap, (64 * 1024 - dft_scratch) / line_bytes));
+        int rl = (int)std::max<int64_t>(1, std::min<int64_t>(cap, 64 * 1024 / line_bytes));
         while (rl > 1 && (int64_t)a->n_pairs * ((n_lines + rl - 1) / rl) < 512) rl >>= 1;
         return rl;
     };
-    int rlf = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 16384 / line_bytes)), L.n0);
-    int rli = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 32768 / line_bytes)), (L.n0 + 1) / 2);
-#ifdef SQ_EXPERIMENTS
-    if (const char *e = getenv("SQ_REG_RLF")) rlf = std::max(1, std::min<int>(atoi(e), (int)(160 * 1024 / line_bytes)));
-    if (const char *e = getenv("SQ_REG_RLI")) rli = std::max(1, std::min<int>(atoi(e), (int)(160 * 1024 / line_bytes)));
-#endif
+    const int rlf = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 16384 / line_bytes)), L.n0);
+    const int rli = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 32768 / line_bytes)), (L.n0 + 1) / 2);
     P.rl_fwd = rlf;
     P.rl_inv = rli;
     // one LONG line per block (a Bluestein line of thousands of points: up to 152 KB of LDS, so one or two blocks per CU):
@@ -1646,12 +1635,8 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
         // 8.45 ms per 992-pair batch with 512, profiles/r03_exp_registration_threads.log)
         return line_bytes >= 32 * 1024 ? 1024 : (line_bytes > 16 * 1024 ? 512 : pick_threads(L.n1));
     };
-    int ntf = line_threads(rlf), nti = line_threads(rli);
-#ifdef SQ_EXPERIMENTS
-    if (const char *e = getenv("SQ_REG_FWD_THREADS")) ntf = std::max(64, std::min(1024, atoi(e)));
-    if (const char *e = getenv("SQ_REG_INV_THREADS")) nti = std::max(64, std::min(1024, atoi(e)));
-#endif
-    const size_t lds_fwd = L.long1 ? 0 : (size_t)(rlf * line_bytes + dft_scratch), lds_inv = L.long1 ? 0 : (size_t)(rli * line_bytes + dft_scratch);
+    const int ntf = line_threads(rlf), nti = line_threads(rli);
+    const size_t lds_fwd = L.long1 ? 0 : (size_t)(rlf * line_bytes), lds_inv = L.long1 ? 0 : (size_t)(rli * line_bytes);
     // the general (mixed-radix) instantiations only where an axis' plan has mixed-radix stages: see lines_fft_plan
     const bool gen0 = L.ax0.nf > 0, gen1 = L.ax1.nf > 0;
 #define SQ_LAUNCH(KERNEL, GRID, THREADS, LDS)                                        \
@@ -1686,7 +1671,7 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
         const size_t lds_col = (size_t)(L.m0 ? L.m0 : L.n0) * 16;
         P.share = 8;
         const dim3 grid_col((L.n1h + 7) / 8 * 8, a->n_pairs);
-        const int ntc = lds_col > 80 * 1024 ? 1024 : SQ_COL_THREADS;     // one block per CU: twice the waves
+        const int ntc = lds_col > 80 * 1024 ? 1024 : COL_THREADS;     // one block per CU: twice the waves
         if (gen0) SQ_LAUNCH(columns_single_kernel<true>, grid_col, ntc, lds_col);
         else SQ_LAUNCH(columns_single_kernel<false>, grid_col, ntc, lds_col);
     } else {

@@ -1,5 +1,5 @@
 """The feather kernels on config 3's geometry with the canvas in a mixed arena (what bench.py's feather leg measures), for A/B runs
-of library variants (SQ_LIB_PATH) and experiment switches:  python tools/feather_probe.py [C=4] [Z=5] [reps=5]"""
+against another build of the library (SQ_LIB_PATH, e.g. one of the base commit):  python tools/feather_probe.py [C=4] [Z=5] [reps=5]"""
 import os, sys
 import numpy as np
 import torch

@@ -25,7 +25,7 @@ def main():
     ap.add_argument('--dense', action='store_true', help='dense canvas stack (plane stride = Hc*Wc): no plane groups')
     ap.add_argument('--flags', type=int, default=0)
     ap.add_argument('--ab', type=int, default=None, help='also time these flags, alternating with --flags in the same process (same buffers)')
-    ap.add_argument('--libs', default=None, help='comma-separated build variants (tools/build_variant.sh names, or "default") timed alternately in this process on the same buffers')
+    ap.add_argument('--libs', default=None, help='comma-separated libraries timed alternately in this process on the same buffers: NAME loads libsquidstitch_NAME.so placed next to the library (a build of another commit, say), "default" the library itself')
     ap.add_argument('--u8', action='store_true', help='uint8 tiles and canvas')
     ap.add_argument('--feather', action='store_true', help='feather plan (uncropped rectangles, blended overlaps)')
     ap.add_argument('--canvas-first', action='store_true', help='allocate the canvas before the tiles')

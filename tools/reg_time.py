@@ -1,5 +1,5 @@
 """Times the headline job's two registration batches (992 horizontal + 992 vertical pairs of a 32 x 32 grid) with events;
-used with experiment builds (SQ_LIB_PATH + SQ_REG_* knobs) to compare launch shapes of the registration kernels."""
+run it against another build of the library (SQ_LIB_PATH, e.g. one of the base commit) to compare registration kernels."""
 import os, sys
 import numpy as np
 import torch
@@ -24,4 +24,4 @@ for name, pairs, n0, n1 in (('h', hp, h0, h1), ('v', vp, v0, v1)):
         r = p.fetch()
         best = min(best, e0.elapsed_time(e1))
     out.append(f'{name} {n0}x{n1}: {best:6.2f} ms')
-print(' | '.join(out), '|', ' '.join(f'{k}={v}' for k, v in os.environ.items() if k.startswith('SQ_REG')))
+print(' | '.join(out))
