@@ -33,6 +33,9 @@ PAIR_DTYPE = np.dtype([('ref_tile', '<i4'), ('mov_tile', '<i4'), ('ref_y0', '<i4
 RESULT_DTYPE = np.dtype([('coarse', '<i4', (2,)), ('fine', '<i4', (2,)), ('ccmax_re', '<f8'),
                          ('ccmax_im', '<f8'), ('src_amp', '<f8'), ('tgt_amp', '<f8')])
 SYNTH_DTYPE = np.dtype([('scene_seed', '<u8'), ('noise_seed', '<u8'), ('oy', '<i8'), ('ox', '<i8')])
+OVERLAP_BATCH = 65535     # window pairs per sq_pair_overlap_moments call (include/squidstitch.h)
+OVERLAP_DTYPE = np.dtype([('ref_tile', '<i4'), ('mov_tile', '<i4'), ('ref_y0', '<i4'), ('ref_x0', '<i4'),
+                          ('mov_y0', '<i4'), ('mov_x0', '<i4'), ('h', '<i4'), ('w', '<i4')])
 
 
 class NativeError(RuntimeError):
@@ -93,6 +96,8 @@ EXPORTS = {
     'sq_fuse_planes': (C.c_int, [C.POINTER(_FuseArgs), C.c_void_p]),
     'sq_tile_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_void_p, C.c_void_p]),
+    'sq_pair_overlap_moments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_normalize_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'sq_downsample2': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
@@ -570,6 +575,46 @@ def tile_minmax(tiles, stream=None, tile_ptrs=None, shape=None, np_dtype=None):
     out = torch.empty((n, 2), dtype=torch.int32, device=device)
     _check(L.sq_tile_minmax(ptrs, base, stride, n, h, w, w, dt, out.data_ptr(), _stream_ptr(stream)),
            'sq_tile_minmax')
+    return out
+
+
+def pair_overlap_moments(tiles, windows, out=None, stream=None, tile_ptrs=None, shape=None, np_dtype=None):
+    """Exact overlap sums of window pairs on a contiguous device stack [N, H, W] (or the dense H x W tiles a device int64
+    pointer table names) -> device int64 tensor [n, 5]: sum a, sum b, sum a^2, sum b^2, sum a*b of window pair i, a from
+    the reference tile, b from the moving one (uint64 on the C side; every sum of uint16 tiles up to 65535 x 65535 pixels
+    stays below 2^63).  ``windows``: OVERLAP_DTYPE records or [n, 8] ints (ref_tile, mov_tile, ref_y0, ref_x0, mov_y0,
+    mov_x0, h, w).  ``out``: an int64 [n, 5] device tensor to write into.  A window outside its tile raises NativeError
+    and leaves ``out`` as it was.  Reads the window table back to check it, i.e. synchronises the stream.  More than
+    OVERLAP_BATCH windows go to the device in batches of that many."""
+    import torch
+    L = lib()
+    ptrs, base, stride, n, h, w, dt = _tile_table(tiles, tile_ptrs, shape, np_dtype)
+    device = tile_ptrs.device if tile_ptrs is not None else tiles.device
+    win = np.asarray(windows)
+    if win.dtype != OVERLAP_DTYPE:
+        win = np.ascontiguousarray(win, dtype=np.int32).reshape(-1, 8).view(OVERLAP_DTYPE).reshape(-1)
+    win = np.ascontiguousarray(win)
+    if out is None:
+        out = torch.empty((len(win), 5), dtype=torch.int64, device=device)
+    if tuple(out.shape) != (len(win), 5) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"out must be a contiguous int64 [{len(win)}, 5] tensor on {device}")
+    if len(win) == 0:
+        return out
+    win_dev = upload_small(torch.from_numpy(win.view(np.uint8).reshape(-1)), device)
+    # the C entry point takes up to OVERLAP_BATCH windows per call (the pair is its grid's y dimension); every window is
+    # checked before the first batch is launched, so a bad one still leaves ``out`` untouched
+    bad = ((win['ref_tile'] < 0) | (win['ref_tile'] >= n) | (win['mov_tile'] < 0) | (win['mov_tile'] >= n) | (win['h'] < 0)
+           | (win['w'] < 0) | (win['ref_y0'] < 0) | (win['ref_x0'] < 0) | (win['mov_y0'] < 0) | (win['mov_x0'] < 0)
+           | (win['ref_y0'].astype(np.int64) + win['h'] > h) | (win['mov_y0'].astype(np.int64) + win['h'] > h)
+           | (win['ref_x0'].astype(np.int64) + win['w'] > w) | (win['mov_x0'].astype(np.int64) + win['w'] > w))
+    if len(win) > OVERLAP_BATCH and bad.any():
+        raise NativeError(f"sq_pair_overlap_moments: window {int(np.flatnonzero(bad)[0])} leaves its tile or names no tile")
+    for i in range(0, len(win), OVERLAP_BATCH):
+        k = min(OVERLAP_BATCH, len(win) - i)
+        _check(L.sq_pair_overlap_moments(ptrs, base, stride, n, h, w, w, dt, win_dev.data_ptr() + i * OVERLAP_DTYPE.itemsize, k,
+                                         out.data_ptr() + i * 5 * 8, _stream_ptr(stream)), 'sq_pair_overlap_moments')
+    if stream is not None:
+        win_dev.record_stream(stream)
     return out
 
 

@@ -368,22 +368,53 @@ def shifts_from_pair_table(pairs, table, height, width, max_x_overlap, max_y_ove
     return Shifts(**pair_table_medians(pairs, table, height, width, max_x_overlap, max_y_overlap, n_rows, scan_pattern))
 
 
+def overlap_ncc(tiles, local_index, pairs, indices, rows: np.ndarray, height: int, width: int, max_x_overlap: int,
+                max_y_overlap: int) -> np.ndarray:
+    """Confidence of registered pairs for global registration: the zero-normalised cross-correlation of the two FULL
+    tiles over their overlap at each pair's integer offset (alignment.pair_offsets), from exact integer sums taken on
+    the device stack the pairs were registered from (native.pair_overlap_moments).  ``rows``: the pairs' [k, 3]
+    {dy, dx, err} from register_pair_subset.  NaN where the shift is not finite, the overlap is empty or a side has no
+    variance."""
+    from . import alignment
+    out = np.full(len(indices), np.nan)
+    if not len(indices):
+        return out
+    kinds = np.fromiter((pairs[i][0] for i in indices), dtype=np.int64, count=len(indices))
+    h_n1 = placement.horizontal_crop_origins(height, width, int(max_x_overlap))[1] if (kinds == PAIR_H).any() else 0
+    v_n0 = placement.vertical_crop_origins(height, width, int(max_y_overlap))[0] if (kinds == PAIR_V).any() else 0
+    exact, d = alignment.pair_offsets(kinds, rows[:, :2], height, width, h_n1, v_n0)
+    windows = alignment.overlap_windows([local_index[pairs[i][1]] for i in indices], [local_index[pairs[i][2]] for i in indices],
+                                        d, height, width)
+    sums = native.pair_overlap_moments(tiles, windows).cpu().numpy()
+    ncc = alignment.ncc_from_sums(sums, windows[:, 6].astype(np.int64) * windows[:, 7])
+    return np.where(np.isfinite(exact).all(axis=1), ncc, np.nan)
+
+
 def register_all_pairs_sharded(pairs, load_cells, height: int, width: int, max_x_overlap: int, max_y_overlap: int,
-                               normalization='phase', rank: int = 0, world: int = 1, device=None, group=None) -> np.ndarray:
+                               normalization='phase', rank: int = 0, world: int = 1, device=None, group=None,
+                               with_overlap_ncc: bool = False) -> np.ndarray:
     """All-pairs registration with the pairs dealt over the ranks.  ``pairs`` = ``grid_pair_list(...)`` (identical on
     every rank); ``load_cells(cells) -> device stack [len(cells), H, W]`` brings in exactly the tiles THIS rank's
     pairs touch (files -> H2D in the product, the device generator in the bench).  Every rank registers its run of
     pairs; the [n_pairs, 3] float64 table {dy, dx, err} is all-gathered (RCCL over xGMI with the nccl backend; the
-    only collective) and returned whole on every rank.  Nothing else is exchanged."""
+    only collective) and returned whole on every rank.  Nothing else is exchanged.
+
+    ``with_overlap_ncc`` (global registration): every rank also forms its pairs' ``overlap_ncc`` on the same device
+    stack, and the table is [n_pairs, 4] {dy, dx, err, ncc}."""
     from . import sharding
     mine = pairs_of_rank(len(pairs), rank, world)
     cells = cells_of_pairs(pairs, mine)
-    local = np.zeros((0, 3), dtype=np.float64)
+    ncols = 4 if with_overlap_ncc else sharding.PAIR_ROW
+    local = np.zeros((0, ncols), dtype=np.float64)
     if mine:
         tiles = load_cells(cells)
-        local = register_pair_subset(tiles, {c: i for i, c in enumerate(cells)}, pairs, mine, height, width,
-                                     max_x_overlap, max_y_overlap, normalization)
-    return sharding.all_gather_pair_table(local, len(pairs), rank, world, device=device, group=group)
+        index = {c: i for i, c in enumerate(cells)}
+        rows = register_pair_subset(tiles, index, pairs, mine, height, width, max_x_overlap, max_y_overlap, normalization)
+        if with_overlap_ncc:
+            ncc = overlap_ncc(tiles, index, pairs, mine, rows, height, width, max_x_overlap, max_y_overlap)
+            rows = np.concatenate([rows, ncc[:, None]], axis=1)
+        local = rows
+    return sharding.all_gather_pair_table(local, len(pairs), rank, world, device=device, group=group, width=ncols)
 
 
 def consensus_shift(shifts: np.ndarray, errors: np.ndarray) -> Tuple[float, float]:

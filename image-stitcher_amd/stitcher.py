@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import native, placement, registration, sharding
+from . import alignment, native, placement, registration, sharding
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -56,7 +56,7 @@ class Stitcher:
     def __init__(self, params: StitchingParameters, device=None, fusion_mode: str = 'overwrite',
                  normalization: Optional[str] = 'phase', zarr_compression: str = 'blosc',
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
-                 all_pairs_registration: bool = False):
+                 all_pairs_registration: bool = False, global_registration: bool = False):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -99,6 +99,12 @@ class Stitcher:
         # the registration plane, per-axis median.  The reference's --dynamic-registration is parsed, stored and ignored
         # (stitcher.py:92, stitcher_parameters.py:24), so that flag keeps the centre-pair result here too.
         self.all_pairs_registration = bool(all_pairs_registration) and self.use_registration
+        # Extension: every tile at its own integer position from a least-squares solve over all registered pairs
+        # (alignment.py).  Positions are per tile, so every (timepoint, region) is registered and solved on its own, as with
+        # per_region_registration; the reference's state attributes still get the all-pairs medians.
+        self.global_registration = bool(global_registration) and self.use_registration
+        self.placements: Dict[tuple, alignment.Placement] = {}     # (timepoint, region) -> solved positions
+        self._global_rects: Dict[tuple, dict] = {}
         self.batch_bytes_limit = 4 << 30          # tile bytes staged (pinned + device) per ingest batch
         self._device = device
         self._plan_cache: Dict[tuple, native.FusePlan] = {}
@@ -286,6 +292,11 @@ class Stitcher:
         return None
 
     # ------------------------------------------------------------- geometry
+    @property
+    def _per_unit_registration(self) -> bool:
+        """Every (timepoint, region) is registered on its own tiles before it is fused."""
+        return self.per_region_registration or self.global_registration
+
     def _shifts(self) -> Shifts:
         rev = getattr(self, 'h_shift_rev', None) if self.scan_pattern == 'S-Pattern' else None
         return Shifts(tuple(self.h_shift), tuple(self.v_shift), None if rev is None else tuple(rev),
@@ -304,10 +315,14 @@ class Stitcher:
         region_data = self.get_region_data(int(timepoint), region)
         self.x_positions = sorted(set(v['x'] for v in region_data.values()))
         self.y_positions = sorted(set(v['y'] for v in region_data.values()))
-        width_pixels, height_pixels = placement.canvas_size(
-            len(self.x_positions), len(self.y_positions), self.input_width, self.input_height,
-            use_registration=self.use_registration, shifts=self._shifts(),
-            xs=self.x_positions, ys=self.y_positions, pixel_size_um=self.pixel_size_um)
+        solved = self.placements.get((int(timepoint), region)) if self.global_registration else None
+        if solved is not None:      # global registration: the canvas the solved positions span
+            height_pixels, width_pixels = solved.canvas_hw
+        else:
+            width_pixels, height_pixels = placement.canvas_size(
+                len(self.x_positions), len(self.y_positions), self.input_width, self.input_height,
+                use_registration=self.use_registration, shifts=self._shifts(),
+                xs=self.x_positions, ys=self.y_positions, pixel_size_um=self.pixel_size_um)
         max_dimension = 1
         if len(self.regions) > 1:
             rows, columns = self.get_rows_and_columns()
@@ -358,6 +373,8 @@ class Stitcher:
         y_positions = sorted(set(v['y'] for v in region_data.values()))
         self.h_shift = (0, 0)
         self.v_shift = (0, 0)
+        self.placements.pop((int(t), region), None)
+        self._global_rects.pop((int(t), region), None)
         if not self.registration_channel:
             self.registration_channel = self.channel_names[0]
         elif self.registration_channel not in self.channel_names:
@@ -370,6 +387,17 @@ class Stitcher:
             self.pixel_size_um, self.pixel_binning)
         print(f"[registration] crop widths from the stage pitch: {max_x_overlap} px horizontal, {max_y_overlap} px vertical")
         registration.check_crop_lengths(self.input_height, self.input_width, max_x_overlap, max_y_overlap)
+        if self.global_registration:
+            # --global-registration (an addition of this build): the all-pairs table with each pair's overlap ncc, its medians
+            # as the reference's state, then every tile's own position from the global solve
+            gtime = time.time()
+            self._calculate_shifts_all_pairs(t, region, x_positions, y_positions, max_x_overlap, max_y_overlap, global_solve=True)
+            print(f"[registration] all pairs: h_shift = {self.h_shift}, v_shift = {self.v_shift}")
+            solved = self.placements.get((int(t), region))
+            if solved is not None:
+                print(solved.summary() + f" ({time.time() - gtime:.3f} s with the registration)")
+            self.calculate_output_dimensions(int(t), region)
+            return
         if self.all_pairs_registration:
             # --all-pairs-registration (an addition of this build; NOT the reference's --dynamic-registration, which it
             # parses and never reads): every adjacent pair of the registration plane, one batch per direction, per-axis
@@ -405,7 +433,7 @@ class Stitcher:
                 print(f"Warning: region {region}: tiles of the reversed row missing, h_shift_rev stays {self.h_shift_rev}")
         print(f"[registration] h_shift = {self.h_shift}, v_shift = {self.v_shift}")
 
-    def _calculate_shifts_all_pairs(self, t, region, xs, ys, max_x_overlap, max_y_overlap):
+    def _calculate_shifts_all_pairs(self, t, region, xs, ys, max_x_overlap, max_y_overlap, global_solve: bool = False):
         """Extension: registration over ALL adjacent tile pairs of the registration plane (batched on the
         device), reduced to the reference's state (h_shift, v_shift[, h_shift_rev]) by a per-axis median --
         a single bad tile (dust, empty field) then cannot derail the whole mosaic.
@@ -413,7 +441,11 @@ class Stitcher:
         Under ``run()`` with several ranks (``self._pair_ranks`` = (rank, world)) the pairs are SHARDED: every rank
         takes one contiguous run of the pair list (tile-row order), reads and uploads only the tiles its pairs touch,
         and the [n_pairs, 3] float64 table {dy, dx, err} is all-gathered (registration.register_all_pairs_sharded);
-        the medians are host arithmetic on that table, so every rank sets the same integers."""
+        the medians are host arithmetic on that table, so every rank sets the same integers.
+
+        ``global_solve`` (--global-registration): the table carries each pair's overlap ncc, and the unit's tile positions
+        are solved from it (alignment.solve_positions; with the pairs sharded rank 0 solves and broadcasts the result) and
+        kept in ``placements[(t, region)]``."""
         import torch
         n_rows, n_cols = len(ys), len(xs)
         at = {}
@@ -435,12 +467,28 @@ class Stitcher:
 
         table = registration.register_all_pairs_sharded(
             pairs, load_cells, self.input_height, self.input_width, max_x_overlap, max_y_overlap, self.normalization,
-            rank=rank, world=world, device=sharding.collective_device(self))
-        self.pair_table = table     # [n_pairs, {dy, dx, err}] float64, pair order = registration.grid_pair_list
+            rank=rank, world=world, device=sharding.collective_device(self), with_overlap_ncc=global_solve)
+        self.pair_table = table     # [n_pairs, {dy, dx, err[, ncc]}] float64, pair order = registration.grid_pair_list
         med = registration.pair_table_medians(pairs, table, self.input_height, self.input_width, max_x_overlap,
                                               max_y_overlap, n_rows, self.scan_pattern)
         for name, value in med.items():
             setattr(self, name, bool(value) if name == 'h_shift_rev_odd' else tuple(value))
+        if not global_solve:
+            return
+        # the prior: where --all-pairs-registration places every cell of the region (any channel), on the medians' lattice
+        cells = sorted({(ys.index(v['y']), xs.index(v['x'])) for v in self.get_region_data(t, region).values()})
+        lattice = placement.grid_rects(n_rows, n_cols, self.input_width, self.input_height, self._shifts(), order=cells, crop=False)
+        prior = {c: (int(r[4]), int(r[5])) for c, r in zip(cells, lattice)}
+        solved = None
+        if rank == 0:
+            h_crop = placement.horizontal_crop_origins(self.input_height, self.input_width, int(max_x_overlap))[:2] \
+                if any(p[0] == registration.PAIR_H for p in pairs) else (0, 0)
+            v_crop = placement.vertical_crop_origins(self.input_height, self.input_width, int(max_y_overlap))[:2] \
+                if any(p[0] == registration.PAIR_V for p in pairs) else (0, 0)
+            solved = alignment.solve_positions(pairs, table, self.input_height, self.input_width, h_crop, v_crop, prior)
+        if world > 1:
+            solved = sharding.broadcast_object(solved)
+        self.placements[(int(t), region)] = solved
 
     # -------------------------------------------------------------- flatfield
     def apply_flatfield_correction(self, tile, channel_idx):
@@ -612,6 +660,14 @@ class Stitcher:
 
     def _tile_rect(self, tile_info):
         """sq_rect of one file: placement (stitcher.py:656-679) + crop (:570-587)."""
+        unit = (int(tile_info['t']), tile_info['region'])
+        solved = self.placements.get(unit) if self.global_registration else None
+        if solved is not None:      # global registration: the tile's own position, crops at the midpoints of solved overlaps
+            rects = self._global_rects.get(unit)
+            if rects is None:
+                make = alignment.overwrite_rects if self.fusion_mode == 'overwrite' else alignment.full_rects
+                rects = self._global_rects[unit] = make(solved, self.input_height, self.input_width)
+            return rects[(self.y_positions.index(tile_info['y']), self.x_positions.index(tile_info['x']))]
         if self.use_registration:
             col = self.x_positions.index(tile_info['x'])
             row = self.y_positions.index(tile_info['y'])
@@ -987,13 +1043,28 @@ class Stitcher:
                        name=f"{region}_t{timepoint}")
         return output_path
 
+    def write_tile_positions(self, timepoint, region) -> Optional[str]:
+        """``<output>/<t>_stitched/<region>_tile_positions.csv`` of a globally registered unit: fov, grid row and column,
+        canvas (y, x) in pixels and whether pairs or the all-pairs lattice (prior) placed the tile."""
+        solved = self.placements.get((int(timepoint), region))
+        if solved is None:
+            return None
+        xs, ys = sorted(set(v['x'] for v in self.get_region_data(timepoint, region).values())), \
+            sorted(set(v['y'] for v in self.get_region_data(timepoint, region).values()))
+        fov_of = {(ys.index(v['y']), xs.index(v['x'])): int(v['fov_idx']) for v in self.get_region_data(timepoint, region).values()}
+        path = os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_tile_positions.csv")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, 'w') as fh:
+            fh.write(alignment.positions_csv(solved, fov_of))
+        return path
+
     def _write_shift_table(self, n_units, my_rows, rank, world, coll, shared: bool = False) -> None:
         """``shift_table.json`` in the output folder: the shifts every (timepoint, region) was fused with.
         With per-region registration every rank contributes the rows it measured: one all-gather of
         ceil(units / world) rows of 8 int32 per rank (RCCL over xGMI with the nccl backend) -- the only
         collective on the path."""
         units = [(int(t), region) for t in self.timepoints for region in self.regions]
-        if self.per_region_registration:
+        if self._per_unit_registration:
             # rows any rank can hold: its block-cyclic share of the units -- or all of them on rank 0 when the
             # ranks share every region plane by plane (fewer units than GPUs) and rank 0 registers each
             per_rank = n_units if shared else -(-n_units // world)
@@ -1060,8 +1131,8 @@ class Stitcher:
         # all-pairs registration (--all-pairs-registration) is sharded by PAIR: every rank registers its run of the pair
         # list and the float64 pair table is all-gathered (registration.register_all_pairs_sharded); the reference's
         # centre-pair scheme is three tiles' worth of work and stays on rank 0, its 8-int32 row all-gathered
-        pair_sharded = world > 1 and self.all_pairs_registration
-        if self.use_registration and not self.per_region_registration:
+        pair_sharded = world > 1 and (self.all_pairs_registration or self.global_registration)
+        if self.use_registration and not self._per_unit_registration:
             if rank == 0 or pair_sharded:
                 print(f"\nCalculating shifts on region {self.regions[0]}...")
                 self._pair_ranks = (rank, world) if pair_sharded else None
@@ -1101,7 +1172,7 @@ class Stitcher:
             # fewer (timepoint, region) units than GPUs: share each region by (channel, z) plane
             # instead -- every rank fuses its planes and writes their chunks into the common store
             for i, (timepoint, region) in enumerate(units):
-                if self.per_region_registration and pair_sharded:
+                if self._per_unit_registration and pair_sharded:
                     # the ranks share this region anyway: they share its pairs too
                     self._pair_ranks = (rank, world)
                     try:
@@ -1110,7 +1181,8 @@ class Stitcher:
                         self._pair_ranks = None
                     if rank == 0:
                         my_rows[i] = sharding.shifts_to_row(self._shifts())
-                elif self.per_region_registration:
+                        self.write_tile_positions(timepoint, region)
+                elif self._per_unit_registration:
                     if rank == 0:
                         self.calculate_shifts(timepoint, region)
                         my_rows[i] = sharding.shifts_to_row(self._shifts())
@@ -1123,9 +1195,10 @@ class Stitcher:
             rtime = time.time()
             print(f"\nProcessing timepoint {timepoint}, region {region}" + (f" (rank {rank}/{world})" if world > 1 else ""))
             os.makedirs(os.path.join(self.output_folder, f"{timepoint}_stitched"), exist_ok=True)
-            if self.per_region_registration:
+            if self._per_unit_registration:
                 self.calculate_shifts(timepoint, region)
                 my_rows[i] = sharding.shifts_to_row(self._shifts())
+                self.write_tile_positions(timepoint, region)
             self.starting_stitching.emit()
             if self.output_format.endswith('.zarr'):
                 # fused planes stream to the store batch by batch; saving overlaps stitching

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus six switches for what this build adds (``--fusion-mode``, ``--normalization``,
-``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``).
+plus seven switches for what this build adds (``--fusion-mode``, ``--normalization``,
+``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
+``--global-registration``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -39,6 +40,10 @@ FLAGS = (
                                          help="with -r: register EVERY adjacent tile pair of the registration plane (batched on the device, "
                                               "sharded by pair over the ranks) and place tiles by the per-axis median shift, instead of the "
                                               "reference's centre-tile pairs")),
+    (('--global-registration',), dict(action='store_true',
+                                      help="with -r: register every adjacent tile pair of every (timepoint, region) and place EACH tile at its "
+                                           "own position from a least-squares solve over the pairs whose overlap correlates (tiles "
+                                           "without one stay on the all-pairs lattice); writes <region>_tile_positions.csv")),
     (('--flatfield-estimator',), dict(choices=['auto', 'basic', 'basicpy', 'mean'], default='auto',
                                       help="with -ff: basicpy's BaSiC fit when that package is installed (auto / basicpy), this "
                                            "build's device restatement of the published BaSiC fit (basic; what auto falls back "
@@ -95,7 +100,8 @@ def main(argv=None):
                             zarr_compression=args.zarr_compression,
                             per_region_registration=args.per_region_registration,
                             flatfield_estimator=args.flatfield_estimator,
-                            all_pairs_registration=args.all_pairs_registration)
+                            all_pairs_registration=args.all_pairs_registration,
+                            global_registration=args.global_registration)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -101,6 +101,8 @@ class GridSpec:
     region_dims: Sequence[Tuple[str, int, int]] = ()   # (region, rows, cols) for regions whose grid is not rows x cols
     blank_fovs: Sequence[int] = ()   # these FOVs are written as a constant image (cap on, empty well) in every plane
     stage_jitter_um: float = 0.0     # coordinate-only tests: every FOV's stage position is off the grid by up to this
+    tile_jitter_px: int = 0          # every tile's scene origin is off its lattice point by its own (dy, dx) in [-j, j]
+                                     # (coordinates.csv keeps the nominal positions): the ground truth of global registration
     sensor_pixel_size_um: float = 5.0
     magnification: float = 10.0
     tube_lens_mm: float = 180.0
@@ -137,6 +139,11 @@ class GridSpec:
             jy = self.jy if self.rev_jy is None else self.rev_jy
         oy = self.base + r * (self.tile_h - self.ov_y) + c * jy
         ox = self.base + c * (self.tile_w - ov_x) + r * self.jx
+        if self.tile_jitter_px:     # deterministic, different for every tile and axis
+            j = int(self.tile_jitter_px)
+            h = int(hash2d(self.seed + 101, np.array([r]), np.array([c]))[0])
+            oy += (h & 0xFFFF) % (2 * j + 1) - j
+            ox += ((h >> 16) & 0xFFFF) % (2 * j + 1) - j
         return oy, ox
 
     def stage_mm(self, r: int, c: int) -> Tuple[float, float]:
@@ -243,6 +250,8 @@ def write_acquisition_device(spec: GridSpec, root: str, device, workers: int = 1
     from . import native
     if spec.rgb_channels:
         raise ValueError("write_acquisition_device writes monochrome channels only")
+    if spec.tile_jitter_px:
+        raise ValueError("write_acquisition_device does not take tile_jitter_px; use write_acquisition")
     os.makedirs(root, exist_ok=True)
     with open(os.path.join(root, 'acquisition parameters.json'), 'w') as fh:
         json.dump(spec.acquisition_parameters(), fh, indent=2)

@@ -289,6 +289,20 @@ int sq_register_line_supported(int32_t n);
 int64_t sq_register_workspace_bytes(int32_t n_pairs, int32_t n0, int32_t n1, int32_t upsample_factor);
 int sq_register_pairs(const sq_register_args *args, void *stream);
 
+/* Overlap moments for the confidence of a registered pair (global registration, alignment.py): the exact integer sums
+ * a zero-normalised cross-correlation is formed from, over the overlap of the two full tiles at the pair's offset.
+ * Tile table as for sq_tile_minmax (pointer table or base + stride, SQ_U8 / SQ_U16). */
+typedef struct sq_overlap {          /* one window pair: h x w pixels at (ref_y0, ref_x0) in ref_tile and (mov_y0, mov_x0) in mov_tile */
+    int32_t ref_tile, mov_tile, ref_y0, ref_x0, mov_y0, mov_x0, h, w;
+} sq_overlap;
+/* out_dev[5*i .. 5*i+4] = sum a, sum b, sum a^2, sum b^2, sum a*b over window pair i (uint64, exact; a window of 65535s
+ * 2048 x 2048 gives sum a*b = 1.8e16).  out_dev is zeroed on `stream` by every call.  h == 0 or w == 0 gives zeros.  A
+ * tile index outside the table or a window that leaves its tile: SQ_ERR_INVALID, nothing launched and out_dev untouched.
+ * To check the windows the call reads pairs_dev back to the host, i.e. it synchronises `stream`.  n_pairs <= 65535. */
+int sq_pair_overlap_moments(const void *const *tile_ptrs_dev, const void *tile_base_dev, int64_t tile_stride, int32_t n_tiles,
+                            int32_t tile_h, int32_t tile_w, int32_t tile_pitch, int32_t tile_dtype,
+                            const sq_overlap *pairs_dev, int32_t n_pairs, uint64_t *out_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Chunk encoding on the device: the chunks of n_planes (t, c, z) planes (chunk_h x chunk_w elements,
  * zero-padded past the plane's edge like zarr pads edge chunks) as Blosc-1 frames -- byte shuffle + LZ4, the
