@@ -4,6 +4,7 @@
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks, see launch_ranks)
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (+ what the last timed step computed, DIR/*.npy)
+    python bench.py --gpus 1 --steps K --warmup W --full   (+ the legs that take runs of their own, see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -30,11 +31,20 @@ runs the same job on one GPU.
 
 Printed JSON (rank 0, one line): whole-job Mvoxel/s, plus
   roofline     fusion kernel, algorithmic bytes / HIP-event launch time vs 8 TB/s HBM peak (rank 0's launches);
-               traffic = HBM bytes per launch from the PMC counters: at N = 1 measured by this run itself (two child passes
-               under rocprofv3 --pmc after the timed region, live_traffic), else the last committed measurement, labelled
-  cpu_baseline the numpy oracle (oracle/stitch_oracle.py) timed on this box's host on a bounded sample of
-               the same workload (N = 1, rank 0 only), and the genuine reference's timing from the authoring
-               container for the record
+               traffic = HBM bytes per launch from the PMC counters: the last committed measurement, labelled as such
+               (--full at N = 1: measured by this run itself, two child passes under rocprofv3 --pmc after the timed
+               region, live_traffic)
+
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds, after the timed
+region and outside every timing (N = 1, rank 0):
+  cpu_baseline the numpy oracle (oracle/stitch_oracle.py) timed on the host on a bounded sample of the same
+               workload, its planes compared voxel by voxel with the GPU canvas, and the genuine reference's timing
+               from the authoring container for the record (--no-cpu-baseline skips it)
+  feather      the distance-weighted blend on the same resident planes, uint16 and float32 canvases, windows
+               compared with the oracle (default workload; --no-feather skips it, --fusion-mode feather asks for it
+               without --full)
+  headline_job_on_this_gpu   the cfg4 job on this one GPU (default workload; scale_* keys)
+  live traffic the two rocprofv3 --pmc passes above (default workload; --no-live-traffic skips them)
 """
 import argparse
 import json
@@ -70,7 +80,7 @@ REFERENCE_TIMING = {'value': 18.6, 'unit': 'Mvoxel/s', 'cores': 8, 'kind': 'refe
                     'where': 'authoring container, 8 host cores (not this box); tools/time_reference.py'}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
@@ -103,26 +113,48 @@ def main():
                          "against this build's own definition oracle.fuse_plane_feather) as a `feather` object to the line: the same "
                          "planes, tiles and gains fused by fuse_feather_zg_kernel into the uint16 canvas and into a float32 one, "
                          "2 rho + 2 (+ 2) bytes per voxel, HIP-event launch times, windows of one plane per channel compared with "
-                         "the oracle.  The default N = 1 run includes it (--no-feather skips it); `value` stays the overwrite "
-                         "fusion, the reference's own")
+                         "the oracle.  A --full run of the default N = 1 workload includes it (--no-feather skips it); `value` "
+                         "stays the overwrite fusion, the reference's own")
     ap.add_argument('--no-feather', action='store_true')
     ap.add_argument('--weak', action='store_true', help='N > 1 with a region workload: one region per rank (weak scaling)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run what takes runs of its own (N = 1): the CPU baseline and its voxel '
+                         'check, and with the default workload the feather leg, the headline job on this GPU and the live '
+                         'PMC traffic passes.  Off by default: a plain run sets up, warms up, times the steps, writes '
+                         '--dump-outputs and prints the line')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--sha-out', default=None,
                     help='cfg4: write {plane: position-weighted digest of its fused canvas} of the last step to this JSON '
                          'file (one file per rank, ".rankR" appended); for the N-rank == 1-rank check, not for timing')
     ap.add_argument('--traffic-bytes', type=float, default=None,
-                    help='HBM bytes per fusion launch from a separate rocprofv3 --pmc pass (else measured live, see --no-live-traffic)')
+                    help='HBM bytes per fusion launch from a separate rocprofv3 --pmc pass (else the committed measurement, or with '
+                         '--full measured live, see --no-live-traffic)')
     ap.add_argument('--no-live-traffic', action='store_true',
-                    help="N = 1 default workload: do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this launch "
-                         "after the timed region; roofline.traffic then carries the last committed measurement, labelled as such")
+                    help="--full, N = 1 default workload: do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this "
+                         "launch after the timed region; roofline.traffic then carries the last committed measurement, labelled as such")
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
                          'at most 64 MB): the shifts, and the fused canvases at a fixed, seeded sample of voxel positions (rank 0)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
+
+def after_timed_legs(args, world):
+    """What this run does after its timed region, besides --dump-outputs and the line.  All of it takes runs of its own
+    and comes with --full only (one GPU); --fusion-mode feather asks for the feather leg by name."""
+    full = args.full and world == 1
+    default = full and args.workload is None and not args.planes
+    return {'cpu_baseline': full and not args.no_cpu_baseline,
+            'feather': world == 1 and (args.fusion_mode == 'feather'
+                                       or (default and not args.no_feather and not os.environ.get('SQ_BENCH_PMC_CHILD'))),
+            'headline_job': default and not os.environ.get('SQ_BENCH_NO_REFERENCE_JOB'),
+            'live_traffic': default and args.traffic_bytes is None and not args.no_live_traffic}
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has not touched the GPU (torch is not
         # even imported yet) and never will: the N ranks are children, their rank 0 prints the JSON line.
@@ -167,7 +199,7 @@ def main():
             raise SystemExit(f"workload {name} on {world} GPUs is a weak-scaling run (one region per rank): pass --weak, "
                              "or use the default workload (cfg4, strong scaling)")
         out = run_region(ctx)
-        if world == 1 and args.workload is None and not args.planes and args.traffic_bytes is None and not args.no_live_traffic:
+        if after_timed_legs(args, world)['live_traffic']:
             while ARENAS:                     # the passes are child processes of their own: they need the HBM this one held
                 ARENAS.pop().close()
             import gc
@@ -309,7 +341,8 @@ def with_scale_keys(out, job):
     from the job it runs afterwards on the same GPU (`headline_job_on_this_gpu`); a line without such a job says null."""
     if job is None:
         out['scale_workload'], out['scale_value'], out['scale_unit'] = None, None, out.get('unit')
-        out['scale_note'] = 'no headline job in this run (a --workload / --planes override, or SQ_BENCH_NO_REFERENCE_JOB)'
+        out['scale_note'] = ('no headline job in this run (a plain run without --full, a --workload / --planes override, '
+                             'or SQ_BENCH_NO_REFERENCE_JOB)')
     else:
         out['scale_workload'], out['scale_value'], out['scale_unit'] = job['workload'], job['value'], job['unit']
         out['scale_ms_per_job'], out['scale_wall_ms_per_job'] = job.get('ms_per_step'), job.get('wall_ms_per_job')
@@ -689,17 +722,16 @@ def run_region(ctx):
         print('[bench] host ms per step: ' + ', '.join(f'{k} {v / n * 1e3:.2f}' for k, v in lap.items()), file=sys.stderr)
     # accuracy side of the metric (BASELINE.json: shift RMSE <= 0.5 px, fused max-rel-err <= 1e-5)
     out['parity'] = shift_parity(state['shifts'], truth)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    legs = after_timed_legs(args, world)
+    if rank == 0 and legs['cpu_baseline']:
         out['cpu_baseline'], check = cpu_baseline(tiles, flat_list, order, spec, xs, ys, g, hc, wc, truth, canvas_of_plane)
         out['cpu_baseline_reference'] = REFERENCE_TIMING
         out['parity'].update(check)
     # (one GPU only: under several ranks the others would sit in the closing collectives while rank 0 blends)
-    want_feather = world == 1 and (args.fusion_mode == 'feather' or (args.workload is None and not args.planes and not args.no_feather
-                                                                     and not os.environ.get('SQ_BENCH_PMC_CHILD')))
-    if want_feather and rank == 0:
+    if rank == 0 and legs['feather']:
         out['feather'] = feather_leg(args, dev, g, hc, wc, n_planes, order, order_rc, state['shifts'], tiles, canvas, canvas_of_plane,
-                                     plane_of_slot, ptrs, flat_list, slot_flats, flat_ptrs, check=not args.no_cpu_baseline)
-    if world == 1 and args.workload is None and not args.planes and not os.environ.get('SQ_BENCH_NO_REFERENCE_JOB'):
+                                     plane_of_slot, ptrs, flat_list, slot_flats, flat_ptrs, check=legs['cpu_baseline'])
+    if legs['headline_job']:
         # The N > 1 runs of this script measure the headline job (cfg4, strong scaling).  For the record, the SAME job on
         # this one GPU (one step after one warm-up, ~3 s): the single-GPU point of that scaling curve, next to the config-3
         # number above, which is this run's `value`.
@@ -1115,7 +1147,7 @@ def run_job(ctx):
     if rank == 0 and os.environ.get('SQ_BENCH_BREAKDOWN'):
         print(f'[bench] rank 0 timed {mine_s / args.steps * 1e3:.2f} ms/job; host ms per job (every job, warm-up first): ' +
               '; '.join(f'{k} ' + ' '.join(f'{x * 1e3:.2f}' for x in v) for k, v in lap.items()), file=sys.stderr)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and after_timed_legs(args, world)['cpu_baseline']:
         # the last batch is still resident: the oracle on a bounded sample of it (2 planes of the 32x32 grid)
         b = batches[-1]
         flat_list = [ffs[p // Z] for p in b]

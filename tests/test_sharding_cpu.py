@@ -301,6 +301,37 @@ def test_bench_launcher_argv(monkeypatch):
     assert e.value.code == 3 and calls['cmd'][-4:] == ['--gpus', '2', '--steps', '1']
 
 
+def test_bench_plain_run_is_lean_and_full_keeps_the_legs(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does nothing after its timed region but the dump and the line; --full
+    brings back the CPU baseline, the feather leg, the headline job on this GPU and the live PMC passes, each with its opt-out."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_for_test5', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for k in ('SQ_BENCH_PMC_CHILD', 'SQ_BENCH_NO_REFERENCE_JOB'):
+        monkeypatch.delenv(k, raising=False)
+    legs = lambda *a, world=1: bench.after_timed_legs(bench.parse_args(['--steps', '3', '--warmup', '1', *a]), world)
+    names = {'cpu_baseline', 'feather', 'headline_job', 'live_traffic'}
+    assert legs() == dict.fromkeys(names, False)
+    assert not any(legs('--dump-outputs', '/tmp/x').values())
+    assert legs('--full') == dict.fromkeys(names, True)
+    assert not any(legs('--full', world=2).values())
+    assert legs('--full', '--no-cpu-baseline', '--no-feather', '--no-live-traffic') == \
+        dict(cpu_baseline=False, feather=False, headline_job=True, live_traffic=False)
+    assert legs('--full', '--traffic-bytes', '1e11')['live_traffic'] is False
+    # another workload or plane count: only the CPU baseline of that workload
+    for extra in (['--workload', 'cfg4'], ['--planes', '8']):
+        assert legs('--full', *extra) == dict(cpu_baseline=True, feather=False, headline_job=False, live_traffic=False)
+    # the feather leg by name, with or without --full
+    assert legs('--fusion-mode', 'feather') == dict(cpu_baseline=False, feather=True, headline_job=False, live_traffic=False)
+    assert legs('--fusion-mode', 'feather', world=2)['feather'] is False
+    # the environment switches of the PMC child passes drop the feather leg and the headline job
+    monkeypatch.setenv('SQ_BENCH_PMC_CHILD', '1')
+    assert legs('--full')['feather'] is False and legs('--full')['headline_job'] is True
+    monkeypatch.setenv('SQ_BENCH_NO_REFERENCE_JOB', '1')
+    assert legs('--full')['headline_job'] is False
+
+
 def test_bench_arena_layout_views_do_not_alias():
     """bench.alloc_planes('arena'): canvas slots and tile stacks interleaved in ONE allocation -- both are plain views (a
     canvas at a plane stride that is a multiple of 128 bytes, dense tile stacks reachable through the pointer table) and
