@@ -2445,3 +2445,308 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
 #undef SQ_FEATHER
 #undef SQ_FEATHER_F
 }
+
+// ---------------------------------------------------------------------------------------------
+// maximum-intensity projection over z (sq_fuse_project_max; an extension: the reference has none)
+// ---------------------------------------------------------------------------------------------
+// One OUTPUT plane from the Z planes of an overwrite plan: per voxel the value sq_fuse_planes would store in each plane (the same
+// divide routines, so every bit is theirs), reduced by an unsigned maximum.  Algorithmic traffic: Z x sizeof(T) B read per covered
+// voxel + sizeof(T) B written per canvas voxel (+ the gains, loaded ONCE per slot for all Z planes when they all name one image).
+// Structure: the persistent grid of the overwrite kernels (static walk or the per-XCD queues of for_each_queued_item) over the
+// plan's items; the z loop runs inside a slot, so one item is one output store stream and nothing is shared between
+// workgroups.  Seam owners are not used: each item writes exactly its own pixels (the partition SQ_FUSE_NO_SEAM_OWNERS keeps).
+// ACC: max(existing, projection) on the covered voxels, uncovered ones untouched.
+namespace {
+constexpr int PROJ_ZU = 4;   // planes whose pixel vectors a lane has in flight at once
+struct ProjAux {
+    int unused;
+};
+
+// per-component unsigned maximum of two 32-bit words of packed pixels (v_pk_max_u16 for uint16)
+template <typename T>
+__device__ __forceinline__ uint32_t max_packed(uint32_t a, uint32_t b) {
+    if constexpr (sizeof(T) == 2) {
+        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+    } else {
+        typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u8x4, a), __builtin_bit_cast(u8x4, b)));
+    }
+}
+// the generic (IEEE) flatfield divide of the per-plane kernel in the gain's precision: exact for every gain
+template <typename T, typename GT>
+__device__ __forceinline__ T flat_generic(T v, GT g) {
+    if constexpr (sizeof(GT) == 8) return flat_f64<T>(v, g);
+    else return flat_f32<T>(v, g);
+}
+// the fast divide's operand range (flat_classify_kernel): 2^FAST_MIN_EXP <= |g| < 2^FAST_END_EXP
+template <typename GT>
+__device__ __forceinline__ bool in_fast_range(GT g) {
+    const GT a = g < 0 ? -g : g;
+    return a >= (GT)__builtin_ldexp(1.0, FAST_MIN_EXP) && a < (GT)__builtin_ldexp(1.0, FAST_END_EXP);   // NaN fails both
+}
+// one 32-bit word of pixels through the generic divide, gains g[0 .. 4 / sizeof(T))
+template <typename T, typename GT>
+__device__ __forceinline__ uint32_t word_generic(uint32_t w, const GT *g) {
+    constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
+    uint32_t out = 0;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) out |= (uint32_t)flat_generic<T, GT>((T)(w >> (BITS * e)), g[e]) << (BITS * e);
+    return out;
+}
+// the same word through the shortened divide of the plane groups (gains in the fast range, r = recip_of<0>(g))
+template <typename T, typename GT>
+__device__ __forceinline__ uint32_t word_fast(uint32_t w, const GT *g, const GT *r) {
+    if constexpr (sizeof(T) == 2) return quot_pair<0, GT>(w, g[0], g[1], r[0], r[1]);
+    else return quot_quad<0, GT>(w, g, r);
+}
+
+// SHARED: every plane names the gain image flat_ptrs[0] (not NULL).  Otherwise each plane's entry is looked up (NULL = identity)
+// and divided by the generic sequence: exact, not fast.
+template <typename T, typename G, bool SHARED, bool ACC>
+__device__ __forceinline__ void project_item(const FuseParams &P, const Item &it, const int wave, const int lane) {
+    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
+    typedef typename std::conditional<GAINS, G, float>::type GT;
+    constexpr uint32_t GSZ = sizeof(GT), TSZ = sizeof(T);
+    constexpr int VEC = 16 / (int)sizeof(T), LINE = 128 / (int)sizeof(T), PER = 4 / (int)sizeof(T);
+    constexpr int SLOTS = BLOCK_COLS / VEC / 64 + 1;
+    const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
+    const int nz = P.n_planes;
+    T *canvas = static_cast<T *>(P.canvas);
+    if (!it.nref) {   // uncovered canvas: zeros, like every plane of the stack (accumulating: left alone)
+        if (!ACC)
+            for (int r = wave; r < rows; r += 4) row_zero<T>(canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x, n, lane);
+        return;
+    }
+    const GT *flat0 = nullptr;
+    if constexpr (GAINS && SHARED) flat0 = sgpr(static_cast<const GT *>(P.flat_ptrs[0]));
+    for (int r = wave; r < rows; r += 4) {
+        char *drow = reinterpret_cast<char *>(canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x);
+        const int64_t soff = (int64_t)(it.b + r) * P.tile_pitch + it.c;   // elements into every plane's tile
+        const int64_t foff = (int64_t)(it.b + r) * P.tile_w + it.c;       // elements into a gain image
+        // vector v covers row pixels [v * VEC - mis, +VEC): stores start on the canvas' 128-byte lines (row_setup)
+        const int mis = (int)((reinterpret_cast<uintptr_t>(drow) / sizeof(T)) & (LINE - 1));
+        const int v_first = (mis + VEC - 1) / VEC, v_end = (n + mis) / VEC;
+#pragma unroll
+        for (int k = 0; k < SLOTS; ++k) {
+            if (64 * k >= v_end || v_end <= v_first) break;   // wave-uniform: no whole vector (left) in this row
+            const int v = lane + 64 * k;
+            const bool act = v >= v_first && v < v_end;
+            // lanes without a vector of their own load the row's first / last whole vector; only their store is masked
+            const uint32_t o = (uint32_t)min(max(v * VEC - mis, v_first * VEC - mis), (v_end - 1) * VEC - mis);
+            u32x4 acc = {0u, 0u, 0u, 0u};
+            if (ACC) acc = ldg<U32x4U>(drow + o * TSZ);
+            GT g[VEC], rc[VEC];
+            bool fast = true;
+            if constexpr (GAINS && SHARED) {
+                load_gains(reinterpret_cast<const char *>(flat0 + foff) + o * GSZ, g);
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    fast = fast && in_fast_range(g[c]);
+                    rc[c] = recip_of<0>(g[c]);
+                }
+            }
+            for (int z0 = 0; z0 < nz; z0 += PROJ_ZU) {
+                u32x4 px[PROJ_ZU];
+#pragma unroll
+                for (int u = 0; u < PROJ_ZU; ++u)
+                    if (z0 + u < nz) px[u] = ldg<U32x4U>(reinterpret_cast<const char *>(tile_ptr<T>(P, z0 + u, it.a) + soff) + o * TSZ);
+#pragma unroll
+                for (int u = 0; u < PROJ_ZU; ++u) {
+                    if (z0 + u >= nz) break;
+                    if constexpr (!GAINS) {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], px[u][c]);
+                    } else if constexpr (SHARED) {
+                        if (fast) {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], word_fast<T, GT>(px[u][c], &g[PER * c], &rc[PER * c]));
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], word_generic<T, GT>(px[u][c], &g[PER * c]));
+                        }
+                    } else {
+                        const GT *fz = sgpr(static_cast<const GT *>(P.flat_ptrs[z0 + u]));
+                        if (fz) {
+                            GT gz[VEC];
+                            load_gains(reinterpret_cast<const char *>(fz + foff) + o * GSZ, gz);
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], word_generic<T, GT>(px[u][c], &gz[PER * c]));
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], px[u][c]);
+                        }
+                    }
+                }
+            }
+            if (act) stg_nt_at(drow, o * TSZ, acc);
+        }
+        // the row's edges (pixels before the first / after the last whole vector): lanes 0..VEC-1 the head, VEC..2VEC-1 the
+        // tail, one pixel each, through the generic divide
+        const int head_end = min(n, v_first * VEC - mis);
+        const int tail_start = max(head_end, v_end * VEC - mis);
+        int ep = -1;
+        if (lane < VEC) {
+            if (lane < head_end) ep = lane;
+        } else if (lane < 2 * VEC) {
+            if (tail_start + (lane - VEC) < n) ep = tail_start + (lane - VEC);
+        }
+        if (ep >= 0) {
+            uint32_t m = ACC ? (uint32_t)ldg_s<T>(drow + ep * TSZ) : 0u;
+            for (int z = 0; z < nz; ++z) {
+                const T t = ldg_s<T>(tile_ptr<T>(P, z, it.a) + soff + ep);
+                uint32_t q = t;
+                if constexpr (GAINS) {
+                    const GT *fz = SHARED ? flat0 : static_cast<const GT *>(P.flat_ptrs[z]);
+                    if (fz) q = flat_generic<T, GT>(t, ldg_s<GT>(fz + foff + ep));
+                }
+                m = max(m, q);
+            }
+            stg_s<T>(drow + ep * TSZ, (T)m);
+        }
+    }
+}
+
+template <typename T, typename G, bool ACC, bool DYN>
+__global__ __launch_bounds__(256) void project_max_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work) {
+    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    bool shared = false;   // every plane names one gain image: load it and take its reciprocals once for all planes
+    if constexpr (GAINS) {
+        const void *f0 = P.flat_ptrs[0];
+        shared = f0 != nullptr;
+        for (int z = 1; z < P.n_planes && shared; ++z) shared = P.flat_ptrs[z] == f0;
+        shared = sgpr((int)shared) != 0;
+    }
+    auto body = [&](const Item &it) {
+        if (!GAINS || shared) project_item<T, G, true, ACC>(P, it, wave, lane);
+        else project_item<T, G, false, ACC>(P, it, wave, lane);
+    };
+    if (!DYN) {
+        for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x) body(sgpr(P.items[w]));
+        return;
+    }
+    for_each_queued_item<ProjAux>(
+        P, n_items, 1u, [&](int, const Item &, int64_t) -> ProjAux { return ProjAux{0}; },
+        [&](int, const Item &it, const ProjAux &) { body(it); });
+}
+
+template <typename K>
+int launch_project(K kernel, const FuseParams &P, int64_t n_items, hipStream_t stream, int grid_override) {
+    if (n_items == 0) return SQ_OK;
+    static thread_local std::map<const void *, int> resident;
+    const void *key = reinterpret_cast<const void *>(kernel);
+    auto it = resident.find(key);
+    if (it == resident.end()) {
+        int dev = 0, cus = 256, per_cu = 8;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+            cus = prop.multiProcessorCount;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+        it = resident.emplace(key, cus * std::min(per_cu, 8)).first;
+    }
+    const int64_t blocks = std::min<int64_t>(n_items, grid_override > 0 ? grid_override : it->second);
+    FuseParams Q = P;
+    Q.chunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(QUEUE_CHUNK, n_items / (blocks * 16)));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, Q, n_items, n_items);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_fuse_project_max: launch failed: %s", hipGetErrorString(e));
+    return SQ_OK;
+}
+}  // namespace
+
+extern "C" int sq_fuse_project_max(const sq_fuse_args *a, int32_t flags, void *stream_) {
+    if (!a || !a->plan || !a->table_dev || !a->canvas_dev)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: NULL plan/table/output");
+    if (a->mode != SQ_FUSE_OVERWRITE)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: mode %d, only SQ_FUSE_OVERWRITE plans can be projected", a->mode);
+    const TableHeader &h = a->plan->header();
+    if (h.mode != SQ_FUSE_OVERWRITE) return fail(SQ_ERR_INVALID, "sq_fuse_project_max: the plan was built for mode %d", h.mode);
+    if (a->plan->spans_only && !a->plan->expanded)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: the plan of sq_fuse_plan_create_spans has not been through sq_fuse_plan_expand");
+    if (a->table_bytes != a->plan->device_bytes())
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: table_bytes %lld != plan %lld", (long long)a->table_bytes,
+                    (long long)a->plan->device_bytes());
+    if (a->n_tiles != h.n_tiles || a->tile_h != h.tile_h || a->tile_w != h.tile_w || a->canvas_h != h.canvas_h ||
+        a->canvas_w != h.canvas_w)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: geometry differs from the plan");
+    if (!a->tile_ptrs_dev && !a->tile_base_dev && h.n_refs > 0)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: no tile table and no tile base");
+    if (a->tile_pitch < a->tile_w || a->canvas_pitch < a->canvas_w)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: pitch smaller than width");
+    if (a->n_planes < 1) return fail(SQ_ERR_INVALID, "sq_fuse_project_max: n_planes %d (at least one plane)", a->n_planes);
+    const int32_t fl = flags | a->flags;
+    if ((fl & ~(SQ_FUSE_FORCE_QUEUES | SQ_FUSE_FORCE_STATIC | SQ_FUSE_NO_PLANE_GROUPS | SQ_FUSE_NO_SEAM_OWNERS | SQ_FUSE_CONSECUTIVE_GROUPS |
+                SQ_PROJECT_ACCUMULATE)) ||
+        a->grid_blocks < 0 || ((fl & SQ_FUSE_FORCE_QUEUES) && (fl & SQ_FUSE_FORCE_STATIC)))
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: flags %d / grid_blocks %d", fl, a->grid_blocks);
+    if (a->tile_dtype != SQ_U8 && a->tile_dtype != SQ_U16)
+        return fail(SQ_ERR_UNSUPPORTED, "sq_fuse_project_max: tile dtype %d (uint8/uint16 only)", a->tile_dtype);
+    if (a->canvas_dtype != a->tile_dtype)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: the output keeps the tile dtype (output %d, tile %d)", a->canvas_dtype,
+                    a->tile_dtype);
+    if (a->flat_ptrs_dev && a->flat_dtype != SQ_F32 && a->flat_dtype != SQ_F64)
+        return fail(SQ_ERR_UNSUPPORTED, "sq_fuse_project_max: flatfield dtype %d (float32/float64 only)", a->flat_dtype);
+    if (reinterpret_cast<uintptr_t>(a->canvas_dev) % (size_t)a->canvas_dtype)
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: output pointer not aligned to its element size");
+
+    FuseParams P{};
+    const char *base = static_cast<const char *>(a->table_dev);
+    P.spans = reinterpret_cast<const Span *>(base + h.off_spans);
+    P.refs = reinterpret_cast<const Ref *>(base + h.off_refs);
+    P.items = reinterpret_cast<const Item *>(base + h.off_items);
+    P.seams = nullptr;
+    P.tile_ptrs = a->tile_ptrs_dev;
+    P.tile_base = a->tile_base_dev;
+    P.tile_plane_stride = a->tile_plane_stride;
+    P.tile_stride = a->tile_stride;
+    P.flat_ptrs = a->flat_ptrs_dev;
+    P.canvas = a->canvas_dev;
+    P.canvas_plane_stride = 0;
+    P.n_tiles = a->n_tiles;
+    P.tile_h = a->tile_h;
+    P.tile_w = a->tile_w;
+    P.tile_pitch = a->tile_pitch;
+    P.canvas_pitch = a->canvas_pitch;
+    P.lane_items = (int32_t)h.lane_items;
+    P.n_planes = a->n_planes;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (a->scratch_dev) {
+        const ScratchLayout SL = scratch_layout(a->n_planes);
+        if (a->scratch_bytes < SL.total)
+            return fail(SQ_ERR_WORKSPACE, "sq_fuse_project_max: scratch %lld < %lld bytes", (long long)a->scratch_bytes,
+                        (long long)SL.total);
+        if (reinterpret_cast<uintptr_t>(a->scratch_dev) % 128)
+            return fail(SQ_ERR_INVALID, "sq_fuse_project_max: scratch not 128-byte aligned");
+        // the device queues: the same size rule as sq_fuse_planes (an item carries all Z planes here)
+        const int64_t n_work = (int64_t)a->n_planes * h.n_items;
+        if ((n_work >= 100000 || (fl & SQ_FUSE_FORCE_QUEUES)) && h.n_items < (int64_t(1) << 31) && !(fl & SQ_FUSE_FORCE_STATIC)) {
+            if (hipMemsetAsync(static_cast<char *>(a->scratch_dev) + SL.queue, 0, 9 * QUEUE_STRIDE * 4, stream) != hipSuccess)
+                return fail(SQ_ERR_HIP, "sq_fuse_project_max: cannot clear the queue counters");
+            P.queue = reinterpret_cast<uint32_t *>(static_cast<char *>(a->scratch_dev) + SL.queue);
+        }
+    } else if (fl & SQ_FUSE_FORCE_QUEUES) {
+        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: SQ_FUSE_FORCE_QUEUES needs scratch_dev");
+    }
+    const bool acc = (fl & SQ_PROJECT_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
+    const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
+#define SQ_PROJECT(T, G)                                                                                                     \
+    do {                                                                                                                     \
+        if (acc) {                                                                                                           \
+            if (P.queue) return launch_project(project_max_kernel<T, G, true, true>, P, h.n_items, stream, a->grid_blocks);   \
+            return launch_project(project_max_kernel<T, G, true, false>, P, h.n_items, stream, a->grid_blocks);              \
+        }                                                                                                                    \
+        if (P.queue) return launch_project(project_max_kernel<T, G, false, true>, P, h.n_items, stream, a->grid_blocks);      \
+        return launch_project(project_max_kernel<T, G, false, false>, P, h.n_items, stream, a->grid_blocks);                 \
+    } while (0)
+    if (u16) {
+        if (flat == 0) SQ_PROJECT(uint16_t, NoGain);
+        if (flat == 1) SQ_PROJECT(uint16_t, float);
+        SQ_PROJECT(uint16_t, double);
+    }
+    if (flat == 0) SQ_PROJECT(uint8_t, NoGain);
+    if (flat == 1) SQ_PROJECT(uint8_t, float);
+    SQ_PROJECT(uint8_t, double);
+#undef SQ_PROJECT
+}

@@ -21,6 +21,7 @@ SQ_U8, SQ_U16, SQ_F32, SQ_F64 = 1, 2, 4, 8
 SQ_FUSE_OVERWRITE, SQ_FUSE_FEATHER = 0, 1
 SQ_NORM_NONE, SQ_NORM_PHASE = 0, 1
 SQ_FUSE_FORCE_QUEUES, SQ_FUSE_FORCE_STATIC, SQ_FUSE_NO_PLANE_GROUPS, SQ_FUSE_NO_SEAM_OWNERS, SQ_FUSE_CONSECUTIVE_GROUPS = 1, 2, 4, 8, 16
+SQ_PROJECT_ACCUMULATE = 32
 SQ_VERSION = 108
 SQ_ARENA_NATURAL_ORDER = 1
 SQ_ARENA_TWO_CLASSES = 2
@@ -94,6 +95,7 @@ EXPORTS = {
     'sq_fuse_plan_stats': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     'sq_fuse_planes': (C.c_int, [C.POINTER(_FuseArgs), C.c_void_p]),
+    'sq_fuse_project_max': (C.c_int, [C.POINTER(_FuseArgs), C.c_int32, C.c_void_p]),
     'sq_tile_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_pair_overlap_moments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -335,42 +337,23 @@ def pointer_table(tensors: Sequence, device):
     return upload_small(torch.tensor(ptrs, dtype=torch.int64), device)
 
 
-def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, stream=None, flat_ptrs=None,
-                flags: int = 0, grid_blocks: int = 0) -> None:
-    """Fuse all planes of ``canvas`` ([P, Hc, Wc] or [..., Hc, Wc] contiguous) from ``tiles``.
-
-    tiles:     contiguous device tensor [P, N, H, W] (N = plan.n_tiles), or None with
-               ``tile_ptrs`` = device int64 tensor [P*N] of tile pointers (dense H x W tiles).
-    flats:     None, or a list of P device tensors / None (H x W float32 or float64 gains);
-               all non-None entries must share one dtype.
-    flat_ptrs: optionally ``pointer_table(flats, device)`` made earlier, for callers that fuse with the same
-               gains again and again (saves a small blocking upload per call).
-    """
+def _fuse_args(plan: FusePlan, tiles, n_planes: int, out, plane_stride: int, pitch: int, flats, tile_ptrs, flat_ptrs, keep):
+    """The sq_fuse_args of ``n_planes`` planes of ``tiles`` (or ``tile_ptrs``) into ``out`` (its geometry given by the caller)."""
     import torch
     L = lib()
-    hc, wc = int(canvas.shape[-2]), int(canvas.shape[-1])
-    n_planes = int(canvas.numel() // (hc * wc)) if hc * wc else 0
-    # contiguous, or [P, Hc, Wc] with dense rows and any row pitch / plane stride (empty_canvas pads the plane stride)
-    pitch, plane_stride = wc, hc * wc
-    if not canvas.is_cuda:
-        raise ValueError("canvas must be a device tensor")
-    if not canvas.is_contiguous():
-        if canvas.dim() != 3 or (wc > 1 and canvas.stride(2) != 1) or canvas.stride(1) < wc or \
-                (n_planes > 1 and canvas.stride(0) < (hc - 1) * canvas.stride(1) + wc):
-            raise ValueError("canvas must be contiguous or a [P, Hc, Wc] tensor with unit-stride rows and non-overlapping planes")
-        pitch, plane_stride = int(canvas.stride(1)), int(canvas.stride(0))
+    hc, wc = int(out.shape[-2]), int(out.shape[-1])
     a = _FuseArgs()
     a.plan = plan.handle
-    table = plan.device_table(canvas.device)
+    table = plan.device_table(out.device)
     a.table_dev = table.data_ptr()
     a.table_bytes = table.numel()
-    keep = [table]
+    keep.append(table)
     if tile_ptrs is not None:
         if tile_ptrs.dtype != torch.int64 or tile_ptrs.numel() != n_planes * plan.n_tiles:
             raise ValueError("tile_ptrs must be int64 with n_planes * n_tiles entries")
         a.tile_ptrs_dev = tile_ptrs.data_ptr()
         a.tile_base_dev = None
-        tile_np = np_dtype_of_torch(canvas.dtype) if plan.mode == SQ_FUSE_OVERWRITE else np.dtype('uint16')
+        tile_np = np_dtype_of_torch(out.dtype) if plan.mode == SQ_FUSE_OVERWRITE else np.dtype('uint16')
         if tiles is not None:
             tile_np = np_dtype_of_torch(tiles.dtype)
     else:
@@ -398,27 +381,92 @@ def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, strea
             if f is not None and (tuple(f.shape) != (plan.tile_h, plan.tile_w) or not f.is_contiguous()):
                 raise ValueError("flatfield must be a contiguous tile_h x tile_w tensor")
         a.flat_dtype = sq_dtype_of(np_dtype_of_torch(dts.pop()))
-        fp = flat_ptrs if flat_ptrs is not None else pointer_table(flats, canvas.device)
+        fp = flat_ptrs if flat_ptrs is not None else pointer_table(flats, out.device)
         if fp.dtype != torch.int64 or fp.numel() != n_planes:
             raise ValueError("flat_ptrs must be int64 with one entry per plane")
         keep.append(fp)
         a.flat_ptrs_dev = fp.data_ptr()
     if n_planes > 0:   # gain classes + work-queue counters (torch allocations are 512-byte aligned)
-        scratch = torch.empty(int(L.sq_fuse_scratch_bytes(n_planes)), dtype=torch.uint8, device=canvas.device)
+        scratch = torch.empty(int(L.sq_fuse_scratch_bytes(n_planes)), dtype=torch.uint8, device=out.device)
         keep.append(scratch)
         a.scratch_dev = scratch.data_ptr()
         a.scratch_bytes = scratch.numel()
-    a.canvas_dev = canvas.data_ptr()
+    a.canvas_dev = out.data_ptr()
     a.canvas_plane_stride = plane_stride
     a.canvas_h, a.canvas_w, a.canvas_pitch = hc, wc, pitch
-    a.canvas_dtype = sq_dtype_of(np_dtype_of_torch(canvas.dtype))
+    a.canvas_dtype = sq_dtype_of(np_dtype_of_torch(out.dtype))
     a.n_planes = n_planes
     a.mode = plan.mode
+    return a
+
+
+def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, stream=None, flat_ptrs=None,
+                flags: int = 0, grid_blocks: int = 0) -> None:
+    """Fuse all planes of ``canvas`` ([P, Hc, Wc] or [..., Hc, Wc] contiguous) from ``tiles``.
+
+    tiles:     contiguous device tensor [P, N, H, W] (N = plan.n_tiles), or None with
+               ``tile_ptrs`` = device int64 tensor [P*N] of tile pointers (dense H x W tiles).
+    flats:     None, or a list of P device tensors / None (H x W float32 or float64 gains);
+               all non-None entries must share one dtype.
+    flat_ptrs: optionally ``pointer_table(flats, device)`` made earlier, for callers that fuse with the same
+               gains again and again (saves a small blocking upload per call).
+    """
+    L = lib()
+    hc, wc = int(canvas.shape[-2]), int(canvas.shape[-1])
+    n_planes = int(canvas.numel() // (hc * wc)) if hc * wc else 0
+    # contiguous, or [P, Hc, Wc] with dense rows and any row pitch / plane stride (empty_canvas pads the plane stride)
+    pitch, plane_stride = wc, hc * wc
+    if not canvas.is_cuda:
+        raise ValueError("canvas must be a device tensor")
+    if not canvas.is_contiguous():
+        if canvas.dim() != 3 or (wc > 1 and canvas.stride(2) != 1) or canvas.stride(1) < wc or \
+                (n_planes > 1 and canvas.stride(0) < (hc - 1) * canvas.stride(1) + wc):
+            raise ValueError("canvas must be contiguous or a [P, Hc, Wc] tensor with unit-stride rows and non-overlapping planes")
+        pitch, plane_stride = int(canvas.stride(1)), int(canvas.stride(0))
+    keep = []
+    a = _fuse_args(plan, tiles, n_planes, canvas, plane_stride, pitch, flats, tile_ptrs, flat_ptrs, keep)
     a.flags, a.grid_blocks = int(flags), int(grid_blocks)
     if stream is not None:      # launched on another stream than the one the helpers above allocated for
         for t in keep:
             t.record_stream(stream)
     _check(L.sq_fuse_planes(C.byref(a), _stream_ptr(stream)), 'sq_fuse_planes')
+
+
+def fuse_project_max(plan: FusePlan, tiles, out, flats=None, tile_ptrs=None, accumulate: bool = False, flags: int = 0,
+                     stream=None, flat_ptrs=None, grid_blocks: int = 0) -> None:
+    """Maximum-intensity projection over z (sq_fuse_project_max; an extension, the reference has none): ``out`` ([Hc, Wc]
+    device tensor with unit-stride rows, the tile dtype) = the per-voxel maximum over the Z planes of ``tiles`` of what
+    ``fuse_planes`` would store in each plane -- bit for bit ``fuse_planes(...)`` followed by ``amax`` over z, without the stack.
+
+    tiles / tile_ptrs / flats / flat_ptrs: as in ``fuse_planes`` with P = Z planes (Z = tiles.shape[0], or
+    tile_ptrs.numel() // plan.n_tiles).  The plan must be an overwrite plan.
+    accumulate: ``out`` = max(out, projection) on the plan's covered voxels, the uncovered ones untouched (a channel's z planes
+    that come in several calls or under different plans); otherwise every voxel of ``out`` is written, uncovered ones 0."""
+    L = lib()
+    if plan.mode != SQ_FUSE_OVERWRITE:
+        raise ValueError("fuse_project_max projects overwrite plans only")
+    if not out.is_cuda or out.dim() != 2 or tuple(out.shape) != (plan.canvas_h, plan.canvas_w):
+        raise ValueError(f"out must be a [{plan.canvas_h}, {plan.canvas_w}] device tensor")
+    hc, wc = int(out.shape[0]), int(out.shape[1])
+    if (wc > 1 and out.stride(1) != 1) or (hc > 1 and out.stride(0) < wc):
+        raise ValueError("out must have unit-stride rows")
+    pitch = int(out.stride(0)) if hc > 1 else wc
+    if tile_ptrs is not None:
+        n_planes = int(tile_ptrs.numel()) // max(plan.n_tiles, 1) if plan.n_tiles else (len(flats) if flats is not None else 1)
+    elif tiles is not None:
+        n_planes = int(tiles.shape[0]) if tiles.dim() == 4 else 1
+    else:
+        raise ValueError("tiles or tile_ptrs is required")
+    if n_planes < 1:
+        raise ValueError("at least one plane to project")
+    keep = []
+    a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
+    a.flags, a.grid_blocks = 0, int(grid_blocks)
+    if stream is not None:
+        for t in keep:
+            t.record_stream(stream)
+    fl = int(flags) | (SQ_PROJECT_ACCUMULATE if accumulate else 0)
+    _check(L.sq_fuse_project_max(C.byref(a), fl, _stream_ptr(stream)), 'sq_fuse_project_max')
 
 
 PLANE_ALIGN_BYTES = 128

@@ -56,7 +56,7 @@ class Stitcher:
     def __init__(self, params: StitchingParameters, device=None, fusion_mode: str = 'overwrite',
                  normalization: Optional[str] = 'phase', zarr_compression: str = 'blosc',
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
-                 all_pairs_registration: bool = False, global_registration: bool = False):
+                 all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none'):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -83,6 +83,14 @@ class Stitcher:
             raise ValueError("fusion_mode must be 'overwrite' or 'feather'")
         self.fusion_mode = fusion_mode            # 'feather' is an extension the reference lacks
         self.normalization = normalization        # scikit-image >= 0.19 default is 'phase'
+        # Extension: per-channel maximum-intensity projection over z from the tiles on the device (sq_fuse_project_max).
+        # 'max' writes <region>_stitched_mip<format> beside the stack, 'max-only' writes the projection alone.
+        if z_projection not in ('none', 'max', 'max-only'):
+            raise ValueError("z_projection must be 'none', 'max' or 'max-only'")
+        if z_projection != 'none' and fusion_mode != 'overwrite':
+            raise ValueError(f"z_projection={z_projection!r} projects overwrite fusion only; it cannot be combined with "
+                             f"fusion_mode={fusion_mode!r}")
+        self.z_projection = z_projection
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -693,7 +701,10 @@ class Stitcher:
         # canvas slots z-major ("spread"): the z planes of a channel -- which share a gain image and go through the
         # fusion kernel together -- then lie num_c planes apart in the canvas allocation instead of side by side; a
         # group of planes writes fastest when they sit in different stretches of device memory (DESIGN.md 5.1 point 8)
-        planes, _ = self.stitch_planes(timepoint, region, None, progress_callback, slot_order='spread')
+        return self._stitch_region(timepoint, region, progress_callback, device_output)
+
+    def _stitch_region(self, timepoint, region, progress_callback=None, device_output: bool = False, project_to=None):
+        planes, _ = self.stitch_planes(timepoint, region, None, progress_callback, slot_order='spread', project_to=project_to)
         shape = (1, self.num_c, self.num_z, planes.shape[-2], planes.shape[-1])
         by_cz = planes.unflatten(0, (self.num_z, self.num_c)).transpose(0, 1)   # [C, Z, Hc, Wc] view of the [Z * C] slots
         if device_output:       # a strided view: planes sit on 128-byte lines, rows are dense
@@ -705,8 +716,27 @@ class Stitcher:
                 out[0, c, z].copy_(by_cz[c, z])
         return out.numpy()
 
+    def project_region(self, timepoint, region, progress_callback=None, device_output: bool = False):
+        """Maximum-intensity projection over z of one (timepoint, region) -> (1, C, 1, Hc, Wc) of the input dtype, equal to
+        ``stitch_region(...).max(axis=2)`` bit for bit, without the stack ever existing: the tiles are staged as for
+        ``stitch_region`` and every channel's z planes are reduced by one kernel (sq_fuse_project_max; an extension, the
+        reference has no projection).  Returns numpy (host) unless ``device_output``."""
+        proj = self._new_projection(timepoint, region)
+        self.stitch_planes(timepoint, region, None, progress_callback, stack=False,
+                           project_to={c: proj[c] for c in range(self.num_c)})
+        out = proj.unsqueeze(0).unsqueeze(2)
+        return out if device_output else out.cpu().numpy()
+
+    def _new_projection(self, timepoint, region, rows=None, n_channels=None):
+        """Device buffer [C, Hc, Wc] (or [n_channels, y1 - y0, Wc] for a row band) of a region's projections, rows dense."""
+        import torch
+        width, height = self.calculate_output_dimensions(timepoint, region)
+        hc = height if rows is None else int(rows[1]) - int(rows[0])
+        n = self.num_c if n_channels is None else int(n_channels)
+        return torch.empty((n, hc, width), dtype=native.torch_dtype_of(self.dtype), device=self.device)
+
     def stitch_planes(self, timepoint, region, only_planes=None, progress_callback=None, stream_to=None, row_band=None,
-                      slot_order: str = 'plane'):
+                      slot_order: str = 'plane', project_to=None, stack: bool = True):
         """Fuse the (channel, z) planes ``only_planes`` (plane = channel * num_z + z; None = all) of one
         (timepoint, region) -> (device tensor [n, Hc, Wc], sorted plane ids).  Planes are independent,
         which is what lets several GPUs share one region.
@@ -719,7 +749,13 @@ class Stitcher:
         several GPUs); the canvas is then y1 - y0 rows high, tiles outside the band are not even read.
 
         ``slot_order``: 'plane' -- the returned tensor's i-th plane is the i-th plane id; 'spread' (all planes only) --
-        plane c * num_z + z sits at slot z * num_c + c, so the planes of a channel are num_c slots apart."""
+        plane c * num_z + z sits at slot z * num_c + c, so the planes of a channel are num_c slots apart.
+
+        ``project_to``: {channel: device tensor [Hc, Wc]} (the band's rows with ``row_band``) that receives the channel's
+        maximum-intensity projection over the z planes among ``only_planes`` (sq_fuse_project_max), computed from the same
+        staged tiles as the stack: the first batch of a channel writes, later batches (and other rectangle lists) accumulate;
+        a channel no file touches comes out as zeros.  ``stack=False``: the projection only -- no canvas, no stream writer,
+        no stack fusion; the return value is then (None, plane ids)."""
         import torch
         start_time = time.time()
         region_data = self.get_region_data(int(timepoint), region)
@@ -742,7 +778,11 @@ class Stitcher:
         if not (0 <= y0 < y1 <= height):
             raise ValueError(f"row band {row_band} outside the {height}-row canvas")
         hc, wc = y1 - y0, width
-        flat_canvas = None if stream_to is not None else \
+        if not stack and project_to is None:
+            raise ValueError("stack=False leaves nothing to compute without project_to")
+        if not stack:
+            stream_to = None
+        flat_canvas = None if (stream_to is not None or not stack) else \
             self._empty_canvas(len(plane_ids), hc, wc, native.torch_dtype_of(self.dtype))
         th, tw = self.input_height, self.input_width
         total_tiles = len(region_data)
@@ -770,7 +810,7 @@ class Stitcher:
 
         mode = native.SQ_FUSE_OVERWRITE if self.fusion_mode == 'overwrite' else native.SQ_FUSE_FEATHER
         # planes no file touches still have to come out as zeros
-        empty = [p for p in plane_ids if p not in planes] if stream_to is None else []   # streamed: fill_value
+        empty = [p for p in plane_ids if p not in planes] if (stream_to is None and stack) else []   # streamed: fill_value
         if empty:
             zplan = self._plan_for(np.zeros((0, 6)), th, tw, hc, wc, native.SQ_FUSE_OVERWRITE)
             for p in empty:
@@ -807,6 +847,7 @@ class Stitcher:
         budget = max(1, min(int(free_bytes * 0.2), int(host_free * 0.1), int(self.batch_bytes_limit)))
         tdtype = native.torch_dtype_of(self.dtype)
         processed = 0
+        projected = set()      # channels whose projection has been written once: later batches accumulate
         pool = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4))
         writer = None
         stream_ctx.__enter__()
@@ -818,6 +859,12 @@ class Stitcher:
             if stream_to is not None and groups:
                 widest = max(len(rect_of[sig]) for sig in groups) * th * tw * np.dtype(self.dtype).itemsize
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
+            if project_to is not None:
+                for t in project_to.values():
+                    t.record_stream(torch.cuda.current_stream(self.device))
+                for c in project_to:
+                    if not any(p // self.num_z == c for p in planes):
+                        project_to[c].zero_()      # no file of this channel: zeros, like its planes of the stack
             for sig, plist in groups.items():
                 # ascending plane ids: the canvas slots of a chunk are then consecutive and the whole chunk
                 # goes out in ONE launch (region_data is in file-name order, i.e. z varies before channel)
@@ -874,7 +921,20 @@ class Stitcher:
                     tiles.copy_(staging[slot][:m], non_blocking=True)
                     flats = [flats_dev.get(p // self.num_z) for p in chunk] if self.apply_flatfield else None
                     slots = [slot_of[p] for p in chunk]
-                    if writer is not None:
+                    if project_to is not None:
+                        # the channels' z planes among this chunk's staged tiles -> their projections (consecutive plane ids)
+                        runs: Dict[int, List[int]] = {}
+                        for pi, p in enumerate(chunk):
+                            if p // self.num_z in project_to:
+                                runs.setdefault(p // self.num_z, []).append(pi)
+                        for c, pis in runs.items():
+                            i0, i1 = pis[0], pis[-1] + 1
+                            native.fuse_project_max(plan, tiles[i0:i1], project_to[c], None if flats is None else flats[i0:i1],
+                                                    accumulate=c in projected)
+                            projected.add(c)
+                    if not stack:      # the projection only
+                        pass
+                    elif writer is not None:
                         native.fuse_planes(plan, tiles, writer.acquire(m), flats)
                         writer.submit([(0, p // self.num_z, p % self.num_z) for p in chunk])
                     elif m == 1 or (slots[1] > slots[0] and all(slots[i + 1] - slots[i] == slots[1] - slots[0] for i in range(m - 1))):
@@ -890,6 +950,8 @@ class Stitcher:
                     done[slot].record()
         finally:
             stream_ctx.__exit__(None, None, None)
+            if side is not None and project_to is not None:
+                torch.cuda.current_stream(self.device).wait_stream(side)      # whatever reads the projections: after its kernels
             pool.shutdown(wait=True)
             if writer is not None and not self._defer_drain:
                 writer.drain()      # everything of this region is on disk when the call returns (run() defers it to its end)
@@ -917,6 +979,40 @@ class Stitcher:
                        name=f"{region}_t{timepoint}", compression=self.zarr_compression, device=self.device)
         return output_path
 
+    def _mip_path(self, timepoint, region) -> str:
+        return os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched_mip{self.output_format}")
+
+    def save_region_mip(self, timepoint, region, mip) -> str:
+        """``<t>_stitched/<region>_stitched_mip<format>``: the (1, C, 1, Hc, Wc) projection (numpy or device tensor) with the
+        stack's channel names, colours, pixel size and pyramid level count, through the same writers as the stack."""
+        output_path = self._mip_path(timepoint, region)
+        os.makedirs(os.path.dirname(output_path), exist_ok=True)
+        if self.output_format.endswith('.zarr'):
+            write_ome_zarr(output_path, mip, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
+                           channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
+                           num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
+                           name=f"{region}_t{timepoint}_mip", compression=self.zarr_compression, device=self.device)
+            return output_path
+        if hasattr(mip, 'cpu'):
+            mip = mip.cpu().numpy()
+        print(f"Writing OME-TIFF to: {output_path}")
+        write_ome_tiff(output_path, np.asarray(mip), pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
+                       channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
+                       name=f"{region}_t{timepoint}_mip")
+        return output_path
+
+    def create_mip_store(self, timepoint, region):
+        """Metadata of the region's projection store (Z = 1, no chunks) -> (path, level shapes)."""
+        output_path = self._mip_path(timepoint, region)
+        os.makedirs(os.path.dirname(output_path), exist_ok=True)
+        width, height = self.calculate_output_dimensions(timepoint, region)
+        shapes = omezarr.create_store(output_path, (1, self.num_c, 1, height, width), self.dtype,
+                                      pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
+                                      channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
+                                      num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
+                                      name=f"{region}_t{timepoint}_mip", compression=self.zarr_compression)
+        return output_path, shapes
+
     def create_region_store(self, timepoint, region):
         """Metadata of the region's OME-Zarr store (no chunks) -> (path, level shapes)."""
         output_path = self._zarr_path(timepoint, region)
@@ -930,7 +1026,7 @@ class Stitcher:
         return output_path, shapes
 
     def stream_region_to_zarr(self, timepoint, region, only_planes=None, progress_callback=None, create: bool = True,
-                              row_band=None):
+                              row_band=None, project_to=None):
         """stitch_region + save_region_ome_zarr without the region ever existing in one piece: planes
         are fused a batch at a time and stream through pyramid kernel, pinned D2H copy and compression
         threads while the next batch is read and fused.  Same store as
@@ -976,7 +1072,8 @@ class Stitcher:
             return made[-1]
 
         before = self._stream_writer.bytes_written if self._stream_writer is not None else 0
-        _, ids = self.stitch_planes(timepoint, region, only_planes, progress_callback, stream_to=make_writer, row_band=row_band)
+        _, ids = self.stitch_planes(timepoint, region, only_planes, progress_callback, stream_to=make_writer, row_band=row_band,
+                                    project_to=project_to)
         # bytes of this region's chunks (under run() the writer is drained at the end: the count then lags by what is in flight)
         self.last_bytes_written = sum(w.bytes_written for w in set(made)) - (before if self._stream_writer in made else 0)
         return output_path
@@ -1012,19 +1109,52 @@ class Stitcher:
         bands = sharding.row_bands(height, self.num_pyramid_levels, (self.chunks or (1, 1, 1, 512, 512))[3])
         units = sharding.plane_band_units(n_planes, bands, rank, world)
         print(f"\nProcessing timepoint {timepoint}, region {region}: (plane, band) units {units} (rank {rank}/{world})")
+        stack = self.z_projection != 'max-only'
         if rank == 0:
-            self.create_region_store(timepoint, region)
+            if stack:
+                self.create_region_store(timepoint, region)
+            if self.z_projection != 'none':
+                self.create_mip_store(timepoint, region)
         sharding.barrier()
         self.starting_stitching.emit()
         self.starting_saving.emit(False)
         output_path = self._zarr_path(timepoint, region)
         by_band = {}
-        for p, b in units:
+        for p, b in units if stack else ():
             by_band.setdefault(b, []).append(p)
         for b, planes in by_band.items():
             output_path = self.stream_region_to_zarr(timepoint, region, planes, progress_callback=self.update_progress.emit,
                                                      create=False, row_band=None if b < 0 else bands[b])
+        if self.z_projection != 'none':
+            output_path = self._project_region_units(timepoint, region, bands, rank, world)
+            if stack:
+                output_path = self._zarr_path(timepoint, region)
         sharding.barrier()
+        return output_path
+
+    def _project_region_units(self, timepoint, region, bands, rank, world) -> str:
+        """This rank's share of a shared region's projection: (channel, row band) units dealt like the stack's (plane, band)
+        units (sharding.plane_band_units over the channels), each projected from the tiles of its channel that reach its band
+        and written as its own chunks of the store rank 0 created.  With 'max' the files of these channels are read a second
+        time (the stack pass dealt planes, not channels, so its staged tiles do not line up with these units)."""
+        cunits = sharding.plane_band_units(self.num_c, bands, rank, world)
+        print(f"Projection of timepoint {timepoint}, region {region}: (channel, band) units {cunits} (rank {rank}/{world})")
+        output_path = self._mip_path(timepoint, region)
+        width, height = self.calculate_output_dimensions(timepoint, region)
+        full = omezarr.level_shapes((1, self.num_c, 1, height, width), self.num_pyramid_levels)
+        chunks = self.chunks or (1, 1, 1, 512, 512)
+        for c, b in cunits:
+            y0, y1 = (0, height) if b < 0 else bands[b]
+            proj = self._new_projection(timepoint, region, (y0, y1), n_channels=1)
+            self.stitch_planes(timepoint, region, [c * self.num_z + z for z in range(self.num_z)],
+                               self.update_progress.emit, row_band=None if b < 0 else (y0, y1), stack=False,
+                               project_to={c: proj[0]})
+            shapes = omezarr.level_shapes((1, self.num_c, 1, y1 - y0, width), len(full))
+            with omezarr.PlaneStreamWriter(output_path, shapes, self.dtype, chunks=chunks, batch=1,
+                                           compression=self.zarr_compression, device=self.device, row_offset=y0,
+                                           level_heights=None if b < 0 else [s[3] for s in full]) as writer:
+                writer.acquire(1).copy_(proj)
+                writer.submit([(0, c, 0)])
         return output_path
 
     def save_region_aics(self, timepoint, region, stitched_region):
@@ -1159,7 +1289,7 @@ class Stitcher:
             print("Note: merging timepoints / HCS regions is an output-format step outside the hot-path scope; "
                   "per-(timepoint, region) stores were written.")
         final_path = os.path.join(self.output_folder, f"{self.timepoints[-1]}_stitched",
-                                  f"{self.regions[-1]}_stitched{self.output_format}")
+                                  f"{self.regions[-1]}_stitched{'_mip' if self.z_projection == 'max-only' else ''}{self.output_format}")
         self.finished_saving.emit(final_path, self.dtype)
         print(f"Total processing time: {time.time() - stime}")
 
@@ -1200,14 +1330,25 @@ class Stitcher:
                 my_rows[i] = sharding.shifts_to_row(self._shifts())
                 self.write_tile_positions(timepoint, region)
             self.starting_stitching.emit()
-            if self.output_format.endswith('.zarr'):
+            # --z-projection: the projection comes from the tiles the stack pass stages (one read of every file)
+            proj = self._new_projection(timepoint, region) if self.z_projection != 'none' else None
+            project_to = None if proj is None else {c: proj[c] for c in range(self.num_c)}
+            if self.z_projection == 'max-only':
+                self.starting_saving.emit(False)
+                self.stitch_planes(timepoint, region, None, self.update_progress.emit, stack=False, project_to=project_to)
+            elif self.output_format.endswith('.zarr'):
                 # fused planes stream to the store batch by batch; saving overlaps stitching
                 self.starting_saving.emit(False)
-                output_path = self.stream_region_to_zarr(timepoint, region, progress_callback=self.update_progress.emit)
+                output_path = self.stream_region_to_zarr(timepoint, region, progress_callback=self.update_progress.emit,
+                                                         project_to=project_to)
             else:
-                stitched_region = self.stitch_region(timepoint, region, progress_callback=self.update_progress.emit)
+                stitched_region = self._stitch_region(timepoint, region, self.update_progress.emit, project_to=project_to)
                 self.starting_saving.emit(False)
                 output_path = self.save_region_aics(timepoint, region, stitched_region)
+            if proj is not None:      # (ordered after the projection kernels: stitch_planes made this stream wait for them)
+                mip_path = self.save_region_mip(timepoint, region, proj.unsqueeze(0).unsqueeze(2))
+                if self.z_projection == 'max-only':
+                    output_path = mip_path
             print(f"Completed region {region} (saved to {output_path}): {time.time() - rtime}")
         if self.use_registration:
             self._write_shift_table(n_units, my_rows, rank, world, coll, shared)

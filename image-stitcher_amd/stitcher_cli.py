@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus seven switches for what this build adds (``--fusion-mode``, ``--normalization``,
+plus eight switches for what this build adds (``--fusion-mode``, ``--normalization``,
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
-``--global-registration``).
+``--global-registration``, ``--z-projection``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -48,6 +48,10 @@ FLAGS = (
                                       help="with -ff: basicpy's BaSiC fit when that package is installed (auto / basicpy), this "
                                            "build's device restatement of the published BaSiC fit (basic; what auto falls back "
                                            "to), or a plain smoothed mean (mean: not BaSiC)")),
+    (('--z-projection',), dict(choices=['none', 'max', 'max-only'], default='none',
+                               help="maximum-intensity projection over z per channel, computed on the device from the tiles: max = "
+                                    "the stack plus <region>_stitched_mip<format>; max-only = the projection alone (overwrite fusion "
+                                    "only)")),
 )
 
 
@@ -101,7 +105,8 @@ def main(argv=None):
                             per_region_registration=args.per_region_registration,
                             flatfield_estimator=args.flatfield_estimator,
                             all_pairs_registration=args.all_pairs_registration,
-                            global_registration=args.global_registration)
+                            global_registration=args.global_registration,
+                            z_projection=args.z_projection)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

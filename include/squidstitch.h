@@ -154,6 +154,25 @@ int64_t sq_fuse_scratch_bytes(int32_t n_planes);
  * the reference starts from da.zeros, stitcher.py:362); no atomics; deterministic. */
 int sq_fuse_planes(const sq_fuse_args *args, void *stream);
 
+/* Maximum-intensity projection over z (extension: the reference has no projection).  ONE output plane from the n_planes = Z
+ * planes the tile fields address: per voxel the unsigned maximum over the Z planes of exactly the value sq_fuse_planes would
+ * store in each of them (same flatfield divide, same clip and truncating cast), so out == max over z of the fused stack, bit
+ * for bit.  Uncovered voxels are 0.  The tiles are read once and only the projection is written: Z x elem bytes read per
+ * covered voxel, elem bytes written per output voxel.  `args` keeps its meaning with these differences:
+ *   - canvas_dev is the single output plane (canvas_h x canvas_w, canvas_pitch elements between rows, canvas_dtype ==
+ *     tile_dtype); canvas_plane_stride is ignored;
+ *   - flat_ptrs_dev has Z entries.  When all of them name one gain image (the z planes of a channel) its gains and their
+ *     reciprocals are taken once per pixel for all Z planes; entries that differ, or NULL entries (identity), are exact too;
+ *   - mode must be SQ_FUSE_OVERWRITE (and the plan an overwrite plan): anything else is SQ_ERR_INVALID;
+ *   - scratch_dev (sq_fuse_scratch_bytes(n_planes) bytes, 128-byte aligned, optional) holds the work-queue counters.
+ * flags (OR-ed with args->flags): the sq_fuse_flags work-distribution bits (FORCE_QUEUES / FORCE_STATIC; the other bits are
+ * accepted and change nothing: there are no plane groups and no seam owners here) plus SQ_PROJECT_ACCUMULATE: the output
+ * becomes max(output, projection) on the plan's covered voxels and its uncovered voxels are left untouched -- for the z planes
+ * of a channel that come in several calls (ingest batches) or under different plans (ragged acquisitions).
+ * Every output voxel is written by one workgroup; no atomics; deterministic.  n_planes >= 1. */
+#define SQ_PROJECT_ACCUMULATE 32
+int sq_fuse_project_max(const sq_fuse_args *args, int32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Canvas memory.  Replaces the allocation behind Stitcher.init_output (stitcher.py:356-362: the reference's canvas is a
  * lazy dask array; here it is device memory the fusion kernel writes once).  WHERE that memory lies decides how fast the
