@@ -2632,8 +2632,10 @@ __global__ __launch_bounds__(256) void project_max_kernel(const FuseParams P, co
         [&](int, const Item &it, const ProjAux &) { body(it); });
 }
 
-template <typename K>
-int launch_project(K kernel, const FuseParams &P, int64_t n_items, hipStream_t stream, int grid_override) {
+
+template <typename K, typename... X>
+int launch_project(const char *who, K kernel, const FuseParams &P, int64_t n_items, hipStream_t stream, int grid_override,
+                   X... extra) {
     if (n_items == 0) return SQ_OK;
     static thread_local std::map<const void *, int> resident;
     const void *key = reinterpret_cast<const void *>(kernel);
@@ -2649,49 +2651,47 @@ int launch_project(K kernel, const FuseParams &P, int64_t n_items, hipStream_t s
     const int64_t blocks = std::min<int64_t>(n_items, grid_override > 0 ? grid_override : it->second);
     FuseParams Q = P;
     Q.chunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(QUEUE_CHUNK, n_items / (blocks * 16)));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, Q, n_items, n_items);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, Q, n_items, n_items, extra...);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_fuse_project_max: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(SQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
     return SQ_OK;
 }
-}  // namespace
 
-extern "C" int sq_fuse_project_max(const sq_fuse_args *a, int32_t flags, void *stream_) {
-    if (!a || !a->plan || !a->table_dev || !a->canvas_dev)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: NULL plan/table/output");
+// The checks and the FuseParams shared by the projections over z (one output plane from the Z planes of one overwrite plan):
+// SQ_OK with P (and P.queue when the work queues are taken) set up and *fl the effective flags, or the failure.
+int project_setup(const char *who, const sq_fuse_args *a, int32_t flags, hipStream_t stream, FuseParams &P, int32_t *fl_out) {
+    if (!a || !a->plan || !a->table_dev || !a->canvas_dev) return fail(SQ_ERR_INVALID, "%s: NULL plan/table/output", who);
     if (a->mode != SQ_FUSE_OVERWRITE)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: mode %d, only SQ_FUSE_OVERWRITE plans can be projected", a->mode);
+        return fail(SQ_ERR_INVALID, "%s: mode %d, only SQ_FUSE_OVERWRITE plans can be projected", who, a->mode);
     const TableHeader &h = a->plan->header();
-    if (h.mode != SQ_FUSE_OVERWRITE) return fail(SQ_ERR_INVALID, "sq_fuse_project_max: the plan was built for mode %d", h.mode);
+    if (h.mode != SQ_FUSE_OVERWRITE) return fail(SQ_ERR_INVALID, "%s: the plan was built for mode %d", who, h.mode);
     if (a->plan->spans_only && !a->plan->expanded)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: the plan of sq_fuse_plan_create_spans has not been through sq_fuse_plan_expand");
+        return fail(SQ_ERR_INVALID, "%s: the plan of sq_fuse_plan_create_spans has not been through sq_fuse_plan_expand", who);
     if (a->table_bytes != a->plan->device_bytes())
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: table_bytes %lld != plan %lld", (long long)a->table_bytes,
+        return fail(SQ_ERR_INVALID, "%s: table_bytes %lld != plan %lld", who, (long long)a->table_bytes,
                     (long long)a->plan->device_bytes());
     if (a->n_tiles != h.n_tiles || a->tile_h != h.tile_h || a->tile_w != h.tile_w || a->canvas_h != h.canvas_h ||
         a->canvas_w != h.canvas_w)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: geometry differs from the plan");
+        return fail(SQ_ERR_INVALID, "%s: geometry differs from the plan", who);
     if (!a->tile_ptrs_dev && !a->tile_base_dev && h.n_refs > 0)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: no tile table and no tile base");
-    if (a->tile_pitch < a->tile_w || a->canvas_pitch < a->canvas_w)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: pitch smaller than width");
-    if (a->n_planes < 1) return fail(SQ_ERR_INVALID, "sq_fuse_project_max: n_planes %d (at least one plane)", a->n_planes);
+        return fail(SQ_ERR_INVALID, "%s: no tile table and no tile base", who);
+    if (a->tile_pitch < a->tile_w || a->canvas_pitch < a->canvas_w) return fail(SQ_ERR_INVALID, "%s: pitch smaller than width", who);
+    if (a->n_planes < 1) return fail(SQ_ERR_INVALID, "%s: n_planes %d (at least one plane)", who, a->n_planes);
     const int32_t fl = flags | a->flags;
     if ((fl & ~(SQ_FUSE_FORCE_QUEUES | SQ_FUSE_FORCE_STATIC | SQ_FUSE_NO_PLANE_GROUPS | SQ_FUSE_NO_SEAM_OWNERS | SQ_FUSE_CONSECUTIVE_GROUPS |
                 SQ_PROJECT_ACCUMULATE)) ||
         a->grid_blocks < 0 || ((fl & SQ_FUSE_FORCE_QUEUES) && (fl & SQ_FUSE_FORCE_STATIC)))
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: flags %d / grid_blocks %d", fl, a->grid_blocks);
+        return fail(SQ_ERR_INVALID, "%s: flags %d / grid_blocks %d", who, fl, a->grid_blocks);
     if (a->tile_dtype != SQ_U8 && a->tile_dtype != SQ_U16)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_fuse_project_max: tile dtype %d (uint8/uint16 only)", a->tile_dtype);
+        return fail(SQ_ERR_UNSUPPORTED, "%s: tile dtype %d (uint8/uint16 only)", who, a->tile_dtype);
     if (a->canvas_dtype != a->tile_dtype)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: the output keeps the tile dtype (output %d, tile %d)", a->canvas_dtype,
-                    a->tile_dtype);
+        return fail(SQ_ERR_INVALID, "%s: the output keeps the tile dtype (output %d, tile %d)", who, a->canvas_dtype, a->tile_dtype);
     if (a->flat_ptrs_dev && a->flat_dtype != SQ_F32 && a->flat_dtype != SQ_F64)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_fuse_project_max: flatfield dtype %d (float32/float64 only)", a->flat_dtype);
+        return fail(SQ_ERR_UNSUPPORTED, "%s: flatfield dtype %d (float32/float64 only)", who, a->flat_dtype);
     if (reinterpret_cast<uintptr_t>(a->canvas_dev) % (size_t)a->canvas_dtype)
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: output pointer not aligned to its element size");
+        return fail(SQ_ERR_INVALID, "%s: output pointer not aligned to its element size", who);
 
-    FuseParams P{};
+    P = FuseParams{};
     const char *base = static_cast<const char *>(a->table_dev);
     P.spans = reinterpret_cast<const Span *>(base + h.off_spans);
     P.refs = reinterpret_cast<const Ref *>(base + h.off_refs);
@@ -2711,34 +2711,43 @@ extern "C" int sq_fuse_project_max(const sq_fuse_args *a, int32_t flags, void *s
     P.canvas_pitch = a->canvas_pitch;
     P.lane_items = (int32_t)h.lane_items;
     P.n_planes = a->n_planes;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (a->scratch_dev) {
         const ScratchLayout SL = scratch_layout(a->n_planes);
         if (a->scratch_bytes < SL.total)
-            return fail(SQ_ERR_WORKSPACE, "sq_fuse_project_max: scratch %lld < %lld bytes", (long long)a->scratch_bytes,
-                        (long long)SL.total);
-        if (reinterpret_cast<uintptr_t>(a->scratch_dev) % 128)
-            return fail(SQ_ERR_INVALID, "sq_fuse_project_max: scratch not 128-byte aligned");
+            return fail(SQ_ERR_WORKSPACE, "%s: scratch %lld < %lld bytes", who, (long long)a->scratch_bytes, (long long)SL.total);
+        if (reinterpret_cast<uintptr_t>(a->scratch_dev) % 128) return fail(SQ_ERR_INVALID, "%s: scratch not 128-byte aligned", who);
         // the device queues: the same size rule as sq_fuse_planes (an item carries all Z planes here)
         const int64_t n_work = (int64_t)a->n_planes * h.n_items;
         if ((n_work >= 100000 || (fl & SQ_FUSE_FORCE_QUEUES)) && h.n_items < (int64_t(1) << 31) && !(fl & SQ_FUSE_FORCE_STATIC)) {
             if (hipMemsetAsync(static_cast<char *>(a->scratch_dev) + SL.queue, 0, 9 * QUEUE_STRIDE * 4, stream) != hipSuccess)
-                return fail(SQ_ERR_HIP, "sq_fuse_project_max: cannot clear the queue counters");
+                return fail(SQ_ERR_HIP, "%s: cannot clear the queue counters", who);
             P.queue = reinterpret_cast<uint32_t *>(static_cast<char *>(a->scratch_dev) + SL.queue);
         }
     } else if (fl & SQ_FUSE_FORCE_QUEUES) {
-        return fail(SQ_ERR_INVALID, "sq_fuse_project_max: SQ_FUSE_FORCE_QUEUES needs scratch_dev");
+        return fail(SQ_ERR_INVALID, "%s: SQ_FUSE_FORCE_QUEUES needs scratch_dev", who);
     }
+    *fl_out = fl;
+    return SQ_OK;
+}
+}  // namespace
+
+extern "C" int sq_fuse_project_max(const sq_fuse_args *a, int32_t flags, void *stream_) {
+    static const char *who = "sq_fuse_project_max";
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    FuseParams P;
+    int32_t fl = 0;
+    if (const int rc = project_setup(who, a, flags, stream, P, &fl)) return rc;
+    const int64_t n_items = a->plan->header().n_items;
     const bool acc = (fl & SQ_PROJECT_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
     const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
 #define SQ_PROJECT(T, G)                                                                                                     \
     do {                                                                                                                     \
         if (acc) {                                                                                                           \
-            if (P.queue) return launch_project(project_max_kernel<T, G, true, true>, P, h.n_items, stream, a->grid_blocks);   \
-            return launch_project(project_max_kernel<T, G, true, false>, P, h.n_items, stream, a->grid_blocks);              \
+            if (P.queue) return launch_project(who, project_max_kernel<T, G, true, true>, P, n_items, stream, a->grid_blocks); \
+            return launch_project(who, project_max_kernel<T, G, true, false>, P, n_items, stream, a->grid_blocks);            \
         }                                                                                                                    \
-        if (P.queue) return launch_project(project_max_kernel<T, G, false, true>, P, h.n_items, stream, a->grid_blocks);      \
-        return launch_project(project_max_kernel<T, G, false, false>, P, h.n_items, stream, a->grid_blocks);                 \
+        if (P.queue) return launch_project(who, project_max_kernel<T, G, false, true>, P, n_items, stream, a->grid_blocks);    \
+        return launch_project(who, project_max_kernel<T, G, false, false>, P, n_items, stream, a->grid_blocks);               \
     } while (0)
     if (u16) {
         if (flat == 0) SQ_PROJECT(uint16_t, NoGain);
@@ -2749,4 +2758,303 @@ extern "C" int sq_fuse_project_max(const sq_fuse_args *a, int32_t flags, void *s
     if (flat == 1) SQ_PROJECT(uint8_t, float);
     SQ_PROJECT(uint8_t, double);
 #undef SQ_PROJECT
+}
+
+// ---------------------------------------------------------------------------------------------
+// best-focus (extended depth of field) projection over z (sq_fuse_project_focus; an extension: the reference has none)
+// ---------------------------------------------------------------------------------------------
+// Definition in include/squidstitch.h (and DESIGN.md 5.2b).  Two stages:
+//  (1) focus_tiles_kernel, tile space: one workgroup per (tile, FOC_BW x FOC_BH block).  Per plane z of the call: the block
+//      plus a halo of R + 1 pixels (coordinates clamped to the tile) into LDS; ML over the block plus a halo of R, each halo
+//      position taking the ML of its clamped position; the separable box sum (columns by a running sum down 8 rows per lane,
+//      rows directly); the running best (score, z level, plane index) of the thread's 8 outputs in registers.  After the last
+//      plane the winners go to the caller's scratch: uint32 score + uint8 plane index per tile pixel.
+//  (2) focus_canvas_kernel, canvas space: the overwrite plan's items like project_max_kernel (static walk or the per-XCD
+//      queues, no seam owners); per voxel the owner pixel's winner, its raw value from the winning plane through that plane's
+//      gains (flat_generic: what sq_fuse_planes stores, bit for bit) and its key; ACC merges by key maximum.
+// Algorithmic traffic: Z x sizeof(T) B read per tile pixel + 5 B written / read per tile pixel of scratch + (sizeof(T) + 8) B
+// written per canvas voxel (+ sizeof(T) + gain bytes read per covered voxel).
+namespace {
+constexpr int FOC_BW = 64, FOC_BH = 32;   // output block of a workgroup: 64 lanes x (4 waves x 8 rows)
+static_assert(FOC_BH == 4 * 8 && FOC_BW == 64, "the F stage maps one column per lane and 8 rows per wave");
+constexpr int FOC_LROWS = (FOC_BH + 2 * SQ_FOCUS_MAX_RADIUS + 2 + 3) / 4;    // raw-block rows a wave loads at most (16)
+constexpr int FOC_LCOLS = (FOC_BW + 2 * SQ_FOCUS_MAX_RADIUS + 2 + 63) / 64;  // 64-lane column runs of a raw-block row (2)
+constexpr int FOC_XU = 4;   // canvas stage: pixels a lane has in flight at once
+
+struct FocusParams {
+    const uint32_t *zlev;   // z level of each of the call's planes
+    uint32_t *score;        // [n_tiles][tile_h][tile_w] best F of every tile pixel
+    uint8_t *plane;         // [n_tiles][tile_h][tile_w] its plane index within the call
+    uint64_t *key;          // the key plane, key_pitch elements between rows
+    int32_t key_pitch;
+    int32_t radius;
+    int32_t bx, by;         // blocks across / down a tile
+};
+
+struct FocusLayout {
+    int64_t score, plane, total;
+};
+FocusLayout focus_layout(int64_t n_tiles, int64_t tile_h, int64_t tile_w) {
+    FocusLayout L;
+    const int64_t px = n_tiles * tile_h * tile_w;
+    L.score = 0;
+    L.plane = (px * 4 + 127) & ~int64_t(127);
+    L.total = L.plane + ((px + 127) & ~int64_t(127));
+    return L;
+}
+// LDS words of one workgroup for radius R: the raw block (later the column sums, which are smaller) + the ML block
+int64_t focus_lds_words(int R) {
+    const int lw = FOC_BW + 2 * R + 2, lh = FOC_BH + 2 * R + 2, mw = FOC_BW + 2 * R, mh = FOC_BH + 2 * R;
+    return (int64_t)lw * lh + (int64_t)mw * mh;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void focus_tiles_kernel(const FuseParams P, const FocusParams F) {
+    extern __shared__ uint32_t s_focus[];
+    const int R = F.radius;
+    const int LW = FOC_BW + 2 * R + 2, LH = FOC_BH + 2 * R + 2, MW = FOC_BW + 2 * R, MH = FOC_BH + 2 * R;
+    uint32_t *sI = s_focus;             // [LH][LW] raw pixels of the block + halo R + 1; then [FOC_BH][MW] column sums
+    uint32_t *sM = s_focus + LW * LH;   // [MH][MW] ML of the block + halo R
+    const int per_tile = F.bx * F.by;
+    const int tile = (int)(blockIdx.x / (unsigned)per_tile);
+    const int blk = (int)blockIdx.x - tile * per_tile;
+    const int by = blk / F.bx;
+    const int x0 = (blk - by * F.bx) * FOC_BW, y0 = by * FOC_BH;
+    const int H = P.tile_h, W = P.tile_w;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int oy = wave * 8;   // this thread's outputs: block column `lane`, block rows oy .. oy + 7
+    uint32_t best[8] = {}, bestz[8] = {}, bestp[8] = {};
+    // the raw block of a plane into registers (clamped reads), issued one plane ahead: the loads of plane z + 1 are in flight
+    // while plane z is reduced.  Lanes past the block's width load a valid pixel that is not kept.
+    uint32_t px[FOC_LROWS][FOC_LCOLS] = {};
+    auto load_raw = [&](int z) {
+        const T *src = sgpr(tile_ptr<T>(P, z, tile));
+#pragma unroll
+        for (int k = 0; k < FOC_LROWS; ++k) {
+            const int i = wave + 4 * k;
+            if (i < LH) {
+                const T *srow = src + (int64_t)min(max(y0 - R - 1 + i, 0), H - 1) * P.tile_pitch;
+#pragma unroll
+                for (int m = 0; m < FOC_LCOLS; ++m) px[k][m] = ldg_s<T>(srow + min(max(x0 - R - 1 + lane + 64 * m, 0), W - 1));
+            }
+        }
+    };
+    load_raw(0);
+    // the ML walk: this thread's first position and the step of 256 positions, as (row, column) of the MH x MW region
+    const int ml_i0 = (int)threadIdx.x / MW, ml_j0 = (int)threadIdx.x - ml_i0 * MW;
+    const int ml_di = 256 / MW, ml_dj = 256 - ml_di * MW;
+    const bool inner = y0 - R >= 0 && y0 + FOC_BH + R <= H && x0 - R >= 0 && x0 + FOC_BW + R <= W;
+    for (int z = 0; z < P.n_planes; ++z) {
+        const uint32_t zl = F.zlev[z];
+        // raw pixels at logical (y0 - R - 1 + i, x0 - R - 1 + j), read at the clamped position
+#pragma unroll
+        for (int k = 0; k < FOC_LROWS; ++k) {
+            const int i = wave + 4 * k;
+#pragma unroll
+            for (int m = 0; m < FOC_LCOLS; ++m)
+                if (i < LH && lane + 64 * m < LW) sI[i * LW + lane + 64 * m] = px[k][m];
+        }
+        __syncthreads();
+        if (z + 1 < P.n_planes) load_raw(z + 1);
+        // ML at logical (y0 - R + i, x0 - R + j) = ML at the clamped position, which lies inside the raw block with its
+        // neighbours (whose values are the clamped reads).  One flat walk over the MH x MW positions (every lane busy: the rows
+        // are wider than 64); a block whose ML region lies inside the tile needs no clamp
+        for (int e = threadIdx.x, i = ml_i0, j = ml_j0; e < MH * MW; e += 256) {
+            const int cy = inner ? i + 1 : min(max(y0 - R + i, 0), H - 1) - (y0 - R - 1);
+            const int cx = inner ? j + 1 : min(max(x0 - R + j, 0), W - 1) - (x0 - R - 1);
+            const int c = cy * LW + cx;
+            const int c2 = 2 * (int)sI[c];
+            const int h = c2 - (int)sI[c - 1] - (int)sI[c + 1];
+            const int v = c2 - (int)sI[c - LW] - (int)sI[c + LW];
+            sM[e] = (uint32_t)(abs(h) + abs(v));
+            i += ml_di;
+            j += ml_dj;
+            if (j >= MW) {
+                j -= MW;
+                ++i;
+            }
+        }
+        __syncthreads();
+        // column sums over 2R + 1 ML rows for the block's rows: a running sum down the wave's 8 rows
+        for (int j = lane; j < MW; j += 64) {
+            uint32_t s = 0;
+            for (int d = 0; d <= 2 * R; ++d) s += sM[(oy + d) * MW + j];
+            sI[oy * MW + j] = s;
+#pragma unroll
+            for (int k = 1; k < 8; ++k) {
+                s += sM[(oy + k + 2 * R) * MW + j] - sM[(oy + k - 1) * MW + j];
+                sI[(oy + k) * MW + j] = s;
+            }
+        }
+        __syncthreads();
+        // row sums over 2R + 1 column sums -> F; keep the larger key (higher score, on a tie the lower z level)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            uint32_t f = 0;
+            for (int d = 0; d <= 2 * R; ++d) f += sI[(oy + k) * MW + lane + d];
+            if (z == 0 || f > best[k] || (f == best[k] && zl < bestz[k])) {
+                best[k] = f;
+                bestz[k] = zl;
+                bestp[k] = (uint32_t)z;
+            }
+        }
+        __syncthreads();   // the next plane's raw pixels overwrite the column sums
+    }
+    const int x = x0 + lane;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int y = y0 + oy + k;
+        if (x < W && y < H) {
+            const int64_t at = ((int64_t)tile * H + y) * W + x;
+            stg_s<uint32_t>(F.score + at, best[k]);
+            stg_s<uint8_t>(F.plane + at, (uint8_t)bestp[k]);
+        }
+    }
+}
+
+template <typename T, typename G, bool ACC>
+__device__ __forceinline__ void focus_item(const FuseParams &P, const FocusParams &F, const Item &it, const int wave, const int lane) {
+    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
+    typedef typename std::conditional<GAINS, G, float>::type GT;
+    const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
+    T *canvas = static_cast<T *>(P.canvas);
+    if (!it.nref) {   // uncovered canvas: 0 and key 0 (accumulating: left alone)
+        if (!ACC)
+            for (int r = wave; r < rows; r += 4) {
+                T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
+                uint64_t *krow = F.key + (int64_t)(it.dst_y + r) * F.key_pitch + it.dst_x;
+                for (int x = lane; x < n; x += 64) {
+                    stg_s<T>(drow + x, (T)0);
+                    stg_s<uint64_t>(krow + x, (uint64_t)0);
+                }
+            }
+        return;
+    }
+    const int64_t tbase = (int64_t)it.a * P.tile_h * P.tile_w;
+    for (int r = wave; r < rows; r += 4) {
+        T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
+        uint64_t *krow = F.key + (int64_t)(it.dst_y + r) * F.key_pitch + it.dst_x;
+        const int64_t soff = (int64_t)(it.b + r) * P.tile_pitch + it.c;   // elements into the winning plane's tile
+        const int64_t foff = (int64_t)(it.b + r) * P.tile_w + it.c;       // elements into a gain image / the winners
+        // FOC_XU pixels per lane at a time, loads of all of them first (clamped to the row: every address is valid), then the
+        // dependent loads, then the stores: the winners' loads do not wait behind the previous pixel's stores
+        for (int x0 = lane; x0 < n; x0 += 64 * FOC_XU) {
+            uint32_t sc[FOC_XU], zi[FOC_XU];
+#pragma unroll
+            for (int u = 0; u < FOC_XU; ++u) {
+                const int xc = min(x0 + 64 * u, n - 1);
+                sc[u] = ldg_s<uint32_t>(F.score + tbase + foff + xc);
+                zi[u] = ldg_s<uint8_t>(F.plane + tbase + foff + xc);
+            }
+            uint64_t key[FOC_XU];
+            T t[FOC_XU];
+            GT g[FOC_XU];
+            bool has_g[FOC_XU], put[FOC_XU];
+#pragma unroll
+            for (int u = 0; u < FOC_XU; ++u) {
+                const int xc = min(x0 + 64 * u, n - 1);
+                key[u] = ((uint64_t)sc[u] << 32) | (uint64_t)(0xFFFFFFFFu - ldg_s<uint32_t>(F.zlev + zi[u]));
+                put[u] = x0 + 64 * u < n;
+                if (ACC) put[u] = put[u] && key[u] > ldg_s<uint64_t>(krow + xc);
+                t[u] = ldg_s<T>(tile_ptr<T>(P, (int)zi[u], it.a) + soff + xc);
+                has_g[u] = false;
+                g[u] = (GT)1;
+                if constexpr (GAINS) {
+                    const GT *fz = static_cast<const GT *>(P.flat_ptrs[zi[u]]);
+                    has_g[u] = fz != nullptr;
+                    if (has_g[u]) g[u] = ldg_s<GT>(fz + foff + xc);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < FOC_XU; ++u) {
+                if (!put[u]) continue;
+                T v = t[u];
+                if constexpr (GAINS) {
+                    if (has_g[u]) v = flat_generic<T, GT>(t[u], g[u]);
+                }
+                stg_s<T>(drow + x0 + 64 * u, v);
+                stg_s<uint64_t>(krow + x0 + 64 * u, key[u]);
+            }
+        }
+    }
+}
+
+template <typename T, typename G, bool ACC, bool DYN>
+__global__ __launch_bounds__(256) void focus_canvas_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work,
+                                                           const FocusParams F) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (!DYN) {
+        for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x) focus_item<T, G, ACC>(P, F, sgpr(P.items[w]), wave, lane);
+        return;
+    }
+    for_each_queued_item<ProjAux>(
+        P, n_items, 1u, [&](int, const Item &, int64_t) -> ProjAux { return ProjAux{0}; },
+        [&](int, const Item &it, const ProjAux &) { focus_item<T, G, ACC>(P, F, it, wave, lane); });
+}
+}  // namespace
+
+extern "C" int64_t sq_focus_scratch_bytes(int32_t n_tiles, int32_t tile_h, int32_t tile_w) {
+    if (n_tiles < 0 || tile_h < 0 || tile_w < 0)
+        return fail(SQ_ERR_INVALID, "sq_focus_scratch_bytes: n_tiles %d, tile %d x %d", n_tiles, tile_h, tile_w);
+    return focus_layout(n_tiles, tile_h, tile_w).total;
+}
+
+extern "C" int sq_fuse_project_focus(const sq_fuse_args *a, const sq_focus_args *f, int32_t flags, void *stream_) {
+    static const char *who = "sq_fuse_project_focus";
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    FuseParams P;
+    int32_t fl = 0;
+    if (const int rc = project_setup(who, a, flags, stream, P, &fl)) return rc;
+    if (!f || !f->z_levels_dev || !f->key_dev) return fail(SQ_ERR_INVALID, "%s: NULL focus arguments / z levels / key plane", who);
+    if (f->radius < 0 || f->radius > SQ_FOCUS_MAX_RADIUS)
+        return fail(SQ_ERR_INVALID, "%s: focus radius %d outside 0..%d", who, f->radius, SQ_FOCUS_MAX_RADIUS);
+    if (a->n_planes > SQ_FOCUS_MAX_PLANES)
+        return fail(SQ_ERR_INVALID, "%s: %d planes, the scratch's uint8 plane index holds %d", who, a->n_planes, SQ_FOCUS_MAX_PLANES);
+    if (f->key_pitch < a->canvas_w || reinterpret_cast<uintptr_t>(f->key_dev) % 8)
+        return fail(SQ_ERR_INVALID, "%s: key plane pitch %d < width %d, or not 8-byte aligned", who, f->key_pitch, a->canvas_w);
+    const FocusLayout FL = focus_layout(a->n_tiles, a->tile_h, a->tile_w);
+    if (FL.total > 0 && (!f->scratch_dev || reinterpret_cast<uintptr_t>(f->scratch_dev) % 128))
+        return fail(SQ_ERR_INVALID, "%s: focus scratch missing or not 128-byte aligned", who);
+    if (f->scratch_bytes < FL.total)
+        return fail(SQ_ERR_WORKSPACE, "%s: focus scratch %lld < %lld bytes", who, (long long)f->scratch_bytes, (long long)FL.total);
+    FocusParams F{};
+    F.zlev = f->z_levels_dev;
+    F.score = reinterpret_cast<uint32_t *>(static_cast<char *>(f->scratch_dev) + FL.score);
+    F.plane = reinterpret_cast<uint8_t *>(static_cast<char *>(f->scratch_dev) + FL.plane);
+    F.key = static_cast<uint64_t *>(f->key_dev);
+    F.key_pitch = f->key_pitch;
+    F.radius = f->radius;
+    F.bx = (a->tile_w + FOC_BW - 1) / FOC_BW;
+    F.by = (a->tile_h + FOC_BH - 1) / FOC_BH;
+    const int64_t tile_blocks = (int64_t)a->n_tiles * F.bx * F.by;
+    if (tile_blocks >= (int64_t(1) << 31)) return fail(SQ_ERR_UNSUPPORTED, "%s: %lld tile blocks", who, (long long)tile_blocks);
+    const bool acc = (fl & SQ_FOCUS_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
+    const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
+    if (tile_blocks > 0) {
+        const size_t lds = (size_t)focus_lds_words(F.radius) * 4;
+        if (u16) hipLaunchKernelGGL(focus_tiles_kernel<uint16_t>, dim3((unsigned)tile_blocks), dim3(256), lds, stream, P, F);
+        else hipLaunchKernelGGL(focus_tiles_kernel<uint8_t>, dim3((unsigned)tile_blocks), dim3(256), lds, stream, P, F);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(SQ_ERR_HIP, "%s: tile stage launch failed: %s", who, hipGetErrorString(e));
+    }
+    const int64_t n_items = a->plan->header().n_items;
+#define SQ_FOCUS(T, G)                                                                                                             \
+    do {                                                                                                                           \
+        if (acc) {                                                                                                                 \
+            if (P.queue) return launch_project(who, focus_canvas_kernel<T, G, true, true>, P, n_items, stream, a->grid_blocks, F);  \
+            return launch_project(who, focus_canvas_kernel<T, G, true, false>, P, n_items, stream, a->grid_blocks, F);             \
+        }                                                                                                                          \
+        if (P.queue) return launch_project(who, focus_canvas_kernel<T, G, false, true>, P, n_items, stream, a->grid_blocks, F);     \
+        return launch_project(who, focus_canvas_kernel<T, G, false, false>, P, n_items, stream, a->grid_blocks, F);                \
+    } while (0)
+    if (u16) {
+        if (flat == 0) SQ_FOCUS(uint16_t, NoGain);
+        if (flat == 1) SQ_FOCUS(uint16_t, float);
+        SQ_FOCUS(uint16_t, double);
+    }
+    if (flat == 0) SQ_FOCUS(uint8_t, NoGain);
+    if (flat == 1) SQ_FOCUS(uint8_t, float);
+    SQ_FOCUS(uint8_t, double);
+#undef SQ_FOCUS
 }

@@ -22,6 +22,9 @@ SQ_FUSE_OVERWRITE, SQ_FUSE_FEATHER = 0, 1
 SQ_NORM_NONE, SQ_NORM_PHASE = 0, 1
 SQ_FUSE_FORCE_QUEUES, SQ_FUSE_FORCE_STATIC, SQ_FUSE_NO_PLANE_GROUPS, SQ_FUSE_NO_SEAM_OWNERS, SQ_FUSE_CONSECUTIVE_GROUPS = 1, 2, 4, 8, 16
 SQ_PROJECT_ACCUMULATE = 32
+SQ_FOCUS_ACCUMULATE = 32
+SQ_FOCUS_MAX_RADIUS = 15
+SQ_FOCUS_MAX_PLANES = 256
 SQ_VERSION = 108
 SQ_ARENA_NATURAL_ORDER = 1
 SQ_ARENA_TWO_CLASSES = 2
@@ -56,6 +59,14 @@ class _FuseArgs(C.Structure):
         ('canvas_dtype', C.c_int32), ('n_planes', C.c_int32), ('mode', C.c_int32),
         ('scratch_dev', C.c_void_p), ('scratch_bytes', C.c_int64),
         ('flags', C.c_int32), ('grid_blocks', C.c_int32),
+    ]
+
+
+class _FocusArgs(C.Structure):
+    _fields_ = [
+        ('z_levels_dev', C.c_void_p), ('radius', C.c_int32),
+        ('scratch_dev', C.c_void_p), ('scratch_bytes', C.c_int64),
+        ('key_dev', C.c_void_p), ('key_pitch', C.c_int32),
     ]
 
 
@@ -96,6 +107,8 @@ EXPORTS = {
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     'sq_fuse_planes': (C.c_int, [C.POINTER(_FuseArgs), C.c_void_p]),
     'sq_fuse_project_max': (C.c_int, [C.POINTER(_FuseArgs), C.c_int32, C.c_void_p]),
+    'sq_focus_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    'sq_fuse_project_focus': (C.c_int, [C.POINTER(_FuseArgs), C.POINTER(_FocusArgs), C.c_int32, C.c_void_p]),
     'sq_tile_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_pair_overlap_moments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -467,6 +480,99 @@ def fuse_project_max(plan: FusePlan, tiles, out, flats=None, tile_ptrs=None, acc
             t.record_stream(stream)
     fl = int(flags) | (SQ_PROJECT_ACCUMULATE if accumulate else 0)
     _check(L.sq_fuse_project_max(C.byref(a), fl, _stream_ptr(stream)), 'sq_fuse_project_max')
+
+
+def focus_scratch_bytes(n_tiles: int, tile_h: int, tile_w: int) -> int:
+    """Bytes of the caller-owned scratch of ``fuse_project_focus`` for a plan of ``n_tiles`` tiles of tile_h x tile_w: the
+    per-tile-pixel winner (uint32 score + uint8 plane index), about 5 B per tile pixel whatever the number of planes."""
+    n = int(lib().sq_focus_scratch_bytes(int(n_tiles), int(tile_h), int(tile_w)))
+    if n < 0:
+        _check(n, 'sq_focus_scratch_bytes')
+    return n
+
+
+def fuse_project_focus(plan: FusePlan, tiles, out, key, z_levels, radius: int = 3, flats=None, scratch=None,
+                       accumulate: bool = False, tile_ptrs=None, flags: int = 0, stream=None, flat_ptrs=None,
+                       grid_blocks: int = 0) -> None:
+    """Best-focus (extended depth of field) projection over z (sq_fuse_project_focus; an extension, the reference has none).
+    Per tile pixel the focus score F = the (2R+1)^2 box sum of the modified Laplacian of the RAW tile (reads clamped to the
+    full staged tile); per canvas voxel the plane with the largest key (F << 32) | (0xFFFFFFFF - z) among the planes whose
+    owner pixel covers it -- the highest score, on a tie the lowest z level -- and ``out`` = what ``fuse_planes`` stores for
+    that plane there (the same flatfield divide), ``key`` = that key.  Uncovered voxels: 0 in both.
+
+    out:      [Hc, Wc] device tensor of the tile dtype with unit-stride rows.
+    key:      [Hc, Wc] device int64 tensor with unit-stride rows (the keys are < 2^63); depth = 0xFFFFFFFF - (key & 0xFFFFFFFF).
+    z_levels: the z level of each of the call's Z planes (a sequence, or a device int64 / int32 tensor); 0 <= z < 2^32.
+    radius:   R, 0..15.
+    tiles / tile_ptrs / flats / flat_ptrs: as in ``fuse_project_max`` (Z = tiles.shape[0]; at most 256 planes per call).
+    scratch:  optional device uint8 tensor of at least ``focus_scratch_bytes(plan.n_tiles, tile_h, tile_w)`` bytes (reuse it
+              across calls); allocated here when None.
+    accumulate: voxels whose new key exceeds ``key`` take the new value and key, the others (and uncovered voxels) stay --
+              the z planes of a channel that come in several calls, in any z order, or under different plans."""
+    import torch
+    L = lib()
+    if plan.mode != SQ_FUSE_OVERWRITE:
+        raise ValueError("fuse_project_focus projects overwrite plans only")
+    if not 0 <= int(radius) <= SQ_FOCUS_MAX_RADIUS:
+        raise ValueError(f"focus radius {radius} outside 0..{SQ_FOCUS_MAX_RADIUS}")
+    shape = (plan.canvas_h, plan.canvas_w)
+    for name, t in (('out', out), ('key', key)):
+        if not t.is_cuda or t.dim() != 2 or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a [{shape[0]}, {shape[1]}] device tensor")
+        if (shape[1] > 1 and t.stride(1) != 1) or (shape[0] > 1 and t.stride(0) < shape[1]):
+            raise ValueError(f"{name} must have unit-stride rows")
+    if key.dtype != torch.int64:
+        raise ValueError("key must be an int64 tensor")
+    hc, wc = shape
+    pitch = int(out.stride(0)) if hc > 1 else wc
+    key_pitch = int(key.stride(0)) if hc > 1 else wc
+    if tile_ptrs is not None:
+        n_planes = int(tile_ptrs.numel()) // max(plan.n_tiles, 1) if plan.n_tiles else (len(flats) if flats is not None else 1)
+    elif tiles is not None:
+        n_planes = int(tiles.shape[0]) if tiles.dim() == 4 else 1
+    else:
+        raise ValueError("tiles or tile_ptrs is required")
+    if not 1 <= n_planes <= SQ_FOCUS_MAX_PLANES:
+        raise ValueError(f"{n_planes} planes: a call projects 1..{SQ_FOCUS_MAX_PLANES}")
+    keep = []
+    if torch.is_tensor(z_levels) and z_levels.is_cuda:
+        zl = z_levels.to(torch.int32)
+    else:
+        zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
+        if any(not 0 <= z < 2 ** 32 for z in zs):
+            raise ValueError("z levels must lie in 0 .. 2^32 - 1")
+        zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
+    if zl.numel() != n_planes:
+        raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
+    keep.append(zl)
+    need = focus_scratch_bytes(plan.n_tiles, plan.tile_h, plan.tile_w)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=out.device)
+    elif scratch.numel() * scratch.element_size() < need or not scratch.is_cuda:
+        raise ValueError(f"focus scratch must be a device tensor of at least {need} bytes")
+    keep.append(scratch)
+    a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
+    a.flags, a.grid_blocks = 0, int(grid_blocks)
+    f = _FocusArgs()
+    f.z_levels_dev = zl.data_ptr()
+    f.radius = int(radius)
+    f.scratch_dev, f.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+    f.key_dev, f.key_pitch = key.data_ptr(), key_pitch
+    if stream is not None:
+        for t in keep:
+            t.record_stream(stream)
+    fl = int(flags) | (SQ_FOCUS_ACCUMULATE if accumulate else 0)
+    _check(L.sq_fuse_project_focus(C.byref(a), C.byref(f), fl, _stream_ptr(stream)), 'sq_fuse_project_focus')
+
+
+def depth_of_keys(key):
+    """The winning z level of each voxel of a key plane (``fuse_project_focus``): 0xFFFFFFFF - the low word, -1 where the key
+    is 0 (no plane covers the voxel).  int64, torch or numpy like ``key``."""
+    import torch
+    if torch.is_tensor(key):
+        return torch.where(key == 0, torch.full_like(key, -1), 0xFFFFFFFF - (key & 0xFFFFFFFF))
+    key = np.asarray(key).astype(np.int64)
+    return np.where(key == 0, -1, 0xFFFFFFFF - (key & 0xFFFFFFFF))
 
 
 PLANE_ALIGN_BYTES = 128

@@ -56,7 +56,8 @@ class Stitcher:
     def __init__(self, params: StitchingParameters, device=None, fusion_mode: str = 'overwrite',
                  normalization: Optional[str] = 'phase', zarr_compression: str = 'blosc',
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
-                 all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none'):
+                 all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none',
+                 focus_radius: int = 3):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -85,12 +86,18 @@ class Stitcher:
         self.normalization = normalization        # scikit-image >= 0.19 default is 'phase'
         # Extension: per-channel maximum-intensity projection over z from the tiles on the device (sq_fuse_project_max).
         # 'max' writes <region>_stitched_mip<format> beside the stack, 'max-only' writes the projection alone.
-        if z_projection not in ('none', 'max', 'max-only'):
-            raise ValueError("z_projection must be 'none', 'max' or 'max-only'")
+        # 'focus' / 'focus-only': the best-focus (extended depth of field) projection instead (sq_fuse_project_focus), written
+        # to <region>_stitched_edf<format>; focus_radius is its window radius R (0..15).
+        if z_projection not in ('none', 'max', 'max-only', 'focus', 'focus-only'):
+            raise ValueError("z_projection must be 'none', 'max', 'max-only', 'focus' or 'focus-only'")
         if z_projection != 'none' and fusion_mode != 'overwrite':
             raise ValueError(f"z_projection={z_projection!r} projects overwrite fusion only; it cannot be combined with "
                              f"fusion_mode={fusion_mode!r}")
+        if isinstance(focus_radius, bool) or not isinstance(focus_radius, (int, np.integer)) or \
+                not 0 <= int(focus_radius) <= native.SQ_FOCUS_MAX_RADIUS:
+            raise ValueError(f"focus_radius must be an integer in 0..{native.SQ_FOCUS_MAX_RADIUS}, got {focus_radius!r}")
         self.z_projection = z_projection
+        self.focus_radius = int(focus_radius)
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -727,6 +734,32 @@ class Stitcher:
         out = proj.unsqueeze(0).unsqueeze(2)
         return out if device_output else out.cpu().numpy()
 
+    def focus_region(self, timepoint, region, progress_callback=None, device_output: bool = False, return_depth: bool = False):
+        """Best-focus (extended depth of field) projection over z of one (timepoint, region) -> (1, C, 1, Hc, Wc) of the input
+        dtype: per voxel the value ``stitch_region`` stores in the z plane whose owner tile pixel has the highest focus score
+        (the box sum of radius ``focus_radius`` of the raw tile's modified Laplacian; on a tie the lowest z), computed from the
+        staged tiles without the stack (sq_fuse_project_focus; an extension, the reference has none).
+        ``return_depth``: also the winning z level of every voxel, (C, Hc, Wc) int32, -1 where no tile covers it.
+        Returns numpy (host) unless ``device_output``."""
+        out, key = self._new_focus(timepoint, region)
+        self.stitch_planes(timepoint, region, None, progress_callback, stack=False,
+                           project_to={c: (out[c], key[c]) for c in range(self.num_c)})
+        import torch
+        img = out.unsqueeze(0).unsqueeze(2)
+        if not device_output:
+            img = img.cpu().numpy()
+        if not return_depth:
+            return img
+        depth = native.depth_of_keys(key).to(torch.int32)
+        return img, (depth if device_output else depth.cpu().numpy())
+
+    def _new_focus(self, timepoint, region, rows=None, n_channels=None):
+        """Device buffers (output [C, Hc, Wc] of the input dtype, key [C, Hc, Wc] int64) of a region's best-focus projections
+        (a row band's rows with ``rows``)."""
+        import torch
+        out = self._new_projection(timepoint, region, rows, n_channels)
+        return out, torch.empty(tuple(out.shape), dtype=torch.int64, device=self.device)
+
     def _new_projection(self, timepoint, region, rows=None, n_channels=None):
         """Device buffer [C, Hc, Wc] (or [n_channels, y1 - y0, Wc] for a row band) of a region's projections, rows dense."""
         import torch
@@ -754,8 +787,11 @@ class Stitcher:
         ``project_to``: {channel: device tensor [Hc, Wc]} (the band's rows with ``row_band``) that receives the channel's
         maximum-intensity projection over the z planes among ``only_planes`` (sq_fuse_project_max), computed from the same
         staged tiles as the stack: the first batch of a channel writes, later batches (and other rectangle lists) accumulate;
-        a channel no file touches comes out as zeros.  ``stack=False``: the projection only -- no canvas, no stream writer,
-        no stack fusion; the return value is then (None, plane ids)."""
+        a channel no file touches comes out as zeros.  A value (output [Hc, Wc], key [Hc, Wc] int64) receives the channel's
+        best-focus projection and its key plane instead (sq_fuse_project_focus, radius ``self.focus_radius``; the windows
+        are the full staged tiles, so a row band projects exactly the rows of the whole region's projection).
+        ``stack=False``: the projection only -- no canvas, no stream writer, no stack fusion; the return value is then
+        (None, plane ids)."""
         import torch
         start_time = time.time()
         region_data = self.get_region_data(int(timepoint), region)
@@ -859,12 +895,15 @@ class Stitcher:
             if stream_to is not None and groups:
                 widest = max(len(rect_of[sig]) for sig in groups) * th * tw * np.dtype(self.dtype).itemsize
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
+            focus = project_to is not None and any(isinstance(t, tuple) for t in project_to.values())
             if project_to is not None:
                 for t in project_to.values():
-                    t.record_stream(torch.cuda.current_stream(self.device))
+                    for u in (t if isinstance(t, tuple) else (t,)):
+                        u.record_stream(torch.cuda.current_stream(self.device))
                 for c in project_to:
                     if not any(p // self.num_z == c for p in planes):
-                        project_to[c].zero_()      # no file of this channel: zeros, like its planes of the stack
+                        for u in (project_to[c] if isinstance(project_to[c], tuple) else (project_to[c],)):
+                            u.zero_()      # no file of this channel: zeros, like its planes of the stack
             for sig, plist in groups.items():
                 # ascending plane ids: the canvas slots of a chunk are then consecutive and the whole chunk
                 # goes out in ONE launch (region_data is in file-name order, i.e. z varies before channel)
@@ -873,7 +912,11 @@ class Stitcher:
                 n = len(rects)
                 plan = self._plan_for(rects, th, tw, hc, wc, mode)
                 per_plane = n * th * tw * np.dtype(self.dtype).itemsize
-                batch = max(1, min(len(plist), budget // max(1, per_plane)))
+                # the best-focus projection's per-tile-pixel winners (5 B per tile pixel, one buffer for the group's calls)
+                focus_scratch = torch.empty(native.focus_scratch_bytes(n, th, tw), dtype=torch.uint8, device=self.device) \
+                    if focus else None
+                staged_budget = budget - (0 if focus_scratch is None else focus_scratch.numel())
+                batch = max(1, min(len(plist), staged_budget // max(1, per_plane)))
                 if writer is not None:
                     batch = min(batch, writer.batch)
                 chunks = [plist[b0:b0 + batch] for b0 in range(0, len(plist), batch)]
@@ -929,8 +972,14 @@ class Stitcher:
                                 runs.setdefault(p // self.num_z, []).append(pi)
                         for c, pis in runs.items():
                             i0, i1 = pis[0], pis[-1] + 1
-                            native.fuse_project_max(plan, tiles[i0:i1], project_to[c], None if flats is None else flats[i0:i1],
-                                                    accumulate=c in projected)
+                            ff = None if flats is None else flats[i0:i1]
+                            if isinstance(project_to[c], tuple):
+                                out, key = project_to[c]
+                                native.fuse_project_focus(plan, tiles[i0:i1], out, key, [p % self.num_z for p in chunk[i0:i1]],
+                                                          self.focus_radius, ff, scratch=focus_scratch,
+                                                          accumulate=c in projected)
+                            else:
+                                native.fuse_project_max(plan, tiles[i0:i1], project_to[c], ff, accumulate=c in projected)
                             projected.add(c)
                     if not stack:      # the projection only
                         pass
@@ -979,38 +1028,55 @@ class Stitcher:
                        name=f"{region}_t{timepoint}", compression=self.zarr_compression, device=self.device)
         return output_path
 
-    def _mip_path(self, timepoint, region) -> str:
-        return os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched_mip{self.output_format}")
+    def _projection_kind(self) -> Optional[str]:
+        """The file-name tag of the projection this run writes: 'mip' (--z-projection max / max-only), 'edf' (focus /
+        focus-only) or None."""
+        return {'max': 'mip', 'max-only': 'mip', 'focus': 'edf', 'focus-only': 'edf'}.get(self.z_projection)
 
-    def save_region_mip(self, timepoint, region, mip) -> str:
-        """``<t>_stitched/<region>_stitched_mip<format>``: the (1, C, 1, Hc, Wc) projection (numpy or device tensor) with the
+    def _projection_target(self, timepoint, region, rows=None, channel=None):
+        """A region's (or one channel's row band's) projection buffers -> (the image [n, Hc, Wc] to write, the stitch_planes
+        ``project_to`` that fills it): the MIP, or the best-focus output with its key plane."""
+        n = None if channel is None else 1
+        chans = range(self.num_c) if channel is None else [channel]
+        if self._projection_kind() == 'edf':
+            out, key = self._new_focus(timepoint, region, rows, n)
+            return out, {c: (out[i], key[i]) for i, c in enumerate(chans)}
+        proj = self._new_projection(timepoint, region, rows, n)
+        return proj, {c: proj[i] for i, c in enumerate(chans)}
+
+    def _mip_path(self, timepoint, region, kind: str = 'mip') -> str:
+        return os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched_{kind}{self.output_format}")
+
+    def save_region_mip(self, timepoint, region, mip, kind: str = 'mip') -> str:
+        """``<t>_stitched/<region>_stitched_<kind><format>`` (kind 'mip': the maximum-intensity projection, 'edf': the best-focus
+        one): the (1, C, 1, Hc, Wc) projection (numpy or device tensor) with the
         stack's channel names, colours, pixel size and pyramid level count, through the same writers as the stack."""
-        output_path = self._mip_path(timepoint, region)
+        output_path = self._mip_path(timepoint, region, kind)
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
         if self.output_format.endswith('.zarr'):
             write_ome_zarr(output_path, mip, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                            channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                            num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                           name=f"{region}_t{timepoint}_mip", compression=self.zarr_compression, device=self.device)
+                           name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression, device=self.device)
             return output_path
         if hasattr(mip, 'cpu'):
             mip = mip.cpu().numpy()
         print(f"Writing OME-TIFF to: {output_path}")
         write_ome_tiff(output_path, np.asarray(mip), pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                        channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
-                       name=f"{region}_t{timepoint}_mip")
+                       name=f"{region}_t{timepoint}_{kind}")
         return output_path
 
-    def create_mip_store(self, timepoint, region):
+    def create_mip_store(self, timepoint, region, kind: str = 'mip'):
         """Metadata of the region's projection store (Z = 1, no chunks) -> (path, level shapes)."""
-        output_path = self._mip_path(timepoint, region)
+        output_path = self._mip_path(timepoint, region, kind)
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
         width, height = self.calculate_output_dimensions(timepoint, region)
         shapes = omezarr.create_store(output_path, (1, self.num_c, 1, height, width), self.dtype,
                                       pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                                       channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                                       num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                                      name=f"{region}_t{timepoint}_mip", compression=self.zarr_compression)
+                                      name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression)
         return output_path, shapes
 
     def create_region_store(self, timepoint, region):
@@ -1109,12 +1175,12 @@ class Stitcher:
         bands = sharding.row_bands(height, self.num_pyramid_levels, (self.chunks or (1, 1, 1, 512, 512))[3])
         units = sharding.plane_band_units(n_planes, bands, rank, world)
         print(f"\nProcessing timepoint {timepoint}, region {region}: (plane, band) units {units} (rank {rank}/{world})")
-        stack = self.z_projection != 'max-only'
+        stack = self.z_projection not in ('max-only', 'focus-only')
         if rank == 0:
             if stack:
                 self.create_region_store(timepoint, region)
             if self.z_projection != 'none':
-                self.create_mip_store(timepoint, region)
+                self.create_mip_store(timepoint, region, self._projection_kind())
         sharding.barrier()
         self.starting_stitching.emit()
         self.starting_saving.emit(False)
@@ -1135,20 +1201,21 @@ class Stitcher:
     def _project_region_units(self, timepoint, region, bands, rank, world) -> str:
         """This rank's share of a shared region's projection: (channel, row band) units dealt like the stack's (plane, band)
         units (sharding.plane_band_units over the channels), each projected from the tiles of its channel that reach its band
-        and written as its own chunks of the store rank 0 created.  With 'max' the files of these channels are read a second
-        time (the stack pass dealt planes, not channels, so its staged tiles do not line up with these units)."""
+        and written as its own chunks of the store rank 0 created.  With 'max' / 'focus' the files of these channels are read a
+        second time (the stack pass dealt planes, not channels, so its staged tiles do not line up with these units).  The
+        best-focus windows are the full staged tiles, so a band's rows equal those of the whole region's projection."""
         cunits = sharding.plane_band_units(self.num_c, bands, rank, world)
         print(f"Projection of timepoint {timepoint}, region {region}: (channel, band) units {cunits} (rank {rank}/{world})")
-        output_path = self._mip_path(timepoint, region)
+        output_path = self._mip_path(timepoint, region, self._projection_kind())
         width, height = self.calculate_output_dimensions(timepoint, region)
         full = omezarr.level_shapes((1, self.num_c, 1, height, width), self.num_pyramid_levels)
         chunks = self.chunks or (1, 1, 1, 512, 512)
         for c, b in cunits:
             y0, y1 = (0, height) if b < 0 else bands[b]
-            proj = self._new_projection(timepoint, region, (y0, y1), n_channels=1)
+            proj, target = self._projection_target(timepoint, region, (y0, y1), channel=c)
             self.stitch_planes(timepoint, region, [c * self.num_z + z for z in range(self.num_z)],
                                self.update_progress.emit, row_band=None if b < 0 else (y0, y1), stack=False,
-                               project_to={c: proj[0]})
+                               project_to=target)
             shapes = omezarr.level_shapes((1, self.num_c, 1, y1 - y0, width), len(full))
             with omezarr.PlaneStreamWriter(output_path, shapes, self.dtype, chunks=chunks, batch=1,
                                            compression=self.zarr_compression, device=self.device, row_offset=y0,
@@ -1289,7 +1356,8 @@ class Stitcher:
             print("Note: merging timepoints / HCS regions is an output-format step outside the hot-path scope; "
                   "per-(timepoint, region) stores were written.")
         final_path = os.path.join(self.output_folder, f"{self.timepoints[-1]}_stitched",
-                                  f"{self.regions[-1]}_stitched{'_mip' if self.z_projection == 'max-only' else ''}{self.output_format}")
+                                  f"{self.regions[-1]}_stitched{'_' + self._projection_kind() if self.z_projection.endswith('-only') else ''}"
+                                  f"{self.output_format}")
         self.finished_saving.emit(final_path, self.dtype)
         print(f"Total processing time: {time.time() - stime}")
 
@@ -1331,9 +1399,8 @@ class Stitcher:
                 self.write_tile_positions(timepoint, region)
             self.starting_stitching.emit()
             # --z-projection: the projection comes from the tiles the stack pass stages (one read of every file)
-            proj = self._new_projection(timepoint, region) if self.z_projection != 'none' else None
-            project_to = None if proj is None else {c: proj[c] for c in range(self.num_c)}
-            if self.z_projection == 'max-only':
+            proj, project_to = self._projection_target(timepoint, region) if self.z_projection != 'none' else (None, None)
+            if self.z_projection in ('max-only', 'focus-only'):
                 self.starting_saving.emit(False)
                 self.stitch_planes(timepoint, region, None, self.update_progress.emit, stack=False, project_to=project_to)
             elif self.output_format.endswith('.zarr'):
@@ -1346,8 +1413,8 @@ class Stitcher:
                 self.starting_saving.emit(False)
                 output_path = self.save_region_aics(timepoint, region, stitched_region)
             if proj is not None:      # (ordered after the projection kernels: stitch_planes made this stream wait for them)
-                mip_path = self.save_region_mip(timepoint, region, proj.unsqueeze(0).unsqueeze(2))
-                if self.z_projection == 'max-only':
+                mip_path = self.save_region_mip(timepoint, region, proj.unsqueeze(0).unsqueeze(2), self._projection_kind())
+                if self.z_projection in ('max-only', 'focus-only'):
                     output_path = mip_path
             print(f"Completed region {region} (saved to {output_path}): {time.time() - rtime}")
         if self.use_registration:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus eight switches for what this build adds (``--fusion-mode``, ``--normalization``,
+plus nine switches for what this build adds (``--fusion-mode``, ``--normalization``,
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
-``--global-registration``, ``--z-projection``).
+``--global-registration``, ``--z-projection``, ``--focus-radius``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -48,10 +48,14 @@ FLAGS = (
                                       help="with -ff: basicpy's BaSiC fit when that package is installed (auto / basicpy), this "
                                            "build's device restatement of the published BaSiC fit (basic; what auto falls back "
                                            "to), or a plain smoothed mean (mean: not BaSiC)")),
-    (('--z-projection',), dict(choices=['none', 'max', 'max-only'], default='none',
-                               help="maximum-intensity projection over z per channel, computed on the device from the tiles: max = "
-                                    "the stack plus <region>_stitched_mip<format>; max-only = the projection alone (overwrite fusion "
-                                    "only)")),
+    (('--z-projection',), dict(choices=['none', 'max', 'max-only', 'focus', 'focus-only'], default='none',
+                               help="projection over z per channel, computed on the device from the tiles: max = the stack plus "
+                                    "the maximum-intensity projection <region>_stitched_mip<format>; focus = the stack plus the "
+                                    "best-focus (extended depth of field) projection <region>_stitched_edf<format>; max-only / "
+                                    "focus-only = the projection alone (overwrite fusion only)")),
+    (('--focus-radius',), dict(type=int, choices=range(0, 16), default=3, metavar='R',
+                               help="with --z-projection focus: radius of the focus window, 0..15 (a (2R+1)^2 box sum of the "
+                                    "modified Laplacian)")),
 )
 
 
@@ -106,7 +110,8 @@ def main(argv=None):
                             flatfield_estimator=args.flatfield_estimator,
                             all_pairs_registration=args.all_pairs_registration,
                             global_registration=args.global_registration,
-                            z_projection=args.z_projection)
+                            z_projection=args.z_projection,
+                            focus_radius=args.focus_radius)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

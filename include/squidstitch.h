@@ -173,6 +173,51 @@ int sq_fuse_planes(const sq_fuse_args *args, void *stream);
 #define SQ_PROJECT_ACCUMULATE 32
 int sq_fuse_project_max(const sq_fuse_args *args, int32_t flags, void *stream);
 
+/* Best-focus (extended depth of field) projection over z (extension: the reference has none).  Per channel c and per staged
+ * tile k of plane (c, z), all integer and exact:
+ *   - I = the tile's RAW staged pixels (before flatfield; for an RGB file the monochrome component the stack pass stages).
+ *     Reads outside the tile clamp to its edge.  Windows use the FULL staged tile, not the overwrite rect or the row band,
+ *     so cropping, row bands and rank splits cannot change the result;
+ *   - ML(y,x) = |2I(y,x) - I(y,x-1) - I(y,x+1)| + |2I(y,x) - I(y-1,x) - I(y+1,x)|  (modified Laplacian, Nayar & Nakagawa);
+ *   - F(y,x) = sum over |dy| <= R, |dx| <= R of ML(clamp(y+dy), clamp(x+dx)); R = focus radius 0..15 (default 3).  F fits in
+ *     uint32 for R <= 15 with 16-bit input (961 x 262140 < 2^28);
+ *   - key of a tile pixel in plane z: (uint64(F) << 32) | (0xFFFFFFFF - z), z = the channel's z level (not the index within a
+ *     batch).  The key is always > 0;
+ *   - each canvas voxel v of each plane z has an owner tile and source pixel under that plane's overwrite plan; key_z(v) is
+ *     that pixel's key, or 0 if plane z does not cover v.  The winning plane z*(v) is the z of max_z key_z(v): the highest
+ *     score, on a tie the lowest z;
+ *   - output v = exactly what sq_fuse_planes stores for plane z* at v (the same divide routines for none / float32 / float64
+ *     gains).  Uncovered voxels are 0.  The depth of v is z*, recovered from the key plane (0xFFFFFFFF - low word).
+ * `args` addresses the n_planes = Z planes of ONE plan as for sq_fuse_project_max (canvas_dev = the one output plane,
+ * canvas_dtype == tile_dtype, overwrite plans only, scratch_dev = optional work-queue counters).  `focus`:
+ *   - z_levels_dev: n_planes uint32 z levels of the call's planes, device memory;
+ *   - radius: R, 0..15;
+ *   - scratch_dev / scratch_bytes: sq_focus_scratch_bytes(n_tiles, tile_h, tile_w) bytes, 128-byte aligned, caller owned: the
+ *     per-tile-pixel winner (uint32 score + uint8 plane index, 5 B per tile pixel) between the two stages of the call;
+ *   - key_dev / key_pitch: the uint64 key plane [canvas_h, key_pitch elements], caller owned, written beside the output.
+ * Two stages on `stream`: (1) per tile and 64 x 32 block, the block plus a halo of R + 1 of each plane into LDS, ML, the
+ * separable box sum and the running best (score, plane) over the Z planes; (2) the plan's items (static walk or the per-XCD
+ * work queues of the overwrite kernels): the winner's raw value from its staged plane through the gains, the output and key
+ * planes written.  flags: the work-distribution bits as for sq_fuse_project_max, plus SQ_FOCUS_ACCUMULATE: a voxel is
+ * rewritten (output and key) only where the new key is greater than the key plane holds; uncovered voxels are left untouched --
+ * for the z planes of a channel that come in several calls (ingest batches, any z order) or under different plans (ragged
+ * input).  Without it every voxel of both planes is written (uncovered: 0 and key 0).  The library allocates nothing on the
+ * device.  SQ_ERR_INVALID for a feather plan, R outside 0..15, n_planes outside 1..256 (the uint8 plane index), a missing key
+ * plane or scratch; SQ_ERR_WORKSPACE for scratch that is too small.  No atomics beyond the queue walk; deterministic. */
+#define SQ_FOCUS_ACCUMULATE 32
+#define SQ_FOCUS_MAX_RADIUS 15
+#define SQ_FOCUS_MAX_PLANES 256
+typedef struct sq_focus_args {
+    const uint32_t *z_levels_dev;
+    int32_t radius;
+    void *scratch_dev;
+    int64_t scratch_bytes;
+    void *key_dev;
+    int32_t key_pitch;
+} sq_focus_args;
+int64_t sq_focus_scratch_bytes(int32_t n_tiles, int32_t tile_h, int32_t tile_w);
+int sq_fuse_project_focus(const sq_fuse_args *args, const sq_focus_args *focus, int32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Canvas memory.  Replaces the allocation behind Stitcher.init_output (stitcher.py:356-362: the reference's canvas is a
  * lazy dask array; here it is device memory the fusion kernel writes once).  WHERE that memory lies decides how fast the
