@@ -117,6 +117,8 @@ EXPORTS = {
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'sq_downsample2': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                  C.c_int32, C.c_int32, C.c_void_p]),
+    'sq_pyramid_mean': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -807,6 +809,52 @@ def downsample2(planes, out=None, stream=None):
     _check(L.sq_downsample2(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), out.data_ptr(), out.stride(0),
                             out.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)), _stream_ptr(stream)),
            'sq_downsample2')
+    return out
+
+
+SQ_PYRAMID_MEAN_MAX_LEVELS = 5     # levels one sq_pyramid_mean launch yields (squidstitch.h); longer requests take further launches
+
+
+def pyramid_mean(planes, n_levels, out=None, stream=None):
+    """The next ``n_levels`` MEAN pyramid levels of ``planes`` [n, h, w] (uint8 / uint16 device tensor, any row pitch) from
+    one read of it -> list of [n, h >> l, w >> l], l = 1 ... : every level is the truncated 2 x 2 mean of the level before,
+    ``(a + b + c + d) >> 2``, a trailing odd row / column dropped (what the reference's zarr_stitcher.py:614-719 stores:
+    ``da.coarsen(np.mean, ..., trim_excess=True)`` cast to the integer dtype).  Levels that would be empty are not returned.
+    ``out`` may be a list of preallocated tensors (any row pitch), one per level that exists."""
+    import torch
+    L = lib()
+    if planes.dim() != 3 or planes.device.type != 'cuda':
+        raise ValueError("planes must be a [n, h, w] device tensor")
+    if planes.stride(2) != 1 and planes.shape[2] > 1:
+        raise ValueError("planes rows must be contiguous")
+    if planes.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"planes must be uint8 or uint16, got {planes.dtype}")
+    dtype = sq_dtype_of(np_dtype_of_torch(planes.dtype))
+    n_levels = int(n_levels)
+    if n_levels < 0:
+        raise ValueError(f"n_levels must be >= 0, got {n_levels}")
+    n, h, w = (int(v) for v in planes.shape)
+    shapes = []
+    while len(shapes) < n_levels and (h >> (len(shapes) + 1)) > 0 and (w >> (len(shapes) + 1)) > 0:
+        shapes.append((n, h >> (len(shapes) + 1), w >> (len(shapes) + 1)))
+    if out is None:
+        out = [torch.empty(s, dtype=planes.dtype, device=planes.device) for s in shapes]
+    out = list(out)
+    if len(out) != len(shapes):
+        raise ValueError(f"out must hold {len(shapes)} tensors (the levels of a {(n, h, w)} stack that exist), got {len(out)}")
+    for s, o in zip(shapes, out):
+        if tuple(o.shape) != s or o.dtype != planes.dtype or o.device != planes.device:
+            raise ValueError(f"out must be {shapes} tensors of the input's dtype and device")
+        if o.stride(2) != 1 and o.shape[2] > 1:
+            raise ValueError("out rows must be contiguous")
+    if not shapes or n == 0:
+        return out
+    k = len(shapes)
+    ptrs = (C.c_void_p * k)(*[o.data_ptr() for o in out])
+    strides = (C.c_int64 * k)(*[o.stride(0) for o in out])
+    pitches = (C.c_int64 * k)(*[o.stride(1) for o in out])
+    _check(L.sq_pyramid_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), ptrs, strides, pitches, k, n, dtype,
+                             _stream_ptr(stream)), 'sq_pyramid_mean')
     return out
 
 

@@ -10,7 +10,10 @@ offline: frames are checked by an independent pure-Python reader in the tests.
 
 Pyramid levels are what ome_zarr's ``Scaler.nearest`` produces (level l+1 = level l sampled at
 [2y+1, 2x+1], floor-halved shape); they are computed on the device (``native.downsample2``,
-csrc/pyramid.hip) -- this module only lays chunks out on disk.  ``PlaneStreamWriter`` is the
+csrc/pyramid.hip) -- this module only lays chunks out on disk.  With ``pyramid_method='mean'`` the levels are instead what
+the reference's other stitchers store (zarr_stitcher.py:614-719: level l+1 = the truncated 2 x 2 mean of level l,
+``(a + b + c + d) >> 2``, same shapes), all of them from one read of level 0 (``native.pyramid_mean``,
+csrc/pyramid_mean.hip).  ``PlaneStreamWriter`` is the
 "next" row 8(f)1: planes leave the GPU batch by batch (pyramid -> pinned D2H -> compression in
 host threads) while the next batch is being fused, so a region never has to exist in host memory.
 """
@@ -134,6 +137,15 @@ def level_shapes(shape: Sequence[int], num_levels: int) -> List[tuple]:
     return out
 
 
+PYRAMID_METHODS = ('nearest', 'mean')
+
+
+def check_pyramid_method(method: str) -> str:
+    if method not in PYRAMID_METHODS:
+        raise ValueError(f"pyramid_method must be 'nearest' or 'mean', got {method!r}")
+    return method
+
+
 def _compressor(compression: str, level: int = 1):
     if compression in (None, 'none', 'raw'):
         return None
@@ -156,9 +168,13 @@ def _zarray_meta(shape, chunks, dtype, compression='zlib', level=1):
 
 def create_store(path: str, shape: Sequence[int], dtype, *, pixel_size_um: float, dz_um: float = 1.0,
                  channel_names: Sequence[str] = (), channel_colors: Sequence[int] = (), num_levels: int = 1,
-                 chunks=(1, 1, 1, 512, 512), name: str = 'stitched', compression: str = 'zlib') -> List[tuple]:
+                 chunks=(1, 1, 1, 512, 512), name: str = 'stitched', compression: str = 'zlib',
+                 pyramid_method: str = 'nearest') -> List[tuple]:
     """Group + array metadata of a multiscale OME-Zarr image, no chunks yet.  Returns the level
-    shapes.  Chunks are then added plane by plane (``write_plane_levels``), by any number of processes."""
+    shapes.  Chunks are then added plane by plane (``write_plane_levels``), by any number of processes.
+    ``pyramid_method='mean'`` names the downscaling in ``multiscales[0]`` ('type' and 'metadata', NGFF 0.4); the default
+    writes neither key."""
+    check_pyramid_method(pyramid_method)
     os.makedirs(path, exist_ok=True)
     _write_json(os.path.join(path, '.zgroup'), {'zarr_format': 2})
     shapes = level_shapes(shape, num_levels)
@@ -185,6 +201,12 @@ def create_store(path: str, shape: Sequence[int], dtype, *, pixel_size_um: float
              'active': True, 'coefficient': 1, 'family': 'linear'}
             for i, n in enumerate(channel_names)]},
     }
+    if pyramid_method == 'mean':
+        attrs['multiscales'][0]['type'] = 'mean'
+        attrs['multiscales'][0]['metadata'] = {
+            'method': 'truncated 2x2 mean of the level before',
+            'description': 'level l+1 [y, x] = (a + b + c + d) >> 2 over the 2 x 2 block of level l at [2y, 2x]; every level '
+                           'has floor(half) the rows and columns of the one before (a trailing odd row / column is dropped)'}
     _write_json(os.path.join(path, '.zattrs'), attrs)
     return shapes
 
@@ -264,9 +286,14 @@ def write_plane_levels(path: str, levels: Sequence[np.ndarray], coords: Sequence
         return sum(tp.map(lambda j: emit_chunk(path, j, compression, level), jobs))
 
 
-def device_levels(planes_dev, n_levels: int, out: Optional[list] = None) -> list:
-    """[planes_dev] + its n_levels - 1 pyramid levels, computed on the device (sq_downsample2)."""
+def device_levels(planes_dev, n_levels: int, out: Optional[list] = None, method: str = 'nearest') -> list:
+    """[planes_dev] + its n_levels - 1 pyramid levels, computed on the device: ``method`` 'nearest' = one sq_downsample2
+    launch per level, 'mean' = all levels from one read of ``planes_dev`` (sq_pyramid_mean)."""
     from . import native
+    check_pyramid_method(method)
+    if method == 'mean':
+        outs = None if out is None else [o[:len(planes_dev)] for o in out[:n_levels - 1]]
+        return [planes_dev] + native.pyramid_mean(planes_dev, n_levels - 1, outs)
     levels = [planes_dev]
     for lv in range(1, n_levels):
         levels.append(native.downsample2(levels[-1], None if out is None else out[lv - 1][:len(planes_dev)]))
@@ -283,7 +310,7 @@ def _pad_planes(full, m: int):
 def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0,
                    channel_names: Sequence[str] = (), channel_colors: Sequence[int] = (),
                    num_levels: int = 1, chunks=(1, 1, 1, 512, 512), name: str = 'stitched', compression: str = 'zlib',
-                   device=None) -> str:
+                   device=None, pyramid_method: str = 'nearest') -> str:
     """Write a (T, C, Z, Y, X) array (numpy, or a device tensor) as a multiscale OME-Zarr image.  The
     pyramid levels come from the device kernel, a batch of planes at a time; with ``num_levels`` 1 no
     GPU is touched for a numpy input."""
@@ -294,7 +321,7 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
     shape = tuple(int(v) for v in image.shape)
     shapes = create_store(path, shape, dtype, pixel_size_um=pixel_size_um, dz_um=dz_um, channel_names=channel_names,
                           channel_colors=channel_colors, num_levels=num_levels, chunks=chunks, name=name,
-                          compression=compression)
+                          compression=compression, pyramid_method=pyramid_method)
     t_, c_, z_ = shape[:3]
     coords = [(t, c, z) for t in range(t_) for c in range(c_) for z in range(z_)]
     planes = image.reshape((-1,) + shape[3:])
@@ -308,7 +335,7 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
         device = device if device is not None else 'cuda:0'
     batch = max(1, (1 << 30) // max(1, shape[3] * shape[4] * dtype.itemsize))
     with PlaneStreamWriter(path, shapes, dtype, chunks=chunks, batch=batch, compression=compression,
-                           device=planes.device if on_device else device) as writer:
+                           device=planes.device if on_device else device, pyramid_method=pyramid_method) as writer:
         for b0 in range(0, len(coords), batch):
             part = planes[b0:b0 + batch]
             dst = writer.acquire(len(part))
@@ -331,7 +358,8 @@ class PlaneStreamWriter:
 
     def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, chunks=(1, 1, 1, 512, 512), batch: int = 1,
                  compression: str = 'zlib', level: int = 1, device='cuda:0', workers: Optional[int] = None, slots: int = 2,
-                 buffers=None, row_offset: int = 0, level_heights: Optional[Sequence[int]] = None, canvas_arena=None):
+                 buffers=None, row_offset: int = 0, level_heights: Optional[Sequence[int]] = None, canvas_arena=None,
+                 pyramid_method: str = 'nearest'):
         import queue
         import threading
         from concurrent.futures import ThreadPoolExecutor
@@ -339,6 +367,8 @@ class PlaneStreamWriter:
         from . import native
         self.path, self.chunks, self.compression, self.level = path, tuple(chunks), compression, level
         self.batch = int(batch)
+        # 'mean': all levels of a slot from one read of its canvas (sq_pyramid_mean) instead of one launch per level
+        self.pyramid_method = check_pyramid_method(pyramid_method)
         # a writer of one row band: ``shapes`` are the band's level shapes, chunks land ``row_offset`` level-0 rows down
         self.row_offset, self.level_heights = int(row_offset), (None if level_heights is None else list(level_heights))
         self.bytes_written = 0
@@ -495,7 +525,7 @@ class PlaneStreamWriter:
         if len(coords) != m:
             raise ValueError(f"{m} planes acquired, {len(coords)} coordinates given")
         dev = self._dev[slot]
-        levels = device_levels(dev[0][:m], len(dev), out=dev[1:])
+        levels = device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
         if self._blosc:        # encode every level's chunks behind the pyramid, on the caller's stream
             from . import native
             for lv, enc in enumerate(self._enc[slot]):
@@ -527,11 +557,12 @@ class PlaneStreamWriter:
         self.path = path
         self.row_offset, self.level_heights = int(row_offset), (None if level_heights is None else list(level_heights))
 
-    def matches(self, shapes: Sequence[tuple], dtype, batch: int, compression: str, chunks) -> bool:
+    def matches(self, shapes: Sequence[tuple], dtype, batch: int, compression: str, chunks, pyramid_method: str = 'nearest') -> bool:
         """Can this writer take planes of these level shapes (its buffers are sized for one geometry)?"""
         from . import native
         yx = [tuple(s[3:]) for s in shapes]
         return (self._thread.is_alive() and self.batch == int(batch) and self.compression == compression and self.chunks == tuple(chunks)
+                and self.pyramid_method == pyramid_method
                 and [tuple(t.shape[1:]) for t in self._dev[0]] == yx
                 and self._dev[0][0].dtype == native.torch_dtype_of(np.dtype(dtype).type))
 

@@ -57,7 +57,7 @@ class Stitcher:
                  normalization: Optional[str] = 'phase', zarr_compression: str = 'blosc',
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
                  all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none',
-                 focus_radius: int = 3):
+                 focus_radius: int = 3, pyramid_method: str = 'nearest'):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -98,6 +98,10 @@ class Stitcher:
             raise ValueError(f"focus_radius must be an integer in 0..{native.SQ_FOCUS_MAX_RADIUS}, got {focus_radius!r}")
         self.z_projection = z_projection
         self.focus_radius = int(focus_radius)
+        # Extension: how the OME-Zarr levels above 0 are made.  'nearest' = the reference's Scaler.nearest (stitcher.py:797-798);
+        # 'mean' = the truncated 2 x 2 mean its other stitchers store (zarr_stitcher.py:614-719), all levels from one read of
+        # level 0 (sq_pyramid_mean).  Applies to every store a run writes (stack, _mip, _edf); .ome.tiff holds level 0 only.
+        self.pyramid_method = omezarr.check_pyramid_method(pyramid_method)
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -1025,7 +1029,8 @@ class Stitcher:
         write_ome_zarr(output_path, stitched_region, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                        channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                        num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                       name=f"{region}_t{timepoint}", compression=self.zarr_compression, device=self.device)
+                       name=f"{region}_t{timepoint}", compression=self.zarr_compression,
+                       pyramid_method=self.pyramid_method, device=self.device)
         return output_path
 
     def _projection_kind(self) -> Optional[str]:
@@ -1057,7 +1062,8 @@ class Stitcher:
             write_ome_zarr(output_path, mip, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                            channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                            num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                           name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression, device=self.device)
+                           name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression,
+                           pyramid_method=self.pyramid_method, device=self.device)
             return output_path
         if hasattr(mip, 'cpu'):
             mip = mip.cpu().numpy()
@@ -1076,7 +1082,8 @@ class Stitcher:
                                       pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                                       channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                                       num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                                      name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression)
+                                      name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression,
+                                      pyramid_method=self.pyramid_method)
         return output_path, shapes
 
     def create_region_store(self, timepoint, region):
@@ -1088,7 +1095,7 @@ class Stitcher:
                                       pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                                       channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                                       num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                                      name=f"{region}_t{timepoint}", compression=self.zarr_compression)
+                                      name=f"{region}_t{timepoint}", compression=self.zarr_compression, pyramid_method=self.pyramid_method)
         return output_path, shapes
 
     def stream_region_to_zarr(self, timepoint, region, only_planes=None, progress_callback=None, create: bool = True,
@@ -1115,7 +1122,7 @@ class Stitcher:
         def make_writer(batch):
             chunks = self.chunks or (1, 1, 1, 512, 512)
             w = self._stream_writer
-            if w is not None and w.matches(shapes, self.dtype, batch, self.zarr_compression, chunks):
+            if w is not None and w.matches(shapes, self.dtype, batch, self.zarr_compression, chunks, self.pyramid_method):
                 w.retarget(output_path, row_offset, level_heights)      # the same geometry: the next store through the same writer
                 made.append(w)
                 return w
@@ -1130,7 +1137,8 @@ class Stitcher:
                 if need >= self.canvas_arena_min_bytes:
                     arena = self._new_arena(need)
             made.append(omezarr.PlaneStreamWriter(output_path, shapes, self.dtype, chunks=self.chunks or (1, 1, 1, 512, 512),
-                                                  batch=batch, compression=self.zarr_compression, device=self.device,
+                                                  batch=batch, compression=self.zarr_compression,
+                                                  pyramid_method=self.pyramid_method, device=self.device,
                                                   buffers=cached, row_offset=row_offset,
                                                   level_heights=level_heights, canvas_arena=arena))
             self._keep_buffers(key, made[-1].buffers)
@@ -1218,7 +1226,8 @@ class Stitcher:
                                project_to=target)
             shapes = omezarr.level_shapes((1, self.num_c, 1, y1 - y0, width), len(full))
             with omezarr.PlaneStreamWriter(output_path, shapes, self.dtype, chunks=chunks, batch=1,
-                                           compression=self.zarr_compression, device=self.device, row_offset=y0,
+                                           compression=self.zarr_compression,
+                                           pyramid_method=self.pyramid_method, device=self.device, row_offset=y0,
                                            level_heights=None if b < 0 else [s[3] for s in full]) as writer:
                 writer.acquire(1).copy_(proj)
                 writer.submit([(0, c, 0)])

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus nine switches for what this build adds (``--fusion-mode``, ``--normalization``,
+plus ten switches for what this build adds (``--fusion-mode``, ``--normalization``,
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
-``--global-registration``, ``--z-projection``, ``--focus-radius``).
+``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -56,6 +56,11 @@ FLAGS = (
     (('--focus-radius',), dict(type=int, choices=range(0, 16), default=3, metavar='R',
                                help="with --z-projection focus: radius of the focus window, 0..15 (a (2R+1)^2 box sum of the "
                                     "modified Laplacian)")),
+    (('--pyramid-method',), dict(choices=['nearest', 'mean'], default='nearest',
+                                 help="how the OME-Zarr levels above 0 are made, in every store of the run (stack, _mip, _edf): "
+                                      "nearest = the reference's Scaler.nearest decimation; mean = the truncated 2 x 2 mean of "
+                                      "the level before, all levels from one read of level 0 on the device.  .ome.tiff output "
+                                      "holds level 0 only, so there the option changes nothing")),
 )
 
 
@@ -111,7 +116,8 @@ def main(argv=None):
                             all_pairs_registration=args.all_pairs_registration,
                             global_registration=args.global_registration,
                             z_projection=args.z_projection,
-                            focus_radius=args.focus_radius)
+                            focus_radius=args.focus_radius,
+                            pyramid_method=args.pyramid_method)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -277,6 +277,26 @@ int sq_downsample2(const void *src_dev, int64_t src_plane_stride, int32_t src_h,
                    void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mean pyramid: levels 1 ... n_levels of the multiscale image from ONE read of the source level.
+ * Restates generate_pyramid_levels -> downsample_block at zarr_stitcher.py:614-719 (and
+ * generate_pyramid, stitcher_process.py:1583-1602), i.e. per plane and level
+ * da.coarsen(np.mean, level, {y: 2, x: 2}, trim_excess=True) of the STORED level before, cast to
+ * the integer dtype (the cast truncates):
+ *     L(l+1)[p][y][x] = (L(l)[p][2y][2x] + L(l)[p][2y][2x+1] + L(l)[p][2y+1][2x] + L(l)[p][2y+1][2x+1]) >> 2,
+ *     L(l+1) is (H_l / 2) x (W_l / 2), floor;  L(0) = src.
+ * dst_dev[l], dst_plane_stride[l], dst_pitch[l] (HOST arrays of n_levels entries) describe level
+ * l + 1, a (src_h >> (l+1)) x (src_w >> (l+1)) image per plane.  Levels that would be empty end
+ * the pyramid: they and everything after them are not written and their entries are not read.
+ * One launch yields up to SQ_PYRAMID_MEAN_MAX_LEVELS levels; a longer request is finished by
+ * further launches from the last level written (the definition composes).  Strides and pitches in
+ * elements; dtype SQ_U8 or SQ_U16; no buffer may overlap another.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_PYRAMID_MEAN_MAX_LEVELS 5
+int sq_pyramid_mean(const void *src_dev, int64_t src_plane_stride, int32_t src_h, int32_t src_w, int64_t src_pitch,
+                    void *const *dst_dev, const int64_t *dst_plane_stride, const int64_t *dst_pitch, int32_t n_levels,
+                    int32_t n_planes, int32_t dtype, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched

@@ -94,6 +94,10 @@ first = native.downsample2(img).clone()
 bad = sum(int(not torch.equal(native.downsample2(img), first)) for _ in range(REPS))
 report('pyramid level 1500x1900 x 2 planes', bad, REPS, t0)
 t0 = time.perf_counter()
+first = [t.clone() for t in native.pyramid_mean(img, 5)]
+bad = sum(int(not all(torch.equal(x, y) for x, y in zip(native.pyramid_mean(img, 5), first))) for _ in range(REPS))
+report('mean pyramid, 5 levels in one launch, 1500x1900 x 2 planes', bad, REPS, t0)
+t0 = time.perf_counter()
 b = native.blosc_encode_planes(img, 512, 512)
 torch.cuda.synchronize()
 off0, out0 = b.offsets.clone(), b.out[:int(b.offsets[-1])].clone()
