@@ -119,6 +119,8 @@ EXPORTS = {
                                  C.c_int32, C.c_int32, C.c_void_p]),
     'sq_pyramid_mean': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p),
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    'sq_histogram_planes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -856,6 +858,55 @@ def pyramid_mean(planes, n_levels, out=None, stream=None):
     _check(L.sq_pyramid_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), ptrs, strides, pitches, k, n, dtype,
                              _stream_ptr(stream)), 'sq_pyramid_mean')
     return out
+
+
+def histogram_bins(dtype) -> int:
+    """Bins of a histogram row of this dtype (one per value): 256 for uint8, 65536 for uint16."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype('uint8'), np.dtype('uint16')):
+        raise ValueError(f"histograms are kept for uint8 and uint16 planes, got {dt}")
+    return 1 << (8 * dt.itemsize)
+
+
+def histogram_planes(planes, rows, hist=None, n_rows=None, stream=None):
+    """Exact value counts of ``planes`` [n, h, w] (uint8 / uint16 device tensor, any row pitch) ADDED into ``hist``, an int64
+    device tensor [n_rows, bins] (bins = 256 / 65536): ``hist[rows[p], v] += count of v in planes[p]``.  ``rows``: one int per
+    plane, 0 <= row < n_rows (several planes may share a row).  ``hist`` None: a zeroed [n_rows, bins] tensor is made
+    (n_rows None: max(rows) + 1).  Returns ``hist``.  The reference has no counterpart (its channel windows are
+    np.iinfo(dtype).max, stitcher.py:846-850); the definition is numpy.bincount."""
+    import torch
+    L = lib()
+    if planes.dim() != 3 or planes.device.type != 'cuda':
+        raise ValueError("planes must be a [n, h, w] device tensor")
+    if planes.stride(2) != 1 and planes.shape[2] > 1:
+        raise ValueError("planes rows must be contiguous")
+    if planes.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"planes must be uint8 or uint16, got {planes.dtype}")
+    np_dtype = np_dtype_of_torch(planes.dtype)
+    bins = histogram_bins(np_dtype)
+    n, h, w = (int(v) for v in planes.shape)
+    rows = [int(r) for r in rows]
+    if len(rows) != n:
+        raise ValueError(f"{n} planes, {len(rows)} rows given")
+    if hist is None:
+        if n_rows is None:
+            n_rows = max(rows) + 1 if rows else 1
+        hist = torch.zeros((int(n_rows), bins), dtype=torch.int64, device=planes.device)
+    if hist.dim() != 2 or hist.shape[1] != bins or hist.dtype != torch.int64 or hist.device != planes.device or \
+            not hist.is_contiguous():
+        raise ValueError(f"hist must be a contiguous int64 [n_rows, {bins}] tensor on the planes' device")
+    if n_rows is not None and int(n_rows) != hist.shape[0]:
+        raise ValueError(f"hist has {hist.shape[0]} rows, n_rows = {n_rows}")
+    if n == 0 or h == 0 or w == 0:
+        if any(not 0 <= r < hist.shape[0] for r in rows):
+            raise ValueError(f"rows must lie in [0, {hist.shape[0]})")
+        return hist
+    table = (C.c_int32 * n)(*rows) if all(-2 ** 31 <= r < 2 ** 31 for r in rows) else None
+    if table is None:
+        raise ValueError(f"rows must lie in [0, {hist.shape[0]})")
+    _check(L.sq_histogram_planes(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype), table,
+                                 int(hist.shape[0]), hist.data_ptr(), _stream_ptr(stream)), 'sq_histogram_planes')
+    return hist
 
 
 _COPY_STREAMS = {}

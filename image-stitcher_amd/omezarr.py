@@ -146,6 +146,113 @@ def check_pyramid_method(method: str) -> str:
     return method
 
 
+CONTRAST_LIMITS = ('dtype', 'percentile')
+
+
+def check_contrast(contrast_limits: str, contrast_percentiles) -> tuple:
+    """-> (contrast_limits, (lo, hi)) validated: 'dtype' | 'percentile', 0 <= lo < hi <= 100."""
+    if contrast_limits not in CONTRAST_LIMITS:
+        raise ValueError(f"contrast_limits must be 'dtype' or 'percentile', got {contrast_limits!r}")
+    try:
+        lo, hi = (float(v) for v in contrast_percentiles)
+    except (TypeError, ValueError):
+        raise ValueError(f"contrast_percentiles must be two numbers LO HI, got {contrast_percentiles!r}") from None
+    if not 0 <= lo < hi <= 100:      # (also refuses NaN)
+        raise ValueError(f"contrast_percentiles must satisfy 0 <= LO < HI <= 100, got {lo:g} {hi:g}")
+    return contrast_limits, (lo, hi)
+
+
+def histogram_percentile(hist_row, q: float) -> Optional[int]:
+    """The q-th percentile of the NON-ZERO voxels counted in ``hist_row`` (counts per value, bin 0 ignored), or None when there
+    is none: the smallest v with cum[v] >= floor(q / 100 * (N - 1)) + 1 -- what ``numpy.percentile(x[x > 0], q,
+    method='lower')`` returns.  Python integers throughout (a channel of a large region passes 2^32 voxels)."""
+    counts = np.asarray(hist_row).astype(np.int64, copy=False)
+    cum = np.cumsum(counts[1:], dtype=np.int64)
+    n = int(cum[-1]) if len(cum) else 0
+    if n <= 0:
+        return None
+    # numpy's virtual index is the float64 product q / 100 * (N - 1); its floor is taken the same way here
+    rank = min(n - 1, int(np.floor(np.float64(q) / 100 * (n - 1)))) + 1
+    return int(np.searchsorted(cum, rank, side='left')) + 1
+
+
+def contrast_window(hist_row, lo: float, hi: float, dtype_max: int) -> tuple:
+    """(start, end) of a channel's rendering window from the exact value counts of what was written: the ``lo``-th and
+    ``hi``-th percentile of the non-zero voxels (value 0 is what the canvas holds where no tile reaches).  ``end <= start``
+    becomes ``end = start + 1`` (inside the dtype's range); a channel without a non-zero voxel keeps ``0 ... dtype_max``."""
+    dtype_max = int(dtype_max)
+    start = histogram_percentile(hist_row, lo)
+    if start is None:
+        return 0, dtype_max
+    end = histogram_percentile(hist_row, hi)
+    if end <= start:
+        end = min(start + 1, dtype_max)
+        if end <= start:
+            start = end - 1
+    return int(start), int(end)
+
+
+def channel_stats(hist, labels: Sequence[str], lo: float, hi: float, dtype_max: int) -> list:
+    """Per channel (row of ``hist``): what ``<stem>_stats.json`` records."""
+    out = []
+    for i, row in enumerate(np.asarray(hist)):
+        row = row.astype(np.int64, copy=False)      # (sums below stay far inside int64: value x count <= 2^16 x 2^47)
+        nz = np.nonzero(row[1:])[0]
+        voxels, nonzero = int(row.sum()), int(row[1:].sum())
+        total = int(np.dot(np.arange(len(row), dtype=np.int64), row))
+        start, end = contrast_window(row, lo, hi, dtype_max)
+        out.append({'label': labels[i] if i < len(labels) else str(i), 'voxels': voxels, 'nonzero_voxels': nonzero,
+                    'min_nonzero': int(nz[0]) + 1 if len(nz) else None, 'max_nonzero': int(nz[-1]) + 1 if len(nz) else None,
+                    'mean': (total / voxels) if voxels else None,
+                    'percentiles': {f'{lo:g}': histogram_percentile(row, lo), f'{hi:g}': histogram_percentile(row, hi)},
+                    'window': {'start': start, 'end': end}})
+    return out
+
+
+def set_channel_windows(path: str, windows: Sequence[tuple]) -> None:
+    """Rewrite ``omero.channels[i].window.start / end`` of a store made by ``create_store`` (one (start, end) per channel);
+    every other key of ``.zattrs`` stays as it is."""
+    zattrs = os.path.join(path, '.zattrs')
+    with open(zattrs) as fh:
+        attrs = json.load(fh)
+    channels = attrs['omero']['channels']
+    if len(windows) != len(channels):
+        raise ValueError(f"{path}: {len(channels)} channels, {len(windows)} windows given")
+    for ch, (start, end) in zip(channels, windows):
+        ch['window']['start'], ch['window']['end'] = int(start), int(end)
+    _write_json(zattrs, attrs)
+
+
+def sidecar_paths(path: str) -> tuple:
+    """(<stem>_histogram.npy, <stem>_stats.json) beside the store ``path`` (<stem>.ome.zarr)."""
+    stem = path[:-len('.ome.zarr')] if path.endswith('.ome.zarr') else os.path.splitext(path)[0]
+    return stem + '_histogram.npy', stem + '_stats.json'
+
+
+def write_contrast(path: str, hist, lo: float, hi: float, dtype) -> list:
+    """A store's windows from the histograms of its own level 0 (``hist``: int64 [C, bins], host): ``.zattrs`` rewritten, the
+    two sidecars written.  Returns the windows.  Planes (or row bands) that no tile reaches are never submitted -- the store
+    holds its fill value 0 there -- so what a channel's counts lack of the store's voxels is added to bin 0."""
+    hist = np.array(hist, dtype=np.int64)
+    with open(os.path.join(path, '0', '.zarray')) as fh:
+        shape = json.load(fh)['shape']
+    per_channel = int(np.prod([int(v) for v in shape[:1] + shape[2:]], dtype=object))
+    missing = per_channel - hist.sum(axis=1)
+    if hist.shape[0] != shape[1] or (missing < 0).any():
+        raise ValueError(f"{path}: the histograms {hist.shape} count more voxels than the store holds ({shape})")
+    hist[:, 0] += missing
+    with open(os.path.join(path, '.zattrs')) as fh:
+        labels = [ch['label'] for ch in json.load(fh)['omero']['channels']]
+    dtype_max = int(np.iinfo(np.dtype(dtype)).max)
+    stats = channel_stats(hist, labels, lo, hi, dtype_max)
+    windows = [(s['window']['start'], s['window']['end']) for s in stats]
+    set_channel_windows(path, windows)
+    npy, js = sidecar_paths(path)
+    np.save(npy, hist)
+    _write_json(js, {'contrast_percentiles': [lo, hi], 'channels': stats})
+    return windows
+
+
 def _compressor(compression: str, level: int = 1):
     if compression in (None, 'none', 'raw'):
         return None
@@ -310,10 +417,11 @@ def _pad_planes(full, m: int):
 def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0,
                    channel_names: Sequence[str] = (), channel_colors: Sequence[int] = (),
                    num_levels: int = 1, chunks=(1, 1, 1, 512, 512), name: str = 'stitched', compression: str = 'zlib',
-                   device=None, pyramid_method: str = 'nearest') -> str:
+                   device=None, pyramid_method: str = 'nearest', histogram=None) -> str:
     """Write a (T, C, Z, Y, X) array (numpy, or a device tensor) as a multiscale OME-Zarr image.  The
     pyramid levels come from the device kernel, a batch of planes at a time; with ``num_levels`` 1 no
-    GPU is touched for a numpy input."""
+    GPU is touched for a numpy input.  ``histogram``: a device int64 [C, bins] tensor the value counts of level 0 are added
+    to (``PlaneStreamWriter.histogram``)."""
     if image.ndim != 5:
         raise ValueError(f"expected a 5-D TCZYX array, got {tuple(image.shape)}")
     on_device = hasattr(image, 'data_ptr')
@@ -325,7 +433,7 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
     t_, c_, z_ = shape[:3]
     coords = [(t, c, z) for t in range(t_) for c in range(c_) for z in range(z_)]
     planes = image.reshape((-1,) + shape[3:])
-    if len(shapes) == 1 and not on_device and compression != 'blosc':
+    if len(shapes) == 1 and not on_device and compression != 'blosc' and histogram is None:
         write_plane_levels(path, [planes], coords, chunks, compression)
         return path
     import torch
@@ -336,6 +444,7 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
     batch = max(1, (1 << 30) // max(1, shape[3] * shape[4] * dtype.itemsize))
     with PlaneStreamWriter(path, shapes, dtype, chunks=chunks, batch=batch, compression=compression,
                            device=planes.device if on_device else device, pyramid_method=pyramid_method) as writer:
+        writer.histogram = histogram
         for b0 in range(0, len(coords), batch):
             part = planes[b0:b0 + batch]
             dst = writer.acquire(len(part))
@@ -372,6 +481,9 @@ class PlaneStreamWriter:
         # a writer of one row band: ``shapes`` are the band's level shapes, chunks land ``row_offset`` level-0 rows down
         self.row_offset, self.level_heights = int(row_offset), (None if level_heights is None else list(level_heights))
         self.bytes_written = 0
+        # optional target of the value counts of level 0: a device int64 [C, bins] tensor; submit() adds the planes it is handed
+        # to row c of it (sq_histogram_planes).  None: nothing is launched.  Callers set it per store (``retarget`` keeps it).
+        self.histogram = None
         tdtype = native.torch_dtype_of(np.dtype(dtype).type)
         yx = [tuple(s[3:]) for s in shapes]
         # ``buffers``: the (device, pinned host) slot buffers of an earlier writer of the same geometry --
@@ -525,6 +637,9 @@ class PlaneStreamWriter:
         if len(coords) != m:
             raise ValueError(f"{m} planes acquired, {len(coords)} coordinates given")
         dev = self._dev[slot]
+        if self.histogram is not None:      # the m planes handed in, not the padding of a partly filled slot
+            from . import native
+            native.histogram_planes(dev[0][:m], [c for _, c, _ in coords], hist=self.histogram)
         levels = device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
         if self._blosc:        # encode every level's chunks behind the pyramid, on the caller's stream
             from . import native

@@ -57,7 +57,8 @@ class Stitcher:
                  normalization: Optional[str] = 'phase', zarr_compression: str = 'blosc',
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
                  all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none',
-                 focus_radius: int = 3, pyramid_method: str = 'nearest'):
+                 focus_radius: int = 3, pyramid_method: str = 'nearest', contrast_limits: str = 'dtype',
+                 contrast_percentiles=(0.1, 99.9)):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -102,6 +103,14 @@ class Stitcher:
         # 'mean' = the truncated 2 x 2 mean its other stitchers store (zarr_stitcher.py:614-719), all levels from one read of
         # level 0 (sq_pyramid_mean).  Applies to every store a run writes (stack, _mip, _edf); .ome.tiff holds level 0 only.
         self.pyramid_method = omezarr.check_pyramid_method(pyramid_method)
+        # Extension: the channel windows of the omero block.  'dtype' = the reference's 0 ... np.iinfo(dtype).max
+        # (stitcher.py:846-850); 'percentile' = contrast_percentiles (lo, hi) of the non-zero voxels of each store's own level 0,
+        # from exact histograms the stream writer keeps on the device (sq_histogram_planes), with a _histogram.npy and a
+        # _stats.json beside every store.  OME-XML has no rendering window, so .ome.tiff output refuses it.
+        self.contrast_limits, self.contrast_percentiles = omezarr.check_contrast(contrast_limits, contrast_percentiles)
+        if self.contrast_limits == 'percentile' and not self.output_format.endswith('.zarr'):
+            raise ValueError("contrast_limits='percentile' needs .ome.zarr output: OME-XML (.ome.tiff) has no rendering window "
+                             "to carry the channel windows")
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -138,6 +147,7 @@ class Stitcher:
         # region k are written while region k + 1 is read, registered and fused); run() drains it once at the end
         self._stream_writer = None
         self._defer_drain = False
+        self._contrast_pending = []      # (store, pinned counts, event, device counts) of streamed regions, see _finish_contrast
         self.canvas_arena_info = None
         self.init_stitching_parameters()
 
@@ -1014,6 +1024,46 @@ class Stitcher:
         return flat_canvas, plane_ids
 
     # ------------------------------------------------------------------ output
+    # ------------------------------------------------------------------ contrast windows
+    def _new_histogram(self):
+        """A zeroed histogram target for one store ([C, bins] int64 on the device), or None with contrast_limits='dtype'."""
+        if self.contrast_limits != 'percentile':
+            return None
+        import torch
+        return torch.zeros((self.num_c, native.histogram_bins(self.dtype)), dtype=torch.int64, device=self.device)
+
+    def _write_contrast(self, path: str, hist, shared: bool = False) -> None:
+        """Windows and sidecars of the store ``path`` from the counts of what was submitted to it.  Reading ``hist`` back waits
+        for the stream the histograms were launched on, not for the writer's chunk pipeline.  ``shared``: the ranks of a shared
+        region each hold the counts of what they wrote; they are summed (every rank takes part) and rank 0 writes."""
+        if hist is None:
+            return
+        side = getattr(self, '_ingest_stream', None)
+        if side is not None:      # run() fuses (and counts) on a stream of its own
+            import torch
+            torch.cuda.current_stream(self.device).wait_stream(side)
+        rank = 0
+        if shared:
+            import torch.distributed as dist
+            rank = dist.get_rank()
+            if dist.get_backend() != 'nccl':
+                host = hist.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM)
+                hist = host
+            else:
+                dist.all_reduce(hist, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            lo, hi = self.contrast_percentiles
+            omezarr.write_contrast(path, hist.cpu().numpy(), lo, hi, self.dtype)
+
+    def _finish_contrast(self, wait: bool) -> None:
+        """Windows and sidecars of the streamed stores whose counts have reached the host (``wait``: of all of them)."""
+        while self._contrast_pending and (wait or self._contrast_pending[0][2].query()):
+            path, host, event, _ = self._contrast_pending.pop(0)
+            event.synchronize()
+            lo, hi = self.contrast_percentiles
+            omezarr.write_contrast(path, host.numpy(), lo, hi, self.dtype)
+
     def _zarr_path(self, timepoint, region) -> str:
         return os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched.ome.zarr")
 
@@ -1026,11 +1076,13 @@ class Stitcher:
         device kernel either way."""
         output_path = self._zarr_path(timepoint, region)
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
+        hist = self._new_histogram()
         write_ome_zarr(output_path, stitched_region, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                        channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                        num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                        name=f"{region}_t{timepoint}", compression=self.zarr_compression,
-                       pyramid_method=self.pyramid_method, device=self.device)
+                       pyramid_method=self.pyramid_method, device=self.device, histogram=hist)
+        self._write_contrast(output_path, hist)
         return output_path
 
     def _projection_kind(self) -> Optional[str]:
@@ -1059,11 +1111,13 @@ class Stitcher:
         output_path = self._mip_path(timepoint, region, kind)
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
         if self.output_format.endswith('.zarr'):
+            hist = self._new_histogram()
             write_ome_zarr(output_path, mip, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                            channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                            num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                            name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression,
-                           pyramid_method=self.pyramid_method, device=self.device)
+                           pyramid_method=self.pyramid_method, device=self.device, histogram=hist)
+            self._write_contrast(output_path, hist)
             return output_path
         if hasattr(mip, 'cpu'):
             mip = mip.cpu().numpy()
@@ -1099,11 +1153,16 @@ class Stitcher:
         return output_path, shapes
 
     def stream_region_to_zarr(self, timepoint, region, only_planes=None, progress_callback=None, create: bool = True,
-                              row_band=None, project_to=None):
+                              row_band=None, project_to=None, histogram=None):
         """stitch_region + save_region_ome_zarr without the region ever existing in one piece: planes
         are fused a batch at a time and stream through pyramid kernel, pinned D2H copy and compression
         threads while the next batch is read and fused.  Same store as
-        ``save_region_ome_zarr(t, r, stitch_region(t, r))``."""
+        ``save_region_ome_zarr(t, r, stitch_region(t, r))``.  ``histogram``: the caller's histogram target (a shared region's
+        ranks call this once per row band and finish the windows themselves); None: with contrast_limits='percentile' a fresh
+        target is taken and the store's windows and sidecars are written when its last plane has been submitted."""
+        own_histogram = histogram is None and create
+        if own_histogram:
+            histogram = self._new_histogram()
         if create:
             output_path, shapes = self.create_region_store(timepoint, region)
         else:
@@ -1124,6 +1183,7 @@ class Stitcher:
             w = self._stream_writer
             if w is not None and w.matches(shapes, self.dtype, batch, self.zarr_compression, chunks, self.pyramid_method):
                 w.retarget(output_path, row_offset, level_heights)      # the same geometry: the next store through the same writer
+                w.histogram = histogram
                 made.append(w)
                 return w
             self._close_stream_writer()
@@ -1143,6 +1203,7 @@ class Stitcher:
                                                   level_heights=level_heights, canvas_arena=arena))
             self._keep_buffers(key, made[-1].buffers)
             self._stream_writer = made[-1]
+            made[-1].histogram = histogram
             return made[-1]
 
         before = self._stream_writer.bytes_written if self._stream_writer is not None else 0
@@ -1150,6 +1211,22 @@ class Stitcher:
                                     project_to=project_to)
         # bytes of this region's chunks (under run() the writer is drained at the end: the count then lags by what is in flight)
         self.last_bytes_written = sum(w.bytes_written for w in set(made)) - (before if self._stream_writer in made else 0)
+        for w in made:
+            w.histogram = None
+        if own_histogram and histogram is not None:
+            if self._defer_drain and getattr(self, '_ingest_stream', None) is not None:
+                # run() streams region after region on a stream of its own: the counts leave the device behind this region's last
+                # launch, and the windows are written once they have arrived (the next region is not held up)
+                import torch
+                host = torch.empty(histogram.shape, dtype=histogram.dtype, pin_memory=True)
+                with torch.cuda.stream(self._ingest_stream):
+                    host.copy_(histogram, non_blocking=True)
+                    event = torch.cuda.Event()
+                    event.record()
+                self._contrast_pending.append((output_path, host, event, histogram))
+                self._finish_contrast(wait=False)
+            else:
+                self._write_contrast(output_path, histogram)
         return output_path
 
     def close(self) -> None:
@@ -1196,17 +1273,23 @@ class Stitcher:
         by_band = {}
         for p, b in units if stack else ():
             by_band.setdefault(b, []).append(p)
+        # --contrast-limits percentile: every rank counts what it writes (planes or row bands), per store
+        stack_hist = self._new_histogram() if stack else None
+        proj_hist = self._new_histogram() if self.z_projection != 'none' else None
         for b, planes in by_band.items():
             output_path = self.stream_region_to_zarr(timepoint, region, planes, progress_callback=self.update_progress.emit,
-                                                     create=False, row_band=None if b < 0 else bands[b])
+                                                     create=False, row_band=None if b < 0 else bands[b], histogram=stack_hist)
         if self.z_projection != 'none':
-            output_path = self._project_region_units(timepoint, region, bands, rank, world)
+            output_path = self._project_region_units(timepoint, region, bands, rank, world, histogram=proj_hist)
             if stack:
                 output_path = self._zarr_path(timepoint, region)
+        # ... and the counts are summed over the ranks (one that was dealt no unit adds zeros), rank 0 writes the windows
+        self._write_contrast(self._zarr_path(timepoint, region), stack_hist, shared=True)
+        self._write_contrast(self._mip_path(timepoint, region, self._projection_kind() or 'mip'), proj_hist, shared=True)
         sharding.barrier()
         return output_path
 
-    def _project_region_units(self, timepoint, region, bands, rank, world) -> str:
+    def _project_region_units(self, timepoint, region, bands, rank, world, histogram=None) -> str:
         """This rank's share of a shared region's projection: (channel, row band) units dealt like the stack's (plane, band)
         units (sharding.plane_band_units over the channels), each projected from the tiles of its channel that reach its band
         and written as its own chunks of the store rank 0 created.  With 'max' / 'focus' the files of these channels are read a
@@ -1229,6 +1312,7 @@ class Stitcher:
                                            compression=self.zarr_compression,
                                            pyramid_method=self.pyramid_method, device=self.device, row_offset=y0,
                                            level_heights=None if b < 0 else [s[3] for s in full]) as writer:
+                writer.histogram = histogram
                 writer.acquire(1).copy_(proj)
                 writer.submit([(0, c, 0)])
         return output_path
@@ -1359,6 +1443,7 @@ class Stitcher:
         finally:
             self._defer_drain = False
             self._close_stream_writer()
+        self._finish_contrast(wait=True)
         sharding.barrier()
         self.starting_saving.emit(True)
         if self.merge_timepoints or self.merge_hcs_regions:

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus ten switches for what this build adds (``--fusion-mode``, ``--normalization``,
+plus twelve switches for what this build adds (``--fusion-mode``, ``--normalization``,
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
-``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``).
+``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``, ``--contrast-limits``,
+``--contrast-percentiles``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -61,6 +62,14 @@ FLAGS = (
                                       "nearest = the reference's Scaler.nearest decimation; mean = the truncated 2 x 2 mean of "
                                       "the level before, all levels from one read of level 0 on the device.  .ome.tiff output "
                                       "holds level 0 only, so there the option changes nothing")),
+    (('--contrast-limits',), dict(choices=['dtype', 'percentile'], default='dtype',
+                                  help="channel windows of the OME-Zarr omero block, in every store of the run (stack, _mip, _edf): "
+                                       "dtype = the reference's 0 ... dtype max; percentile = two percentiles of the non-zero "
+                                       "voxels of the store's own level 0, from exact histograms kept on the device, plus "
+                                       "<stem>_histogram.npy and <stem>_stats.json beside the store (.ome.zarr output only)")),
+    (('--contrast-percentiles',), dict(type=float, nargs=2, default=(0.1, 99.9), metavar=('LO', 'HI'),
+                                       help="with --contrast-limits percentile: the window's start and end percentile, "
+                                            "0 <= LO < HI <= 100")),
 )
 
 
@@ -117,7 +126,9 @@ def main(argv=None):
                             global_registration=args.global_registration,
                             z_projection=args.z_projection,
                             focus_radius=args.focus_radius,
-                            pyramid_method=args.pyramid_method)
+                            pyramid_method=args.pyramid_method,
+                            contrast_limits=args.contrast_limits,
+                            contrast_percentiles=tuple(args.contrast_percentiles))
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -297,6 +297,23 @@ int sq_pyramid_mean(const void *src_dev, int64_t src_plane_stride, int32_t src_h
                     int32_t n_planes, int32_t dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Histogram: exact per-value counts of a batch of 2-D planes, ADDED into caller-owned 64-bit rows
+ * (the caller zeroes them once):
+ *     hist[row_of_plane[p]][v] += #{ (y, x) : planes[p][y][x] == v }      for p < n_planes.
+ * The reference has no counterpart: the channel windows of its OME-Zarr stores are
+ * np.iinfo(self.dtype).max (stitcher.py:846-850); these counts are what --contrast-limits
+ * percentile derives the windows from.  dtype SQ_U16 (65536 bins per row) or SQ_U8 (256);
+ * plane_stride and pitch in elements, any positive h and w, no alignment asked of the base or
+ * the pitch beyond the element's own.  row_of_plane is a HOST array of n_planes entries,
+ * 0 <= row < n_rows; hist_dev is [n_rows][bins] uint64 on the device.  A row out of range is
+ * SQ_ERR_INVALID and nothing is launched.  Integer adds only: the result does not depend on
+ * arrival order.  No scratch, no allocation.
+ * ---------------------------------------------------------------------------------------- */
+int sq_histogram_planes(const void *planes_dev, int64_t plane_stride, int32_t h, int32_t w, int64_t pitch,
+                        int32_t n_planes, int32_t dtype, const int32_t *row_of_plane, int32_t n_rows,
+                        uint64_t *hist_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched

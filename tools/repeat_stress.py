@@ -98,6 +98,11 @@ first = [t.clone() for t in native.pyramid_mean(img, 5)]
 bad = sum(int(not all(torch.equal(x, y) for x, y in zip(native.pyramid_mean(img, 5), first))) for _ in range(REPS))
 report('mean pyramid, 5 levels in one launch, 1500x1900 x 2 planes', bad, REPS, t0)
 t0 = time.perf_counter()
+first = native.histogram_planes(img, [0, 1]).clone()
+bad = sum(int(not torch.equal(native.histogram_planes(img, [0, 1]), first)) for _ in range(REPS))
+bad += int(not torch.equal(first[0], torch.bincount(img[0].flatten().to(torch.int32), minlength=65536)))
+report('value histogram 1500x1900 x 2 planes, against torch.bincount and itself', bad, REPS, t0)
+t0 = time.perf_counter()
 b = native.blosc_encode_planes(img, 512, 512)
 torch.cuda.synchronize()
 off0, out0 = b.offsets.clone(), b.out[:int(b.offsets[-1])].clone()
