@@ -3058,3 +3058,258 @@ extern "C" int sq_fuse_project_focus(const sq_fuse_args *a, const sq_focus_args 
     SQ_FOCUS(uint8_t, double);
 #undef SQ_FOCUS
 }
+
+// ---------------------------------------------------------------------------------------------
+// guide channel of the best-focus projection (sq_focus_depth_plane, sq_fuse_select_depth)
+// ---------------------------------------------------------------------------------------------
+// Definition in include/squidstitch.h.  depth_plane_kernel: key plane -> unsigned depth plane (z* + 1, 0 = uncovered), streaming.
+// select_depth_kernel, canvas space: the overwrite plan's items like focus_canvas_kernel; per voxel the guide's depth, the plane
+// of this call at that z level (a table in LDS) and that plane's owner pixel through that plane's gains.
+// Algorithmic traffic of the select: 1..2 B (depth) read per voxel + sizeof(T) + gain bytes read per covered voxel whose depth is
+// in the call, sizeof(T) B written per voxel.
+namespace {
+constexpr int DEPTH_PER = 8;      // keys of a lane: four 16-byte loads, one 8- or 16-byte store
+constexpr int SEL_XU = 4;         // select: pixels a lane has in flight at once
+constexpr int SEL_MAP = 1024;     // z levels (counted from the call's lowest) the direct LDS table holds; beyond: a search
+
+template <typename D>
+__device__ __forceinline__ uint32_t depth_of_key(uint32_t lo, uint32_t hi) {
+    constexpr uint32_t TOP = sizeof(D) == 1 ? 0xFFu : 0xFFFFu;
+    if ((lo | hi) == 0) return 0u;             // no plane covers the voxel
+    const uint32_t z = 0xFFFFFFFFu - lo;
+    return z >= TOP ? TOP : z + 1u;            // (a z level the dtype cannot hold saturates; the caller sizes the dtype)
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void depth_plane_kernel(const uint64_t *key, int64_t key_pitch, int h, int w, D *depth,
+                                                          int64_t depth_pitch) {
+    const int x0 = (int)(blockIdx.x * 256 + threadIdx.x) * DEPTH_PER;
+    if (x0 >= w) return;
+    for (int y = blockIdx.y; y < h; y += gridDim.y) {
+        const uint64_t *krow = key + (int64_t)y * key_pitch + x0;
+        D *drow = depth + (int64_t)y * depth_pitch + x0;
+        if (x0 + DEPTH_PER <= w) {
+            u32x4 k[DEPTH_PER / 2];
+#pragma unroll
+            for (int i = 0; i < DEPTH_PER / 2; ++i) k[i] = ldg<U32x4U>(krow + 2 * i);
+            uint32_t d[DEPTH_PER];
+#pragma unroll
+            for (int i = 0; i < DEPTH_PER / 2; ++i) {
+                d[2 * i] = depth_of_key<D>(k[i][0], k[i][1]);
+                d[2 * i + 1] = depth_of_key<D>(k[i][2], k[i][3]);
+            }
+            if constexpr (sizeof(D) == 1) {
+                ((SQ_GLOBAL U32x2U *)drow)->v =
+                    u32x2{d[0] | (d[1] << 8) | (d[2] << 16) | (d[3] << 24), d[4] | (d[5] << 8) | (d[6] << 16) | (d[7] << 24)};
+            } else {
+                ((SQ_GLOBAL U32x4U *)drow)->v = u32x4{d[0] | (d[1] << 16), d[2] | (d[3] << 16), d[4] | (d[5] << 16), d[6] | (d[7] << 16)};
+            }
+        } else {
+            for (int i = 0; x0 + i < w; ++i) {
+                const u32x2 k = ldg<U32x2U>(krow + i);
+                stg_s<D>(drow + i, (D)depth_of_key<D>(k[0], k[1]));
+            }
+        }
+    }
+}
+
+struct SelectParams {
+    const void *depth;      // the guide's depth plane, depth_pitch elements between rows
+    const uint32_t *zlev;   // z level of each of the call's planes
+    int32_t depth_pitch;
+    int32_t depth16;        // elements are uint16 (else uint8)
+};
+
+// the call's z levels for one workgroup: s_zlev[plane] and the direct table s_map[z - lowest z] = plane + 1 (0: not in the
+// call; of two planes with one z level the first).  -> (lowest z, whether a level lies beyond the table)
+__device__ __forceinline__ void select_table(const FuseParams &P, const SelectParams &S, uint32_t *s_zlev, uint16_t *s_map,
+                                             uint32_t &zmin, bool &sparse) {
+    const int nz = P.n_planes;
+    for (int p = threadIdx.x; p < nz; p += 256) s_zlev[p] = ldg_s<uint32_t>(S.zlev + p);
+    __syncthreads();
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (int p = 0; p < nz; ++p) {
+        lo = min(lo, s_zlev[p]);
+        hi = max(hi, s_zlev[p]);
+    }
+    for (int e = threadIdx.x; e < SEL_MAP; e += 256) {
+        uint32_t m = 0;
+        for (int p = nz - 1; p >= 0; --p)
+            if (s_zlev[p] - lo == (uint32_t)e) m = (uint32_t)p + 1u;
+        s_map[e] = (uint16_t)m;
+    }
+    __syncthreads();
+    zmin = (uint32_t)sgpr((int)lo);
+    sparse = sgpr((int)(hi - lo >= (uint32_t)SEL_MAP)) != 0;
+}
+
+// plane index within the call of depth value d (z + 1; 0 = uncovered), -1 when the call has no plane at that level
+__device__ __forceinline__ int select_plane(uint32_t d, uint32_t zmin, bool sparse, int nz, const uint32_t *s_zlev,
+                                            const uint16_t *s_map) {
+    if (d == 0u) return -1;
+    const uint32_t rel = d - 1u - zmin;
+    if (rel < (uint32_t)SEL_MAP) return (int)s_map[rel] - 1;
+    if (sparse)
+        for (int p = 0; p < nz; ++p)
+            if (s_zlev[p] == d - 1u) return p;
+    return -1;
+}
+
+template <typename T, typename G, bool ACC>
+__device__ __forceinline__ void select_item(const FuseParams &P, const SelectParams &S, const Item &it, const int wave, const int lane,
+                                            const uint32_t zmin, const bool sparse, const uint32_t *s_zlev, const uint16_t *s_map) {
+    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
+    typedef typename std::conditional<GAINS, G, float>::type GT;
+    const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
+    const int nz = P.n_planes;
+    T *canvas = static_cast<T *>(P.canvas);
+    const bool d16 = S.depth16 != 0;
+    auto depth_at = [&](const char *row, int x) -> uint32_t {
+        return d16 ? (uint32_t)ldg_s<uint16_t>(row + 2 * x) : (uint32_t)ldg_s<uint8_t>(row + x);
+    };
+    if (!it.nref) {   // uncovered canvas: 0, like that plane of the stack (accumulating: only where the depth is this call's)
+        for (int r = wave; r < rows; r += 4) {
+            T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
+            if (!ACC) {
+                row_zero<T>(drow, n, lane);
+                continue;
+            }
+            const char *prow = static_cast<const char *>(S.depth) + ((int64_t)(it.dst_y + r) * S.depth_pitch + it.dst_x) * (d16 ? 2 : 1);
+            for (int x = lane; x < n; x += 64)
+                if (select_plane(depth_at(prow, x), zmin, sparse, nz, s_zlev, s_map) >= 0) stg_s<T>(drow + x, (T)0);
+        }
+        return;
+    }
+    for (int r = wave; r < rows; r += 4) {
+        T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
+        const char *prow = static_cast<const char *>(S.depth) + ((int64_t)(it.dst_y + r) * S.depth_pitch + it.dst_x) * (d16 ? 2 : 1);
+        const int64_t soff = (int64_t)(it.b + r) * P.tile_pitch + it.c;   // elements into the chosen plane's tile
+        const int64_t foff = (int64_t)(it.b + r) * P.tile_w + it.c;       // elements into a gain image
+        // SEL_XU pixels per lane at a time: the depths of all of them first (clamped to the row: every address is valid), then
+        // the loads that depend on them, then the stores
+        for (int x0 = lane; x0 < n; x0 += 64 * SEL_XU) {
+            uint32_t d[SEL_XU];
+#pragma unroll
+            for (int u = 0; u < SEL_XU; ++u) d[u] = depth_at(prow, min(x0 + 64 * u, n - 1));
+            int zi[SEL_XU];
+            T t[SEL_XU];
+            GT g[SEL_XU];
+            bool has_g[SEL_XU];
+#pragma unroll
+            for (int u = 0; u < SEL_XU; ++u) {
+                const int xc = min(x0 + 64 * u, n - 1);
+                zi[u] = select_plane(d[u], zmin, sparse, nz, s_zlev, s_map);
+                const int zp = max(zi[u], 0);      // (a voxel without a plane loads plane 0's pixel and does not use it)
+                t[u] = ldg_s<T>(tile_ptr<T>(P, zp, it.a) + soff + xc);
+                has_g[u] = false;
+                g[u] = (GT)1;
+                if constexpr (GAINS) {
+                    const GT *fz = static_cast<const GT *>(P.flat_ptrs[zp]);
+                    has_g[u] = fz != nullptr;
+                    if (has_g[u]) g[u] = ldg_s<GT>(fz + foff + xc);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SEL_XU; ++u) {
+                if (x0 + 64 * u >= n) continue;
+                if (zi[u] < 0) {
+                    if (!ACC) stg_s<T>(drow + x0 + 64 * u, (T)0);
+                    continue;
+                }
+                T v = t[u];
+                if constexpr (GAINS) {
+                    if (has_g[u]) v = flat_generic<T, GT>(t[u], g[u]);
+                }
+                stg_s<T>(drow + x0 + 64 * u, v);
+            }
+        }
+    }
+}
+
+template <typename T, typename G, bool ACC, bool DYN>
+__global__ __launch_bounds__(256) void select_depth_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work,
+                                                           const SelectParams S) {
+    __shared__ uint32_t s_zlev[SQ_FOCUS_MAX_PLANES];
+    __shared__ uint16_t s_map[SEL_MAP];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    uint32_t zmin;
+    bool sparse;
+    select_table(P, S, s_zlev, s_map, zmin, sparse);
+    if (!DYN) {
+        for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x)
+            select_item<T, G, ACC>(P, S, sgpr(P.items[w]), wave, lane, zmin, sparse, s_zlev, s_map);
+        return;
+    }
+    for_each_queued_item<ProjAux>(
+        P, n_items, 1u, [&](int, const Item &, int64_t) -> ProjAux { return ProjAux{0}; },
+        [&](int, const Item &it, const ProjAux &) { select_item<T, G, ACC>(P, S, it, wave, lane, zmin, sparse, s_zlev, s_map); });
+}
+}  // namespace
+
+extern "C" int sq_focus_depth_plane(const void *key_dev, int32_t key_pitch, int32_t h, int32_t w, void *depth_dev,
+                                    int32_t depth_pitch, int32_t depth_dtype, void *stream_) {
+    static const char *who = "sq_focus_depth_plane";
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (h < 0 || w < 0) return fail(SQ_ERR_INVALID, "%s: plane %d x %d", who, h, w);
+    if (depth_dtype != SQ_U8 && depth_dtype != SQ_U16)
+        return fail(SQ_ERR_INVALID, "%s: depth dtype %d (uint8/uint16 only)", who, depth_dtype);
+    if (h == 0 || w == 0) return SQ_OK;
+    if (!key_dev || !depth_dev) return fail(SQ_ERR_INVALID, "%s: NULL key / depth plane", who);
+    if (key_pitch < w || depth_pitch < w) return fail(SQ_ERR_INVALID, "%s: pitch smaller than width", who);
+    if (reinterpret_cast<uintptr_t>(key_dev) % 8 || reinterpret_cast<uintptr_t>(depth_dev) % (size_t)depth_dtype)
+        return fail(SQ_ERR_INVALID, "%s: key plane not 8-byte aligned or depth plane not aligned to its element size", who);
+    const dim3 grid((unsigned)((w + 256 * DEPTH_PER - 1) / (256 * DEPTH_PER)), (unsigned)std::min(h, 65535));
+    if (depth_dtype == SQ_U8)
+        hipLaunchKernelGGL(depth_plane_kernel<uint8_t>, grid, dim3(256), 0, stream, static_cast<const uint64_t *>(key_dev),
+                           (int64_t)key_pitch, h, w, static_cast<uint8_t *>(depth_dev), (int64_t)depth_pitch);
+    else
+        hipLaunchKernelGGL(depth_plane_kernel<uint16_t>, grid, dim3(256), 0, stream, static_cast<const uint64_t *>(key_dev),
+                           (int64_t)key_pitch, h, w, static_cast<uint16_t *>(depth_dev), (int64_t)depth_pitch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return SQ_OK;
+}
+
+extern "C" int sq_fuse_select_depth(const sq_fuse_args *a, const void *depth_dev, int32_t depth_pitch, int32_t depth_dtype,
+                                    const uint32_t *z_levels_dev, int32_t flags, void *stream_) {
+    static const char *who = "sq_fuse_select_depth";
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    FuseParams P;
+    int32_t fl = 0;
+    if (const int rc = project_setup(who, a, flags, stream, P, &fl)) return rc;
+    if (!depth_dev || !z_levels_dev) return fail(SQ_ERR_INVALID, "%s: NULL depth plane / z levels", who);
+    if (depth_dtype != SQ_U8 && depth_dtype != SQ_U16)
+        return fail(SQ_ERR_INVALID, "%s: depth dtype %d (uint8/uint16 only)", who, depth_dtype);
+    if (a->n_planes > SQ_FOCUS_MAX_PLANES)
+        return fail(SQ_ERR_INVALID, "%s: %d planes, a call selects among at most %d", who, a->n_planes, SQ_FOCUS_MAX_PLANES);
+    if (depth_pitch < a->canvas_w || reinterpret_cast<uintptr_t>(depth_dev) % (size_t)depth_dtype)
+        return fail(SQ_ERR_INVALID, "%s: depth plane pitch %d < width %d, or not aligned to its element size", who, depth_pitch,
+                    a->canvas_w);
+    SelectParams S{};
+    S.depth = depth_dev;
+    S.zlev = z_levels_dev;
+    S.depth_pitch = depth_pitch;
+    S.depth16 = depth_dtype == SQ_U16;
+    const int64_t n_items = a->plan->header().n_items;
+    const bool acc = (fl & SQ_SELECT_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
+    const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
+#define SQ_SELECT(T, G)                                                                                                            \
+    do {                                                                                                                           \
+        if (acc) {                                                                                                                 \
+            if (P.queue) return launch_project(who, select_depth_kernel<T, G, true, true>, P, n_items, stream, a->grid_blocks, S);  \
+            return launch_project(who, select_depth_kernel<T, G, true, false>, P, n_items, stream, a->grid_blocks, S);             \
+        }                                                                                                                          \
+        if (P.queue) return launch_project(who, select_depth_kernel<T, G, false, true>, P, n_items, stream, a->grid_blocks, S);     \
+        return launch_project(who, select_depth_kernel<T, G, false, false>, P, n_items, stream, a->grid_blocks, S);                \
+    } while (0)
+    if (u16) {
+        if (flat == 0) SQ_SELECT(uint16_t, NoGain);
+        if (flat == 1) SQ_SELECT(uint16_t, float);
+        SQ_SELECT(uint16_t, double);
+    }
+    if (flat == 0) SQ_SELECT(uint8_t, NoGain);
+    if (flat == 1) SQ_SELECT(uint8_t, float);
+    SQ_SELECT(uint8_t, double);
+#undef SQ_SELECT
+}

@@ -23,6 +23,7 @@ SQ_NORM_NONE, SQ_NORM_PHASE = 0, 1
 SQ_FUSE_FORCE_QUEUES, SQ_FUSE_FORCE_STATIC, SQ_FUSE_NO_PLANE_GROUPS, SQ_FUSE_NO_SEAM_OWNERS, SQ_FUSE_CONSECUTIVE_GROUPS = 1, 2, 4, 8, 16
 SQ_PROJECT_ACCUMULATE = 32
 SQ_FOCUS_ACCUMULATE = 32
+SQ_SELECT_ACCUMULATE = 32
 SQ_FOCUS_MAX_RADIUS = 15
 SQ_FOCUS_MAX_PLANES = 256
 SQ_VERSION = 108
@@ -109,6 +110,8 @@ EXPORTS = {
     'sq_fuse_project_max': (C.c_int, [C.POINTER(_FuseArgs), C.c_int32, C.c_void_p]),
     'sq_focus_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'sq_fuse_project_focus': (C.c_int, [C.POINTER(_FuseArgs), C.POINTER(_FocusArgs), C.c_int32, C.c_void_p]),
+    'sq_focus_depth_plane': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    'sq_fuse_select_depth': (C.c_int, [C.POINTER(_FuseArgs), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     'sq_tile_minmax': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_pair_overlap_moments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -577,6 +580,99 @@ def depth_of_keys(key):
         return torch.where(key == 0, torch.full_like(key, -1), 0xFFFFFFFF - (key & 0xFFFFFFFF))
     key = np.asarray(key).astype(np.int64)
     return np.where(key == 0, -1, 0xFFFFFFFF - (key & 0xFFFFFFFF))
+
+
+def depth_dtype_for(num_z: int) -> np.dtype:
+    """The dtype of the unsigned depth plane (z* + 1, 0 = uncovered) of a stack of ``num_z`` levels: uint8 up to 255 levels."""
+    if not 1 <= int(num_z) <= 65535:
+        raise ValueError(f"a depth plane holds 1..65535 z levels, got {num_z}")
+    return np.dtype('uint8') if int(num_z) <= 255 else np.dtype('uint16')
+
+
+def _check_plane(name, t, shape):
+    if not t.is_cuda or t.dim() != 2 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a [{shape[0]}, {shape[1]}] device tensor")
+    if (shape[1] > 1 and t.stride(1) != 1) or (shape[0] > 1 and t.stride(0) < shape[1]):
+        raise ValueError(f"{name} must have unit-stride rows")
+
+
+def focus_depth_plane(key, out=None, dtype=None, stream=None):
+    """The unsigned depth plane of a key plane of ``fuse_project_focus`` (sq_focus_depth_plane): z* + 1 per voxel, 0 where the
+    key is 0 (no plane covers the voxel).  key: [Hc, Wc] device int64 tensor with unit-stride rows.  out: [Hc, Wc] device uint8 /
+    uint16 tensor with unit-stride rows, allocated here (``dtype``, default uint8) when None.  Levels the dtype cannot hold
+    saturate: size it with ``depth_dtype_for(num_z)``."""
+    import torch
+    if not torch.is_tensor(key) or key.dtype != torch.int64 or key.dim() != 2:
+        raise ValueError("key must be a [Hc, Wc] int64 device tensor")
+    shape = tuple(key.shape)
+    _check_plane('key', key, shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch_dtype_of(np.dtype(dtype or 'uint8')), device=key.device)
+    elif dtype is not None and np_dtype_of_torch(out.dtype) != np.dtype(dtype):
+        raise ValueError(f"out is {out.dtype}, dtype asks for {np.dtype(dtype)}")
+    _check_plane('out', out, shape)
+    if out.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("the depth plane is uint8 or uint16")
+    h, w = shape
+    _check(lib().sq_focus_depth_plane(key.data_ptr(), int(key.stride(0)) if h > 1 else w, h, w, out.data_ptr(),
+                                      int(out.stride(0)) if h > 1 else w, sq_dtype_of(np_dtype_of_torch(out.dtype)),
+                                      _stream_ptr(stream)), 'sq_focus_depth_plane')
+    return out
+
+
+def fuse_select_depth(plan: FusePlan, tiles, out, depth, z_levels, flats=None, accumulate: bool = False, tile_ptrs=None,
+                      flags: int = 0, stream=None, flat_ptrs=None, grid_blocks: int = 0) -> None:
+    """A follower channel of the best-focus projection with a guide channel (sq_fuse_select_depth): per voxel
+    ``out`` = what ``fuse_planes`` stores there for the plane of this call whose z level is the guide's depth, 0 where the plan
+    does not cover the voxel.
+
+    out:      [Hc, Wc] device tensor of the tile dtype with unit-stride rows.
+    depth:    [Hc, Wc] device uint8 / uint16 tensor with unit-stride rows: the guide's depth plane (``focus_depth_plane``).
+    z_levels: the distinct z levels of the call's Z planes (a sequence, or a device int64 / int32 tensor).
+    tiles / tile_ptrs / flats / flat_ptrs: as in ``fuse_project_max`` (Z = tiles.shape[0]; at most 256 planes per call).
+    accumulate: voxels whose depth is not among ``z_levels`` are left untouched (the z planes of a channel that come in several
+              calls, in any z order, or under different plans); otherwise they are written 0, so every voxel is written."""
+    import torch
+    L = lib()
+    if plan.mode != SQ_FUSE_OVERWRITE:
+        raise ValueError("fuse_select_depth selects from overwrite plans only")
+    shape = (plan.canvas_h, plan.canvas_w)
+    _check_plane('out', out, shape)
+    _check_plane('depth', depth, shape)
+    if depth.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("depth must be a uint8 or uint16 tensor")
+    hc, wc = shape
+    pitch = int(out.stride(0)) if hc > 1 else wc
+    depth_pitch = int(depth.stride(0)) if hc > 1 else wc
+    if tile_ptrs is not None:
+        n_planes = int(tile_ptrs.numel()) // max(plan.n_tiles, 1) if plan.n_tiles else (len(flats) if flats is not None else 1)
+    elif tiles is not None:
+        n_planes = int(tiles.shape[0]) if tiles.dim() == 4 else 1
+    else:
+        raise ValueError("tiles or tile_ptrs is required")
+    if not 1 <= n_planes <= SQ_FOCUS_MAX_PLANES:
+        raise ValueError(f"{n_planes} planes: a call selects among 1..{SQ_FOCUS_MAX_PLANES}")
+    keep = []
+    if torch.is_tensor(z_levels) and z_levels.is_cuda:
+        zl = z_levels.to(torch.int32)
+    else:
+        zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
+        if any(not 0 <= z < 2 ** 32 for z in zs):
+            raise ValueError("z levels must lie in 0 .. 2^32 - 1")
+        if len(set(zs)) != len(zs):
+            raise ValueError("the z levels of a call must be distinct")
+        zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
+    if zl.numel() != n_planes:
+        raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
+    keep.append(zl)
+    a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
+    a.flags, a.grid_blocks = 0, int(grid_blocks)
+    if stream is not None:
+        for t in keep:
+            t.record_stream(stream)
+    fl = int(flags) | (SQ_SELECT_ACCUMULATE if accumulate else 0)
+    _check(L.sq_fuse_select_depth(C.byref(a), depth.data_ptr(), depth_pitch, sq_dtype_of(np_dtype_of_torch(depth.dtype)),
+                                  zl.data_ptr(), fl, _stream_ptr(stream)), 'sq_fuse_select_depth')
 
 
 PLANE_ALIGN_BYTES = 128

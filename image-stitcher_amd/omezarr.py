@@ -453,6 +453,39 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
     return path
 
 
+def depth_labels(channel_names: Sequence[str], guide: Optional[str] = None) -> List[str]:
+    """Channel labels of a depth store: ``depth(<guide>)`` alone with a guide channel, else ``depth(<name>)`` per channel."""
+    return [f'depth({guide})'] if guide is not None else [f'depth({n})' for n in channel_names]
+
+
+def write_depth_store(path: str, depth, *, num_z: int, labels: Sequence[str], pixel_size_um: float, dz_um: float = 1.0,
+                      num_levels: int = 1, chunks=(1, 1, 1, 512, 512), name: str = 'depth', compression: str = 'zlib',
+                      device=None) -> str:
+    """The depth map of a best-focus projection as an OME-Zarr image: ``depth`` (1, K, 1, Y, X) uint8 / uint16 (numpy or a
+    device tensor) holds z* + 1 per voxel, 0 = uncovered.  The levels above 0 are always the NEAREST decimation (a mean of
+    depths is no depth) and every channel's window is 0 ... ``num_z``, whatever the run's pyramid method and contrast limits.
+    A numpy array with a host codec is decimated and written on the host; everything else goes through ``write_ome_zarr``."""
+    if depth.ndim != 5 or depth.shape[0] != 1 or depth.shape[2] != 1 or depth.shape[1] != len(labels):
+        raise ValueError(f"expected a (1, {len(labels)}, 1, Y, X) depth array, got {tuple(depth.shape)}")
+    if str(depth.dtype).replace('torch.', '') not in ('uint8', 'uint16'):
+        raise ValueError(f"the depth plane is uint8 or uint16, got {depth.dtype}")
+    colors = [0xFFFFFF] * len(labels)
+    if not hasattr(depth, 'data_ptr') and compression in HOST_CODECS:
+        shape = tuple(int(v) for v in depth.shape)
+        shapes = create_store(path, shape, depth.dtype, pixel_size_um=pixel_size_um, dz_um=dz_um, channel_names=labels,
+                              channel_colors=colors, num_levels=num_levels, chunks=chunks, name=name, compression=compression)
+        levels = [np.ascontiguousarray(depth.reshape((-1,) + shape[3:]))]
+        for shp in shapes[1:]:      # index 2 o + 1 of the level before (Scaler.nearest, as sq_downsample2)
+            levels.append(np.ascontiguousarray(levels[-1][:, 1::2, 1::2][:, :shp[3], :shp[4]]))
+        write_plane_levels(path, levels, [(0, c, 0) for c in range(shape[1])], chunks, compression)
+    else:
+        write_ome_zarr(path, depth, pixel_size_um=pixel_size_um, dz_um=dz_um, channel_names=labels, channel_colors=colors,
+                       num_levels=num_levels, chunks=chunks, name=name, compression=compression, device=device,
+                       pyramid_method='nearest')
+    set_channel_windows(path, [(0, int(num_z))] * len(labels))
+    return path
+
+
 class PlaneStreamWriter:
     """Streams fused planes from the device into a store made by ``create_store``.
 

@@ -52,13 +52,25 @@ class Signal:
             fn(*args)
 
 
+class FocusFollower:
+    """A ``stitch_planes(project_to=...)`` target for a channel that follows the guide channel of the best-focus projection:
+    ``out`` [Hc, Wc] receives, per voxel, the channel's fused value at the guide's depth (sq_fuse_select_depth); ``depth``
+    [Hc, Wc] uint8 / uint16 is the guide's unsigned depth plane.  ``guide``: the guide's channel index when its (output, key)
+    target is in the same ``project_to`` -- ``depth`` is then derived there once the guide's last plane has been projected --
+    or None when ``depth`` is already filled."""
+    __slots__ = ('out', 'depth', 'guide')
+
+    def __init__(self, out, depth, guide=None):
+        self.out, self.depth, self.guide = out, depth, guide
+
+
 class Stitcher:
     def __init__(self, params: StitchingParameters, device=None, fusion_mode: str = 'overwrite',
                  normalization: Optional[str] = 'phase', zarr_compression: str = 'blosc',
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
                  all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none',
                  focus_radius: int = 3, pyramid_method: str = 'nearest', contrast_limits: str = 'dtype',
-                 contrast_percentiles=(0.1, 99.9)):
+                 contrast_percentiles=(0.1, 99.9), focus_guide_channel: Optional[str] = None, focus_depth_map: bool = False):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -99,6 +111,17 @@ class Stitcher:
             raise ValueError(f"focus_radius must be an integer in 0..{native.SQ_FOCUS_MAX_RADIUS}, got {focus_radius!r}")
         self.z_projection = z_projection
         self.focus_radius = int(focus_radius)
+        # Extension of the best-focus projection: focus_guide_channel = a name out of monochrome_channels whose depth decides
+        # for every channel (the others take their fused value at the guide's depth: sq_fuse_select_depth);
+        # focus_depth_map = also write the depth (z* + 1, 0 = uncovered) to <region>_stitched_depth<format>.
+        if (focus_guide_channel is not None or focus_depth_map) and z_projection not in ('focus', 'focus-only'):
+            raise ValueError("focus_guide_channel / focus_depth_map belong to the best-focus projection: they need "
+                             f"z_projection 'focus' or 'focus-only', got {z_projection!r}")
+        if focus_guide_channel is not None and not isinstance(focus_guide_channel, str):
+            raise ValueError(f"focus_guide_channel must be a channel name, got {focus_guide_channel!r}")
+        self.focus_guide_channel = focus_guide_channel
+        self.focus_depth_map = bool(focus_depth_map)
+        self._guide = None      # the guide's index in monochrome_channels, once the metadata is parsed
         # Extension: how the OME-Zarr levels above 0 are made.  'nearest' = the reference's Scaler.nearest (stitcher.py:797-798);
         # 'mean' = the truncated 2 x 2 mean its other stitchers store (zarr_stitcher.py:614-719), all levels from one read of
         # level 0 (sq_pyramid_mean).  Applies to every store a run writes (stack, _mip, _edf); .ome.tiff holds level 0 only.
@@ -284,6 +307,11 @@ class Stitcher:
                 self.monochrome_channels.append(channel)
         self.num_c = len(self.monochrome_channels)
         self.monochrome_colors = [self.get_channel_color(n) for n in self.monochrome_channels]
+        if self.focus_guide_channel is not None:
+            if self.focus_guide_channel not in self.monochrome_channels:
+                raise ValueError(f"focus_guide_channel {self.focus_guide_channel!r} is not a channel of this acquisition: "
+                                 f"{self.monochrome_channels}")
+            self._guide = self.monochrome_channels.index(self.focus_guide_channel)
         print(f"[metadata] regions {self.regions}; channels {self.channel_names}")
         print(f"[metadata] tile {self.input_height} x {self.input_width} {np.dtype(self.dtype)}")
         print(f"[metadata] {self.num_z} z levels, {self.num_t} timepoints, {self.num_fovs_per_region} fovs per region")
@@ -755,9 +783,8 @@ class Stitcher:
         staged tiles without the stack (sq_fuse_project_focus; an extension, the reference has none).
         ``return_depth``: also the winning z level of every voxel, (C, Hc, Wc) int32, -1 where no tile covers it.
         Returns numpy (host) unless ``device_output``."""
-        out, key = self._new_focus(timepoint, region)
-        self.stitch_planes(timepoint, region, None, progress_callback, stack=False,
-                           project_to={c: (out[c], key[c]) for c in range(self.num_c)})
+        out, key, _, project_to = self._focus_target(timepoint, region)
+        self.stitch_planes(timepoint, region, None, progress_callback, stack=False, project_to=project_to)
         import torch
         img = out.unsqueeze(0).unsqueeze(2)
         if not device_output:
@@ -765,7 +792,37 @@ class Stitcher:
         if not return_depth:
             return img
         depth = native.depth_of_keys(key).to(torch.int32)
+        if self._guide is not None:      # one depth for all channels: the guide's
+            depth = depth.expand(self.num_c, -1, -1)
         return img, (depth if device_output else depth.cpu().numpy())
+
+    def _depth_dtype(self):
+        return native.torch_dtype_of(native.depth_dtype_for(self.num_z))
+
+    def _focus_target(self, timepoint, region, rows=None, channels=None, depth=None):
+        """Device buffers and the stitch_planes ``project_to`` of the best-focus projection of ``channels`` (None = all) of a
+        region (a row band's rows with ``rows``) -> (output [n, Hc, Wc], key [k, Hc, Wc] int64, depth [k, Hc, Wc] unsigned or
+        None, project_to).  Without a guide channel every channel has its own key plane (k = n) and no depth plane is taken.
+        With one, only the guide has a key plane (k = 1, or 0 when it is not among ``channels``) and the other channels
+        follow ``depth`` [1, Hc, Wc]: the caller's, already filled, or a fresh one that stitch_planes derives from the guide's
+        key plane -- the guide then has to be among ``channels``."""
+        import torch
+        chans = list(range(self.num_c)) if channels is None else [int(c) for c in channels]
+        out = self._new_projection(timepoint, region, rows, len(chans))
+        g = self._guide
+        if g is None:
+            key = torch.empty(tuple(out.shape), dtype=torch.int64, device=self.device)
+            return out, key, None, {c: (out[i], key[i]) for i, c in enumerate(chans)}
+        key = torch.empty((1 if g in chans else 0,) + tuple(out.shape[1:]), dtype=torch.int64, device=self.device)
+        derive = depth is None
+        if derive:
+            if g not in chans and len(chans):
+                raise ValueError("channels that follow the guide need its depth plane, or the guide among them")
+            depth = torch.empty((1,) + tuple(out.shape[1:]), dtype=self._depth_dtype(), device=self.device)
+        project_to = {}
+        for i, c in enumerate(chans):
+            project_to[c] = (out[i], key[0]) if c == g else FocusFollower(out[i], depth[0], g if derive else None)
+        return out, key, depth, project_to
 
     def _new_focus(self, timepoint, region, rows=None, n_channels=None):
         """Device buffers (output [C, Hc, Wc] of the input dtype, key [C, Hc, Wc] int64) of a region's best-focus projections
@@ -803,7 +860,10 @@ class Stitcher:
         staged tiles as the stack: the first batch of a channel writes, later batches (and other rectangle lists) accumulate;
         a channel no file touches comes out as zeros.  A value (output [Hc, Wc], key [Hc, Wc] int64) receives the channel's
         best-focus projection and its key plane instead (sq_fuse_project_focus, radius ``self.focus_radius``; the windows
-        are the full staged tiles, so a row band projects exactly the rows of the whole region's projection).
+        are the full staged tiles, so a row band projects exactly the rows of the whole region's projection).  A
+        ``FocusFollower`` value receives the channel's fused value at the guide channel's depth (sq_fuse_select_depth): the
+        guide's planes are staged and projected first, over all rectangle lists, its depth plane is derived once
+        (sq_focus_depth_plane), and only then are the followers' planes staged.
         ``stack=False``: the projection only -- no canvas, no stream writer, no stack fusion; the return value is then
         (None, plane ids)."""
         import torch
@@ -909,20 +969,47 @@ class Stitcher:
             if stream_to is not None and groups:
                 widest = max(len(rect_of[sig]) for sig in groups) * th * tw * np.dtype(self.dtype).itemsize
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
-            focus = project_to is not None and any(isinstance(t, tuple) for t in project_to.values())
+            def parts_of(t):      # the tensors of a target that this call writes
+                return t if isinstance(t, tuple) else ((t.out,) if isinstance(t, FocusFollower) else (t,))
+
+            # the guide channel whose depth plane followers of this call wait for (FocusFollower.guide), if any
+            followers = {c: t for c, t in (project_to or {}).items() if isinstance(t, FocusFollower)}
+            guides = {t.guide for t in followers.values() if t.guide is not None}
+            if len(guides) > 1 or any(not isinstance(project_to.get(g), tuple) for g in guides):
+                raise ValueError("followers of one call share one guide channel, whose (output, key) target is in project_to")
+            guide = guides.pop() if guides else None
             if project_to is not None:
                 for t in project_to.values():
-                    for u in (t if isinstance(t, tuple) else (t,)):
+                    for u in parts_of(t) + ((t.depth,) if isinstance(t, FocusFollower) else ()):
                         u.record_stream(torch.cuda.current_stream(self.device))
                 for c in project_to:
                     if not any(p // self.num_z == c for p in planes):
-                        for u in (project_to[c] if isinstance(project_to[c], tuple) else (project_to[c],)):
+                        for u in parts_of(project_to[c]):
                             u.zero_()      # no file of this channel: zeros, like its planes of the stack
-            for sig, plist in groups.items():
+            # the passes over the rectangle lists: normally one per list.  With a guide channel: its planes first, over ALL lists;
+            # then its depth plane; then the channels below and above it (a chunk never mixes the guide with another channel,
+            # and never spans the gap it leaves: the stack pass keeps its evenly spaced canvas slots and single launch)
+            work = []
+            if guide is None:
+                work = [(sig, sorted(plist)) for sig, plist in groups.items()]
+            else:
+                work = [(sig, sorted(p for p in plist if p // self.num_z == guide)) for sig, plist in groups.items()]
+                work.append((None, None))
+                work += [(sig, sorted(p for p in plist if p // self.num_z < guide)) for sig, plist in groups.items()]
+                work += [(sig, sorted(p for p in plist if p // self.num_z > guide)) for sig, plist in groups.items()]
+            for sig, plist in work:
+                if sig is None:      # every plane of the guide has been projected: its depth plane, once, for all followers
+                    depth_planes = {id(t.depth): t.depth for t in followers.values() if t.guide is not None}
+                    for d in depth_planes.values():
+                        native.focus_depth_plane(project_to[guide][1], out=d)
+                    continue
+                if not plist:
+                    continue
                 # ascending plane ids: the canvas slots of a chunk are then consecutive and the whole chunk
                 # goes out in ONE launch (region_data is in file-name order, i.e. z varies before channel)
-                plist = sorted(plist)
                 rects = rect_of[sig]
+                # (the winners' scratch is for the planes that are scored: a follower's batch does not pay for it)
+                focus = project_to is not None and any(isinstance(project_to.get(p // self.num_z), tuple) for p in plist)
                 n = len(rects)
                 plan = self._plan_for(rects, th, tw, hc, wc, mode)
                 per_plane = n * th * tw * np.dtype(self.dtype).itemsize
@@ -987,7 +1074,10 @@ class Stitcher:
                         for c, pis in runs.items():
                             i0, i1 = pis[0], pis[-1] + 1
                             ff = None if flats is None else flats[i0:i1]
-                            if isinstance(project_to[c], tuple):
+                            if isinstance(project_to[c], FocusFollower):
+                                native.fuse_select_depth(plan, tiles[i0:i1], project_to[c].out, project_to[c].depth,
+                                                         [p % self.num_z for p in chunk[i0:i1]], ff, accumulate=c in projected)
+                            elif isinstance(project_to[c], tuple):
                                 out, key = project_to[c]
                                 native.fuse_project_focus(plan, tiles[i0:i1], out, key, [p % self.num_z for p in chunk[i0:i1]],
                                                           self.focus_radius, ff, scratch=focus_scratch,
@@ -1097,7 +1187,7 @@ class Stitcher:
         chans = range(self.num_c) if channel is None else [channel]
         if self._projection_kind() == 'edf':
             out, key = self._new_focus(timepoint, region, rows, n)
-            return out, {c: (out[i], key[i]) for i, c in enumerate(chans)}
+            return out, {c: (out[i], key[i]) for i, c in enumerate(chans)}      # (every channel on its own: no guide)
         proj = self._new_projection(timepoint, region, rows, n)
         return proj, {c: proj[i] for i, c in enumerate(chans)}
 
@@ -1138,6 +1228,53 @@ class Stitcher:
                                       num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                                       name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression,
                                       pyramid_method=self.pyramid_method)
+        return output_path, shapes
+
+    def _depth_labels(self) -> List[str]:
+        return omezarr.depth_labels(self.monochrome_channels, self.focus_guide_channel)
+
+    def _depths_of_keys(self, key, depth=None):
+        """[k, Hc, Wc] key planes -> their unsigned depth planes (``depth``: the guide's, already derived by stitch_planes)."""
+        import torch
+        if depth is not None:
+            return depth
+        depth = torch.empty(tuple(key.shape), dtype=self._depth_dtype(), device=self.device)
+        for i in range(len(key)):
+            native.focus_depth_plane(key[i], out=depth[i])
+        return depth
+
+    def save_region_depth(self, timepoint, region, depth) -> str:
+        """``<t>_stitched/<region>_stitched_depth<format>``: the (1, K, 1, Hc, Wc) unsigned depth planes of the best-focus
+        projection (z* + 1, 0 = uncovered; K = 1 with a guide channel, else one per channel), with the _edf store's pixel size,
+        chunking, compression and level count; levels by nearest, windows 0 ... num_z, no histogram sidecars."""
+        output_path = self._mip_path(timepoint, region, 'depth')
+        os.makedirs(os.path.dirname(output_path), exist_ok=True)
+        labels = self._depth_labels()
+        if self.output_format.endswith('.zarr'):
+            return omezarr.write_depth_store(output_path, depth, num_z=self.num_z, labels=labels,
+                                             pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
+                                             num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
+                                             name=f"{region}_t{timepoint}_depth", compression=self.zarr_compression,
+                                             device=depth.device if hasattr(depth, 'data_ptr') else self._device)
+        if hasattr(depth, 'cpu'):
+            depth = depth.cpu().numpy()
+        print(f"Writing OME-TIFF to: {output_path}")
+        write_ome_tiff(output_path, np.asarray(depth), pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
+                       channel_names=labels, channel_colors=[0xFFFFFF] * len(labels), name=f"{region}_t{timepoint}_depth")
+        return output_path
+
+    def create_depth_store(self, timepoint, region):
+        """Metadata of the region's depth store (no chunks) -> (path, level shapes)."""
+        output_path = self._mip_path(timepoint, region, 'depth')
+        os.makedirs(os.path.dirname(output_path), exist_ok=True)
+        width, height = self.calculate_output_dimensions(timepoint, region)
+        labels = self._depth_labels()
+        shapes = omezarr.create_store(output_path, (1, len(labels), 1, height, width), native.depth_dtype_for(self.num_z),
+                                      pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(), channel_names=labels,
+                                      channel_colors=[0xFFFFFF] * len(labels), num_levels=self.num_pyramid_levels,
+                                      chunks=self.chunks or (1, 1, 1, 512, 512), name=f"{region}_t{timepoint}_depth",
+                                      compression=self.zarr_compression)
+        omezarr.set_channel_windows(output_path, [(0, self.num_z)] * len(labels))
         return output_path, shapes
 
     def create_region_store(self, timepoint, region):
@@ -1266,6 +1403,8 @@ class Stitcher:
                 self.create_region_store(timepoint, region)
             if self.z_projection != 'none':
                 self.create_mip_store(timepoint, region, self._projection_kind())
+                if self.focus_depth_map:
+                    self.create_depth_store(timepoint, region)
         sharding.barrier()
         self.starting_stitching.emit()
         self.starting_saving.emit(False)
@@ -1301,20 +1440,54 @@ class Stitcher:
         width, height = self.calculate_output_dimensions(timepoint, region)
         full = omezarr.level_shapes((1, self.num_c, 1, height, width), self.num_pyramid_levels)
         chunks = self.chunks or (1, 1, 1, 512, 512)
-        for c, b in cunits:
-            y0, y1 = (0, height) if b < 0 else bands[b]
-            proj, target = self._projection_target(timepoint, region, (y0, y1), channel=c)
-            self.stitch_planes(timepoint, region, [c * self.num_z + z for z in range(self.num_z)],
-                               self.update_progress.emit, row_band=None if b < 0 else (y0, y1), stack=False,
-                               project_to=target)
-            shapes = omezarr.level_shapes((1, self.num_c, 1, y1 - y0, width), len(full))
-            with omezarr.PlaneStreamWriter(output_path, shapes, self.dtype, chunks=chunks, batch=1,
-                                           compression=self.zarr_compression,
-                                           pyramid_method=self.pyramid_method, device=self.device, row_offset=y0,
+        edf = self._projection_kind() == 'edf'
+        g = self._guide if edf else None
+        band_depth = {}      # with a guide channel: band -> the guide's (depth plane, output), while this rank's units of the band last
+        last_of_band = {b: i for i, (_, b) in enumerate(cunits)}
+
+        def write_band(path, plane, dtype, n_channels, c, y0, y1, b, method, hist):
+            shapes = omezarr.level_shapes((1, n_channels, 1, y1 - y0, width), len(full))
+            with omezarr.PlaneStreamWriter(path, shapes, dtype, chunks=chunks, batch=1, compression=self.zarr_compression,
+                                           pyramid_method=method, device=self.device, row_offset=y0,
                                            level_heights=None if b < 0 else [s[3] for s in full]) as writer:
-                writer.histogram = histogram
-                writer.acquire(1).copy_(proj)
+                writer.histogram = hist
+                writer.acquire(1).copy_(plane)
                 writer.submit([(0, c, 0)])
+
+        def project(chans, y0, y1, b, depth=None):
+            out, key, depth, target = self._focus_target(timepoint, region, (y0, y1), chans, depth)
+            self.stitch_planes(timepoint, region, [c * self.num_z + z for c in chans for z in range(self.num_z)],
+                               self.update_progress.emit, row_band=None if b < 0 else (y0, y1), stack=False, project_to=target)
+            return out, key, depth
+
+        depth_path = self._mip_path(timepoint, region, 'depth')
+        depth_dtype = native.depth_dtype_for(self.num_z) if edf else None
+        for i, (c, b) in enumerate(cunits):
+            y0, y1 = (0, height) if b < 0 else bands[b]
+            if not edf:
+                proj, target = self._projection_target(timepoint, region, (y0, y1), channel=c)
+                self.stitch_planes(timepoint, region, [c * self.num_z + z for z in range(self.num_z)],
+                                   self.update_progress.emit, row_band=None if b < 0 else (y0, y1), stack=False,
+                                   project_to=target)
+            elif g is None:
+                proj, key, _ = project([c], y0, y1, b)
+                if self.focus_depth_map:
+                    write_band(depth_path, self._depths_of_keys(key), depth_dtype, self.num_c, c, y0, y1, b, 'nearest', None)
+            else:
+                # the guide's depth of this band: computed once on this rank (whichever of its units of the band comes first),
+                # by projecting the guide's rows -- the windows are whole staged tiles, so they equal the whole region's
+                if b not in band_depth:
+                    gout, gkey, _ = project([g], y0, y1, b)
+                    band_depth[b] = (self._depths_of_keys(gkey), gout)
+                if c == g:
+                    proj = band_depth[b][1]
+                    if self.focus_depth_map:      # written by the rank that was dealt the guide's unit of the band
+                        write_band(depth_path, band_depth[b][0], depth_dtype, 1, 0, y0, y1, b, 'nearest', None)
+                else:
+                    proj = project([c], y0, y1, b, band_depth[b][0])[0]
+                if last_of_band[b] == i:
+                    del band_depth[b]
+            write_band(output_path, proj, self.dtype, self.num_c, c, y0, y1, b, self.pyramid_method, histogram)
         return output_path
 
     def save_region_aics(self, timepoint, region, stitched_region):
@@ -1493,7 +1666,11 @@ class Stitcher:
                 self.write_tile_positions(timepoint, region)
             self.starting_stitching.emit()
             # --z-projection: the projection comes from the tiles the stack pass stages (one read of every file)
-            proj, project_to = self._projection_target(timepoint, region) if self.z_projection != 'none' else (None, None)
+            proj, project_to, keys, depth = None, None, None, None
+            if self._projection_kind() == 'edf':
+                proj, keys, depth, project_to = self._focus_target(timepoint, region)
+            elif self.z_projection != 'none':
+                proj, project_to = self._projection_target(timepoint, region)
             if self.z_projection in ('max-only', 'focus-only'):
                 self.starting_saving.emit(False)
                 self.stitch_planes(timepoint, region, None, self.update_progress.emit, stack=False, project_to=project_to)
@@ -1510,6 +1687,10 @@ class Stitcher:
                 mip_path = self.save_region_mip(timepoint, region, proj.unsqueeze(0).unsqueeze(2), self._projection_kind())
                 if self.z_projection in ('max-only', 'focus-only'):
                     output_path = mip_path
+                if self.focus_depth_map:
+                    if self.num_c == 1:
+                        depth = None      # no follower: stitch_planes had no reason to derive the guide's depth plane
+                    self.save_region_depth(timepoint, region, self._depths_of_keys(keys, depth).unsqueeze(0).unsqueeze(2))
             print(f"Completed region {region} (saved to {output_path}): {time.time() - rtime}")
         if self.use_registration:
             self._write_shift_table(n_units, my_rows, rank, world, coll, shared)

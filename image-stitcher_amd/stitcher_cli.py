@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus twelve switches for what this build adds (``--fusion-mode``, ``--normalization``,
+plus fourteen switches for what this build adds (``--fusion-mode``, ``--normalization``,
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
 ``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``, ``--contrast-limits``,
-``--contrast-percentiles``).
+``--contrast-percentiles``, ``--focus-guide-channel``, ``--focus-depth-map``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -70,6 +70,14 @@ FLAGS = (
     (('--contrast-percentiles',), dict(type=float, nargs=2, default=(0.1, 99.9), metavar=('LO', 'HI'),
                                        help="with --contrast-limits percentile: the window's start and end percentile, "
                                             "0 <= LO < HI <= 100")),
+    (('--focus-guide-channel',), dict(metavar='NAME', default=None,
+                                      help="with --z-projection focus / focus-only: decide the depth on this channel (a name out of "
+                                           "the output channels, for an RGB file e.g. <base>_G) and give every other channel its "
+                                           "value at that depth, instead of a depth of its own per channel")),
+    (('--focus-depth-map',), dict(action='store_true',
+                                  help="with --z-projection focus / focus-only: also write <region>_stitched_depth<format>, the "
+                                       "winning z level + 1 of every voxel (0 = no tile): one plane with --focus-guide-channel, "
+                                       "else one per channel; levels by nearest, windows 0 ... number of z levels")),
 )
 
 
@@ -128,7 +136,9 @@ def main(argv=None):
                             focus_radius=args.focus_radius,
                             pyramid_method=args.pyramid_method,
                             contrast_limits=args.contrast_limits,
-                            contrast_percentiles=tuple(args.contrast_percentiles))
+                            contrast_percentiles=tuple(args.contrast_percentiles),
+                            focus_guide_channel=args.focus_guide_channel,
+                            focus_depth_map=args.focus_depth_map)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

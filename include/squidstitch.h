@@ -218,6 +218,40 @@ typedef struct sq_focus_args {
 int64_t sq_focus_scratch_bytes(int32_t n_tiles, int32_t tile_h, int32_t tile_w);
 int sq_fuse_project_focus(const sq_fuse_args *args, const sq_focus_args *focus, int32_t flags, void *stream);
 
+/* Guide channel of the best-focus projection: decide the depth on ONE channel g, apply it to the others (all integer, exact).
+ * Let depth_g(v) be the depth sq_fuse_project_focus reports for g at canvas voxel v (-1 where no plane of g covers v).  For
+ * every channel c != g:
+ *     out_c(v) = stack[c, depth_g(v)](v)   if depth_g(v) >= 0,   else 0
+ * where stack[c, z] is exactly what sq_fuse_planes stores for plane (c, z): the same owner tile under that plane's own
+ * overwrite plan, the same divide routine for none / float32 / float64 gains, 0 where plane (c, z) does not cover v (ragged
+ * input) or does not exist.  In numpy: take_along_axis of the fused stack along z by the guide's depth, 0 where it is -1.
+ * The guide's own output is sq_fuse_project_focus's, unchanged.
+ *
+ * The depth plane handed between the two stages (and written to disk by --focus-depth-map) is unsigned: z* + 1, 0 = uncovered;
+ * SQ_U8 when every z level is < 255, else SQ_U16 (z < 65535).  A level the dtype cannot hold saturates to its maximum.
+ *
+ * sq_focus_depth_plane: key plane (uint64 [h, key_pitch elements], 8-byte aligned, as sq_fuse_project_focus writes it) ->
+ * depth plane ([h, depth_pitch elements] of depth_dtype): 0xFFFFFFFF - low word + 1, key 0 -> 0.  One streaming kernel, 8 B
+ * read and 1-2 B written per voxel.  SQ_ERR_INVALID for a NULL plane, a pitch below w, a dtype other than SQ_U8 / SQ_U16.
+ *
+ * sq_fuse_select_depth: `args` addresses the n_planes staged planes of ONE overwrite plan exactly as for sq_fuse_project_max
+ * (canvas_dev = the one output plane of channel c, canvas_dtype == tile_dtype, scratch_dev = optional work-queue counters);
+ * z_levels_dev: n_planes distinct uint32 z levels of these planes, device memory; depth_dev: the guide's depth plane
+ * [canvas_h, depth_pitch elements].  The plan's items are walked on the persistent grid of the projections (static walk or the
+ * per-XCD work queues, same size rule and flags).  Per voxel: the depth, the call's plane at that z level, and -- where the
+ * item covers the voxel -- the owner pixel of that plane through that plane's gains, stored; 0 where the item does not cover
+ * it.  flags: the work-distribution bits plus SQ_SELECT_ACCUMULATE: voxels whose depth is not among this call's z levels are
+ * left untouched; without it they are written 0 (so every voxel is written).  That lets the z planes of a channel arrive in
+ * several calls (ingest batches), in any z order, under different plans, the first call without the flag.  Reads 1-2 B of
+ * depth per voxel + pixel and gain per selected voxel, writes the pixel: 1 + 2 + 4 B read, 2 B written with uint16 tiles,
+ * float32 gains and a uint8 depth.  SQ_ERR_INVALID for a feather plan, n_planes outside 1..256, a NULL depth plane or z
+ * levels, a depth dtype other than SQ_U8 / SQ_U16.  No atomics beyond the queue walk, no device allocation; deterministic. */
+#define SQ_SELECT_ACCUMULATE 32
+int sq_focus_depth_plane(const void *key_dev, int32_t key_pitch, int32_t h, int32_t w, void *depth_dev, int32_t depth_pitch,
+                         int32_t depth_dtype, void *stream);
+int sq_fuse_select_depth(const sq_fuse_args *args, const void *depth_dev, int32_t depth_pitch, int32_t depth_dtype,
+                         const uint32_t *z_levels_dev, int32_t flags, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Canvas memory.  Replaces the allocation behind Stitcher.init_output (stitcher.py:356-362: the reference's canvas is a
  * lazy dask array; here it is device memory the fusion kernel writes once).  WHERE that memory lies decides how fast the

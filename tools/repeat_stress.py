@@ -139,3 +139,28 @@ for _ in range(REPS):
     native.fuse_planes(planf, d_tl, canvas, [d_flat] * planes, flags=native.SQ_FUSE_FORCE_QUEUES)
     bad += int((canvas.to(torch.int32) != wantf).sum() > 0)
 report('feather fusion with gains, plane groups + queues, against the oracle', bad, REPS, t0)
+
+# --- guide channel of the best-focus projection: depth plane and select kernels (queues and static walk, one call and two) ---
+key = torch.empty((hc, wc), dtype=torch.int64, device=dev)
+edf = torch.empty((hc, wc), dtype=torch.uint16, device=dev)
+native.fuse_project_focus(plan, d_tl, edf, key, list(range(planes)), 3, [d_flat] * planes)
+t0 = time.perf_counter()
+first = native.focus_depth_plane(key).clone()
+bad = sum(int(not torch.equal(native.focus_depth_plane(key), first)) for _ in range(REPS))
+bad += int(not torch.equal(first.to(torch.int64), native.depth_of_keys(key) + 1))
+report('depth plane of a key plane, against the torch expression and itself', bad, REPS, t0)
+follower = torch.from_numpy(rng.integers(0, 65536, size=(planes, g * g, th, th)).astype(np.uint16)).to(dev)
+for name, flags in (('queues', native.SQ_FUSE_FORCE_QUEUES), ('static', native.SQ_FUSE_FORCE_STATIC)):
+    t0 = time.perf_counter()
+    ref = None
+    bad = 0
+    for _ in range(REPS + 1):
+        sel = torch.full((hc, wc), 65529, dtype=torch.uint16, device=dev)
+        native.fuse_select_depth(plan, follower[:4], sel, first, list(range(4)), [d_flat] * 4, flags=flags)
+        native.fuse_select_depth(plan, follower[4:], sel, first, list(range(4, planes)), [d_flat] * (planes - 4), accumulate=True,
+                                 flags=flags)
+        if ref is None:
+            ref = sel
+        else:
+            bad += int(not torch.equal(sel, ref))
+    report(f'select at the guide depth, two calls, {name}', bad, REPS, t0)
