@@ -124,6 +124,10 @@ EXPORTS = {
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_histogram_planes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                       C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
+    'sq_block_mean': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'sq_composite_render': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_void_p, C.c_int64, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1003,6 +1007,90 @@ def histogram_planes(planes, rows, hist=None, n_rows=None, stream=None):
     _check(L.sq_histogram_planes(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype), table,
                                  int(hist.shape[0]), hist.data_ptr(), _stream_ptr(stream)), 'sq_histogram_planes')
     return hist
+
+
+SQ_BLOCK_MEAN_MAX_K = 8            # block sums of uint16 values fit 32 bits up to 256 x 256 (squidstitch.h)
+SQ_COMPOSITE_MAX_PLANES = 16
+
+
+def block_mean(planes, k, out=None, rows=None, stream=None):
+    """Block means of ``planes`` [n, H, W] (uint8 / uint16 device tensor, any row pitch) -> [n, ceil(H / f), ceil(W / f)] of the
+    same dtype, f = 2^k, k = 0 ... 8: the truncated mean of every f x f block over the pixels of it that exist (partial blocks
+    at the bottom and right edge; k = 0 is the identity).  Replaces the host copy of stitcher.py:861-885 (_save_debug_slice);
+    the definition is ``tests/composite_ref.block_mean``.  ``rows`` = (y0, y1): only source rows [y0, y1) are read and rows
+    y0 / f ... of ``out`` written (y0 a multiple of f, y1 - y0 a multiple of f or y1 = H) -- what a rank that wrote a row band
+    reduces.  ``out`` may be a preallocated tensor (any row pitch); without it a fresh one is made (zeroed when ``rows`` leaves
+    part of it unwritten)."""
+    import torch
+    L = lib()
+    if planes.dim() != 3 or planes.device.type != 'cuda':
+        raise ValueError("planes must be a [n, h, w] device tensor")
+    if planes.stride(2) != 1 and planes.shape[2] > 1:
+        raise ValueError("planes rows must be contiguous")
+    if planes.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"planes must be uint8 or uint16, got {planes.dtype}")
+    k = int(k)
+    if not 0 <= k <= SQ_BLOCK_MEAN_MAX_K:
+        raise ValueError(f"k must lie in 0..{SQ_BLOCK_MEAN_MAX_K}, got {k}")
+    f = 1 << k
+    n, h, w = (int(v) for v in planes.shape)
+    shape = (n, -(-h // f), -(-w // f))
+    y0, y1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
+    if not (0 <= y0 <= y1 <= h) or y0 % f or ((y1 - y0) % f and y1 != h):
+        raise ValueError(f"rows {rows} of {h}: a band starts on a multiple of {f} and is a multiple of it long, or runs to the last row")
+    if out is None:
+        out = (torch.empty if (y0, y1) == (0, h) else torch.zeros)(shape, dtype=planes.dtype, device=planes.device)
+    if tuple(out.shape) != shape or out.dtype != planes.dtype or out.device != planes.device:
+        raise ValueError(f"out must be a {shape} tensor of the input's dtype and device")
+    if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
+        raise ValueError("out rows must be contiguous")
+    if n == 0 or h == 0 or w == 0 or y1 == y0:
+        return out
+    _check(L.sq_block_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)),
+                           k, y0, y1 - y0, out.data_ptr(), out.stride(0), out.stride(1), _stream_ptr(stream)), 'sq_block_mean')
+    return out
+
+
+def composite_render(means, windows, colors, out=None, stream=None):
+    """``means`` [n, h, w] (uint8 / uint16 device tensor, n <= 16, any row pitch), one window (start, end) and one colour
+    0xRRGGBB per plane -> interleaved RGB8 [h, w, 3] on the device: every plane is mapped through its window to 0 ... 255
+    (0 at or below start, 255 at or above end, floor((m - start) * 255 / (end - start)) between), scaled by its colour
+    (floor(v * component / 255)) and the planes are added, saturating at 255.  Replaces the min/max normalisation of
+    stitcher.py:861-885 (_save_debug_slice); the definition is ``tests/composite_ref.render``.  ``out``: a preallocated uint8
+    [h, w, 3] tensor whose pixels are contiguous (any row pitch)."""
+    import torch
+    L = lib()
+    if means.dim() != 3 or means.device.type != 'cuda':
+        raise ValueError("means must be a [n, h, w] device tensor")
+    if means.stride(2) != 1 and means.shape[2] > 1:
+        raise ValueError("means rows must be contiguous")
+    if means.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"means must be uint8 or uint16, got {means.dtype}")
+    n, h, w = (int(v) for v in means.shape)
+    if not 1 <= n <= SQ_COMPOSITE_MAX_PLANES:
+        raise ValueError(f"1..{SQ_COMPOSITE_MAX_PLANES} planes, got {n}")
+    windows = [(int(a), int(b)) for a, b in windows]
+    colors = [int(c) for c in colors]
+    if len(windows) != n or len(colors) != n:
+        raise ValueError(f"{n} planes, {len(windows)} windows and {len(colors)} colours given")
+    if any(not 0 <= a < b <= 65535 for a, b in windows):
+        raise ValueError(f"windows must satisfy 0 <= start < end <= 65535, got {windows}")
+    if any(not 0 <= c <= 0xFFFFFF for c in colors):
+        raise ValueError(f"colours are 0xRRGGBB, got {colors}")
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=means.device)
+    if tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != means.device:
+        raise ValueError(f"out must be a uint8 {(h, w, 3)} tensor on the planes' device")
+    if out.numel() and (out.stride(2) != 1 or out.stride(1) != 3):
+        raise ValueError("out pixels must be contiguous (strides (pitch, 3, 1))")
+    if h == 0 or w == 0:
+        return out
+    win = (C.c_int32 * (2 * n))(*[v for ab in windows for v in ab])
+    col = (C.c_uint32 * n)(*colors)
+    _check(L.sq_composite_render(means.data_ptr(), means.stride(0), h, w, means.stride(1), n,
+                                 sq_dtype_of(np_dtype_of_torch(means.dtype)), win, col, out.data_ptr(), out.stride(0),
+                                 _stream_ptr(stream)), 'sq_composite_render')
+    return out
 
 
 _COPY_STREAMS = {}

@@ -417,11 +417,12 @@ def _pad_planes(full, m: int):
 def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0,
                    channel_names: Sequence[str] = (), channel_colors: Sequence[int] = (),
                    num_levels: int = 1, chunks=(1, 1, 1, 512, 512), name: str = 'stitched', compression: str = 'zlib',
-                   device=None, pyramid_method: str = 'nearest', histogram=None) -> str:
+                   device=None, pyramid_method: str = 'nearest', histogram=None, composite=None) -> str:
     """Write a (T, C, Z, Y, X) array (numpy, or a device tensor) as a multiscale OME-Zarr image.  The
     pyramid levels come from the device kernel, a batch of planes at a time; with ``num_levels`` 1 no
     GPU is touched for a numpy input.  ``histogram``: a device int64 [C, bins] tensor the value counts of level 0 are added
-    to (``PlaneStreamWriter.histogram``)."""
+    to (``PlaneStreamWriter.histogram``); ``composite``: a composite.CompositeTarget that is handed every plane
+    (``PlaneStreamWriter.composite``)."""
     if image.ndim != 5:
         raise ValueError(f"expected a 5-D TCZYX array, got {tuple(image.shape)}")
     on_device = hasattr(image, 'data_ptr')
@@ -433,7 +434,7 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
     t_, c_, z_ = shape[:3]
     coords = [(t, c, z) for t in range(t_) for c in range(c_) for z in range(z_)]
     planes = image.reshape((-1,) + shape[3:])
-    if len(shapes) == 1 and not on_device and compression != 'blosc' and histogram is None:
+    if len(shapes) == 1 and not on_device and compression != 'blosc' and histogram is None and composite is None:
         write_plane_levels(path, [planes], coords, chunks, compression)
         return path
     import torch
@@ -445,6 +446,7 @@ def write_ome_zarr(path: str, image, *, pixel_size_um: float, dz_um: float = 1.0
     with PlaneStreamWriter(path, shapes, dtype, chunks=chunks, batch=batch, compression=compression,
                            device=planes.device if on_device else device, pyramid_method=pyramid_method) as writer:
         writer.histogram = histogram
+        writer.composite = composite
         for b0 in range(0, len(coords), batch):
             part = planes[b0:b0 + batch]
             dst = writer.acquire(len(part))
@@ -517,6 +519,9 @@ class PlaneStreamWriter:
         # optional target of the value counts of level 0: a device int64 [C, bins] tensor; submit() adds the planes it is handed
         # to row c of it (sq_histogram_planes).  None: nothing is launched.  Callers set it per store (``retarget`` keeps it).
         self.histogram = None
+        # optional composite.CompositeTarget: submit() hands it the planes (and this writer's row offset) before the slot is
+        # released, so that it can reduce its source planes where they are final.  None: nothing is launched.
+        self.composite = None
         tdtype = native.torch_dtype_of(np.dtype(dtype).type)
         yx = [tuple(s[3:]) for s in shapes]
         # ``buffers``: the (device, pinned host) slot buffers of an earlier writer of the same geometry --
@@ -673,6 +678,8 @@ class PlaneStreamWriter:
         if self.histogram is not None:      # the m planes handed in, not the padding of a partly filled slot
             from . import native
             native.histogram_planes(dev[0][:m], [c for _, c, _ in coords], hist=self.histogram)
+        if self.composite is not None:
+            self.composite.add(dev[0][:m], coords, self.row_offset)
         levels = device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
         if self._blosc:        # encode every level's chunks behind the pyramid, on the caller's stream
             from . import native

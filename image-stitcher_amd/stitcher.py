@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import alignment, native, placement, registration, sharding
+from . import alignment, composite as composite_mod, native, placement, registration, sharding
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -70,7 +70,9 @@ class Stitcher:
                  per_region_registration: bool = False, flatfield_estimator: str = 'auto',
                  all_pairs_registration: bool = False, global_registration: bool = False, z_projection: str = 'none',
                  focus_radius: int = 3, pyramid_method: str = 'nearest', contrast_limits: str = 'dtype',
-                 contrast_percentiles=(0.1, 99.9), focus_guide_channel: Optional[str] = None, focus_depth_map: bool = False):
+                 contrast_percentiles=(0.1, 99.9), focus_guide_channel: Optional[str] = None, focus_depth_map: bool = False,
+                 composite: bool = False, composite_max_side: int = 4096, composite_z: Optional[int] = None,
+                 composite_channels=None):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -134,6 +136,18 @@ class Stitcher:
         if self.contrast_limits == 'percentile' and not self.output_format.endswith('.zarr'):
             raise ValueError("contrast_limits='percentile' needs .ome.zarr output: OME-XML (.ome.tiff) has no rendering window "
                              "to carry the channel windows")
+        # Extension: composite = one colour quick-look PNG (+ JSON sidecar) per (timepoint, region) instead of the reference's
+        # dormant _save_debug_slice (stitcher.py:861-885): the projection the run writes, or z plane composite_z (default
+        # num_z // 2) of the stack, reduced on the device to block means of at most composite_max_side pixels a side
+        # (sq_block_mean), windowed by contrast_percentiles of its own value counts -- whatever contrast_limits says -- and added
+        # in the channel colours (sq_composite_render).  composite_channels restricts and orders the channels (names out of
+        # monochrome_channels).  Off: nothing is launched and no file appears.
+        self.composite, self.composite_max_side, self.composite_z, self.composite_channels = \
+            composite_mod.check_options(composite, composite_max_side, composite_z, composite_channels)
+        self._composite_pending = []     # (target, pinned counts, event) of streamed regions, see _finish_composites
+        self._composite_jobs = []        # PNG encodings under way on the pool
+        self._composite_pool = None
+        self._composite_async = False    # run(): PNGs are encoded on a worker thread
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -312,6 +326,15 @@ class Stitcher:
                 raise ValueError(f"focus_guide_channel {self.focus_guide_channel!r} is not a channel of this acquisition: "
                                  f"{self.monochrome_channels}")
             self._guide = self.monochrome_channels.index(self.focus_guide_channel)
+        if self.composite:
+            if self.composite_z is not None and not 0 <= self.composite_z < self.num_z:
+                raise ValueError(f"composite_z = {self.composite_z} is outside the acquisition's z levels 0..{self.num_z - 1}")
+            unknown = [n for n in (self.composite_channels or []) if n not in self.monochrome_channels]
+            if unknown:
+                raise ValueError(f"composite_channels {unknown} are not channels of this acquisition: {self.monochrome_channels}")
+            if len(self.composite_channels or self.monochrome_channels) > composite_mod.MAX_CHANNELS:
+                raise ValueError(f"a composite adds at most {composite_mod.MAX_CHANNELS} channels; name them with "
+                                 f"composite_channels ({len(self.monochrome_channels)} in this acquisition)")
         print(f"[metadata] regions {self.regions}; channels {self.channel_names}")
         print(f"[metadata] tile {self.input_height} x {self.input_width} {np.dtype(self.dtype)}")
         print(f"[metadata] {self.num_z} z levels, {self.num_t} timepoints, {self.num_fovs_per_region} fovs per region")
@@ -752,10 +775,13 @@ class Stitcher:
         # group of planes writes fastest when they sit in different stretches of device memory (DESIGN.md 5.1 point 8)
         return self._stitch_region(timepoint, region, progress_callback, device_output)
 
-    def _stitch_region(self, timepoint, region, progress_callback=None, device_output: bool = False, project_to=None):
+    def _stitch_region(self, timepoint, region, progress_callback=None, device_output: bool = False, project_to=None,
+                       composite=None):
         planes, _ = self.stitch_planes(timepoint, region, None, progress_callback, slot_order='spread', project_to=project_to)
         shape = (1, self.num_c, self.num_z, planes.shape[-2], planes.shape[-1])
         by_cz = planes.unflatten(0, (self.num_z, self.num_c)).transpose(0, 1)   # [C, Z, Hc, Wc] view of the [Z * C] slots
+        if composite is not None:      # the resident canvas: the source planes are reduced before it leaves the device
+            composite.add(by_cz[:, composite.z], [(0, c, composite.z) for c in range(self.num_c)])
         if device_output:       # a strided view: planes sit on 128-byte lines, rows are dense
             return by_cz.unsqueeze(0)
         import torch
@@ -1154,6 +1180,99 @@ class Stitcher:
             lo, hi = self.contrast_percentiles
             omezarr.write_contrast(path, host.numpy(), lo, hi, self.dtype)
 
+    # ------------------------------------------------------------------ composite
+    def _composite_kind(self) -> str:
+        """What the composite's source is: the projection this run writes ('mip' / 'edf'), else the stack."""
+        return self._projection_kind() or 'stack'
+
+    def _new_composite(self, timepoint, region, shared_hist=None):
+        """The device target of one region's composite (composite.CompositeTarget), or None without --composite."""
+        if not self.composite:
+            return None
+        kind = self._composite_kind()
+        tag = '' if kind == 'stack' else '_' + kind
+        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
+        os.makedirs(folder, exist_ok=True)
+        width, height = self.calculate_output_dimensions(timepoint, region)
+        names = self.composite_channels or self.monochrome_channels
+        chans = [self.monochrome_channels.index(n) for n in names]
+        z = None if kind != 'stack' else (self.num_z // 2 if self.composite_z is None else self.composite_z)
+        return composite_mod.CompositeTarget(
+            os.path.join(folder, f"{region}_stitched{tag}_composite"), store=f"{region}_stitched{tag}{self.output_format}",
+            kind=kind, z=z, channels=chans, labels=list(names), colors=[self.monochrome_colors[c] for c in chans],
+            height=height, width=width, max_side=self.composite_max_side, dtype=self.dtype,
+            percentiles=self.contrast_percentiles, device=self.device, shared_hist=shared_hist)
+
+    def _emit_composite(self, comp, windows, rgb) -> None:
+        """PNG and sidecar: on a worker thread under run() (finished before it returns), at once otherwise."""
+        meta = comp.meta(windows)
+        if not self._composite_async:
+            composite_mod.write_outputs(comp.stem, rgb, meta)
+            return
+        if self._composite_pool is None:
+            self._composite_pool = ThreadPoolExecutor(max_workers=min(4, os.cpu_count() or 2), thread_name_prefix='composite-png')
+        self._composite_jobs.append(self._composite_pool.submit(composite_mod.write_outputs, comp.stem, rgb, meta))
+
+    def _finish_composite(self, comp, shared: bool = False) -> None:
+        """Windows from the counts read back, render, PNG and sidecar of a composite whose source planes have all been added.
+        ``shared``: the ranks of a shared region each hold the means and counts of what they wrote (zeros elsewhere); both are
+        summed (every rank takes part, the means widened to int32) and rank 0 renders and writes."""
+        if comp is None:
+            return
+        import torch
+        side = getattr(self, '_ingest_stream', None)
+        if side is not None:      # run() fuses (and reduces) on a stream of its own
+            torch.cuda.current_stream(self.device).wait_stream(side)
+        rank, means = 0, None
+        if shared:
+            import torch.distributed as dist
+            rank = dist.get_rank()
+            if dist.get_backend() != 'nccl':
+                hist = comp.hist.cpu()
+                wide = torch.from_numpy(comp.means.cpu().numpy().astype(np.int32))
+            else:
+                hist = comp.hist.clone()      # (a projection store's own target is summed again for its windows)
+                wide = comp.means.to(torch.int32)
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM)
+            dist.all_reduce(wide, op=dist.ReduceOp.SUM)
+            if rank == 0:
+                means = torch.from_numpy(wide.cpu().numpy().astype(comp.dtype)).to(self.device)
+            hist = hist.cpu()
+        else:
+            hist = comp.hist.cpu()
+        if rank == 0:
+            windows = comp.windows(comp.counts(hist.numpy()))
+            self._emit_composite(comp, windows, comp.render(windows, means))
+
+    def _defer_composite(self, comp) -> None:
+        """A streamed region under run(): the counts leave the device behind the region's last launch; the picture is rendered
+        and written once they have arrived (the next region is not held up, the chunk pipeline is not drained)."""
+        import torch
+        host = torch.empty(comp.hist.shape, dtype=comp.hist.dtype, pin_memory=True)
+        with torch.cuda.stream(self._ingest_stream):
+            host.copy_(comp.hist, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        self._composite_pending.append((comp, host, event))
+        self._finish_composites(wait=False)
+
+    def _finish_composites(self, wait: bool) -> None:
+        """Pictures of the streamed regions whose counts have reached the host (``wait``: of all of them, and every PNG is on
+        disk)."""
+        while self._composite_pending and (wait or self._composite_pending[0][2].query()):
+            comp, host, event = self._composite_pending.pop(0)
+            event.synchronize()      # (the means were written before the counts were copied, on the same stream)
+            windows = comp.windows(comp.counts(host.numpy()))
+            self._emit_composite(comp, windows, comp.render(windows))
+        if wait:
+            jobs, self._composite_jobs = self._composite_jobs, []
+            for job in jobs:
+                job.result()
+            self._composite_async = False
+            if self._composite_pool is not None:
+                self._composite_pool.shutdown(wait=True)
+                self._composite_pool = None
+
     def _zarr_path(self, timepoint, region) -> str:
         return os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched.ome.zarr")
 
@@ -1167,12 +1286,14 @@ class Stitcher:
         output_path = self._zarr_path(timepoint, region)
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
         hist = self._new_histogram()
+        comp = self._new_composite(timepoint, region) if self._composite_kind() == 'stack' else None
         write_ome_zarr(output_path, stitched_region, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                        channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                        num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                        name=f"{region}_t{timepoint}", compression=self.zarr_compression,
-                       pyramid_method=self.pyramid_method, device=self.device, histogram=hist)
+                       pyramid_method=self.pyramid_method, device=self.device, histogram=hist, composite=comp)
         self._write_contrast(output_path, hist)
+        self._finish_composite(comp)
         return output_path
 
     def _projection_kind(self) -> Optional[str]:
@@ -1202,13 +1323,22 @@ class Stitcher:
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
         if self.output_format.endswith('.zarr'):
             hist = self._new_histogram()
+            # the composite's source is this store: with percentile windows its histogram target holds the same counts
+            comp = self._new_composite(timepoint, region, shared_hist=hist) if kind == self._composite_kind() else None
             write_ome_zarr(output_path, mip, pixel_size_um=self.pixel_size_um, dz_um=self._dz_um(),
                            channel_names=self.monochrome_channels, channel_colors=self.monochrome_colors,
                            num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                            name=f"{region}_t{timepoint}_{kind}", compression=self.zarr_compression,
-                           pyramid_method=self.pyramid_method, device=self.device, histogram=hist)
+                           pyramid_method=self.pyramid_method, device=self.device, histogram=hist, composite=comp)
+            self._finish_composite(comp)
             self._write_contrast(output_path, hist)
             return output_path
+        comp = self._new_composite(timepoint, region) if kind == self._composite_kind() else None
+        if comp is not None:      # the projection buffer, while it is on the device
+            import torch
+            planes = mip if hasattr(mip, 'data_ptr') else torch.from_numpy(np.ascontiguousarray(mip)).to(self.device)
+            comp.add(planes.reshape((-1,) + tuple(planes.shape[3:])), [(0, c, 0) for c in range(int(planes.shape[1]))])
+            self._finish_composite(comp)
         if hasattr(mip, 'cpu'):
             mip = mip.cpu().numpy()
         print(f"Writing OME-TIFF to: {output_path}")
@@ -1290,13 +1420,18 @@ class Stitcher:
         return output_path, shapes
 
     def stream_region_to_zarr(self, timepoint, region, only_planes=None, progress_callback=None, create: bool = True,
-                              row_band=None, project_to=None, histogram=None):
+                              row_band=None, project_to=None, histogram=None, composite=None):
         """stitch_region + save_region_ome_zarr without the region ever existing in one piece: planes
         are fused a batch at a time and stream through pyramid kernel, pinned D2H copy and compression
         threads while the next batch is read and fused.  Same store as
         ``save_region_ome_zarr(t, r, stitch_region(t, r))``.  ``histogram``: the caller's histogram target (a shared region's
         ranks call this once per row band and finish the windows themselves); None: with contrast_limits='percentile' a fresh
-        target is taken and the store's windows and sidecars are written when its last plane has been submitted."""
+        target is taken and the store's windows and sidecars are written when its last plane has been submitted.
+        ``composite``: the caller's composite target (a shared region); None: with --composite and the stack as its source a
+        fresh one is taken and the picture written."""
+        own_composite = composite is None and create and self.composite and self._composite_kind() == 'stack'
+        if own_composite:
+            composite = self._new_composite(timepoint, region)
         own_histogram = histogram is None and create
         if own_histogram:
             histogram = self._new_histogram()
@@ -1321,6 +1456,7 @@ class Stitcher:
             if w is not None and w.matches(shapes, self.dtype, batch, self.zarr_compression, chunks, self.pyramid_method):
                 w.retarget(output_path, row_offset, level_heights)      # the same geometry: the next store through the same writer
                 w.histogram = histogram
+                w.composite = composite
                 made.append(w)
                 return w
             self._close_stream_writer()
@@ -1341,6 +1477,7 @@ class Stitcher:
             self._keep_buffers(key, made[-1].buffers)
             self._stream_writer = made[-1]
             made[-1].histogram = histogram
+            made[-1].composite = composite
             return made[-1]
 
         before = self._stream_writer.bytes_written if self._stream_writer is not None else 0
@@ -1350,6 +1487,12 @@ class Stitcher:
         self.last_bytes_written = sum(w.bytes_written for w in set(made)) - (before if self._stream_writer in made else 0)
         for w in made:
             w.histogram = None
+            w.composite = None
+        if own_composite:
+            if self._defer_drain and getattr(self, '_ingest_stream', None) is not None:
+                self._defer_composite(composite)
+            else:
+                self._finish_composite(composite)
         if own_histogram and histogram is not None:
             if self._defer_drain and getattr(self, '_ingest_stream', None) is not None:
                 # run() streams region after region on a stream of its own: the counts leave the device behind this region's last
@@ -1415,20 +1558,25 @@ class Stitcher:
         # --contrast-limits percentile: every rank counts what it writes (planes or row bands), per store
         stack_hist = self._new_histogram() if stack else None
         proj_hist = self._new_histogram() if self.z_projection != 'none' else None
+        # --composite: every rank reduces what it writes of the source (the projection, else the stack) into a zeroed target
+        comp = self._new_composite(timepoint, region, shared_hist=proj_hist)
+        stack_comp = comp if self._composite_kind() == 'stack' else None
         for b, planes in by_band.items():
             output_path = self.stream_region_to_zarr(timepoint, region, planes, progress_callback=self.update_progress.emit,
-                                                     create=False, row_band=None if b < 0 else bands[b], histogram=stack_hist)
+                                                     create=False, row_band=None if b < 0 else bands[b], histogram=stack_hist,
+                                                     composite=stack_comp)
         if self.z_projection != 'none':
-            output_path = self._project_region_units(timepoint, region, bands, rank, world, histogram=proj_hist)
+            output_path = self._project_region_units(timepoint, region, bands, rank, world, histogram=proj_hist, composite=comp)
             if stack:
                 output_path = self._zarr_path(timepoint, region)
+        self._finish_composite(comp, shared=True)      # means and counts summed over the ranks, rank 0 renders and writes
         # ... and the counts are summed over the ranks (one that was dealt no unit adds zeros), rank 0 writes the windows
         self._write_contrast(self._zarr_path(timepoint, region), stack_hist, shared=True)
         self._write_contrast(self._mip_path(timepoint, region, self._projection_kind() or 'mip'), proj_hist, shared=True)
         sharding.barrier()
         return output_path
 
-    def _project_region_units(self, timepoint, region, bands, rank, world, histogram=None) -> str:
+    def _project_region_units(self, timepoint, region, bands, rank, world, histogram=None, composite=None) -> str:
         """This rank's share of a shared region's projection: (channel, row band) units dealt like the stack's (plane, band)
         units (sharding.plane_band_units over the channels), each projected from the tiles of its channel that reach its band
         and written as its own chunks of the store rank 0 created.  With 'max' / 'focus' the files of these channels are read a
@@ -1445,12 +1593,13 @@ class Stitcher:
         band_depth = {}      # with a guide channel: band -> the guide's (depth plane, output), while this rank's units of the band last
         last_of_band = {b: i for i, (_, b) in enumerate(cunits)}
 
-        def write_band(path, plane, dtype, n_channels, c, y0, y1, b, method, hist):
+        def write_band(path, plane, dtype, n_channels, c, y0, y1, b, method, hist, comp=None):
             shapes = omezarr.level_shapes((1, n_channels, 1, y1 - y0, width), len(full))
             with omezarr.PlaneStreamWriter(path, shapes, dtype, chunks=chunks, batch=1, compression=self.zarr_compression,
                                            pyramid_method=method, device=self.device, row_offset=y0,
                                            level_heights=None if b < 0 else [s[3] for s in full]) as writer:
                 writer.histogram = hist
+                writer.composite = comp
                 writer.acquire(1).copy_(plane)
                 writer.submit([(0, c, 0)])
 
@@ -1487,7 +1636,7 @@ class Stitcher:
                     proj = project([c], y0, y1, b, band_depth[b][0])[0]
                 if last_of_band[b] == i:
                     del band_depth[b]
-            write_band(output_path, proj, self.dtype, self.num_c, c, y0, y1, b, self.pyramid_method, histogram)
+            write_band(output_path, proj, self.dtype, self.num_c, c, y0, y1, b, self.pyramid_method, histogram, composite)
         return output_path
 
     def save_region_aics(self, timepoint, region, stitched_region):
@@ -1612,11 +1761,13 @@ class Stitcher:
         output_path = None
         try:
             self._defer_drain = True      # regions of one geometry stream through ONE writer; it is drained once, below
+            self._composite_async = True
             output_path = self._run_units(units, n_units, rank, world, coll, pair_sharded)
         finally:
             self._defer_drain = False
             self._close_stream_writer()
         self._finish_contrast(wait=True)
+        self._finish_composites(wait=True)
         sharding.barrier()
         self.starting_saving.emit(True)
         if self.merge_timepoints or self.merge_hcs_regions:
@@ -1680,7 +1831,10 @@ class Stitcher:
                 output_path = self.stream_region_to_zarr(timepoint, region, progress_callback=self.update_progress.emit,
                                                          project_to=project_to)
             else:
-                stitched_region = self._stitch_region(timepoint, region, self.update_progress.emit, project_to=project_to)
+                comp = self._new_composite(timepoint, region) if self._composite_kind() == 'stack' else None
+                stitched_region = self._stitch_region(timepoint, region, self.update_progress.emit, project_to=project_to,
+                                                      composite=comp)
+                self._finish_composite(comp)
                 self.starting_saving.emit(False)
                 output_path = self.save_region_aics(timepoint, region, stitched_region)
             if proj is not None:      # (ordered after the projection kernels: stitch_planes made this stream wait for them)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Command line of the stitcher: the reference's flags (stitcher_cli.py:14-62) unchanged,
-plus fourteen switches for what this build adds (``--fusion-mode``, ``--normalization``,
+plus eighteen switches for what this build adds (``--fusion-mode``, ``--normalization``,
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
 ``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``, ``--contrast-limits``,
-``--contrast-percentiles``, ``--focus-guide-channel``, ``--focus-depth-map``).
+``--contrast-percentiles``, ``--focus-guide-channel``, ``--focus-depth-map``, ``--composite``, ``--composite-max-side``,
+``--composite-z``, ``--composite-channels``).
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -78,6 +79,19 @@ FLAGS = (
                                   help="with --z-projection focus / focus-only: also write <region>_stitched_depth<format>, the "
                                        "winning z level + 1 of every voxel (0 = no tile): one plane with --focus-guide-channel, "
                                        "else one per channel; levels by nearest, windows 0 ... number of z levels")),
+    (('--composite',), dict(action='store_true',
+                            help="also write one colour quick-look picture per (timepoint, region): <region>_stitched[_mip|_edf]"
+                                 "_composite.png and .json -- the projection the run writes, else one z plane of the stack, "
+                                 "reduced on the device to block means, windowed by --contrast-percentiles of its own values "
+                                 "and added in the channel colours")),
+    (('--composite-max-side',), dict(type=int, default=4096, metavar='N',
+                                     help="with --composite: the picture's longer side is at most N pixels (16..16384); the block "
+                                          "size is the smallest power of two, up to 256, that achieves it")),
+    (('--composite-z',), dict(type=int, default=None, metavar='Z',
+                              help="with --composite and no projection: the z level shown (default: the middle one)")),
+    (('--composite-channels',), dict(nargs='+', default=None, metavar='NAME',
+                                     help="with --composite: the channels shown, in this order (names out of the output channels, "
+                                          "for an RGB file e.g. <base>_G; default: all)")),
 )
 
 
@@ -138,7 +152,11 @@ def main(argv=None):
                             contrast_limits=args.contrast_limits,
                             contrast_percentiles=tuple(args.contrast_percentiles),
                             focus_guide_channel=args.focus_guide_channel,
-                            focus_depth_map=args.focus_depth_map)
+                            focus_depth_map=args.focus_depth_map,
+                            composite=args.composite,
+                            composite_max_side=args.composite_max_side,
+                            composite_z=args.composite_z,
+                            composite_channels=args.composite_channels)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -348,6 +348,34 @@ int sq_histogram_planes(const void *planes_dev, int64_t plane_stride, int32_t h,
                         uint64_t *hist_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Composite (--composite: one colour quick-look picture per region).  Additions of 0.1.7; integers only, the definition
+ * is the numpy restatement in tests/composite_ref.py ("Composite").
+ *
+ * sq_block_mean replaces the host-side stack copy and slicing of stitcher.py:861-885, _save_debug_slice: n_planes planes
+ * [h, w] -> n_planes planes [ceil(h / f), ceil(w / f)] of the same dtype (SQ_U8 / SQ_U16), f = 2^k, k = 0 ... 8:
+ *     dst[p][Y][X] = floor(sum of src[p] over rows Y f ... min(h, (Y + 1) f) - 1 and the same columns / number of those pixels)
+ * (partial blocks at the bottom and right edge average the pixels that exist; k = 0 is the identity).  Strides and pitches in
+ * elements; no alignment asked of a base or a pitch beyond the element's own.  Row band: only source rows
+ * [row0, row0 + n_rows) are read and destination rows row0 / f ... written -- row0 a multiple of f, n_rows a multiple of f or
+ * running to h (else SQ_ERR_INVALID); dst_dev is always the address of destination row 0.  One read of the source, no atomics,
+ * no scratch, no allocation; deterministic.  n_planes <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+int sq_block_mean(const void *planes_dev, int64_t plane_stride, int32_t h, int32_t w, int64_t pitch, int32_t n_planes,
+                  int32_t dtype, int32_t k, int32_t row0, int32_t n_rows, void *dst_dev, int64_t dst_plane_stride,
+                  int64_t dst_pitch, void *stream);
+
+/* sq_composite_render replaces the min/max normalisation and RGB stacking of stitcher.py:861-885, _save_debug_slice:
+ * n_planes <= 16 planes [h, w] (SQ_U8 / SQ_U16), a window (start, end) and a colour 0xRRGGBB each -> interleaved RGB8
+ * rgb_dev[h][rgb_pitch bytes], 3 w bytes of every row written and nothing else:
+ *     v_c = 0 where m <= start_c, 255 where m >= end_c, else floor((m - start_c) * 255 / (end_c - start_c))
+ *     rgb[j] = min(255, sum over c of floor(v_c * colour_c[j] / 255))
+ * windows (2 n_planes int32: start, end, 0 <= start < end <= 65535) and colors (n_planes uint32) are HOST arrays; they travel
+ * in the kernel arguments.  h <= 65535. */
+int sq_composite_render(const void *means_dev, int64_t plane_stride, int32_t h, int32_t w, int64_t pitch, int32_t n_planes,
+                        int32_t dtype, const int32_t *windows, const uint32_t *colors, uint8_t *rgb_dev, int64_t rgb_pitch,
+                        void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
