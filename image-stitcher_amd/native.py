@@ -128,6 +128,9 @@ EXPORTS = {
                                 C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'sq_composite_render': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                       C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_void_p, C.c_int64, C.c_void_p]),
+    'sq_tophat_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'sq_tophat_tiles': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1091,6 +1094,80 @@ def composite_render(means, windows, colors, out=None, stream=None):
                                  sq_dtype_of(np_dtype_of_torch(means.dtype)), win, col, out.data_ptr(), out.stride(0),
                                  _stream_ptr(stream)), 'sq_composite_render')
     return out
+
+
+SQ_TOPHAT_MAX_RADIUS = 127
+
+
+def tophat_scratch_bytes(n_images: int, h: int, w: int, dtype) -> int:
+    """Bytes of the caller-owned scratch of ``tophat_tiles`` for ``n_images`` planes of h x w (uint8 / uint16): the erosion of
+    the batch, as many bytes as the planes themselves."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype('uint8'), np.dtype('uint16')):
+        raise ValueError(f"the top-hat filters uint8 and uint16 planes, got {dt}")
+    if int(n_images) < 0 or int(h) < 1 or int(w) < 1:
+        raise ValueError(f"bad sizes: {n_images} planes of {h} x {w}")
+    n = int(lib().sq_tophat_scratch_bytes(int(n_images), int(h), int(w), sq_dtype_of(dt)))
+    if n < 0:
+        _check(n, 'sq_tophat_scratch_bytes')
+    return n
+
+
+def tophat_tiles(tiles, radius: int, scratch=None, stream=None):
+    """White top-hat of every H x W plane of ``tiles`` IN PLACE (sq_tophat_tiles; an extension, the reference has none): the plane
+    minus its morphological opening with a square (2R+1) x (2R+1) window clipped to the plane -- ``tests/tophat_ref.tophat``.
+
+    tiles:   uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
+             uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    radius:  R, 1..127 (windows larger than the plane are fine).
+    scratch: optional device uint8 tensor of at least ``tophat_scratch_bytes(n_planes, H, W, dtype)`` bytes (reuse it across
+             calls); allocated here when None.
+    Returns ``tiles``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= SQ_TOPHAT_MAX_RADIUS:
+        raise ValueError(f"top-hat radius must be an integer in 1..{SQ_TOPHAT_MAX_RADIUS}, got {radius!r}")
+    h, w = int(tiles.shape[-2]), int(tiles.shape[-1])
+    if h < 1 or w < 1:
+        raise ValueError(f"planes of {h} x {w}")
+    if w > 1 and tiles.stride(-1) != 1:
+        raise ValueError("tiles rows must be contiguous")
+    pitch = int(tiles.stride(-2)) if h > 1 else w
+    if pitch < w:
+        raise ValueError("tiles rows overlap")
+    # the leading dimensions as one run of planes a uniform stride apart
+    lead = [(int(n), int(s)) for n, s in zip(tiles.shape[:-2], tiles.stride()[:-2]) if n != 1]
+    n_images = 1
+    for n, _ in lead:
+        n_images *= n
+    plane_stride = (h - 1) * pitch + w
+    if n_images > 1:
+        for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+            if s0 != n1 * s1:
+                raise ValueError("the planes of tiles must be a uniform stride apart (a contiguous stack or a regular view of one)")
+        plane_stride = lead[-1][1]
+        if plane_stride < (h - 1) * pitch + w:
+            raise ValueError("the planes of tiles overlap")
+    np_dtype = np_dtype_of_torch(tiles.dtype)
+    need = tophat_scratch_bytes(n_images, h, w, np_dtype)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=tiles.device)
+        if stream is not None:
+            scratch.record_stream(stream)
+    elif not torch.is_tensor(scratch) or not scratch.is_cuda or not scratch.is_contiguous() or \
+            scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"top-hat scratch must be a contiguous device tensor of at least {need} bytes")
+    if scratch.data_ptr() % 16:
+        raise ValueError("top-hat scratch must be aligned to 16 bytes")
+    if n_images == 0:
+        return tiles
+    _check(lib().sq_tophat_tiles(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype), int(radius),
+                                 scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream_ptr(stream)),
+           'sq_tophat_tiles')
+    return tiles
 
 
 _COPY_STREAMS = {}

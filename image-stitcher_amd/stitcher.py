@@ -72,7 +72,7 @@ class Stitcher:
                  focus_radius: int = 3, pyramid_method: str = 'nearest', contrast_limits: str = 'dtype',
                  contrast_percentiles=(0.1, 99.9), focus_guide_channel: Optional[str] = None, focus_depth_map: bool = False,
                  composite: bool = False, composite_max_side: int = 4096, composite_z: Optional[int] = None,
-                 composite_channels=None):
+                 composite_channels=None, background_subtract: str = 'none', background_radius: int = 50):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -148,6 +148,19 @@ class Stitcher:
         self._composite_jobs = []        # PNG encodings under way on the pool
         self._composite_pool = None
         self._composite_async = False    # run(): PNGs are encoded on a worker thread
+        # Extension: background_subtract='tophat' removes the slowly varying additive background of every staged tile plane on the
+        # device before anything is projected or fused (sq_tophat_tiles): the plane minus its opening with a square window of
+        # radius background_radius (1..127), clipped to the tile -- what filtering the files beforehand gives.  It runs on the
+        # raw tile, before the flatfield divide; registration and the flatfield estimate keep reading raw tiles.  Meant for
+        # fluorescence; on brightfield it is simply what the definition says.  'none': nothing is launched or allocated.  A
+        # radius without 'tophat' is accepted and unused.
+        if background_subtract not in ('none', 'tophat'):
+            raise ValueError(f"background_subtract must be 'none' or 'tophat', got {background_subtract!r}")
+        if isinstance(background_radius, bool) or not isinstance(background_radius, (int, np.integer)) or \
+                not 1 <= int(background_radius) <= native.SQ_TOPHAT_MAX_RADIUS:
+            raise ValueError(f"background_radius must be an integer in 1..{native.SQ_TOPHAT_MAX_RADIUS}, got {background_radius!r}")
+        self.background_subtract = background_subtract
+        self.background_radius = int(background_radius)
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -923,6 +936,8 @@ class Stitcher:
         th, tw = self.input_height, self.input_width
         total_tiles = len(region_data)
         print(f"Beginning stitching of {total_tiles} tiles for region {region} timepoint {timepoint}")
+        if self.background_subtract == 'tophat':
+            self._write_background_note(timepoint, region)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1043,7 +1058,9 @@ class Stitcher:
                 focus_scratch = torch.empty(native.focus_scratch_bytes(n, th, tw), dtype=torch.uint8, device=self.device) \
                     if focus else None
                 staged_budget = budget - (0 if focus_scratch is None else focus_scratch.numel())
-                batch = max(1, min(len(plist), staged_budget // max(1, per_plane)))
+                # the top-hat's scratch (the erosion of a batch: as many bytes as its tiles) counts against the budget too
+                tophat = self.background_subtract == 'tophat'
+                batch = max(1, min(len(plist), staged_budget // max(1, per_plane * (2 if tophat else 1))))
                 if writer is not None:
                     batch = min(batch, writer.batch)
                 chunks = [plist[b0:b0 + batch] for b0 in range(0, len(plist), batch)]
@@ -1061,6 +1078,14 @@ class Stitcher:
                 # the slots' "copy and fusion finished" events live with the buffers: another group (or the next
                 # region) that gets the same cached staging must wait for the H2D copy still reading it
                 staging, on_dev, done, turn = bufs
+                tophat_scratch = None
+                if tophat:      # one scratch beside the ingest buffers: the launches of one stream follow each other
+                    tkey = ('tophat', batch, n, th, tw, np.dtype(self.dtype).str)
+                    tophat_scratch = self._buffer_cache.get(tkey)
+                    if tophat_scratch is None:
+                        tophat_scratch = torch.empty(native.tophat_scratch_bytes(batch * n, th, tw, self.dtype), dtype=torch.uint8,
+                                                     device=self.device)
+                        self._keep_buffers(tkey, tophat_scratch)
                 for k, chunk in enumerate(chunks):
                     slot = turn[0] % n_slots      # (the turn goes on across calls: the next region starts on the other slot)
                     turn[0] += 1
@@ -1089,6 +1114,8 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
+                    if tophat:      # in place on the staged tiles: everything below reads the filtered planes
+                        native.tophat_tiles(tiles, self.background_radius, tophat_scratch)
                     flats = [flats_dev.get(p // self.num_z) for p in chunk] if self.apply_flatfield else None
                     slots = [slot_of[p] for p in chunk]
                     if project_to is not None:
@@ -1138,6 +1165,19 @@ class Stitcher:
             torch.cuda.synchronize(self.device)
         print(f"Time to stitch region {region} timepoint {timepoint}: {time.time() - start_time}")
         return flat_canvas, plane_ids
+
+    def _write_background_note(self, timepoint, region) -> None:
+        """``<t>_stitched/<region>_stitched_background.json``: what was removed from the tiles of every store of this region
+        (the same bytes from every rank and call, put in place atomically)."""
+        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"{region}_stitched_background.json")
+        note = {'method': 'tophat', 'radius': self.background_radius, 'window': 2 * self.background_radius + 1,
+                'applies_to': 'every staged tile plane, before the flatfield divide'}
+        tmp = f"{path}.{os.getpid()}.tmp"
+        with open(tmp, 'w') as fh:
+            json.dump(note, fh, indent=1)
+        os.replace(tmp, path)
 
     # ------------------------------------------------------------------ output
     # ------------------------------------------------------------------ contrast windows

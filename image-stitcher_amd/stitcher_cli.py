@@ -4,7 +4,8 @@ plus eighteen switches for what this build adds (``--fusion-mode``, ``--normaliz
 ``--zarr-compression``, ``--per-region-registration``, ``--flatfield-estimator``, ``--all-pairs-registration``,
 ``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``, ``--contrast-limits``,
 ``--contrast-percentiles``, ``--focus-guide-channel``, ``--focus-depth-map``, ``--composite``, ``--composite-max-side``,
-``--composite-z``, ``--composite-channels``).
+``--composite-z``, ``--composite-channels``).  Two more select the background removal of the staged tiles:
+``--background-subtract`` and ``--background-radius``.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -92,6 +93,15 @@ FLAGS = (
     (('--composite-channels',), dict(nargs='+', default=None, metavar='NAME',
                                      help="with --composite: the channels shown, in this order (names out of the output channels, "
                                           "for an RGB file e.g. <base>_G; default: all)")),
+    (('--background-subtract',), dict(choices=['none', 'tophat'], default='none',
+                                      help="remove the slowly varying additive background of every tile on the device before it is "
+                                           "projected or fused: tophat = the tile minus its morphological opening with a square "
+                                           "window of --background-radius, clipped to the tile (meant for fluorescence; registration "
+                                           "and the flatfield estimate keep reading raw tiles); writes "
+                                           "<region>_stitched_background.json")),
+    (('--background-radius',), dict(type=int, default=50, metavar='R',
+                                    help="with --background-subtract tophat: radius of the window, 1..127 (larger than the "
+                                         "structures to keep, smaller than the background's variation)")),
 )
 
 
@@ -156,7 +166,9 @@ def main(argv=None):
                             composite=args.composite,
                             composite_max_side=args.composite_max_side,
                             composite_z=args.composite_z,
-                            composite_channels=args.composite_channels)
+                            composite_channels=args.composite_channels,
+                            background_subtract=args.background_subtract,
+                            background_radius=args.background_radius)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

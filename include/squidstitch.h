@@ -376,6 +376,26 @@ int sq_composite_render(const void *means_dev, int64_t plane_stride, int32_t h, 
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Background removal (--background-subtract tophat; extension: the reference has none -- its BaSiC runs with
+ * get_darkfield=False, so nothing there removes an additive term).  A white top-hat with a square window of radius R per plane
+ * I [h, w] (SQ_U8 / SQ_U16), IN PLACE:
+ *     E(y, x) = min I over the (2R+1) x (2R+1) window centred on (y, x), clipped to the plane
+ *     O(y, x) = max E over the same clipped window
+ *     I      := I - O                       (O <= I, so nothing wraps)
+ * The definition is the numpy restatement in tests/tophat_ref.py.  n_images planes plane_stride elements apart, rows pitch
+ * elements apart (pitch >= w); no alignment asked of the base or the pitch beyond the element's own.  1 <= radius <= 127, any
+ * h, w >= 1 (windows larger than the plane included).  The caller owns the scratch (16-byte aligned, at least
+ * sq_tophat_scratch_bytes(n_images, h, w, dtype) bytes: the erosion of the batch); the library allocates nothing.  Two launches
+ * (erosion into the scratch; dilation, subtraction and store), the work per pixel independent of R (running extrema, csrc/tophat.hip);
+ * integers only, no atomics, deterministic.  SQ_ERR_INVALID for a radius out of range, a pitch below w, a NULL or misaligned
+ * buffer; SQ_ERR_WORKSPACE for scratch that is too small.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_TOPHAT_MAX_RADIUS 127
+int64_t sq_tophat_scratch_bytes(int32_t n_images, int32_t h, int32_t w, int32_t dtype);
+int sq_tophat_tiles(void *tiles_dev, int32_t n_images, int32_t h, int32_t w, int64_t plane_stride, int64_t pitch,
+                    int32_t dtype, int32_t radius, void *scratch_dev, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
