@@ -1474,6 +1474,114 @@ int allow_lds(K kernel, size_t bytes) {
 
 int pick_threads(int n) { return n <= 128 ? 64 : (n <= 512 ? 128 : 256); }
 
+// Every launch choice of sq_register_pairs for a batch of n_pairs crops with layout L: sq_register_pairs launches from
+// the struct this fills, and sq_register_describe hands the same struct out (host only, no device call).
+sq_register_plan make_plan(int n_pairs, const Layout &L) {
+    sq_register_plan pl{};
+    pl.m0 = L.m0;
+    pl.m1 = L.m1;
+    pl.long0 = L.long0;
+    pl.long1 = L.long1;
+    // the general (mixed-radix) instantiations only where an axis' plan has mixed-radix stages: see lines_fft_plan
+    pl.gen0 = L.ax0.nf > 0;
+    pl.gen1 = L.ax1.nf > 0;
+    pl.nf0 = L.ax0.nf;
+    pl.nf1 = L.ax1.nf;
+    static_assert(sizeof(pl.radix0) == MAX_STAGES && sizeof(pl.radix1) == MAX_STAGES, "sq_register_plan holds MAX_STAGES radices per axis");
+    for (int i = 0; i < MAX_STAGES; ++i) {
+        pl.radix0[i] = L.ax0.radix[i];
+        pl.radix1[i] = L.ax1.radix[i];
+    }
+    // columns per block (directly transformed axis 0): two [tc][n0] complex arrays in LDS; a column too long for two to fit
+    // (n0 > 4608), or one that needs a Bluestein line, goes one per block (columns_single_kernel).  SMALL blocks: a block
+    // runs its phases one after the other (strided load, transforms, product, store, inverse, store), and only other
+    // blocks of the CU can fill the gaps -- 16 KiB of columns per block (2 x 256 or, for longer columns, a single one)
+    // with 256 threads measured 9.5 / 10.0 ms per 992-pair batch of 256- / 1024-point columns against 11.2 / 11.2 ms
+    // with 128 KiB / 512 threads (profiles/r03_exp_registration_shapes.log).  A power of two, so that 8 / tc blocks
+    // share the spectra's 128-byte lines (P.share).
+    int tc = 0;
+    if (!L.m0 && !L.long0 && 2 * (int64_t)L.n0 * 16 <= 144 * 1024) {
+        tc = 1;
+        while (tc < 8 && 2 * (int64_t)(2 * tc) * L.n0 * 16 <= 16 * 1024) tc *= 2;
+        // ... but enough lines that a stage has a butterfly for every thread: n0 / r of them per line, r the largest radix
+        int rmax = 4;
+        for (int i = 0; i < L.ax0.nf; ++i) rmax = std::max<int>(rmax, L.ax0.radix[i]);
+        while (tc < 8 && 2 * (int64_t)tc * (L.n0 / rmax) < 256 && 2 * (int64_t)(2 * tc) * L.n0 * 16 <= 144 * 1024) tc *= 2;
+    }
+    pl.tc = tc;
+    // Lines per block of the row kernels, measured on 240-pair batches: the forward kernel (global loads
+    // + a float64 normalisation per pixel) likes many small blocks -- 16 KB of lines; the inverse kernel
+    // (LDS FFT + a per-wave argmax) likes up to 8 lines within 64 KB.  Never more than keeps ~2 blocks
+    // per CU busy when the batch is small (the bench's single centre pairs).
+    const int64_t line_bytes = (int64_t)(L.m1 ? L.m1 : L.n1) * 16;   // a Bluestein line is m1 points long
+    auto lines_per_block = [&](int cap, int n_lines) {
+        if (L.long1) return 1;
+        int rl = (int)std::max<int64_t>(1, std::min<int64_t>(cap, 64 * 1024 / line_bytes));
+        while (rl > 1 && (int64_t)n_pairs * ((n_lines + rl - 1) / rl) < 512) rl >>= 1;
+        return rl;
+    };
+    const int rlf = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 16384 / line_bytes)), L.n0);
+    const int rli = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 32768 / line_bytes)), (L.n0 + 1) / 2);
+    pl.rl_fwd = rlf;
+    pl.rl_inv = rli;
+    // one LONG line per block (a Bluestein line of thousands of points: up to 152 KB of LDS, so one or two blocks per CU):
+    // the block brings the waves that hide its latencies itself -- 1024 threads from 32 KB of line on, 512 from 16 KB
+    // (measured on 312 x 3122 crops, lines of 6400 points: rows forward 2.87 -> see profiles/r03_kernel_probe_registration.log)
+    auto line_threads = [&](int rl) {
+        if (rl > 1) return 256;
+        // (a 1024-point line on its own, 16 KB exactly: 256 threads = one radix-4 butterfly each per pass, 8.05 against
+        // 8.45 ms per 992-pair batch with 512, profiles/r03_exp_registration_threads.log)
+        return line_bytes >= 32 * 1024 ? 1024 : (line_bytes > 16 * 1024 ? 512 : pick_threads(L.n1));
+    };
+    // a long axis: LONG_SLOTS workgroups (fewer when there are fewer lines), each with its scratch line, walk over the lines
+    auto grid_long = [&](int32_t *g, int64_t lines) {
+        g[0] = (int32_t)std::min<int64_t>(L.n_slots, lines);
+        g[1] = 1;
+    };
+    if (L.long1) {
+        pl.threads_fwd = pl.threads_inv = LONG_THREADS;
+        grid_long(pl.grid_fwd, (int64_t)n_pairs * L.n0);
+        grid_long(pl.grid_inv, (int64_t)n_pairs * ((L.n0 + 1) / 2));
+    } else {
+        pl.threads_fwd = line_threads(rlf);
+        pl.threads_inv = line_threads(rli);
+        pl.lds_fwd = rlf * line_bytes;
+        pl.lds_inv = rli * line_bytes;
+        pl.grid_fwd[0] = (L.n0 + rlf - 1) / rlf;
+        pl.grid_fwd[1] = n_pairs;
+        pl.grid_inv[0] = ((L.n0 + 1) / 2 + rli - 1) / rli;
+        pl.grid_inv[1] = n_pairs;
+    }
+    if (L.long0) {
+        pl.columns_single = 1;
+        pl.columns_single_threads = LONG_THREADS;
+        grid_long(pl.grid_col, (int64_t)n_pairs * L.n1h);
+    } else if (tc < 1) {
+        pl.columns_single = 1;
+        pl.lds_col = (int64_t)(L.m0 ? L.m0 : L.n0) * 16;
+        pl.share = 8;
+        pl.grid_col[0] = (L.n1h + 7) / 8 * 8;
+        pl.grid_col[1] = n_pairs;
+        pl.columns_single_threads = pl.lds_col > 80 * 1024 ? 1024 : COL_THREADS;     // one block per CU: twice the waves
+    } else {
+        pl.lds_col = (int64_t)2 * tc * L.n0 * 16;
+        const int share = (tc == 1 || tc == 2 || tc == 4) ? 8 / tc : 1;
+        pl.share = share;
+        pl.grid_col[0] = ((L.n1h + tc - 1) / tc + share - 1) / share * share;
+        pl.grid_col[1] = n_pairs;
+        pl.col_threads = pl.lds_col >= 64 * 1024 ? COL_THREADS : 256;   // a long column brings its own waves
+    }
+    if (L.up > 1) {
+        const int row_pairs = (L.n0 + 1) / 2;    // slots of a row and its mirror (upsample_rows_kernel)
+        const bool wide = (int64_t)n_pairs * ((row_pairs + 63) / 64) >= 256;
+        pl.upsample_rows_tb = wide ? 4 : 1;
+        pl.upsample_rows_kc = wide ? 16 : 32;
+        pl.grid_up_rows[0] = wide ? (row_pairs + 63) / 64 : (row_pairs + 15) / 16;
+        pl.grid_up_rows[1] = n_pairs;
+    }
+    return pl;
+}
+
 }  // namespace
 
 extern "C" int sq_tile_minmax(const void *const *tile_ptrs_dev, const void *tile_base_dev, int64_t tile_stride,
@@ -1546,6 +1654,20 @@ extern "C" int64_t sq_register_workspace_bytes(int32_t n_pairs, int32_t n0, int3
     return make_layout(n_pairs, n0, n1, upsample_factor).total;
 }
 
+extern "C" int sq_register_describe(int32_t n_pairs, int32_t n0, int32_t n1, int32_t upsample_factor, int32_t tile_dtype,
+                                    sq_register_plan *out) {
+    if (!out) return fail(SQ_ERR_INVALID, "sq_register_describe: NULL argument");
+    if (n_pairs < 1 || n_pairs > 65535) return fail(SQ_ERR_INVALID, "sq_register_describe: n_pairs %d out of range", n_pairs);
+    if (upsample_factor < 1 || upsample_factor > 100)
+        return fail(SQ_ERR_INVALID, "sq_register_describe: upsample_factor %d out of range", upsample_factor);
+    if (tile_dtype != SQ_U8 && tile_dtype != SQ_U16) return fail(SQ_ERR_UNSUPPORTED, "sq_register_describe: dtype %d", tile_dtype);
+    int rc;
+    if ((rc = check_line(n0, "axis-0")) != SQ_OK) return rc;
+    if ((rc = check_line(n1, "axis-1")) != SQ_OK) return rc;
+    *out = make_plan(n_pairs, make_layout(n_pairs, n0, n1, upsample_factor));
+    return SQ_OK;
+}
+
 extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
     if (!a || (!a->tile_ptrs_dev && !a->tile_base_dev) || !a->minmax_dev || !a->pairs_dev || !a->results_dev ||
         !a->workspace_dev)
@@ -1567,6 +1689,7 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
     if (reinterpret_cast<uintptr_t>(a->workspace_dev) % 16) return fail(SQ_ERR_INVALID, "sq_register_pairs: workspace not 16-byte aligned");
     if (a->n_pairs == 0) return SQ_OK;
 
+    const sq_register_plan pl = make_plan(a->n_pairs, L);
     RegParams P{};
     P.tile_ptrs = a->tile_ptrs_dev;
     P.tile_base = a->tile_base_dev;
@@ -1582,24 +1705,10 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
     P.n_tiles = a->n_tiles;
     P.tile_h = a->tile_h;
     P.tile_w = a->tile_w;
-    // columns per block (directly transformed axis 0): two [tc][n0] complex arrays in LDS; a column too long for two to fit
-    // (n0 > 4608), or one that needs a Bluestein line, goes one per block (columns_single_kernel).  SMALL blocks: a block
-    // runs its phases one after the other (strided load, transforms, product, store, inverse, store), and only other
-    // blocks of the CU can fill the gaps -- 16 KiB of columns per block (2 x 256 or, for longer columns, a single one)
-    // with 256 threads measured 9.5 / 10.0 ms per 992-pair batch of 256- / 1024-point columns against 11.2 / 11.2 ms
-    // with 128 KiB / 512 threads (profiles/r03_exp_registration_shapes.log).  A power of two, so that 8 / tc blocks
-    // share the spectra's 128-byte lines (P.share).
-    int tc = 0;
-    if (!L.m0 && !L.long0 && 2 * (int64_t)L.n0 * 16 <= 144 * 1024) {
-        tc = 1;
-        while (tc < 8 && 2 * (int64_t)(2 * tc) * L.n0 * 16 <= 16 * 1024) tc *= 2;
-        // ... but enough lines that a stage has a butterfly for every thread: n0 / r of them per line, r the largest radix
-        int rmax = 4;
-        for (int i = 0; i < L.ax0.nf; ++i) rmax = std::max<int>(rmax, L.ax0.radix[i]);
-        while (tc < 8 && 2 * (int64_t)tc * (L.n0 / rmax) < 256 && 2 * (int64_t)(2 * tc) * L.n0 * 16 <= 144 * 1024) tc *= 2;
-    }
-    const int col_threads = 2 * (int64_t)std::max(tc, 1) * L.n0 * 16 >= 64 * 1024 ? COL_THREADS : 256;   // a long column brings its own waves
-    P.tc = tc;
+    P.tc = pl.tc;
+    P.rl_fwd = pl.rl_fwd;
+    P.rl_inv = pl.rl_inv;
+    P.share = pl.share;
     hipStream_t s = static_cast<hipStream_t>(stream_);
 
     hipLaunchKernelGGL(init_tables_kernel, dim3(64), dim3(256), 0, s, P);
@@ -1611,92 +1720,52 @@ extern "C" int sq_register_pairs(const sq_register_args *a, void *stream_) {
     for (int axis = 0; axis < 2; ++axis)      // ... of a long axis: in place in the workspace
         if ((axis ? L.m1 : L.m0) && (axis ? L.long1 : L.long0))
             hipLaunchKernelGGL(init_chirp_kernel<true>, dim3(1), dim3(1024), 0, s, P, axis);
-    // Lines per block of the row kernels, measured on 240-pair batches: the forward kernel (global loads
-    // + a float64 normalisation per pixel) likes many small blocks -- 16 KB of lines; the inverse kernel
-    // (LDS FFT + a per-wave argmax) likes up to 8 lines within 64 KB.  Never more than keeps ~2 blocks
-    // per CU busy when the batch is small (the bench's single centre pairs).
-    const int64_t line_bytes = (int64_t)(L.m1 ? L.m1 : L.n1) * 16;   // a Bluestein line is m1 points long
-    auto lines_per_block = [&](int cap, int n_lines) {
-        if (L.long1) return 1;
-        int rl = (int)std::max<int64_t>(1, std::min<int64_t>(cap, 64 * 1024 / line_bytes));
-        while (rl > 1 && (int64_t)a->n_pairs * ((n_lines + rl - 1) / rl) < 512) rl >>= 1;
-        return rl;
-    };
-    const int rlf = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 16384 / line_bytes)), L.n0);
-    const int rli = lines_per_block((int)std::max<int64_t>(1, std::min<int64_t>(8, 32768 / line_bytes)), (L.n0 + 1) / 2);
-    P.rl_fwd = rlf;
-    P.rl_inv = rli;
-    // one LONG line per block (a Bluestein line of thousands of points: up to 152 KB of LDS, so one or two blocks per CU):
-    // the block brings the waves that hide its latencies itself -- 1024 threads from 32 KB of line on, 512 from 16 KB
-    // (measured on 312 x 3122 crops, lines of 6400 points: rows forward 2.87 -> see profiles/r03_kernel_probe_registration.log)
-    auto line_threads = [&](int rl) {
-        if (rl > 1) return 256;
-        // (a 1024-point line on its own, 16 KB exactly: 256 threads = one radix-4 butterfly each per pass, 8.05 against
-        // 8.45 ms per 992-pair batch with 512, profiles/r03_exp_registration_threads.log)
-        return line_bytes >= 32 * 1024 ? 1024 : (line_bytes > 16 * 1024 ? 512 : pick_threads(L.n1));
-    };
-    const int ntf = line_threads(rlf), nti = line_threads(rli);
-    const size_t lds_fwd = L.long1 ? 0 : (size_t)(rlf * line_bytes), lds_inv = L.long1 ? 0 : (size_t)(rli * line_bytes);
-    // the general (mixed-radix) instantiations only where an axis' plan has mixed-radix stages: see lines_fft_plan
-    const bool gen0 = L.ax0.nf > 0, gen1 = L.ax1.nf > 0;
+    const bool gen0 = pl.gen0 != 0, gen1 = pl.gen1 != 0;
+    const size_t lds_fwd = (size_t)pl.lds_fwd, lds_col = (size_t)pl.lds_col, lds_inv = (size_t)pl.lds_inv;
+    const dim3 grid_fwd(pl.grid_fwd[0], pl.grid_fwd[1]), grid_col(pl.grid_col[0], pl.grid_col[1]), grid_inv(pl.grid_inv[0], pl.grid_inv[1]);
 #define SQ_LAUNCH(KERNEL, GRID, THREADS, LDS)                                        \
     do {                                                                             \
         if ((rc = allow_lds(KERNEL, LDS)) != SQ_OK) return rc;                       \
         hipLaunchKernelGGL(KERNEL, GRID, dim3(THREADS), LDS, s, P);                  \
     } while (0)
-    const dim3 grid_fwd((L.n0 + rlf - 1) / rlf, a->n_pairs);
-    // a long axis: LONG_SLOTS workgroups (fewer when there are fewer lines), each with its scratch line, walk over the lines
-    auto grid_long = [&](int64_t lines) { return dim3((unsigned)std::min<int64_t>(L.n_slots, lines)); };
     if (L.long1) {
-        const dim3 g = grid_long((int64_t)a->n_pairs * L.n0);
         if (a->tile_dtype == SQ_U16) {
-            if (gen1) SQ_LAUNCH((rows_forward_kernel<uint16_t, true, true>), g, LONG_THREADS, 0);
-            else SQ_LAUNCH((rows_forward_kernel<uint16_t, false, true>), g, LONG_THREADS, 0);
+            if (gen1) SQ_LAUNCH((rows_forward_kernel<uint16_t, true, true>), grid_fwd, pl.threads_fwd, lds_fwd);
+            else SQ_LAUNCH((rows_forward_kernel<uint16_t, false, true>), grid_fwd, pl.threads_fwd, lds_fwd);
         } else {
-            if (gen1) SQ_LAUNCH((rows_forward_kernel<uint8_t, true, true>), g, LONG_THREADS, 0);
-            else SQ_LAUNCH((rows_forward_kernel<uint8_t, false, true>), g, LONG_THREADS, 0);
+            if (gen1) SQ_LAUNCH((rows_forward_kernel<uint8_t, true, true>), grid_fwd, pl.threads_fwd, lds_fwd);
+            else SQ_LAUNCH((rows_forward_kernel<uint8_t, false, true>), grid_fwd, pl.threads_fwd, lds_fwd);
         }
     } else if (a->tile_dtype == SQ_U16) {
-        if (gen1) SQ_LAUNCH((rows_forward_kernel<uint16_t, true>), grid_fwd, ntf, lds_fwd);
-        else SQ_LAUNCH((rows_forward_kernel<uint16_t, false>), grid_fwd, ntf, lds_fwd);
+        if (gen1) SQ_LAUNCH((rows_forward_kernel<uint16_t, true>), grid_fwd, pl.threads_fwd, lds_fwd);
+        else SQ_LAUNCH((rows_forward_kernel<uint16_t, false>), grid_fwd, pl.threads_fwd, lds_fwd);
     } else {
-        if (gen1) SQ_LAUNCH((rows_forward_kernel<uint8_t, true>), grid_fwd, ntf, lds_fwd);
-        else SQ_LAUNCH((rows_forward_kernel<uint8_t, false>), grid_fwd, ntf, lds_fwd);
+        if (gen1) SQ_LAUNCH((rows_forward_kernel<uint8_t, true>), grid_fwd, pl.threads_fwd, lds_fwd);
+        else SQ_LAUNCH((rows_forward_kernel<uint8_t, false>), grid_fwd, pl.threads_fwd, lds_fwd);
     }
     if (L.long0) {
-        const dim3 g = grid_long((int64_t)a->n_pairs * L.n1h);
-        if (gen0) SQ_LAUNCH((columns_single_kernel<true, true>), g, LONG_THREADS, 0);
-        else SQ_LAUNCH((columns_single_kernel<false, true>), g, LONG_THREADS, 0);
-    } else if (tc < 1) {
-        const size_t lds_col = (size_t)(L.m0 ? L.m0 : L.n0) * 16;
-        P.share = 8;
-        const dim3 grid_col((L.n1h + 7) / 8 * 8, a->n_pairs);
-        const int ntc = lds_col > 80 * 1024 ? 1024 : COL_THREADS;     // one block per CU: twice the waves
-        if (gen0) SQ_LAUNCH(columns_single_kernel<true>, grid_col, ntc, lds_col);
-        else SQ_LAUNCH(columns_single_kernel<false>, grid_col, ntc, lds_col);
+        if (gen0) SQ_LAUNCH((columns_single_kernel<true, true>), grid_col, pl.columns_single_threads, lds_col);
+        else SQ_LAUNCH((columns_single_kernel<false, true>), grid_col, pl.columns_single_threads, lds_col);
+    } else if (pl.columns_single) {
+        if (gen0) SQ_LAUNCH(columns_single_kernel<true>, grid_col, pl.columns_single_threads, lds_col);
+        else SQ_LAUNCH(columns_single_kernel<false>, grid_col, pl.columns_single_threads, lds_col);
     } else {
-        const size_t lds_col = (size_t)2 * tc * L.n0 * 16;
-        const int share = (tc == 1 || tc == 2 || tc == 4) ? 8 / tc : 1;
-        P.share = share;
-        const dim3 grid_col(((L.n1h + tc - 1) / tc + share - 1) / share * share, a->n_pairs);
-        if (gen0) SQ_LAUNCH(columns_kernel<true>, grid_col, col_threads, lds_col);
-        else SQ_LAUNCH(columns_kernel<false>, grid_col, col_threads, lds_col);
+        if (gen0) SQ_LAUNCH(columns_kernel<true>, grid_col, pl.col_threads, lds_col);
+        else SQ_LAUNCH(columns_kernel<false>, grid_col, pl.col_threads, lds_col);
     }
-    const dim3 grid_inv(((L.n0 + 1) / 2 + rli - 1) / rli, a->n_pairs);
     if (L.long1) {
-        const dim3 g = grid_long((int64_t)a->n_pairs * ((L.n0 + 1) / 2));
-        if (gen1) SQ_LAUNCH((rows_inverse_kernel<true, true>), g, LONG_THREADS, 0);
-        else SQ_LAUNCH((rows_inverse_kernel<false, true>), g, LONG_THREADS, 0);
-    } else if (gen1) SQ_LAUNCH(rows_inverse_kernel<true>, grid_inv, nti, lds_inv);
-    else SQ_LAUNCH(rows_inverse_kernel<false>, grid_inv, nti, lds_inv);
+        if (gen1) SQ_LAUNCH((rows_inverse_kernel<true, true>), grid_inv, pl.threads_inv, lds_inv);
+        else SQ_LAUNCH((rows_inverse_kernel<false, true>), grid_inv, pl.threads_inv, lds_inv);
+    } else if (gen1) SQ_LAUNCH(rows_inverse_kernel<true>, grid_inv, pl.threads_inv, lds_inv);
+    else SQ_LAUNCH(rows_inverse_kernel<false>, grid_inv, pl.threads_inv, lds_inv);
 #undef SQ_LAUNCH
     hipLaunchKernelGGL(peak_kernel, dim3(a->n_pairs), dim3(256), 0, s, P);
     if (a->upsample_factor > 1) {
-        const int row_pairs = (L.n0 + 1) / 2;    // slots of a row and its mirror (upsample_rows_kernel)
-        if ((int64_t)a->n_pairs * ((row_pairs + 63) / 64) >= 256)
-            hipLaunchKernelGGL((upsample_rows_kernel<4, 16>), dim3((row_pairs + 63) / 64, a->n_pairs), dim3(256), 0, s, P);
+        const dim3 grid_up(pl.grid_up_rows[0], pl.grid_up_rows[1]);
+        if (pl.upsample_rows_tb == 4)
+            hipLaunchKernelGGL((upsample_rows_kernel<4, 16>), grid_up, dim3(256), 0, s, P);
         else
-            hipLaunchKernelGGL((upsample_rows_kernel<1, 32>), dim3((row_pairs + 15) / 16, a->n_pairs), dim3(256), 0, s, P);
+            hipLaunchKernelGGL((upsample_rows_kernel<1, 32>), grid_up, dim3(256), 0, s, P);
         hipLaunchKernelGGL(upsample_cols_kernel, dim3(L.region, a->n_pairs), dim3(256), 0, s, P);
         hipLaunchKernelGGL(upsample_peak_kernel, dim3(a->n_pairs), dim3(256), 0, s, P);
     }

@@ -82,6 +82,21 @@ class _RegisterArgs(C.Structure):
     ]
 
 
+class _RegisterPlan(C.Structure):
+    _fields_ = [
+        ('m0', C.c_int32), ('m1', C.c_int32), ('long0', C.c_int32), ('long1', C.c_int32),
+        ('gen0', C.c_int32), ('gen1', C.c_int32), ('nf0', C.c_int32), ('nf1', C.c_int32),
+        ('radix0', C.c_uint8 * 16), ('radix1', C.c_uint8 * 16),
+        ('tc', C.c_int32), ('share', C.c_int32), ('col_threads', C.c_int32),
+        ('columns_single', C.c_int32), ('columns_single_threads', C.c_int32),
+        ('rl_fwd', C.c_int32), ('rl_inv', C.c_int32), ('threads_fwd', C.c_int32), ('threads_inv', C.c_int32),
+        ('upsample_rows_tb', C.c_int32), ('upsample_rows_kc', C.c_int32),
+        ('grid_fwd', C.c_int32 * 2), ('grid_col', C.c_int32 * 2), ('grid_inv', C.c_int32 * 2),
+        ('grid_up_rows', C.c_int32 * 2),
+        ('lds_fwd', C.c_int64), ('lds_col', C.c_int64), ('lds_inv', C.c_int64),
+    ]
+
+
 class _ArenaInfo(C.Structure):
     _fields_ = [('base_dev', C.c_void_p), ('bytes', C.c_int64), ('slice_bytes', C.c_int64), ('n_slices', C.c_int32),
                 ('n_candidates', C.c_int32), ('n_classes', C.c_int32), ('class_slices', C.c_int32 * 8),
@@ -134,6 +149,7 @@ EXPORTS = {
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
+    'sq_register_describe': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_RegisterPlan)]),
     'sq_selftest_flat_divide': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_selftest_flat_divide_f64': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]),
     'sq_selftest_normalise_divide': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1261,6 +1277,26 @@ def register_pairs(tiles, minmax, pairs: np.ndarray, n0: int, n1: int, upsample_
     """register_pairs_async + fetch: returns a RESULT_DTYPE host array (synchronises)."""
     return register_pairs_async(tiles, minmax, pairs, n0, n1, upsample_factor, normalization, stream,
                                 tile_ptrs, shape, np_dtype).fetch()
+
+
+def register_describe(n_pairs: int, n0: int, n1: int, upsample_factor: int = 10, np_dtype='uint16') -> dict:
+    """The launches sq_register_pairs issues for such a batch (sq_register_plan as a dict; host only, no device needed):
+    ``radix0`` / ``radix1`` are the stage lists (empty for a power of two), ``upsample_rows`` is the (TB, KC) instantiation
+    of the first upsampling kernel or None at ``upsample_factor`` 1, the grids are (x, y) tuples."""
+    plan = _RegisterPlan()
+    _check(lib().sq_register_describe(int(n_pairs), int(n0), int(n1), int(upsample_factor), sq_dtype_of(np_dtype), C.byref(plan)),
+           'sq_register_describe')
+    d = {name: getattr(plan, name) for name in (
+        'm0', 'm1', 'tc', 'share', 'col_threads', 'columns_single_threads', 'rl_fwd', 'rl_inv', 'threads_fwd', 'threads_inv',
+        'lds_fwd', 'lds_col', 'lds_inv')}
+    for name in ('long0', 'long1', 'gen0', 'gen1', 'columns_single'):
+        d[name] = bool(getattr(plan, name))
+    d['radix0'] = [int(r) for r in plan.radix0[:plan.nf0]]
+    d['radix1'] = [int(r) for r in plan.radix1[:plan.nf1]]
+    d['upsample_rows'] = (plan.upsample_rows_tb, plan.upsample_rows_kc) if plan.upsample_rows_tb else None
+    for name in ('grid_fwd', 'grid_col', 'grid_inv', 'grid_up_rows'):
+        d[name] = tuple(int(v) for v in getattr(plan, name))
+    return d
 
 
 def write_files(paths: Sequence[str], data: np.ndarray, data_offsets: np.ndarray, n_threads: int = 16) -> int:

@@ -472,6 +472,32 @@ int sq_register_line_supported(int32_t n);
 int64_t sq_register_workspace_bytes(int32_t n_pairs, int32_t n0, int32_t n1, int32_t upsample_factor);
 int sq_register_pairs(const sq_register_args *args, void *stream);
 
+/* The launches sq_register_pairs issues for a batch of n_pairs crops of n0 x n1: which transform each axis gets and which
+ * kernel instantiation, block size and grid each stage runs with.  sq_register_pairs launches from this very struct, so
+ * a test can state which path a case takes and assert it.  Grids are (x, y) in blocks. */
+typedef struct sq_register_plan {
+    int32_t m0, m1;            /* Bluestein length per axis; 0 = the axis length is smooth and transformed directly      */
+    int32_t long0, long1;      /* the axis' line (m or n points) does not fit the LDS: scratch line of the workspace     */
+    int32_t gen0, gen1;        /* mixed-radix stages (else the power-of-two transform)                                  */
+    int32_t nf0, nf1;          /* stages of the transform of length (m ? m : n), innermost first; 0 = a power of two    */
+    uint8_t radix0[16], radix1[16];
+    int32_t tc;                /* columns per block of the column kernel; 0 = one column per block (columns_single)     */
+    int32_t share;             /* column blocks that share 128-byte lines of the spectra; 0 for a long axis 0           */
+    int32_t col_threads;       /* threads of the tc-column kernel; 0 when columns_single runs                           */
+    int32_t columns_single;    /* 1: one column per block (a Bluestein column, a column past 4608 points, a long one)   */
+    int32_t columns_single_threads; /* its threads; 0 when the tc-column kernel runs                                    */
+    int32_t rl_fwd, rl_inv;    /* lines per block of the forward / inverse row kernel                                   */
+    int32_t threads_fwd, threads_inv;
+    int32_t upsample_rows_tb, upsample_rows_kc; /* instantiation <TB, KC> of the first upsampling kernel; 0, 0 at u = 1 */
+    int32_t grid_fwd[2], grid_col[2], grid_inv[2], grid_up_rows[2];
+    int64_t lds_fwd, lds_col, lds_inv; /* dynamic LDS bytes per block of the three transform stages                     */
+} sq_register_plan;
+/* Host only: touches no device, launches nothing.  n_pairs 1 ... 65535, tile_dtype SQ_U8 | SQ_U16 (it selects the pixel
+ * type of the forward row kernel, no launch shape).  (An entry point added without changing an existing one keeps
+ * SQ_VERSION: every caller built against 108 still links and runs.) */
+int sq_register_describe(int32_t n_pairs, int32_t n0, int32_t n1, int32_t upsample_factor, int32_t tile_dtype,
+                         sq_register_plan *out);
+
 /* Overlap moments for the confidence of a registered pair (global registration, alignment.py): the exact integer sums
  * a zero-normalised cross-correlation is formed from, over the overlap of the two full tiles at the pair's offset.
  * Tile table as for sq_tile_minmax (pointer table or base + stride, SQ_U8 / SQ_U16). */

@@ -106,7 +106,8 @@ def phase_cross_correlation(ref: np.ndarray, mov: np.ndarray, upsample_factor: i
         err = np.sqrt(np.abs(1.0 - ccmax * ccmax.conj() / (src_amp * tgt_amp)))   # skimage :91-106
     phasediff = math.atan2(ccmax.imag, ccmax.real)
     detail = dict(coarse=[int(v) for v in coarse], fine=None if fine is None else [int(v) for v in fine],
-                  ccmax_abs=float(abs(ccmax)), src_amp=float(src_amp), tgt_amp=float(tgt_amp))
+                  ccmax_abs=float(abs(ccmax)), ccmax_re=float(ccmax.real), ccmax_im=float(ccmax.imag),
+                  src_amp=float(src_amp), tgt_amp=float(tgt_amp))
     return shifts, float(err), float(phasediff), detail
 
 

@@ -173,10 +173,12 @@ def test_long_non_power_of_two_lines():
         ref = big[32:32 + n0, 32:32 + n1].astype(np.uint16)
         mov = (big[32 - dy:32 - dy + n0, 32 - dx:32 - dx + n1] + synth.noise_patch(3, n0, n1, 200)).astype(np.uint16)
         for norm in (None, 'phase'):
-            want = O.phase_cross_correlation(ref, mov, 10, norm)[0]
-            got = registration.phase_cross_correlation(ref, mov, upsample_factor=10, normalization=norm)[0]
+            want, werr = O.phase_cross_correlation(ref, mov, 10, norm)[:2]
+            got, gerr, _ = registration.phase_cross_correlation(ref, mov, upsample_factor=10, normalization=norm)
             np.testing.assert_array_equal(got, want, err_msg=f'{n0}x{n1} {norm}')
             assert np.abs(want - np.array([-dy, -dx])).max() <= 0.15      # the planted shift, to the 0.1-px grid
+            if norm is None:
+                assert gerr == pytest.approx(werr, rel=1e-6, abs=1e-7), f'{n0}x{n1}'
 
 
 def test_lines_too_long_for_the_lds():
@@ -191,10 +193,12 @@ def test_lines_too_long_for_the_lds():
         ref = big[32:32 + n0, 32:32 + n1].astype(np.uint16)
         mov = (big[32 - dy:32 - dy + n0, 32 - dx:32 - dx + n1] + synth.noise_patch(3, n0, n1, 200)).astype(np.uint16)
         for norm in ((None, 'phase') if n0 * n1 < 1 << 20 else (None,)):
-            want = O.phase_cross_correlation(ref, mov, 10, norm)[0]
-            got = registration.phase_cross_correlation(ref, mov, upsample_factor=10, normalization=norm)[0]
+            want, werr = O.phase_cross_correlation(ref, mov, 10, norm)[:2]
+            got, gerr, _ = registration.phase_cross_correlation(ref, mov, upsample_factor=10, normalization=norm)
             np.testing.assert_array_equal(got, want, err_msg=f'{n0}x{n1} {norm}')
             assert np.abs(want - np.array([-dy, -dx])).max() <= 0.15, f'{n0}x{n1}: {want}'
+            if norm is None:
+                assert gerr == pytest.approx(werr, rel=1e-6, abs=1e-7), f'{n0}x{n1}'
 
 
 def test_long_lines_several_pairs_per_launch():
