@@ -17,244 +17,9 @@
 //
 // Measured on MI355X: 0.53-0.55 of the 8 TB/s HBM peak with float32 gains,
 // 0.58-0.63 without, 0.70 on one huge aligned tile (the ceiling of this structure).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdlib>
-#include <map>
-
-#include "common.h"
-
-using namespace sq;
+#include "fuse_device.h"
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-struct __attribute__((packed)) U32x4U {  // 16 bytes at any alignment
-    u32x4 v;
-};
-struct __attribute__((packed)) F32x4U {
-    f32x4 v;
-};
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-struct __attribute__((packed)) U32x2U {  // 8 bytes at any alignment
-    u32x2 v;
-};
-struct __attribute__((packed)) F64x2U {
-    f64x2 v;
-};
-
-#define SQ_GLOBAL __attribute__((address_space(1)))
-// Explicit global-address-space accessors: pointers that come out of a table are generic to the
-// compiler and would be lowered to flat_* instructions.
-template <typename V>
-__device__ __forceinline__ auto ldg(const void *p) {
-    return ((const SQ_GLOBAL V *)p)->v;
-}
-template <typename S>
-__device__ __forceinline__ S ldg_s(const void *p) {
-    return *(const SQ_GLOBAL S *)p;
-}
-__device__ __forceinline__ void stg_nt(void *p, u32x4 v) {
-    __builtin_nontemporal_store(v, (SQ_GLOBAL u32x4 *)p);
-}
-// 16-byte non-temporal store at scalar base + 32-bit lane offset (bytes): no 64-bit address pair in vector registers
-// (nt measured best here too: 0.623 against 0.599 plain, 0.622 "sc1 nt", 0.602 "sc0 sc1"; profiles/r02_exp21_store_policy.log)
-__device__ __forceinline__ void stg_nt_at(void *base, uint32_t byte_off, u32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt" ::"v"(byte_off), "v"(v), "s"(base) : "memory");
-}
-template <typename S>
-__device__ __forceinline__ void stg_s(void *p, S v) {
-    *(SQ_GLOBAL S *)p = v;
-}
-
-struct FuseParams {
-    const Span *spans;
-    const Ref *refs;
-    const Item *items;
-    const Seam *seams;            // per item, who writes the canvas line a vertical seam falls in (overwrite plans), or NULL
-    const void *const *tile_ptrs;
-    const void *tile_base;
-    int64_t tile_plane_stride, tile_stride;
-    const void *const *flat_ptrs;
-    void *canvas;
-    int64_t canvas_plane_stride;
-    int32_t n_tiles, tile_h, tile_w, tile_pitch;
-    int32_t canvas_pitch;
-    const uint32_t *flat_class;   // per plane: bit 0 clear = every gain is a normal float in the fast divide's range; bit 1 clear =
-                                  // every gain is also moderate (2^-20 <= |g| < 2^20: what the grouped feather blend asks for)
-    uint32_t *queue;              // 9 chunk counters (8 XCD lanes + the rest), one 128-byte line each; NULL = static stride
-    int32_t lane_items;           // list positions [0, 8 * lane_items) of a plane are lane-interleaved
-    int32_t n_planes;
-    int32_t chunk;                // consecutive lane positions a workgroup takes per atomic, 1..QUEUE_CHUNK
-    const struct PlaneGroup *groups;   // plane groups of the float32-gain kernel (build_groups_kernel), else NULL
-    const uint32_t *n_groups;          // how many there are (device side: the host never learns it)
-};
-// Planes that are divided by the SAME gain image (the z planes of a channel) and whose canvas rows sit at the same
-// phase inside a 128-byte line are carried through an item together: the gains and their reciprocals are loaded /
-// computed once per group instead of once per plane.  32 bytes.
-constexpr int ZB = 5;                // most planes in a group
-static_assert(ZB >= 1 && ZB <= 7, "a PlaneGroup holds at most 7 planes");
-struct PlaneGroup {
-    int32_t n;          // 1..ZB
-    int32_t plane[7];
-};
-static_assert(sizeof(PlaneGroup) == 32, "PlaneGroup layout");
-constexpr int QUEUE_STRIDE = 32;   // uint32 words between the counters
-constexpr int QUEUE_CHUNK = 8;     // most consecutive lane positions a workgroup takes per atomic
-
-template <typename T>
-__device__ __forceinline__ const T *tile_ptr(const FuseParams &P, int plane, int tile) {
-    if (P.tile_ptrs) return static_cast<const T *>(P.tile_ptrs[(int64_t)plane * P.n_tiles + tile]);
-    return static_cast<const T *>(P.tile_base) + plane * P.tile_plane_stride + tile * P.tile_stride;
-}
-
-// divide -> clip -> truncating cast of apply_flatfield_correction (stitcher.py:609-610), in the
-// flatfield's own precision like numpy's uint16 / floatXX promotion.  NaN (0/0) -> 0, which is
-// what the x86 cast of the reference produces; +inf -> dtype max through the clip.
-// RND = 0: truncate (the reference's astype).  RND = 1: round half to even first -- feather mode's
-// integer output (np.rint) for a voxel a single tile covers.
-template <typename T, int RND = 0>
-__device__ __forceinline__ T flat_f32(T v, float g) {
-    float q = __fdiv_rn((float)v, g);
-    if (RND) q = rintf(q);
-    const float hi = sizeof(T) == 1 ? 255.0f : 65535.0f;
-    q = fminf(fmaxf(q, 0.0f), hi);
-    return (T)q;
-}
-// Fast exact flatfield divide for THIS operand class: numerator an integer in [0, 65535], gain a
-// float32 with 2^-100 <= |g| < 2^100 (either sign).  Markstein's scheme -- the hardware reciprocal
-// (v_rcp_f32, 1 ulp), one quotient, one exact-residual correction -- gives the correctly rounded
-// quotient here: with r = (1/g)(1 + e), q = n r has relative error h <= |e| + 2^-24, the residual
-// n - g q is exact in one FMA, and q + rem r = (n/g)(1 - h e), i.e. wrong by < 2^-44 relative
-// before its single rounding, while a 16-bit numerator keeps n/g at least 2^-41 (relative) away
-// from every rounding boundary.  A Newton step on r (two more FMAs) is therefore not needed; it was
-// there in earlier versions.  Below 2^-112 the first quotient
-// would overflow and the correction turn into inf - inf; the guard leaves a wide margin.  None of
-// this is taken on faith: sq_selftest_flat_divide compares the final clipped integers with the
-// IEEE path for ALL 2^23 mantissas x 65536 numerators in every binade of the range, on the GPU the
-// tests run on (tests/test_fuse_gpu.py).  Zeros, denormals, tiny gains, infinities and NaNs among
-// a plane's gains are found by a pre-pass (flat_classify_kernel) and send that plane through the
-// generic IEEE sequence instead.
-// 4 VALU slots + the reciprocal instead of the 11 of the IEEE sequence (two v_div_scale, v_div_fmas,
-// v_div_fixup, two refinements).  Doing two pixels per instruction on the packed-float32 pipe
-// (v_pk_mul_f32 / v_pk_fma_f32) was tried: it needs 86 VGPRs (5 waves) and measured no faster.
-__device__ __forceinline__ float div_u16_normal(float n, float g) {
-    const float r = __builtin_amdgcn_rcpf(g);
-    const float q = n * r;
-    const float rem = fmaf(-g, q, n);
-    return fmaf(rem, r, q);
-}
-constexpr int FAST_MIN_EXP = -100;   // fast divide allowed for 2^FAST_MIN_EXP <= |g| < 2^FAST_END_EXP:
-constexpr int FAST_END_EXP = 100;    // (every non-zero quotient n/g is then a normal float)
-constexpr int BLEND_ACC_MIN_EXP = -44, BLEND_ACC_END_EXP = 53, BLEND_WSUM_MAX = 16384;   // what the grouped blend's last division sees
-constexpr int MODERATE_EXP = 20;     // grouped feather blend: 2^-20 <= |g| < 2^20 keeps sums of weighted quotients far from the range ends
-
-// float -> uint32 the way the hardware does it: negative and NaN -> 0, too large -> 0xFFFFFFFF.
-// (C++'s (uint32_t)f is undefined outside the range, so say the instruction.)
-__device__ __forceinline__ uint32_t cvt_u32_sat(float f) {
-    uint32_t r;
-    asm("v_cvt_u32_f32 %0, %1" : "=v"(r) : "v"(f));
-    return r;
-}
-
-// RND = 1 (feather mode rounds the float32 quotient half to even): the reference's result then hangs
-// on how n/g rounds to float32 right next to a representable k + 0.5, and n/g can be within 2^-48 of
-// that float midpoint -- with the RAW hardware reciprocal the short sequence is not enough there (401 of
-// the 2^39 operand pairs of a binade come out one ulp off, e.g. 4075 / 0x1.dbf3fep-3).  With ONE Newton
-// step on the reciprocal it is: on gfx950 v_rcp_f32 + one step IS the correctly rounded reciprocal for
-// every one of the 2^23 mantissas, and Markstein's theorem then makes quotient + one exact-residual
-// correction the correctly rounded quotient (tools/div_probe.hip: 0 of 2^39 pairs differ in every binade
-// tried, either sign; the second correction of rounds 1-3 -- the compiler's own IEEE sequence has it --
-// changed nothing).  6 slots, not the compiler's 11; sq_selftest_flat_divide compares it with the
-// compiler's division for every operand pair, on the GPU the tests run on.
-__device__ __forceinline__ float div_u16_normal_ieee(float n, float g) {
-    float r = __builtin_amdgcn_rcpf(g);
-    r = fmaf(fmaf(-g, r, 1.0f), r, r);
-    const float q = n * r;
-    return fmaf(fmaf(-g, q, n), r, q);
-}
-template <int RND>
-__device__ __forceinline__ float quotient_u16_normal(float n, float g) {
-    if (!RND) return div_u16_normal(n, g);
-    return __builtin_rintf(div_u16_normal_ieee(n, g));   // v_rndne_f32
-}
-template <typename T, int RND = 0>
-__device__ __forceinline__ T flat_f32_fast(T v, float g) {
-    // clip(q, 0, max) then truncate == saturating conversions: NaN never occurs on this path
-    const uint32_t k = cvt_u32_sat(quotient_u16_normal<RND>((float)v, g));
-    return (T)min(k, sizeof(T) == 1 ? 255u : 65535u);
-}
-// two pixels of one 32-bit word at once: v_cvt_pk_u16_u32 saturates to 65535 and packs
-template <int RND = 0>
-__device__ __forceinline__ uint32_t flat_f32_fast_pair(uint32_t word, float g_lo, float g_hi) {
-    const uint32_t a = cvt_u32_sat(quotient_u16_normal<RND>((float)(word & 0xFFFFu), g_lo));
-    const uint32_t b = cvt_u32_sat(quotient_u16_normal<RND>((float)(word >> 16), g_hi));
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    const u16x2 p = __builtin_amdgcn_cvt_pk_u16(a, b);
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-}
-
-// float64 gains: the compiler's IEEE sequence is v_div_scale x2, v_rcp_f64, two Newton steps, quotient,
-// residual, v_div_fmas, v_div_fixup.  For a numerator in [0, 65535] and a gain with 2^-100 <= |g| < 2^100
-// the scaling is the identity and the fix-up never fires, so the same arithmetic without those three
-// instructions yields the same double, bit for bit (sq_selftest_flat_divide_f64 compares the doubles and
-// the clipped integers for 2^15 random gains per binade x every numerator; tests/test_fuse_gpu.py).
-// v_cvt_u32_f64 saturates like its float32 sibling: clip + truncate in one instruction.
-__device__ __forceinline__ double div_u16_normal_f64(double n, double g) {
-    double r = __builtin_amdgcn_rcp(g);
-    r = fma(r, fma(-g, r, 1.0), r);
-    r = fma(r, fma(-g, r, 1.0), r);
-    const double q = n * r;
-    return fma(fma(-g, q, n), r, q);
-}
-__device__ __forceinline__ uint32_t cvt_u32_sat(double f) {
-    uint32_t r;
-    asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(f));
-    return r;
-}
-template <typename T>
-__device__ __forceinline__ T flat_f64_fast(T v, double g) {
-    return (T)min(cvt_u32_sat(div_u16_normal_f64((double)v, g)), sizeof(T) == 1 ? 255u : 65535u);
-}
-
-template <typename T>
-__device__ __forceinline__ T flat_f64(T v, double g) {
-    double q = __ddiv_rn((double)v, g);
-    const double hi = sizeof(T) == 1 ? 255.0 : 65535.0;
-    q = fmin(fmax(q, 0.0), hi);
-    return (T)q;
-}
-
-template <typename T, int FLAT>
-__device__ __forceinline__ T correct_one(T v, const void *frow, int p) {
-    if (FLAT == 1) return flat_f32<T>(v, ldg_s<float>(static_cast<const float *>(frow) + p));
-    if (FLAT == 2) return flat_f64<T>(v, ldg_s<double>(static_cast<const double *>(frow) + p));
-    return v;
-}
-
-template <typename T>
-struct Pix;  // 16 bytes of pixels
-template <>
-struct Pix<uint16_t> {
-    static constexpr int N = 8;
-    __device__ static uint16_t get(const u32x4 &v, int e) { return (uint16_t)(v[e >> 1] >> ((e & 1) * 16)); }
-    __device__ static void set(u32x4 &v, int e, uint16_t x) {
-        v[e >> 1] = (e & 1) ? ((v[e >> 1] & 0x0000FFFFu) | ((uint32_t)x << 16)) : ((v[e >> 1] & 0xFFFF0000u) | x);
-    }
-};
-template <>
-struct Pix<uint8_t> {
-    static constexpr int N = 16;
-    __device__ static uint8_t get(const u32x4 &v, int e) { return (uint8_t)(v[e >> 2] >> ((e & 3) * 8)); }
-    __device__ static void set(u32x4 &v, int e, uint8_t x) {
-        const int sh = (e & 3) * 8;
-        v[e >> 2] = (v[e >> 2] & ~(0xFFu << sh)) | ((uint32_t)x << sh);
-    }
-};
 
 // ---------------------------------------------------------------------------------------------
 // overwrite mode (the reference's semantics)
@@ -272,22 +37,6 @@ struct Pix<uint8_t> {
 // one 2-byte store per wave and row each.  Where the item owns the seam on its left (Seam in common.h;
 // uint16 only: a line is 64 pixels = the wave) the head is the seam's whole line: lane j writes byte 2j
 // of it, the pixels before the item's first from the left neighbour's tile (or zero fill).
-constexpr int NO_EDGE = -(1 << 20);
-template <typename T>
-struct Row {
-    T *drow;
-    const T *srow;
-    const char *frow;
-    const T *lsrow;       // seam owner: the left neighbour's pixel that would land on drow[0] ...
-    const char *lfrow;    // ... and its gain
-    int mis, n;
-    int v_first, v_end;   // whole vectors are v in [v_first, v_end)
-    int edge_p;           // this lane's head pixel: before the first whole vector, or lane - mis over the seam's line
-                          // (< 0: the left neighbour's); NO_EDGE: none
-    int tail_p;           // this lane's pixel after the last whole vector (or -1)
-    bool lzero;           // the left neighbour is zero fill
-};
-
 template <typename T, int FLAT>
 struct Slot {
     static constexpr int VEC = Pix<T>::N;
@@ -298,27 +47,6 @@ struct Slot {
     float eg32;
     double eg64;
 };
-
-template <typename T>
-__device__ __forceinline__ void row_setup(Row<T> &J, int lane, int seam_flags = 0) {
-    constexpr int VEC = Pix<T>::N;
-    // Vector v covers row pixels [v*VEC - mis, +VEC).  mis is the row's phase inside a 128-byte
-    // line, not just inside 16 bytes: vector 0 then starts ON a line boundary, so every 1 KiB
-    // wave-store covers 8 whole lines instead of straddling 9 (measured +10-15 % on canvases
-    // whose pitch is not a multiple of 128 bytes, which is the normal case).
-    constexpr int LINE = 128 / (int)sizeof(T);
-    J.mis = (int)((reinterpret_cast<uintptr_t>(J.drow) / sizeof(T)) & (LINE - 1));
-    const bool seams = sizeof(T) == 2 && J.n > 0;
-    const bool head_line = seams && (seam_flags & SEAM_HAS_LEFT) && J.mis > 0;
-    const int n_own = (seams && (seam_flags & SEAM_LEAVE_TAIL)) ? J.n - ((J.n + J.mis) & (LINE - 1)) : J.n;   // n >= LINE there
-    J.v_first = head_line ? LINE / VEC : (J.mis + VEC - 1) / VEC;
-    J.v_end = (n_own + J.mis) / VEC;
-    const int head_end = head_line ? 0 : min(n_own, J.v_first * VEC - J.mis);   // pixels [0, head_end)
-    const int tail_start = max(head_end, J.v_end * VEC - J.mis);               // pixels [tail_start, n_own)
-    J.edge_p = head_line ? lane - J.mis : (lane < head_end ? lane : NO_EDGE);
-    J.tail_p = (lane < VEC && tail_start + lane < n_own) ? tail_start + lane : -1;
-    J.lzero = (seam_flags & SEAM_LEFT_ZERO) != 0;
-}
 
 // plain loads: the tile is read once, but non-temporal loads measured 3-8 % slower here
 template <typename T, int FLAT>
@@ -402,25 +130,6 @@ __device__ __forceinline__ void slot_store(Slot<T, FLAT> &S, const Row<T> &J, in
         }
         stg_s<T>(J.drow + (head ? J.edge_p : J.tail_p), t);
     }
-}
-
-template <typename T>
-__device__ __forceinline__ void row_zero(T *drow, int n, int lane, bool leave_tail = false) {
-    constexpr int VEC = Pix<T>::N;
-    constexpr int SLOTS = BLOCK_COLS / VEC / 64 + 1;
-    Row<T> J;
-    J.drow = drow;
-    J.n = n;
-    // leave_tail: the line the row ends in is written by the right neighbour (Seam in common.h; n >= one line)
-    row_setup<T>(J, lane, leave_tail ? SEAM_LEAVE_TAIL : 0);
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) {
-        const int v = lane + 64 * k;
-        // (plain instead of non-temporal stores for the zeros: 0.634 against 0.642 for the whole launch)
-        if (v >= J.v_first && v < J.v_end) stg_nt(drow + (v * VEC - J.mis), u32x4{0, 0, 0, 0});
-    }
-    if (J.edge_p > NO_EDGE) stg_s<T>(drow + J.edge_p, 0);
-    if (J.tail_p >= 0) stg_s<T>(drow + J.tail_p, 0);
 }
 
 constexpr int DEPTH_PLAIN = 16, DEPTH_F32 = 2, DEPTH_F64 = 1;   // slot pipeline depth wanted without gains / with float32 / float64 gains
@@ -521,127 +230,6 @@ __device__ __forceinline__ void process_item(const FuseParams &P, int plane, con
     }
 }
 
-// Work distribution.
-//  * static (no scratch given): a persistent grid-stride walk, block b takes items b, b + G, ...
-//  * dynamic: per plane the item list is 8 interleaved lanes (one per XCD: lane x holds the items of the
-//    tile-row blocks == x mod 8, see plan.cpp) followed by a short rest.  Nine device counters hand out
-//    chunks of QUEUE_CHUNK consecutive positions of a lane; a workgroup reads the XCD it really runs on
-//    (HW_REG_XCC_ID), pulls from THAT lane, and moves on to the next lane / the rest once its own is
-//    drained.  The items in flight on an XCD are then always one contiguous window of its lane -- same
-//    flatfield rows, fetched into that XCD's L2 once, however unevenly workgroups progress (with the
-//    static stride they drift apart over a 35 ms launch: PMC, 52 GB of gains re-fetched per launch)
-//    -- and the launch ends with every workgroup busy.  One atomic and one barrier per chunk (the
-//    first attempt paid both per item and lost 7 %); the atomic for the next chunk is issued before
-//    the current chunk is processed and its result only looked at afterwards.
-struct Chunk {
-    int q;         // 0..7 lane, 8 rest, -1 none
-    uint32_t c;    // chunk index inside the queue
-};
-
-// wave-uniform values the compiler cannot prove uniform (they come out of LDS): pin them to scalar registers
-__device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ Item sgpr(Item it) {
-    it.dst_y = sgpr(it.dst_y);
-    it.dst_x = sgpr(it.dst_x);
-    it.hw = sgpr(it.hw);
-    it.nref = sgpr(it.nref);
-    it.a = sgpr(it.a);
-    it.b = sgpr(it.b);
-    it.c = sgpr(it.c);
-    it.span = sgpr(it.span);
-    return it;
-}
-template <typename T>
-__device__ __forceinline__ const T *sgpr(const T *p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = (uint32_t)sgpr((int)(uint32_t)v), hi = (uint32_t)sgpr((int)(uint32_t)(v >> 32));
-    return reinterpret_cast<const T *>(((uint64_t)hi << 32) | lo);
-}
-
-// The queue walk shared by the fusion kernels: calls body(plane, item, aux) for every (plane, item) this
-// workgroup is handed, all threads of the workgroup together, arguments in scalar registers.
-// aux = pre(plane, item, list position) is evaluated by the thread that loads the descriptor (the overwrite kernel
-// fetches the tile pointer there, so that eight of them are in flight at once).
-template <typename Aux, typename Pre, typename Body>
-__device__ __forceinline__ void for_each_queued_item(const FuseParams &P, const int64_t n_items, const uint32_t n_units, Pre pre,
-                                                     Body body) {
-    __shared__ int s_q[2];
-    __shared__ uint32_t s_c[2];
-    __shared__ Item s_item[QUEUE_CHUNK];          // the chunk's descriptors, loaded by QUEUE_CHUNK threads at once
-    __shared__ int s_plane[QUEUE_CHUNK];
-    __shared__ Aux s_aux[QUEUE_CHUNK];
-    const int home = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u);   // HW_REG_XCC_ID[3:0]
-    // queue q holds n_planes * per_plane(q) positions; 32-bit arithmetic (the host checks the sizes)
-    auto per_plane_of = [&](int q) { return (uint32_t)(q < 8 ? (int64_t)P.lane_items : n_items - 8 * (int64_t)P.lane_items); };
-    auto total_of = [&](int q) { return n_units * per_plane_of(q); };
-    int given_up = 0;   // thread 0: queues found empty so far (own lane first, then the others, then the rest)
-    auto queue_of = [&](int k) { return k < 8 ? ((home + k) & 7) : 8; };
-    auto settle = [&](uint32_t c) -> Chunk {   // thread 0: make (given_up, c) a real chunk or move on
-        while (true) {
-            const int q = queue_of(given_up);
-            if ((uint64_t)c * (uint32_t)P.chunk < total_of(q)) return {q, c};
-            if (++given_up > 8) return {-1, 0u};
-            c = atomicAdd(&P.queue[queue_of(given_up) * QUEUE_STRIDE], 1u);
-        }
-    };
-    // lds_written(): s_waitcnt lgkmcnt(0) by the wave that has just written the NEXT chunk's (queue, index) into LDS.  The
-    // barrier at the top of the loop is what publishes them, and a barrier only orders what has completed: the compiler
-    // (ROCm 7.2) puts the wait in front of the barrier after the descriptor stores below but NOT in front of the one at the
-    // top of the loop, which it reaches round the back edge straight after thread 0's ds_write -- the other waves could
-    // then read the slot before the write landed, i.e. the (queue, index) of two chunks ago: they repeated an old chunk
-    // (harmless) and skipped their share of the new one.  Found in round 3 as 28 ... 508 unwritten voxels in 1-2 % of the
-    // launches of the per-plane feather kernel on a small plan (tools/queue_stress.py; the plane-group kernels never
-    // showed it in thousands of launches, but their code had the same gap).
-    // 0xc07f is the s_waitcnt immediate of the gfx9 family (vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8]): lgkmcnt(0) with
-    // vmcnt / expcnt at their maxima.  gfx10+ lay the fields out differently -- there the same bits would wait on something else
-    // and the race would be back, silently -- so a device pass for anything but gfx9 stops here (tools/barrier_scan.py,
-    // run by tests/test_isa_cpu.py, checks the listing of the build that ships).
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    auto lds_written = [] { __builtin_amdgcn_s_waitcnt(0xc07f); };
-    if (threadIdx.x == 0) {
-        const Chunk first = settle(atomicAdd(&P.queue[queue_of(0) * QUEUE_STRIDE], 1u));
-        s_q[0] = first.q;
-        s_c[0] = first.c;
-        lds_written();
-    }
-    for (int iter = 0;; ++iter) {
-        __syncthreads();
-        const int q = sgpr(s_q[iter & 1]);
-        if (q < 0) break;
-        const uint32_t c = (uint32_t)sgpr((int)s_c[iter & 1]);
-        uint32_t pending = 0;
-        const bool pull = threadIdx.x == 0 && given_up <= 8;
-        if (pull) pending = atomicAdd(&P.queue[queue_of(given_up) * QUEUE_STRIDE], 1u);   // next chunk; looked at after this one
-        const uint32_t u0 = c * (uint32_t)P.chunk;
-        const int count = (int)min((uint32_t)P.chunk, total_of(q) - u0);
-        if ((int)threadIdx.x < count) {   // one descriptor per thread: queue position -> (plane, list position)
-            const uint32_t per_plane = per_plane_of(q);
-            const uint32_t u = u0 + threadIdx.x;
-            // (unit-major: all items of unit 0, then unit 1 ...  The other way round -- position r of every unit, then r + 1,
-            // so that the chip writes into ALL groups' planes at once -- was measured in round 3: 0.680 whatever the grouping,
-            // between consecutive groups (0.647) and spread + dealt ones (0.692) on the same buffers;
-            // profiles/r03_exp_unit_minor_*.log)
-            const int plane = (int)(u / per_plane);
-            const uint32_t r = u - (uint32_t)plane * per_plane;
-            const int64_t pos = q < 8 ? (int64_t)r * 8 + q : 8 * (int64_t)P.lane_items + r;
-            const Item it = P.items[pos];
-            s_item[threadIdx.x] = it;
-            s_plane[threadIdx.x] = plane;
-            s_aux[threadIdx.x] = pre(plane, it, pos);
-        }
-        __syncthreads();
-        for (int j = 0; j < count; ++j) body(sgpr(s_plane[j]), sgpr(s_item[j]), s_aux[j]);
-        if (threadIdx.x == 0) {
-            const Chunk nxt = pull ? settle(pending) : Chunk{-1, 0u};
-            s_q[(iter + 1) & 1] = nxt.q;
-            s_c[(iter + 1) & 1] = nxt.c;
-            lds_written();
-        }
-    }
-}
-
 // what a (plane, item) of the per-plane kernel needs beside its descriptor
 struct PlaneAux {
     const void *tile, *ltile;
@@ -654,13 +242,6 @@ __device__ __forceinline__ PlaneAux plane_aux(const FuseParams &P, int plane, co
     A.seam = (sizeof(T) == 2 && P.seams) ? P.seams[pos] : Seam{-1, 0, 0, 0};
     A.ltile = ((A.seam.flags & SEAM_HAS_LEFT) && !(A.seam.flags & SEAM_LEFT_ZERO)) ? tile_ptr<T>(P, plane, A.seam.a) : nullptr;
     return A;
-}
-__device__ __forceinline__ Seam sgpr(Seam s) {
-    s.a = sgpr(s.a);
-    s.b = sgpr(s.b);
-    s.c = sgpr(s.c);
-    s.flags = sgpr(s.flags);
-    return s;
 }
 
 template <typename T, int FLAT, bool DYN>
@@ -734,118 +315,10 @@ struct FeatherAux : UnitAux {
     const void *xtile[2][ZB];
 };
 
-// RND = 0 (overwrite: truncate): Markstein with r = v_rcp_f32(g), the arithmetic of div_u16_normal.
-// RND = 1 (feather, a voxel one tile covers: round half to even): the arithmetic of div_u16_normal_ieee with its Newton
-// step on the reciprocal hoisted -- r arrives refined (recip_for), two exact-residual corrections here, v_rndne.
-template <int RND>
-__device__ __forceinline__ float recip_for(float g) {
-    float r = __builtin_amdgcn_rcpf(g);
-    if (RND) r = fmaf(fmaf(-g, r, 1.0f), r, r);
-    return r;
-}
-template <int RND>
-__device__ __forceinline__ float quot_one(float n, float g, float r) {
-    float q = n * r;
-    q = fmaf(fmaf(-g, q, n), r, q);      // r refined (RND = 1): the correctly rounded quotient (div_u16_normal_ieee)
-    if (RND) q = __builtin_rintf(q);
-    return q;
-}
-// float64 gains (overwrite mode): the arithmetic of div_u16_normal_f64 with its reciprocal -- v_rcp_f64 and two Newton
-// steps, 5 of its 8 instructions -- hoisted out of the planes' loop
-__device__ __forceinline__ double recip_f64(double g) {
-    double r = __builtin_amdgcn_rcp(g);
-    r = fma(r, fma(-g, r, 1.0), r);
-    return fma(r, fma(-g, r, 1.0), r);
-}
-template <int RND>
-__device__ __forceinline__ float recip_of(float g) { return recip_for<RND>(g); }
-template <int RND>
-__device__ __forceinline__ double recip_of(double g) { return recip_f64(g); }
-template <int RND>
-__device__ __forceinline__ float quot_of(float n, float g, float r) { return quot_one<RND>(n, g, r); }
-template <int RND>
-__device__ __forceinline__ double quot_of(double n, double g, double r) {
-    const double q = n * r;
-    return fma(fma(-g, q, n), r, q);
-}
-// Two float32 lanes per instruction (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32: IEEE per component, so every bit is the scalar
-// form's).  The overwrite quotient (RND = 0: 3 of its 5.8 instructions per pixel) measured no faster packed, twice (round 1 on the
-// per-plane kernel, round 4 on the grouped structure in a mixed arena: tools/membw_gains "A2", 0.712 against 0.713) -- that path
-// waits on memory.  The feather paths do 8.5 (one tile, rounded) to 27 (two-tile strips) instructions per pixel: there it pays.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-// div_u16_normal_ieee / div_by_refined on two lanes: n / d correctly rounded, r = the refined reciprocal of d
-__device__ __forceinline__ f32x2 div_by_refined2(f32x2 n, f32x2 d, f32x2 r) {
-    const f32x2 q = n * r;
-    return pk_fma(pk_fma(-d, q, n), r, q);
-}
-template <int RND, typename G>
-__device__ __forceinline__ uint32_t quot_pair(uint32_t word, G g_lo, G g_hi, G r_lo, G r_hi) {
-    if constexpr (RND == 1 && std::is_same<G, float>::value) {
-        const f32x2 n = {(float)(word & 0xFFFFu), (float)(word >> 16)};
-        const f32x2 q = div_by_refined2(n, f32x2{g_lo, g_hi}, f32x2{r_lo, r_hi});
-        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-        const u16x2 p = __builtin_amdgcn_cvt_pk_u16(cvt_u32_sat(__builtin_rintf(q[0])), cvt_u32_sat(__builtin_rintf(q[1])));
-        return (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-    }
-    const G n0 = (G)(word & 0xFFFFu), n1 = (G)(word >> 16);
-    const uint32_t a = cvt_u32_sat(quot_of<RND>(n0, g_lo, r_lo));
-    const uint32_t b = cvt_u32_sat(quot_of<RND>(n1, g_hi, r_hi));
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    const u16x2 p = __builtin_amdgcn_cvt_pk_u16(a, b);
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 16);
-}
-// four uint8 pixels of one 32-bit word (uint8 planes in groups, round 4): the same quotient -- the exhaustive proof of the
-// shortened divide covers every numerator below 65536 -- clipped to 255 and packed
-template <int RND, typename G>
-__device__ __forceinline__ uint32_t quot_quad(uint32_t word, const G *g, const G *r) {
-    uint32_t out = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const G n = (G)((word >> (8 * k)) & 0xFFu);
-        out |= min(cvt_u32_sat(quot_of<RND>(n, g[k], r[k])), 255u) << (8 * k);
-    }
-    return out;
-}
-// 8 consecutive gains at any alignment
-__device__ __forceinline__ void load_gains(const char *p, float (&g)[8]) {
-    const f32x4 a = ldg<F32x4U>(p), b = ldg<F32x4U>(p + 16);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        g[e] = a[e];
-        g[4 + e] = b[e];
-    }
-}
-__device__ __forceinline__ void load_gains(const char *p, double (&g)[8]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const f64x2 a = ldg<F64x2U>(p + 16 * q);
-        g[2 * q] = a[0];
-        g[2 * q + 1] = a[1];
-    }
-}
-
-// 16 consecutive gains (a uint8 plane's 16-byte pixel vector)
-template <typename GT>
-__device__ __forceinline__ void load_gains(const char *p, GT (&g)[16]) {
-    GT lo[8], hi[8];
-    load_gains(p, lo);
-    load_gains(p + 8 * sizeof(GT), hi);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        g[e] = lo[e];
-        g[8 + e] = hi[e];
-    }
-}
-
 // (One row per workgroup -- wave w taking slot w, 2 + ZB loads and ZB stores per thread -- launched one-shot, the regime
 // in which a bare copy gains 10 %, was built and measured with groups of 5 / 3 / 2: 0.53 / 0.43 / 0.39 against 0.62-0.64
 // for this form on the same box; the descriptor, its LDS hand-over and the tile pointers cost more per 14-36 KB workgroup
 // than the access pattern gives back.  profiles/r02_exp20_row_per_workgroup.log)
-// G = NoGain: planes WITHOUT a flatfield carried through an item together -- nothing is shared between them but the
-// geometry, yet five planes per thread write faster than one plane per launch when the planes lie in different stretches
-// of device memory (DESIGN.md 5.1 point 9: the bare 5-plane copy 0.72-0.75 of peak against 0.64-0.65 plane by plane)
-struct NoGain {};
 // T = uint8_t (round 4): the same row loop with 16 pixels per lane and slot and 128 pixels per line.  uint8 planes have no seam
 // owners (a line is 128 pixels, two per lane in the whole-line pass: not built) -- the kernel ignores the plan's seam records for
 // the whole plane, which is a partition of the canvas like honouring them for the whole plane is.
@@ -2009,60 +1482,6 @@ __global__ __launch_bounds__(256, FLAT ? WAVES_FEATHER_ZG : 1) void fuse_feather
     }
 }
 
-// Persistent launch: as many workgroups as the chip keeps resident (queried once per kernel),
-// each walking the (plane, item) list with a grid stride.
-template <typename K>
-int launch(K kernel, const FuseParams &P, int64_t n_items, int n_planes, hipStream_t stream, int grid_override = 0) {
-    const int64_t n_work = n_items * n_planes;
-    if (n_work == 0) return SQ_OK;
-    static thread_local std::map<const void *, int> resident;
-    const void *key = reinterpret_cast<const void *>(kernel);
-    auto it = resident.find(key);
-    if (it == resident.end()) {
-        int dev = 0, cus = 256, per_cu = 8;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-        it = resident.emplace(key, cus * std::min(per_cu, 8)).first;
-    }
-    const int64_t blocks = std::min<int64_t>(n_work, grid_override > 0 ? grid_override : it->second);
-    // work-queue chunk: QUEUE_CHUNK items per atomic when every workgroup gets many chunks, fewer for small
-    // launches so that the last round does not leave workgroups idle
-    FuseParams Q = P;
-    Q.chunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(QUEUE_CHUNK, n_work / (blocks * 16)));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, Q, n_items, n_work);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_fuse_planes: launch failed: %s", hipGetErrorString(e));
-    return SQ_OK;
-}
-
-// the plane-group kernel: the number of work units (groups x items) is only known on the device, so the grid is
-// the resident workgroups (fewer only when even one plane per group would not fill them)
-template <typename K>
-int launch_zg(K kernel, const FuseParams &P, int64_t n_items, int n_planes, hipStream_t stream, int grid_override) {
-    if (n_items == 0 || n_planes == 0) return SQ_OK;
-    static thread_local std::map<const void *, int> resident;
-    const void *key = reinterpret_cast<const void *>(kernel);
-    auto it = resident.find(key);
-    if (it == resident.end()) {
-        int dev = 0, cus = 256, per_cu = 8;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-        it = resident.emplace(key, cus * std::min(per_cu, 8)).first;
-    }
-    const int64_t min_units = n_items * ((n_planes + ZB - 1) / ZB);
-    const int64_t blocks = std::min<int64_t>(min_units, grid_override > 0 ? grid_override : it->second);
-    FuseParams Q = P;
-    Q.chunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(QUEUE_CHUNK, min_units / (blocks * 16)));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, Q, n_items);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_fuse_planes: launch failed: %s", hipGetErrorString(e));
-    return SQ_OK;
-}
-
 // pre-pass: does a plane's flatfield hold anything outside the fast divide's range?
 template <typename G>
 __global__ __launch_bounds__(256) void flat_classify_kernel(const void *const *flat_ptrs, int64_t n, uint32_t *cls) {
@@ -2234,90 +1653,30 @@ extern "C" int sq_selftest_flat_divide_f64(int32_t exponent, int32_t n_binades, 
     return SQ_OK;
 }
 
-// scratch: one uint32 gain class per plane | the nine chunk counters of the work queues, a 128-byte line each |
-// the number of plane groups (a line) | the plane groups (32 bytes per plane at most)
-namespace {
-struct ScratchLayout {
-    int64_t queue, n_groups, groups, total;
-};
-ScratchLayout scratch_layout(int64_t n_planes) {
-    ScratchLayout L;
-    L.queue = (n_planes * 4 + 127) & ~int64_t(127);
-    L.n_groups = L.queue + 9 * QUEUE_STRIDE * 4;
-    L.groups = L.n_groups + 128;
-    L.total = L.groups + n_planes * (int64_t)sizeof(PlaneGroup);
-    return L;
-}
-}  // namespace
-
 extern "C" int64_t sq_fuse_scratch_bytes(int32_t n_planes) {
     if (n_planes < 0) return fail(SQ_ERR_INVALID, "sq_fuse_scratch_bytes: n_planes %d", n_planes);
     return scratch_layout(n_planes).total;
 }
 
 extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
-    if (!a || !a->plan || !a->table_dev || !a->canvas_dev)
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: NULL plan/table/canvas");
+    static const char *who = "sq_fuse_planes";
+    FuseParams P;
+    int32_t fl = 0;
+    if (const int rc = fuse_setup(who, a, fl, SQ_FUSE_FORCE_QUEUES | SQ_FUSE_FORCE_STATIC | SQ_FUSE_NO_PLANE_GROUPS | SQ_FUSE_NO_SEAM_OWNERS |
+                                      SQ_FUSE_CONSECUTIVE_GROUPS, 0, true, P))
+        return rc;
     const TableHeader &h = a->plan->header();
-    if (a->plan->spans_only && !a->plan->expanded)
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: the plan of sq_fuse_plan_create_spans has not been through sq_fuse_plan_expand");
-    if (a->table_bytes != a->plan->device_bytes())
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: table_bytes %lld != plan %lld", (long long)a->table_bytes,
-                    (long long)a->plan->device_bytes());
-    if (a->mode != h.mode) return fail(SQ_ERR_INVALID, "sq_fuse_planes: mode %d but plan was built for %d", a->mode, h.mode);
-    if (a->n_tiles != h.n_tiles || a->tile_h != h.tile_h || a->tile_w != h.tile_w || a->canvas_h != h.canvas_h ||
-        a->canvas_w != h.canvas_w)
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: geometry differs from the plan (tiles %d/%d %dx%d/%dx%d canvas %dx%d/%dx%d)",
-                    a->n_tiles, h.n_tiles, a->tile_h, a->tile_w, h.tile_h, h.tile_w, a->canvas_h, a->canvas_w, h.canvas_h,
-                    h.canvas_w);
-    if (!a->tile_ptrs_dev && !a->tile_base_dev && h.n_refs > 0)
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: no tile table and no tile base");
-    if (a->tile_pitch < a->tile_w || a->canvas_pitch < a->canvas_w)
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: pitch smaller than width");
-    if (a->n_planes < 0) return fail(SQ_ERR_INVALID, "sq_fuse_planes: n_planes %d out of range", a->n_planes);
-    if ((a->flags & ~(SQ_FUSE_FORCE_QUEUES | SQ_FUSE_FORCE_STATIC | SQ_FUSE_NO_PLANE_GROUPS | SQ_FUSE_NO_SEAM_OWNERS | SQ_FUSE_CONSECUTIVE_GROUPS)) || a->grid_blocks < 0 ||
-        ((a->flags & SQ_FUSE_FORCE_QUEUES) && (a->flags & SQ_FUSE_FORCE_STATIC)))
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: flags %d / grid_blocks %d", a->flags, a->grid_blocks);
-    if (a->tile_dtype != SQ_U8 && a->tile_dtype != SQ_U16)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_fuse_planes: tile dtype %d (uint8/uint16 only)", a->tile_dtype);
-    if (a->flat_ptrs_dev && a->flat_dtype != SQ_F32 && a->flat_dtype != SQ_F64)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_fuse_planes: flatfield dtype %d (float32/float64 only)", a->flat_dtype);
     if (a->canvas_plane_stride < (int64_t)a->canvas_h * a->canvas_pitch && a->n_planes > 1)
         return fail(SQ_ERR_INVALID, "sq_fuse_planes: canvas planes overlap");
-    const size_t esz = a->canvas_dtype == SQ_F32 ? 4 : (size_t)a->canvas_dtype;
-    if (reinterpret_cast<uintptr_t>(a->canvas_dev) % esz)
-        return fail(SQ_ERR_INVALID, "sq_fuse_planes: canvas pointer not aligned to its element size");
-
-    FuseParams P{};
-    const char *base = static_cast<const char *>(a->table_dev);
-    P.spans = reinterpret_cast<const Span *>(base + h.off_spans);
-    P.refs = reinterpret_cast<const Ref *>(base + h.off_refs);
-    P.items = reinterpret_cast<const Item *>(base + h.off_items);
-    P.seams = (h.off_seams && !(a->flags & SQ_FUSE_NO_SEAM_OWNERS)) ? reinterpret_cast<const Seam *>(base + h.off_seams) : nullptr;
-    P.tile_ptrs = a->tile_ptrs_dev;
-    P.tile_base = a->tile_base_dev;
-    P.tile_plane_stride = a->tile_plane_stride;
-    P.tile_stride = a->tile_stride;
-    P.flat_ptrs = a->flat_ptrs_dev;
-    P.canvas = a->canvas_dev;
     P.canvas_plane_stride = a->canvas_plane_stride;
-    P.n_tiles = a->n_tiles;
-    P.tile_h = a->tile_h;
-    P.tile_w = a->tile_w;
-    P.tile_pitch = a->tile_pitch;
-    P.canvas_pitch = a->canvas_pitch;
-    P.flat_class = nullptr;
+    const size_t esz = a->canvas_dtype == SQ_F32 ? 4 : (size_t)a->canvas_dtype;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
-    P.queue = nullptr;
-    P.lane_items = (int32_t)h.lane_items;
-    P.n_planes = a->n_planes;
     const ScratchLayout SL = scratch_layout(a->n_planes);
+    // what the walks of the per-plane kernels count: (plane, item) pairs -- every plane goes through every item on its own
+    const int64_t n_work = (int64_t)a->n_planes * h.n_items;
     if (a->scratch_dev && a->n_planes > 0) {
-        if (a->scratch_bytes < sq_fuse_scratch_bytes(a->n_planes))
-            return fail(SQ_ERR_WORKSPACE, "sq_fuse_planes: scratch %lld < %lld bytes", (long long)a->scratch_bytes,
-                        (long long)sq_fuse_scratch_bytes(a->n_planes));
-        if (reinterpret_cast<uintptr_t>(a->scratch_dev) % 128) return fail(SQ_ERR_INVALID, "sq_fuse_planes: scratch not 128-byte aligned");
+        if (const int rc = scratch_check(who, a, SL)) return rc;
         if (hipMemsetAsync(a->scratch_dev, 0, (size_t)SL.groups, stream) != hipSuccess)   // classes, counters, group count
             return fail(SQ_ERR_HIP, "sq_fuse_planes: cannot clear the scratch");
         if (flat) {
@@ -2333,24 +1692,27 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
                                    static_cast<uint32_t *>(a->scratch_dev));
             P.flat_class = static_cast<const uint32_t *>(a->scratch_dev);
         }
-        // the queues count in 32 bits; a launch with fewer than ~64 items per resident workgroup is over
-        // before the queues pay for their barriers (measured on the 8x8-grid, one-plane case): static walk
-        const int64_t n_work = (int64_t)a->n_planes * h.n_items;
+        // the queues count (plane, item) pairs in 32 bits (the projections' count items: project_setup); a launch with fewer
+        // than ~64 items per resident workgroup is over before the queues pay for their barriers (measured on the 8x8-grid,
+        // one-plane case): static walk
         // (args->flags can force either one whatever the size -- tests)
-        if ((n_work >= 100000 || (a->flags & SQ_FUSE_FORCE_QUEUES)) && n_work < (int64_t(1) << 31) && !(a->flags & SQ_FUSE_FORCE_STATIC))
+        if ((n_work >= 100000 || (fl & SQ_FUSE_FORCE_QUEUES)) && n_work < (int64_t(1) << 31) && !(fl & SQ_FUSE_FORCE_STATIC))
             P.queue = reinterpret_cast<uint32_t *>(static_cast<char *>(a->scratch_dev) + SL.queue);
     }
+    // the plane-group kernels: the number of work units (groups x items) is only known on the device, so the grid is the
+    // resident workgroups, fewer only when even full groups would not fill them
+    const int64_t min_units = h.n_items * ((a->n_planes + ZB - 1) / ZB);
     const bool u16 = a->tile_dtype == SQ_U16;
     // plane groups in the scratch (build_groups_kernel): planes that share a gain image whose class has no bit of cls_mask
     // set go through the items together; with gains NULL any planes may
-    const bool grouping = a->scratch_dev && a->n_planes > 1 && ZB > 1 && !(a->flags & SQ_FUSE_NO_PLANE_GROUPS);
+    const bool grouping = a->scratch_dev && a->n_planes > 1 && ZB > 1 && !(fl & SQ_FUSE_NO_PLANE_GROUPS);
     auto build_groups = [&](const void *const *gains, uint32_t cls_mask) {
         char *sc = static_cast<char *>(a->scratch_dev);
         uint32_t *n_groups = reinterpret_cast<uint32_t *>(sc + SL.n_groups);
         PlaneGroup *groups = reinterpret_cast<PlaneGroup *>(sc + SL.groups);
         hipLaunchKernelGGL(build_groups_kernel, dim3(1), dim3(256), 0, stream, gains, P.flat_class, cls_mask, a->n_planes,
                            a->canvas_plane_stride * (int64_t)esz, ZB, n_groups, groups,
-                           (a->flags & SQ_FUSE_CONSECUTIVE_GROUPS) != 0);
+                           (fl & SQ_FUSE_CONSECUTIVE_GROUPS) != 0);
         P.groups = groups;
         P.n_groups = n_groups;
     };
@@ -2361,16 +1723,16 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
                         a->canvas_dtype, a->tile_dtype);
 #define SQ_OVERWRITE(T, F)                                                                                  \
     do {                                                                                                      \
-        if (P.queue) return launch(fuse_overwrite_kernel<T, F, true>, P, h.n_items, a->n_planes, stream, a->grid_blocks);     \
-        return launch(fuse_overwrite_kernel<T, F, false>, P, h.n_items, a->n_planes, stream, a->grid_blocks);                 \
+        if (P.queue) return launch(who, fuse_overwrite_kernel<T, F, true>, P, n_work, stream, a->grid_blocks, h.n_items, n_work);  \
+        return launch(who, fuse_overwrite_kernel<T, F, false>, P, n_work, stream, a->grid_blocks, h.n_items, n_work);        \
     } while (0)
         if (flat && grouping) {
             // planes that share a gain image go through the items together (fuse_overwrite_zg_kernel)
             build_groups(a->flat_ptrs_dev, 1u);
 #define SQ_ZG(G, T)                                                                                                                  \
     do {                                                                                                                              \
-        if (P.queue) return launch_zg(fuse_overwrite_zg_kernel<G, true, T>, P, h.n_items, a->n_planes, stream, a->grid_blocks);       \
-        return launch_zg(fuse_overwrite_zg_kernel<G, false, T>, P, h.n_items, a->n_planes, stream, a->grid_blocks);                   \
+        if (P.queue) return launch(who, fuse_overwrite_zg_kernel<G, true, T>, P, min_units, stream, a->grid_blocks, h.n_items);          \
+        return launch(who, fuse_overwrite_zg_kernel<G, false, T>, P, min_units, stream, a->grid_blocks, h.n_items);                      \
     } while (0)
             if (u16) {
                 if (flat == 2) SQ_ZG(double, uint16_t);
@@ -2404,8 +1766,8 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
         return fail(SQ_ERR_INVALID, "sq_fuse_planes: feather canvas must be float32 or the tile dtype");
 #define SQ_FEATHER_F(T, O, F)                                                                              \
     do {                                                                                                    \
-        if (P.queue) return launch(fuse_feather_kernel<T, O, F, true>, P, h.n_items, a->n_planes, stream, a->grid_blocks);  \
-        return launch(fuse_feather_kernel<T, O, F, false>, P, h.n_items, a->n_planes, stream, a->grid_blocks);              \
+        if (P.queue) return launch(who, fuse_feather_kernel<T, O, F, true>, P, n_work, stream, a->grid_blocks, h.n_items, n_work);  \
+        return launch(who, fuse_feather_kernel<T, O, F, false>, P, n_work, stream, a->grid_blocks, h.n_items, n_work);      \
     } while (0)
 #define SQ_FEATHER(T, O)                 \
     do {                                 \
@@ -2423,8 +1785,8 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
         build_groups(a->flat_ptrs_dev, f32out ? 7u : 3u);
 #define SQ_FEATHER_ZG(F, O)                                                                                                      \
     do {                                                                                                                          \
-        if (P.queue) return launch_zg(fuse_feather_zg_kernel<F, true, O>, P, h.n_items, a->n_planes, stream, a->grid_blocks);    \
-        return launch_zg(fuse_feather_zg_kernel<F, false, O>, P, h.n_items, a->n_planes, stream, a->grid_blocks);                \
+        if (P.queue) return launch(who, fuse_feather_zg_kernel<F, true, O>, P, min_units, stream, a->grid_blocks, h.n_items);          \
+        return launch(who, fuse_feather_zg_kernel<F, false, O>, P, min_units, stream, a->grid_blocks, h.n_items);                      \
     } while (0)
         if (f32out) {      // float32 canvas: every item through the grouped form (blend_item_zg with NREF = 2 / 1 / 0)
             if (flat == 2) SQ_FEATHER_ZG(2, float);
@@ -2444,872 +1806,4 @@ extern "C" int sq_fuse_planes(const sq_fuse_args *a, void *stream_) {
     SQ_FEATHER(uint8_t, uint8_t);
 #undef SQ_FEATHER
 #undef SQ_FEATHER_F
-}
-
-// ---------------------------------------------------------------------------------------------
-// maximum-intensity projection over z (sq_fuse_project_max; an extension: the reference has none)
-// ---------------------------------------------------------------------------------------------
-// One OUTPUT plane from the Z planes of an overwrite plan: per voxel the value sq_fuse_planes would store in each plane (the same
-// divide routines, so every bit is theirs), reduced by an unsigned maximum.  Algorithmic traffic: Z x sizeof(T) B read per covered
-// voxel + sizeof(T) B written per canvas voxel (+ the gains, loaded ONCE per slot for all Z planes when they all name one image).
-// Structure: the persistent grid of the overwrite kernels (static walk or the per-XCD queues of for_each_queued_item) over the
-// plan's items; the z loop runs inside a slot, so one item is one output store stream and nothing is shared between
-// workgroups.  Seam owners are not used: each item writes exactly its own pixels (the partition SQ_FUSE_NO_SEAM_OWNERS keeps).
-// ACC: max(existing, projection) on the covered voxels, uncovered ones untouched.
-namespace {
-constexpr int PROJ_ZU = 4;   // planes whose pixel vectors a lane has in flight at once
-struct ProjAux {
-    int unused;
-};
-
-// per-component unsigned maximum of two 32-bit words of packed pixels (v_pk_max_u16 for uint16)
-template <typename T>
-__device__ __forceinline__ uint32_t max_packed(uint32_t a, uint32_t b) {
-    if constexpr (sizeof(T) == 2) {
-        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-    } else {
-        typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
-        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u8x4, a), __builtin_bit_cast(u8x4, b)));
-    }
-}
-// the generic (IEEE) flatfield divide of the per-plane kernel in the gain's precision: exact for every gain
-template <typename T, typename GT>
-__device__ __forceinline__ T flat_generic(T v, GT g) {
-    if constexpr (sizeof(GT) == 8) return flat_f64<T>(v, g);
-    else return flat_f32<T>(v, g);
-}
-// the fast divide's operand range (flat_classify_kernel): 2^FAST_MIN_EXP <= |g| < 2^FAST_END_EXP
-template <typename GT>
-__device__ __forceinline__ bool in_fast_range(GT g) {
-    const GT a = g < 0 ? -g : g;
-    return a >= (GT)__builtin_ldexp(1.0, FAST_MIN_EXP) && a < (GT)__builtin_ldexp(1.0, FAST_END_EXP);   // NaN fails both
-}
-// one 32-bit word of pixels through the generic divide, gains g[0 .. 4 / sizeof(T))
-template <typename T, typename GT>
-__device__ __forceinline__ uint32_t word_generic(uint32_t w, const GT *g) {
-    constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-    uint32_t out = 0;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) out |= (uint32_t)flat_generic<T, GT>((T)(w >> (BITS * e)), g[e]) << (BITS * e);
-    return out;
-}
-// the same word through the shortened divide of the plane groups (gains in the fast range, r = recip_of<0>(g))
-template <typename T, typename GT>
-__device__ __forceinline__ uint32_t word_fast(uint32_t w, const GT *g, const GT *r) {
-    if constexpr (sizeof(T) == 2) return quot_pair<0, GT>(w, g[0], g[1], r[0], r[1]);
-    else return quot_quad<0, GT>(w, g, r);
-}
-
-// SHARED: every plane names the gain image flat_ptrs[0] (not NULL).  Otherwise each plane's entry is looked up (NULL = identity)
-// and divided by the generic sequence: exact, not fast.
-template <typename T, typename G, bool SHARED, bool ACC>
-__device__ __forceinline__ void project_item(const FuseParams &P, const Item &it, const int wave, const int lane) {
-    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
-    typedef typename std::conditional<GAINS, G, float>::type GT;
-    constexpr uint32_t GSZ = sizeof(GT), TSZ = sizeof(T);
-    constexpr int VEC = 16 / (int)sizeof(T), LINE = 128 / (int)sizeof(T), PER = 4 / (int)sizeof(T);
-    constexpr int SLOTS = BLOCK_COLS / VEC / 64 + 1;
-    const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
-    const int nz = P.n_planes;
-    T *canvas = static_cast<T *>(P.canvas);
-    if (!it.nref) {   // uncovered canvas: zeros, like every plane of the stack (accumulating: left alone)
-        if (!ACC)
-            for (int r = wave; r < rows; r += 4) row_zero<T>(canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x, n, lane);
-        return;
-    }
-    const GT *flat0 = nullptr;
-    if constexpr (GAINS && SHARED) flat0 = sgpr(static_cast<const GT *>(P.flat_ptrs[0]));
-    for (int r = wave; r < rows; r += 4) {
-        char *drow = reinterpret_cast<char *>(canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x);
-        const int64_t soff = (int64_t)(it.b + r) * P.tile_pitch + it.c;   // elements into every plane's tile
-        const int64_t foff = (int64_t)(it.b + r) * P.tile_w + it.c;       // elements into a gain image
-        // vector v covers row pixels [v * VEC - mis, +VEC): stores start on the canvas' 128-byte lines (row_setup)
-        const int mis = (int)((reinterpret_cast<uintptr_t>(drow) / sizeof(T)) & (LINE - 1));
-        const int v_first = (mis + VEC - 1) / VEC, v_end = (n + mis) / VEC;
-#pragma unroll
-        for (int k = 0; k < SLOTS; ++k) {
-            if (64 * k >= v_end || v_end <= v_first) break;   // wave-uniform: no whole vector (left) in this row
-            const int v = lane + 64 * k;
-            const bool act = v >= v_first && v < v_end;
-            // lanes without a vector of their own load the row's first / last whole vector; only their store is masked
-            const uint32_t o = (uint32_t)min(max(v * VEC - mis, v_first * VEC - mis), (v_end - 1) * VEC - mis);
-            u32x4 acc = {0u, 0u, 0u, 0u};
-            if (ACC) acc = ldg<U32x4U>(drow + o * TSZ);
-            GT g[VEC], rc[VEC];
-            bool fast = true;
-            if constexpr (GAINS && SHARED) {
-                load_gains(reinterpret_cast<const char *>(flat0 + foff) + o * GSZ, g);
-#pragma unroll
-                for (int c = 0; c < VEC; ++c) {
-                    fast = fast && in_fast_range(g[c]);
-                    rc[c] = recip_of<0>(g[c]);
-                }
-            }
-            for (int z0 = 0; z0 < nz; z0 += PROJ_ZU) {
-                u32x4 px[PROJ_ZU];
-#pragma unroll
-                for (int u = 0; u < PROJ_ZU; ++u)
-                    if (z0 + u < nz) px[u] = ldg<U32x4U>(reinterpret_cast<const char *>(tile_ptr<T>(P, z0 + u, it.a) + soff) + o * TSZ);
-#pragma unroll
-                for (int u = 0; u < PROJ_ZU; ++u) {
-                    if (z0 + u >= nz) break;
-                    if constexpr (!GAINS) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], px[u][c]);
-                    } else if constexpr (SHARED) {
-                        if (fast) {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], word_fast<T, GT>(px[u][c], &g[PER * c], &rc[PER * c]));
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], word_generic<T, GT>(px[u][c], &g[PER * c]));
-                        }
-                    } else {
-                        const GT *fz = sgpr(static_cast<const GT *>(P.flat_ptrs[z0 + u]));
-                        if (fz) {
-                            GT gz[VEC];
-                            load_gains(reinterpret_cast<const char *>(fz + foff) + o * GSZ, gz);
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], word_generic<T, GT>(px[u][c], &gz[PER * c]));
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[c] = max_packed<T>(acc[c], px[u][c]);
-                        }
-                    }
-                }
-            }
-            if (act) stg_nt_at(drow, o * TSZ, acc);
-        }
-        // the row's edges (pixels before the first / after the last whole vector): lanes 0..VEC-1 the head, VEC..2VEC-1 the
-        // tail, one pixel each, through the generic divide
-        const int head_end = min(n, v_first * VEC - mis);
-        const int tail_start = max(head_end, v_end * VEC - mis);
-        int ep = -1;
-        if (lane < VEC) {
-            if (lane < head_end) ep = lane;
-        } else if (lane < 2 * VEC) {
-            if (tail_start + (lane - VEC) < n) ep = tail_start + (lane - VEC);
-        }
-        if (ep >= 0) {
-            uint32_t m = ACC ? (uint32_t)ldg_s<T>(drow + ep * TSZ) : 0u;
-            for (int z = 0; z < nz; ++z) {
-                const T t = ldg_s<T>(tile_ptr<T>(P, z, it.a) + soff + ep);
-                uint32_t q = t;
-                if constexpr (GAINS) {
-                    const GT *fz = SHARED ? flat0 : static_cast<const GT *>(P.flat_ptrs[z]);
-                    if (fz) q = flat_generic<T, GT>(t, ldg_s<GT>(fz + foff + ep));
-                }
-                m = max(m, q);
-            }
-            stg_s<T>(drow + ep * TSZ, (T)m);
-        }
-    }
-}
-
-template <typename T, typename G, bool ACC, bool DYN>
-__global__ __launch_bounds__(256) void project_max_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work) {
-    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    bool shared = false;   // every plane names one gain image: load it and take its reciprocals once for all planes
-    if constexpr (GAINS) {
-        const void *f0 = P.flat_ptrs[0];
-        shared = f0 != nullptr;
-        for (int z = 1; z < P.n_planes && shared; ++z) shared = P.flat_ptrs[z] == f0;
-        shared = sgpr((int)shared) != 0;
-    }
-    auto body = [&](const Item &it) {
-        if (!GAINS || shared) project_item<T, G, true, ACC>(P, it, wave, lane);
-        else project_item<T, G, false, ACC>(P, it, wave, lane);
-    };
-    if (!DYN) {
-        for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x) body(sgpr(P.items[w]));
-        return;
-    }
-    for_each_queued_item<ProjAux>(
-        P, n_items, 1u, [&](int, const Item &, int64_t) -> ProjAux { return ProjAux{0}; },
-        [&](int, const Item &it, const ProjAux &) { body(it); });
-}
-
-
-template <typename K, typename... X>
-int launch_project(const char *who, K kernel, const FuseParams &P, int64_t n_items, hipStream_t stream, int grid_override,
-                   X... extra) {
-    if (n_items == 0) return SQ_OK;
-    static thread_local std::map<const void *, int> resident;
-    const void *key = reinterpret_cast<const void *>(kernel);
-    auto it = resident.find(key);
-    if (it == resident.end()) {
-        int dev = 0, cus = 256, per_cu = 8;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-        it = resident.emplace(key, cus * std::min(per_cu, 8)).first;
-    }
-    const int64_t blocks = std::min<int64_t>(n_items, grid_override > 0 ? grid_override : it->second);
-    FuseParams Q = P;
-    Q.chunk = (int32_t)std::max<int64_t>(1, std::min<int64_t>(QUEUE_CHUNK, n_items / (blocks * 16)));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, Q, n_items, n_items, extra...);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return SQ_OK;
-}
-
-// The checks and the FuseParams shared by the projections over z (one output plane from the Z planes of one overwrite plan):
-// SQ_OK with P (and P.queue when the work queues are taken) set up and *fl the effective flags, or the failure.
-int project_setup(const char *who, const sq_fuse_args *a, int32_t flags, hipStream_t stream, FuseParams &P, int32_t *fl_out) {
-    if (!a || !a->plan || !a->table_dev || !a->canvas_dev) return fail(SQ_ERR_INVALID, "%s: NULL plan/table/output", who);
-    if (a->mode != SQ_FUSE_OVERWRITE)
-        return fail(SQ_ERR_INVALID, "%s: mode %d, only SQ_FUSE_OVERWRITE plans can be projected", who, a->mode);
-    const TableHeader &h = a->plan->header();
-    if (h.mode != SQ_FUSE_OVERWRITE) return fail(SQ_ERR_INVALID, "%s: the plan was built for mode %d", who, h.mode);
-    if (a->plan->spans_only && !a->plan->expanded)
-        return fail(SQ_ERR_INVALID, "%s: the plan of sq_fuse_plan_create_spans has not been through sq_fuse_plan_expand", who);
-    if (a->table_bytes != a->plan->device_bytes())
-        return fail(SQ_ERR_INVALID, "%s: table_bytes %lld != plan %lld", who, (long long)a->table_bytes,
-                    (long long)a->plan->device_bytes());
-    if (a->n_tiles != h.n_tiles || a->tile_h != h.tile_h || a->tile_w != h.tile_w || a->canvas_h != h.canvas_h ||
-        a->canvas_w != h.canvas_w)
-        return fail(SQ_ERR_INVALID, "%s: geometry differs from the plan", who);
-    if (!a->tile_ptrs_dev && !a->tile_base_dev && h.n_refs > 0)
-        return fail(SQ_ERR_INVALID, "%s: no tile table and no tile base", who);
-    if (a->tile_pitch < a->tile_w || a->canvas_pitch < a->canvas_w) return fail(SQ_ERR_INVALID, "%s: pitch smaller than width", who);
-    if (a->n_planes < 1) return fail(SQ_ERR_INVALID, "%s: n_planes %d (at least one plane)", who, a->n_planes);
-    const int32_t fl = flags | a->flags;
-    if ((fl & ~(SQ_FUSE_FORCE_QUEUES | SQ_FUSE_FORCE_STATIC | SQ_FUSE_NO_PLANE_GROUPS | SQ_FUSE_NO_SEAM_OWNERS | SQ_FUSE_CONSECUTIVE_GROUPS |
-                SQ_PROJECT_ACCUMULATE)) ||
-        a->grid_blocks < 0 || ((fl & SQ_FUSE_FORCE_QUEUES) && (fl & SQ_FUSE_FORCE_STATIC)))
-        return fail(SQ_ERR_INVALID, "%s: flags %d / grid_blocks %d", who, fl, a->grid_blocks);
-    if (a->tile_dtype != SQ_U8 && a->tile_dtype != SQ_U16)
-        return fail(SQ_ERR_UNSUPPORTED, "%s: tile dtype %d (uint8/uint16 only)", who, a->tile_dtype);
-    if (a->canvas_dtype != a->tile_dtype)
-        return fail(SQ_ERR_INVALID, "%s: the output keeps the tile dtype (output %d, tile %d)", who, a->canvas_dtype, a->tile_dtype);
-    if (a->flat_ptrs_dev && a->flat_dtype != SQ_F32 && a->flat_dtype != SQ_F64)
-        return fail(SQ_ERR_UNSUPPORTED, "%s: flatfield dtype %d (float32/float64 only)", who, a->flat_dtype);
-    if (reinterpret_cast<uintptr_t>(a->canvas_dev) % (size_t)a->canvas_dtype)
-        return fail(SQ_ERR_INVALID, "%s: output pointer not aligned to its element size", who);
-
-    P = FuseParams{};
-    const char *base = static_cast<const char *>(a->table_dev);
-    P.spans = reinterpret_cast<const Span *>(base + h.off_spans);
-    P.refs = reinterpret_cast<const Ref *>(base + h.off_refs);
-    P.items = reinterpret_cast<const Item *>(base + h.off_items);
-    P.seams = nullptr;
-    P.tile_ptrs = a->tile_ptrs_dev;
-    P.tile_base = a->tile_base_dev;
-    P.tile_plane_stride = a->tile_plane_stride;
-    P.tile_stride = a->tile_stride;
-    P.flat_ptrs = a->flat_ptrs_dev;
-    P.canvas = a->canvas_dev;
-    P.canvas_plane_stride = 0;
-    P.n_tiles = a->n_tiles;
-    P.tile_h = a->tile_h;
-    P.tile_w = a->tile_w;
-    P.tile_pitch = a->tile_pitch;
-    P.canvas_pitch = a->canvas_pitch;
-    P.lane_items = (int32_t)h.lane_items;
-    P.n_planes = a->n_planes;
-    if (a->scratch_dev) {
-        const ScratchLayout SL = scratch_layout(a->n_planes);
-        if (a->scratch_bytes < SL.total)
-            return fail(SQ_ERR_WORKSPACE, "%s: scratch %lld < %lld bytes", who, (long long)a->scratch_bytes, (long long)SL.total);
-        if (reinterpret_cast<uintptr_t>(a->scratch_dev) % 128) return fail(SQ_ERR_INVALID, "%s: scratch not 128-byte aligned", who);
-        // the device queues: the same size rule as sq_fuse_planes (an item carries all Z planes here)
-        const int64_t n_work = (int64_t)a->n_planes * h.n_items;
-        if ((n_work >= 100000 || (fl & SQ_FUSE_FORCE_QUEUES)) && h.n_items < (int64_t(1) << 31) && !(fl & SQ_FUSE_FORCE_STATIC)) {
-            if (hipMemsetAsync(static_cast<char *>(a->scratch_dev) + SL.queue, 0, 9 * QUEUE_STRIDE * 4, stream) != hipSuccess)
-                return fail(SQ_ERR_HIP, "%s: cannot clear the queue counters", who);
-            P.queue = reinterpret_cast<uint32_t *>(static_cast<char *>(a->scratch_dev) + SL.queue);
-        }
-    } else if (fl & SQ_FUSE_FORCE_QUEUES) {
-        return fail(SQ_ERR_INVALID, "%s: SQ_FUSE_FORCE_QUEUES needs scratch_dev", who);
-    }
-    *fl_out = fl;
-    return SQ_OK;
-}
-}  // namespace
-
-extern "C" int sq_fuse_project_max(const sq_fuse_args *a, int32_t flags, void *stream_) {
-    static const char *who = "sq_fuse_project_max";
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    FuseParams P;
-    int32_t fl = 0;
-    if (const int rc = project_setup(who, a, flags, stream, P, &fl)) return rc;
-    const int64_t n_items = a->plan->header().n_items;
-    const bool acc = (fl & SQ_PROJECT_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
-    const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
-#define SQ_PROJECT(T, G)                                                                                                     \
-    do {                                                                                                                     \
-        if (acc) {                                                                                                           \
-            if (P.queue) return launch_project(who, project_max_kernel<T, G, true, true>, P, n_items, stream, a->grid_blocks); \
-            return launch_project(who, project_max_kernel<T, G, true, false>, P, n_items, stream, a->grid_blocks);            \
-        }                                                                                                                    \
-        if (P.queue) return launch_project(who, project_max_kernel<T, G, false, true>, P, n_items, stream, a->grid_blocks);    \
-        return launch_project(who, project_max_kernel<T, G, false, false>, P, n_items, stream, a->grid_blocks);               \
-    } while (0)
-    if (u16) {
-        if (flat == 0) SQ_PROJECT(uint16_t, NoGain);
-        if (flat == 1) SQ_PROJECT(uint16_t, float);
-        SQ_PROJECT(uint16_t, double);
-    }
-    if (flat == 0) SQ_PROJECT(uint8_t, NoGain);
-    if (flat == 1) SQ_PROJECT(uint8_t, float);
-    SQ_PROJECT(uint8_t, double);
-#undef SQ_PROJECT
-}
-
-// ---------------------------------------------------------------------------------------------
-// best-focus (extended depth of field) projection over z (sq_fuse_project_focus; an extension: the reference has none)
-// ---------------------------------------------------------------------------------------------
-// Definition in include/squidstitch.h (and DESIGN.md 5.2b).  Two stages:
-//  (1) focus_tiles_kernel, tile space: one workgroup per (tile, FOC_BW x FOC_BH block).  Per plane z of the call: the block
-//      plus a halo of R + 1 pixels (coordinates clamped to the tile) into LDS; ML over the block plus a halo of R, each halo
-//      position taking the ML of its clamped position; the separable box sum (columns by a running sum down 8 rows per lane,
-//      rows directly); the running best (score, z level, plane index) of the thread's 8 outputs in registers.  After the last
-//      plane the winners go to the caller's scratch: uint32 score + uint8 plane index per tile pixel.
-//  (2) focus_canvas_kernel, canvas space: the overwrite plan's items like project_max_kernel (static walk or the per-XCD
-//      queues, no seam owners); per voxel the owner pixel's winner, its raw value from the winning plane through that plane's
-//      gains (flat_generic: what sq_fuse_planes stores, bit for bit) and its key; ACC merges by key maximum.
-// Algorithmic traffic: Z x sizeof(T) B read per tile pixel + 5 B written / read per tile pixel of scratch + (sizeof(T) + 8) B
-// written per canvas voxel (+ sizeof(T) + gain bytes read per covered voxel).
-namespace {
-constexpr int FOC_BW = 64, FOC_BH = 32;   // output block of a workgroup: 64 lanes x (4 waves x 8 rows)
-static_assert(FOC_BH == 4 * 8 && FOC_BW == 64, "the F stage maps one column per lane and 8 rows per wave");
-constexpr int FOC_LROWS = (FOC_BH + 2 * SQ_FOCUS_MAX_RADIUS + 2 + 3) / 4;    // raw-block rows a wave loads at most (16)
-constexpr int FOC_LCOLS = (FOC_BW + 2 * SQ_FOCUS_MAX_RADIUS + 2 + 63) / 64;  // 64-lane column runs of a raw-block row (2)
-constexpr int FOC_XU = 4;   // canvas stage: pixels a lane has in flight at once
-
-struct FocusParams {
-    const uint32_t *zlev;   // z level of each of the call's planes
-    uint32_t *score;        // [n_tiles][tile_h][tile_w] best F of every tile pixel
-    uint8_t *plane;         // [n_tiles][tile_h][tile_w] its plane index within the call
-    uint64_t *key;          // the key plane, key_pitch elements between rows
-    int32_t key_pitch;
-    int32_t radius;
-    int32_t bx, by;         // blocks across / down a tile
-};
-
-struct FocusLayout {
-    int64_t score, plane, total;
-};
-FocusLayout focus_layout(int64_t n_tiles, int64_t tile_h, int64_t tile_w) {
-    FocusLayout L;
-    const int64_t px = n_tiles * tile_h * tile_w;
-    L.score = 0;
-    L.plane = (px * 4 + 127) & ~int64_t(127);
-    L.total = L.plane + ((px + 127) & ~int64_t(127));
-    return L;
-}
-// LDS words of one workgroup for radius R: the raw block (later the column sums, which are smaller) + the ML block
-int64_t focus_lds_words(int R) {
-    const int lw = FOC_BW + 2 * R + 2, lh = FOC_BH + 2 * R + 2, mw = FOC_BW + 2 * R, mh = FOC_BH + 2 * R;
-    return (int64_t)lw * lh + (int64_t)mw * mh;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void focus_tiles_kernel(const FuseParams P, const FocusParams F) {
-    extern __shared__ uint32_t s_focus[];
-    const int R = F.radius;
-    const int LW = FOC_BW + 2 * R + 2, LH = FOC_BH + 2 * R + 2, MW = FOC_BW + 2 * R, MH = FOC_BH + 2 * R;
-    uint32_t *sI = s_focus;             // [LH][LW] raw pixels of the block + halo R + 1; then [FOC_BH][MW] column sums
-    uint32_t *sM = s_focus + LW * LH;   // [MH][MW] ML of the block + halo R
-    const int per_tile = F.bx * F.by;
-    const int tile = (int)(blockIdx.x / (unsigned)per_tile);
-    const int blk = (int)blockIdx.x - tile * per_tile;
-    const int by = blk / F.bx;
-    const int x0 = (blk - by * F.bx) * FOC_BW, y0 = by * FOC_BH;
-    const int H = P.tile_h, W = P.tile_w;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int oy = wave * 8;   // this thread's outputs: block column `lane`, block rows oy .. oy + 7
-    uint32_t best[8] = {}, bestz[8] = {}, bestp[8] = {};
-    // the raw block of a plane into registers (clamped reads), issued one plane ahead: the loads of plane z + 1 are in flight
-    // while plane z is reduced.  Lanes past the block's width load a valid pixel that is not kept.
-    uint32_t px[FOC_LROWS][FOC_LCOLS] = {};
-    auto load_raw = [&](int z) {
-        const T *src = sgpr(tile_ptr<T>(P, z, tile));
-#pragma unroll
-        for (int k = 0; k < FOC_LROWS; ++k) {
-            const int i = wave + 4 * k;
-            if (i < LH) {
-                const T *srow = src + (int64_t)min(max(y0 - R - 1 + i, 0), H - 1) * P.tile_pitch;
-#pragma unroll
-                for (int m = 0; m < FOC_LCOLS; ++m) px[k][m] = ldg_s<T>(srow + min(max(x0 - R - 1 + lane + 64 * m, 0), W - 1));
-            }
-        }
-    };
-    load_raw(0);
-    // the ML walk: this thread's first position and the step of 256 positions, as (row, column) of the MH x MW region
-    const int ml_i0 = (int)threadIdx.x / MW, ml_j0 = (int)threadIdx.x - ml_i0 * MW;
-    const int ml_di = 256 / MW, ml_dj = 256 - ml_di * MW;
-    const bool inner = y0 - R >= 0 && y0 + FOC_BH + R <= H && x0 - R >= 0 && x0 + FOC_BW + R <= W;
-    for (int z = 0; z < P.n_planes; ++z) {
-        const uint32_t zl = F.zlev[z];
-        // raw pixels at logical (y0 - R - 1 + i, x0 - R - 1 + j), read at the clamped position
-#pragma unroll
-        for (int k = 0; k < FOC_LROWS; ++k) {
-            const int i = wave + 4 * k;
-#pragma unroll
-            for (int m = 0; m < FOC_LCOLS; ++m)
-                if (i < LH && lane + 64 * m < LW) sI[i * LW + lane + 64 * m] = px[k][m];
-        }
-        __syncthreads();
-        if (z + 1 < P.n_planes) load_raw(z + 1);
-        // ML at logical (y0 - R + i, x0 - R + j) = ML at the clamped position, which lies inside the raw block with its
-        // neighbours (whose values are the clamped reads).  One flat walk over the MH x MW positions (every lane busy: the rows
-        // are wider than 64); a block whose ML region lies inside the tile needs no clamp
-        for (int e = threadIdx.x, i = ml_i0, j = ml_j0; e < MH * MW; e += 256) {
-            const int cy = inner ? i + 1 : min(max(y0 - R + i, 0), H - 1) - (y0 - R - 1);
-            const int cx = inner ? j + 1 : min(max(x0 - R + j, 0), W - 1) - (x0 - R - 1);
-            const int c = cy * LW + cx;
-            const int c2 = 2 * (int)sI[c];
-            const int h = c2 - (int)sI[c - 1] - (int)sI[c + 1];
-            const int v = c2 - (int)sI[c - LW] - (int)sI[c + LW];
-            sM[e] = (uint32_t)(abs(h) + abs(v));
-            i += ml_di;
-            j += ml_dj;
-            if (j >= MW) {
-                j -= MW;
-                ++i;
-            }
-        }
-        __syncthreads();
-        // column sums over 2R + 1 ML rows for the block's rows: a running sum down the wave's 8 rows
-        for (int j = lane; j < MW; j += 64) {
-            uint32_t s = 0;
-            for (int d = 0; d <= 2 * R; ++d) s += sM[(oy + d) * MW + j];
-            sI[oy * MW + j] = s;
-#pragma unroll
-            for (int k = 1; k < 8; ++k) {
-                s += sM[(oy + k + 2 * R) * MW + j] - sM[(oy + k - 1) * MW + j];
-                sI[(oy + k) * MW + j] = s;
-            }
-        }
-        __syncthreads();
-        // row sums over 2R + 1 column sums -> F; keep the larger key (higher score, on a tie the lower z level)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            uint32_t f = 0;
-            for (int d = 0; d <= 2 * R; ++d) f += sI[(oy + k) * MW + lane + d];
-            if (z == 0 || f > best[k] || (f == best[k] && zl < bestz[k])) {
-                best[k] = f;
-                bestz[k] = zl;
-                bestp[k] = (uint32_t)z;
-            }
-        }
-        __syncthreads();   // the next plane's raw pixels overwrite the column sums
-    }
-    const int x = x0 + lane;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int y = y0 + oy + k;
-        if (x < W && y < H) {
-            const int64_t at = ((int64_t)tile * H + y) * W + x;
-            stg_s<uint32_t>(F.score + at, best[k]);
-            stg_s<uint8_t>(F.plane + at, (uint8_t)bestp[k]);
-        }
-    }
-}
-
-template <typename T, typename G, bool ACC>
-__device__ __forceinline__ void focus_item(const FuseParams &P, const FocusParams &F, const Item &it, const int wave, const int lane) {
-    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
-    typedef typename std::conditional<GAINS, G, float>::type GT;
-    const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
-    T *canvas = static_cast<T *>(P.canvas);
-    if (!it.nref) {   // uncovered canvas: 0 and key 0 (accumulating: left alone)
-        if (!ACC)
-            for (int r = wave; r < rows; r += 4) {
-                T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
-                uint64_t *krow = F.key + (int64_t)(it.dst_y + r) * F.key_pitch + it.dst_x;
-                for (int x = lane; x < n; x += 64) {
-                    stg_s<T>(drow + x, (T)0);
-                    stg_s<uint64_t>(krow + x, (uint64_t)0);
-                }
-            }
-        return;
-    }
-    const int64_t tbase = (int64_t)it.a * P.tile_h * P.tile_w;
-    for (int r = wave; r < rows; r += 4) {
-        T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
-        uint64_t *krow = F.key + (int64_t)(it.dst_y + r) * F.key_pitch + it.dst_x;
-        const int64_t soff = (int64_t)(it.b + r) * P.tile_pitch + it.c;   // elements into the winning plane's tile
-        const int64_t foff = (int64_t)(it.b + r) * P.tile_w + it.c;       // elements into a gain image / the winners
-        // FOC_XU pixels per lane at a time, loads of all of them first (clamped to the row: every address is valid), then the
-        // dependent loads, then the stores: the winners' loads do not wait behind the previous pixel's stores
-        for (int x0 = lane; x0 < n; x0 += 64 * FOC_XU) {
-            uint32_t sc[FOC_XU], zi[FOC_XU];
-#pragma unroll
-            for (int u = 0; u < FOC_XU; ++u) {
-                const int xc = min(x0 + 64 * u, n - 1);
-                sc[u] = ldg_s<uint32_t>(F.score + tbase + foff + xc);
-                zi[u] = ldg_s<uint8_t>(F.plane + tbase + foff + xc);
-            }
-            uint64_t key[FOC_XU];
-            T t[FOC_XU];
-            GT g[FOC_XU];
-            bool has_g[FOC_XU], put[FOC_XU];
-#pragma unroll
-            for (int u = 0; u < FOC_XU; ++u) {
-                const int xc = min(x0 + 64 * u, n - 1);
-                key[u] = ((uint64_t)sc[u] << 32) | (uint64_t)(0xFFFFFFFFu - ldg_s<uint32_t>(F.zlev + zi[u]));
-                put[u] = x0 + 64 * u < n;
-                if (ACC) put[u] = put[u] && key[u] > ldg_s<uint64_t>(krow + xc);
-                t[u] = ldg_s<T>(tile_ptr<T>(P, (int)zi[u], it.a) + soff + xc);
-                has_g[u] = false;
-                g[u] = (GT)1;
-                if constexpr (GAINS) {
-                    const GT *fz = static_cast<const GT *>(P.flat_ptrs[zi[u]]);
-                    has_g[u] = fz != nullptr;
-                    if (has_g[u]) g[u] = ldg_s<GT>(fz + foff + xc);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < FOC_XU; ++u) {
-                if (!put[u]) continue;
-                T v = t[u];
-                if constexpr (GAINS) {
-                    if (has_g[u]) v = flat_generic<T, GT>(t[u], g[u]);
-                }
-                stg_s<T>(drow + x0 + 64 * u, v);
-                stg_s<uint64_t>(krow + x0 + 64 * u, key[u]);
-            }
-        }
-    }
-}
-
-template <typename T, typename G, bool ACC, bool DYN>
-__global__ __launch_bounds__(256) void focus_canvas_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work,
-                                                           const FocusParams F) {
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (!DYN) {
-        for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x) focus_item<T, G, ACC>(P, F, sgpr(P.items[w]), wave, lane);
-        return;
-    }
-    for_each_queued_item<ProjAux>(
-        P, n_items, 1u, [&](int, const Item &, int64_t) -> ProjAux { return ProjAux{0}; },
-        [&](int, const Item &it, const ProjAux &) { focus_item<T, G, ACC>(P, F, it, wave, lane); });
-}
-}  // namespace
-
-extern "C" int64_t sq_focus_scratch_bytes(int32_t n_tiles, int32_t tile_h, int32_t tile_w) {
-    if (n_tiles < 0 || tile_h < 0 || tile_w < 0)
-        return fail(SQ_ERR_INVALID, "sq_focus_scratch_bytes: n_tiles %d, tile %d x %d", n_tiles, tile_h, tile_w);
-    return focus_layout(n_tiles, tile_h, tile_w).total;
-}
-
-extern "C" int sq_fuse_project_focus(const sq_fuse_args *a, const sq_focus_args *f, int32_t flags, void *stream_) {
-    static const char *who = "sq_fuse_project_focus";
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    FuseParams P;
-    int32_t fl = 0;
-    if (const int rc = project_setup(who, a, flags, stream, P, &fl)) return rc;
-    if (!f || !f->z_levels_dev || !f->key_dev) return fail(SQ_ERR_INVALID, "%s: NULL focus arguments / z levels / key plane", who);
-    if (f->radius < 0 || f->radius > SQ_FOCUS_MAX_RADIUS)
-        return fail(SQ_ERR_INVALID, "%s: focus radius %d outside 0..%d", who, f->radius, SQ_FOCUS_MAX_RADIUS);
-    if (a->n_planes > SQ_FOCUS_MAX_PLANES)
-        return fail(SQ_ERR_INVALID, "%s: %d planes, the scratch's uint8 plane index holds %d", who, a->n_planes, SQ_FOCUS_MAX_PLANES);
-    if (f->key_pitch < a->canvas_w || reinterpret_cast<uintptr_t>(f->key_dev) % 8)
-        return fail(SQ_ERR_INVALID, "%s: key plane pitch %d < width %d, or not 8-byte aligned", who, f->key_pitch, a->canvas_w);
-    const FocusLayout FL = focus_layout(a->n_tiles, a->tile_h, a->tile_w);
-    if (FL.total > 0 && (!f->scratch_dev || reinterpret_cast<uintptr_t>(f->scratch_dev) % 128))
-        return fail(SQ_ERR_INVALID, "%s: focus scratch missing or not 128-byte aligned", who);
-    if (f->scratch_bytes < FL.total)
-        return fail(SQ_ERR_WORKSPACE, "%s: focus scratch %lld < %lld bytes", who, (long long)f->scratch_bytes, (long long)FL.total);
-    FocusParams F{};
-    F.zlev = f->z_levels_dev;
-    F.score = reinterpret_cast<uint32_t *>(static_cast<char *>(f->scratch_dev) + FL.score);
-    F.plane = reinterpret_cast<uint8_t *>(static_cast<char *>(f->scratch_dev) + FL.plane);
-    F.key = static_cast<uint64_t *>(f->key_dev);
-    F.key_pitch = f->key_pitch;
-    F.radius = f->radius;
-    F.bx = (a->tile_w + FOC_BW - 1) / FOC_BW;
-    F.by = (a->tile_h + FOC_BH - 1) / FOC_BH;
-    const int64_t tile_blocks = (int64_t)a->n_tiles * F.bx * F.by;
-    if (tile_blocks >= (int64_t(1) << 31)) return fail(SQ_ERR_UNSUPPORTED, "%s: %lld tile blocks", who, (long long)tile_blocks);
-    const bool acc = (fl & SQ_FOCUS_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
-    const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
-    if (tile_blocks > 0) {
-        const size_t lds = (size_t)focus_lds_words(F.radius) * 4;
-        if (u16) hipLaunchKernelGGL(focus_tiles_kernel<uint16_t>, dim3((unsigned)tile_blocks), dim3(256), lds, stream, P, F);
-        else hipLaunchKernelGGL(focus_tiles_kernel<uint8_t>, dim3((unsigned)tile_blocks), dim3(256), lds, stream, P, F);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "%s: tile stage launch failed: %s", who, hipGetErrorString(e));
-    }
-    const int64_t n_items = a->plan->header().n_items;
-#define SQ_FOCUS(T, G)                                                                                                             \
-    do {                                                                                                                           \
-        if (acc) {                                                                                                                 \
-            if (P.queue) return launch_project(who, focus_canvas_kernel<T, G, true, true>, P, n_items, stream, a->grid_blocks, F);  \
-            return launch_project(who, focus_canvas_kernel<T, G, true, false>, P, n_items, stream, a->grid_blocks, F);             \
-        }                                                                                                                          \
-        if (P.queue) return launch_project(who, focus_canvas_kernel<T, G, false, true>, P, n_items, stream, a->grid_blocks, F);     \
-        return launch_project(who, focus_canvas_kernel<T, G, false, false>, P, n_items, stream, a->grid_blocks, F);                \
-    } while (0)
-    if (u16) {
-        if (flat == 0) SQ_FOCUS(uint16_t, NoGain);
-        if (flat == 1) SQ_FOCUS(uint16_t, float);
-        SQ_FOCUS(uint16_t, double);
-    }
-    if (flat == 0) SQ_FOCUS(uint8_t, NoGain);
-    if (flat == 1) SQ_FOCUS(uint8_t, float);
-    SQ_FOCUS(uint8_t, double);
-#undef SQ_FOCUS
-}
-
-// ---------------------------------------------------------------------------------------------
-// guide channel of the best-focus projection (sq_focus_depth_plane, sq_fuse_select_depth)
-// ---------------------------------------------------------------------------------------------
-// Definition in include/squidstitch.h.  depth_plane_kernel: key plane -> unsigned depth plane (z* + 1, 0 = uncovered), streaming.
-// select_depth_kernel, canvas space: the overwrite plan's items like focus_canvas_kernel; per voxel the guide's depth, the plane
-// of this call at that z level (a table in LDS) and that plane's owner pixel through that plane's gains.
-// Algorithmic traffic of the select: 1..2 B (depth) read per voxel + sizeof(T) + gain bytes read per covered voxel whose depth is
-// in the call, sizeof(T) B written per voxel.
-namespace {
-constexpr int DEPTH_PER = 8;      // keys of a lane: four 16-byte loads, one 8- or 16-byte store
-constexpr int SEL_XU = 4;         // select: pixels a lane has in flight at once
-constexpr int SEL_MAP = 1024;     // z levels (counted from the call's lowest) the direct LDS table holds; beyond: a search
-
-template <typename D>
-__device__ __forceinline__ uint32_t depth_of_key(uint32_t lo, uint32_t hi) {
-    constexpr uint32_t TOP = sizeof(D) == 1 ? 0xFFu : 0xFFFFu;
-    if ((lo | hi) == 0) return 0u;             // no plane covers the voxel
-    const uint32_t z = 0xFFFFFFFFu - lo;
-    return z >= TOP ? TOP : z + 1u;            // (a z level the dtype cannot hold saturates; the caller sizes the dtype)
-}
-
-template <typename D>
-__global__ __launch_bounds__(256) void depth_plane_kernel(const uint64_t *key, int64_t key_pitch, int h, int w, D *depth,
-                                                          int64_t depth_pitch) {
-    const int x0 = (int)(blockIdx.x * 256 + threadIdx.x) * DEPTH_PER;
-    if (x0 >= w) return;
-    for (int y = blockIdx.y; y < h; y += gridDim.y) {
-        const uint64_t *krow = key + (int64_t)y * key_pitch + x0;
-        D *drow = depth + (int64_t)y * depth_pitch + x0;
-        if (x0 + DEPTH_PER <= w) {
-            u32x4 k[DEPTH_PER / 2];
-#pragma unroll
-            for (int i = 0; i < DEPTH_PER / 2; ++i) k[i] = ldg<U32x4U>(krow + 2 * i);
-            uint32_t d[DEPTH_PER];
-#pragma unroll
-            for (int i = 0; i < DEPTH_PER / 2; ++i) {
-                d[2 * i] = depth_of_key<D>(k[i][0], k[i][1]);
-                d[2 * i + 1] = depth_of_key<D>(k[i][2], k[i][3]);
-            }
-            if constexpr (sizeof(D) == 1) {
-                ((SQ_GLOBAL U32x2U *)drow)->v =
-                    u32x2{d[0] | (d[1] << 8) | (d[2] << 16) | (d[3] << 24), d[4] | (d[5] << 8) | (d[6] << 16) | (d[7] << 24)};
-            } else {
-                ((SQ_GLOBAL U32x4U *)drow)->v = u32x4{d[0] | (d[1] << 16), d[2] | (d[3] << 16), d[4] | (d[5] << 16), d[6] | (d[7] << 16)};
-            }
-        } else {
-            for (int i = 0; x0 + i < w; ++i) {
-                const u32x2 k = ldg<U32x2U>(krow + i);
-                stg_s<D>(drow + i, (D)depth_of_key<D>(k[0], k[1]));
-            }
-        }
-    }
-}
-
-struct SelectParams {
-    const void *depth;      // the guide's depth plane, depth_pitch elements between rows
-    const uint32_t *zlev;   // z level of each of the call's planes
-    int32_t depth_pitch;
-    int32_t depth16;        // elements are uint16 (else uint8)
-};
-
-// the call's z levels for one workgroup: s_zlev[plane] and the direct table s_map[z - lowest z] = plane + 1 (0: not in the
-// call; of two planes with one z level the first).  -> (lowest z, whether a level lies beyond the table)
-__device__ __forceinline__ void select_table(const FuseParams &P, const SelectParams &S, uint32_t *s_zlev, uint16_t *s_map,
-                                             uint32_t &zmin, bool &sparse) {
-    const int nz = P.n_planes;
-    for (int p = threadIdx.x; p < nz; p += 256) s_zlev[p] = ldg_s<uint32_t>(S.zlev + p);
-    __syncthreads();
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-    for (int p = 0; p < nz; ++p) {
-        lo = min(lo, s_zlev[p]);
-        hi = max(hi, s_zlev[p]);
-    }
-    for (int e = threadIdx.x; e < SEL_MAP; e += 256) {
-        uint32_t m = 0;
-        for (int p = nz - 1; p >= 0; --p)
-            if (s_zlev[p] - lo == (uint32_t)e) m = (uint32_t)p + 1u;
-        s_map[e] = (uint16_t)m;
-    }
-    __syncthreads();
-    zmin = (uint32_t)sgpr((int)lo);
-    sparse = sgpr((int)(hi - lo >= (uint32_t)SEL_MAP)) != 0;
-}
-
-// plane index within the call of depth value d (z + 1; 0 = uncovered), -1 when the call has no plane at that level
-__device__ __forceinline__ int select_plane(uint32_t d, uint32_t zmin, bool sparse, int nz, const uint32_t *s_zlev,
-                                            const uint16_t *s_map) {
-    if (d == 0u) return -1;
-    const uint32_t rel = d - 1u - zmin;
-    if (rel < (uint32_t)SEL_MAP) return (int)s_map[rel] - 1;
-    if (sparse)
-        for (int p = 0; p < nz; ++p)
-            if (s_zlev[p] == d - 1u) return p;
-    return -1;
-}
-
-template <typename T, typename G, bool ACC>
-__device__ __forceinline__ void select_item(const FuseParams &P, const SelectParams &S, const Item &it, const int wave, const int lane,
-                                            const uint32_t zmin, const bool sparse, const uint32_t *s_zlev, const uint16_t *s_map) {
-    constexpr bool GAINS = !std::is_same<G, NoGain>::value;
-    typedef typename std::conditional<GAINS, G, float>::type GT;
-    const int rows = it.hw >> 16, n = it.hw & 0xFFFF;
-    const int nz = P.n_planes;
-    T *canvas = static_cast<T *>(P.canvas);
-    const bool d16 = S.depth16 != 0;
-    auto depth_at = [&](const char *row, int x) -> uint32_t {
-        return d16 ? (uint32_t)ldg_s<uint16_t>(row + 2 * x) : (uint32_t)ldg_s<uint8_t>(row + x);
-    };
-    if (!it.nref) {   // uncovered canvas: 0, like that plane of the stack (accumulating: only where the depth is this call's)
-        for (int r = wave; r < rows; r += 4) {
-            T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
-            if (!ACC) {
-                row_zero<T>(drow, n, lane);
-                continue;
-            }
-            const char *prow = static_cast<const char *>(S.depth) + ((int64_t)(it.dst_y + r) * S.depth_pitch + it.dst_x) * (d16 ? 2 : 1);
-            for (int x = lane; x < n; x += 64)
-                if (select_plane(depth_at(prow, x), zmin, sparse, nz, s_zlev, s_map) >= 0) stg_s<T>(drow + x, (T)0);
-        }
-        return;
-    }
-    for (int r = wave; r < rows; r += 4) {
-        T *drow = canvas + (int64_t)(it.dst_y + r) * P.canvas_pitch + it.dst_x;
-        const char *prow = static_cast<const char *>(S.depth) + ((int64_t)(it.dst_y + r) * S.depth_pitch + it.dst_x) * (d16 ? 2 : 1);
-        const int64_t soff = (int64_t)(it.b + r) * P.tile_pitch + it.c;   // elements into the chosen plane's tile
-        const int64_t foff = (int64_t)(it.b + r) * P.tile_w + it.c;       // elements into a gain image
-        // SEL_XU pixels per lane at a time: the depths of all of them first (clamped to the row: every address is valid), then
-        // the loads that depend on them, then the stores
-        for (int x0 = lane; x0 < n; x0 += 64 * SEL_XU) {
-            uint32_t d[SEL_XU];
-#pragma unroll
-            for (int u = 0; u < SEL_XU; ++u) d[u] = depth_at(prow, min(x0 + 64 * u, n - 1));
-            int zi[SEL_XU];
-            T t[SEL_XU];
-            GT g[SEL_XU];
-            bool has_g[SEL_XU];
-#pragma unroll
-            for (int u = 0; u < SEL_XU; ++u) {
-                const int xc = min(x0 + 64 * u, n - 1);
-                zi[u] = select_plane(d[u], zmin, sparse, nz, s_zlev, s_map);
-                const int zp = max(zi[u], 0);      // (a voxel without a plane loads plane 0's pixel and does not use it)
-                t[u] = ldg_s<T>(tile_ptr<T>(P, zp, it.a) + soff + xc);
-                has_g[u] = false;
-                g[u] = (GT)1;
-                if constexpr (GAINS) {
-                    const GT *fz = static_cast<const GT *>(P.flat_ptrs[zp]);
-                    has_g[u] = fz != nullptr;
-                    if (has_g[u]) g[u] = ldg_s<GT>(fz + foff + xc);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < SEL_XU; ++u) {
-                if (x0 + 64 * u >= n) continue;
-                if (zi[u] < 0) {
-                    if (!ACC) stg_s<T>(drow + x0 + 64 * u, (T)0);
-                    continue;
-                }
-                T v = t[u];
-                if constexpr (GAINS) {
-                    if (has_g[u]) v = flat_generic<T, GT>(t[u], g[u]);
-                }
-                stg_s<T>(drow + x0 + 64 * u, v);
-            }
-        }
-    }
-}
-
-template <typename T, typename G, bool ACC, bool DYN>
-__global__ __launch_bounds__(256) void select_depth_kernel(const FuseParams P, const int64_t n_items, const int64_t n_work,
-                                                           const SelectParams S) {
-    __shared__ uint32_t s_zlev[SQ_FOCUS_MAX_PLANES];
-    __shared__ uint16_t s_map[SEL_MAP];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    uint32_t zmin;
-    bool sparse;
-    select_table(P, S, s_zlev, s_map, zmin, sparse);
-    if (!DYN) {
-        for (int64_t w = blockIdx.x; w < n_work; w += gridDim.x)
-            select_item<T, G, ACC>(P, S, sgpr(P.items[w]), wave, lane, zmin, sparse, s_zlev, s_map);
-        return;
-    }
-    for_each_queued_item<ProjAux>(
-        P, n_items, 1u, [&](int, const Item &, int64_t) -> ProjAux { return ProjAux{0}; },
-        [&](int, const Item &it, const ProjAux &) { select_item<T, G, ACC>(P, S, it, wave, lane, zmin, sparse, s_zlev, s_map); });
-}
-}  // namespace
-
-extern "C" int sq_focus_depth_plane(const void *key_dev, int32_t key_pitch, int32_t h, int32_t w, void *depth_dev,
-                                    int32_t depth_pitch, int32_t depth_dtype, void *stream_) {
-    static const char *who = "sq_focus_depth_plane";
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (h < 0 || w < 0) return fail(SQ_ERR_INVALID, "%s: plane %d x %d", who, h, w);
-    if (depth_dtype != SQ_U8 && depth_dtype != SQ_U16)
-        return fail(SQ_ERR_INVALID, "%s: depth dtype %d (uint8/uint16 only)", who, depth_dtype);
-    if (h == 0 || w == 0) return SQ_OK;
-    if (!key_dev || !depth_dev) return fail(SQ_ERR_INVALID, "%s: NULL key / depth plane", who);
-    if (key_pitch < w || depth_pitch < w) return fail(SQ_ERR_INVALID, "%s: pitch smaller than width", who);
-    if (reinterpret_cast<uintptr_t>(key_dev) % 8 || reinterpret_cast<uintptr_t>(depth_dev) % (size_t)depth_dtype)
-        return fail(SQ_ERR_INVALID, "%s: key plane not 8-byte aligned or depth plane not aligned to its element size", who);
-    const dim3 grid((unsigned)((w + 256 * DEPTH_PER - 1) / (256 * DEPTH_PER)), (unsigned)std::min(h, 65535));
-    if (depth_dtype == SQ_U8)
-        hipLaunchKernelGGL(depth_plane_kernel<uint8_t>, grid, dim3(256), 0, stream, static_cast<const uint64_t *>(key_dev),
-                           (int64_t)key_pitch, h, w, static_cast<uint8_t *>(depth_dev), (int64_t)depth_pitch);
-    else
-        hipLaunchKernelGGL(depth_plane_kernel<uint16_t>, grid, dim3(256), 0, stream, static_cast<const uint64_t *>(key_dev),
-                           (int64_t)key_pitch, h, w, static_cast<uint16_t *>(depth_dev), (int64_t)depth_pitch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return SQ_OK;
-}
-
-extern "C" int sq_fuse_select_depth(const sq_fuse_args *a, const void *depth_dev, int32_t depth_pitch, int32_t depth_dtype,
-                                    const uint32_t *z_levels_dev, int32_t flags, void *stream_) {
-    static const char *who = "sq_fuse_select_depth";
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    FuseParams P;
-    int32_t fl = 0;
-    if (const int rc = project_setup(who, a, flags, stream, P, &fl)) return rc;
-    if (!depth_dev || !z_levels_dev) return fail(SQ_ERR_INVALID, "%s: NULL depth plane / z levels", who);
-    if (depth_dtype != SQ_U8 && depth_dtype != SQ_U16)
-        return fail(SQ_ERR_INVALID, "%s: depth dtype %d (uint8/uint16 only)", who, depth_dtype);
-    if (a->n_planes > SQ_FOCUS_MAX_PLANES)
-        return fail(SQ_ERR_INVALID, "%s: %d planes, a call selects among at most %d", who, a->n_planes, SQ_FOCUS_MAX_PLANES);
-    if (depth_pitch < a->canvas_w || reinterpret_cast<uintptr_t>(depth_dev) % (size_t)depth_dtype)
-        return fail(SQ_ERR_INVALID, "%s: depth plane pitch %d < width %d, or not aligned to its element size", who, depth_pitch,
-                    a->canvas_w);
-    SelectParams S{};
-    S.depth = depth_dev;
-    S.zlev = z_levels_dev;
-    S.depth_pitch = depth_pitch;
-    S.depth16 = depth_dtype == SQ_U16;
-    const int64_t n_items = a->plan->header().n_items;
-    const bool acc = (fl & SQ_SELECT_ACCUMULATE) != 0, u16 = a->tile_dtype == SQ_U16;
-    const int flat = a->flat_ptrs_dev ? (a->flat_dtype == SQ_F64 ? 2 : 1) : 0;
-#define SQ_SELECT(T, G)                                                                                                            \
-    do {                                                                                                                           \
-        if (acc) {                                                                                                                 \
-            if (P.queue) return launch_project(who, select_depth_kernel<T, G, true, true>, P, n_items, stream, a->grid_blocks, S);  \
-            return launch_project(who, select_depth_kernel<T, G, true, false>, P, n_items, stream, a->grid_blocks, S);             \
-        }                                                                                                                          \
-        if (P.queue) return launch_project(who, select_depth_kernel<T, G, false, true>, P, n_items, stream, a->grid_blocks, S);     \
-        return launch_project(who, select_depth_kernel<T, G, false, false>, P, n_items, stream, a->grid_blocks, S);                \
-    } while (0)
-    if (u16) {
-        if (flat == 0) SQ_SELECT(uint16_t, NoGain);
-        if (flat == 1) SQ_SELECT(uint16_t, float);
-        SQ_SELECT(uint16_t, double);
-    }
-    if (flat == 0) SQ_SELECT(uint8_t, NoGain);
-    if (flat == 1) SQ_SELECT(uint8_t, float);
-    SQ_SELECT(uint8_t, double);
-#undef SQ_SELECT
 }

@@ -80,7 +80,7 @@ __device__ __forceinline__ void add<uint8_t>(uint32_t *lds, unsigned long long *
 }
 
 // s_waitcnt lgkmcnt(0) by the wave that has just added into LDS: a no-return ds_add in front of a barrier was seen without the
-// wait that publishes it (the case tools/barrier_scan.py looks for; encoding and history: lds_written() in fuse.hip).
+// wait that publishes it (the case tools/barrier_scan.py looks for; encoding and history: lds_written() in fuse_device.h).
 __device__ __forceinline__ void lds_written() {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
 #error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"

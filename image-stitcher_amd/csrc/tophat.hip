@@ -57,7 +57,7 @@ struct MorphArgs {
 };
 
 // s_waitcnt lgkmcnt(0) by the wave that has just written LDS, in front of a barrier (the case tools/barrier_scan.py looks for;
-// encoding and history: lds_written() in fuse.hip).
+// encoding and history: lds_written() in fuse_device.h).
 __device__ __forceinline__ void lds_written() {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
 #error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"

@@ -717,7 +717,7 @@ def test_feather_plane_groups_with_a_float32_canvas(seed, queues):
 
 @pytest.mark.parametrize('out_dtype', ['float32', 'uint16'])
 def test_device_queues_lose_no_work_on_small_launches(out_dtype):
-    """Regression test of the queue walk's LDS hazard (csrc/fuse.hip, for_each_queued_item / lds_written): a small
+    """Regression test of the queue walk's LDS hazard (csrc/fuse_device.h, for_each_queued_item / lds_written): a small
     feather plan (71 items x 12 planes, one or two work units per workgroup) through the per-plane kernel with the device
     queues, 300 launches, every one compared with the oracle on the device.  Before the fix 1-2 % of such launches left a
     wave's share of an item unwritten (profiles/r03_queue_stress_before_fix.log)."""

@@ -1,6 +1,6 @@
 """Static check of the gfx950 listings: an s_barrier publishes LDS writes only if the writing wave has WAITED for them
 (s_waitcnt lgkmcnt(0)) -- and ROCm 7.2 was seen to omit that wait in front of a loop-top barrier reached round the back
-edge straight after a ds_write (csrc/fuse.hip, for_each_queued_item).  For every s_barrier of every kernel this walks the
+edge straight after a ds_write (csrc/fuse_device.h, for_each_queued_item).  For every s_barrier of every kernel this walks the
 control-flow graph backwards (fall-through and branch edges, up to DEPTH instructions per path) and reports paths that
 reach an LDS write before an lgkmcnt(0) wait.
 

@@ -1,7 +1,7 @@
 """Stress of the device work queues on a SMALL plan (71 items x 12 planes, as many workgroups as the kernel keeps resident):
 hundreds of launches of each kernel family, every launch compared with the oracle on the device.  Round 3 found the
 per-plane feather kernel leaving 28 ... 508 voxels unwritten in 1-2 % of such launches: a missing LDS wait in front of
-the queue walk's loop-top barrier (csrc/fuse.hip, for_each_queued_item / lds_written)."""
+the queue walk's loop-top barrier (csrc/fuse_device.h, for_each_queued_item / lds_written)."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
