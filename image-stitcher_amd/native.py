@@ -146,6 +146,8 @@ EXPORTS = {
     'sq_tophat_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_tophat_tiles': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_int64, C.c_void_p]),
+    'sq_despeckle_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1184,6 +1186,93 @@ def tophat_tiles(tiles, radius: int, scratch=None, stream=None):
                                  scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream_ptr(stream)),
            'sq_tophat_tiles')
     return tiles
+
+
+SQ_DESPECKLE_HOT = 1
+SQ_DESPECKLE_BOTH = 2
+DESPECKLE_MODES = {'hot': SQ_DESPECKLE_HOT, 'both': SQ_DESPECKLE_BOTH}
+SQ_DESPECKLE_MAX_THRESHOLD = 65535
+
+
+def _plane_layout(t, what):
+    """(n_planes, h, w, plane stride, pitch) of a [..., H, W] tensor with unit-stride rows whose leading dimensions are one
+    uniform plane stride apart (elements); ValueError otherwise."""
+    h, w = int(t.shape[-2]), int(t.shape[-1])
+    if h < 1 or w < 1:
+        raise ValueError(f"{what}: planes of {h} x {w}")
+    if w > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{what} rows must be contiguous")
+    pitch = int(t.stride(-2)) if h > 1 else w
+    if pitch < w:
+        raise ValueError(f"{what} rows overlap")
+    lead = [(int(n), int(s)) for n, s in zip(t.shape[:-2], t.stride()[:-2]) if n != 1]
+    n_images = 1
+    for n, _ in lead:
+        n_images *= n
+    plane_stride = (h - 1) * pitch + w
+    if n_images > 1:
+        for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+            if s0 != n1 * s1:
+                raise ValueError(f"the planes of {what} must be a uniform stride apart (a contiguous stack or a regular view "
+                                 "of one)")
+        plane_stride = lead[-1][1]
+        if plane_stride < (h - 1) * pitch + w:
+            raise ValueError(f"the planes of {what} overlap")
+    return n_images, h, w, plane_stride, pitch
+
+
+def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=None, stream=None):
+    """Hot-pixel removal of every H x W plane of ``tiles`` into ``out`` (sq_despeckle_tiles; an extension, the reference has
+    none): a pixel that differs from the median m of its edge-replicated 3 x 3 window by more than ``threshold`` -- mode 'hot':
+    I - m > T; mode 'both': |I - m| > T -- is replaced by m, every m taken from the unfiltered plane --
+    ``tests/despeckle_ref.despeckle``.  The filter is out of place: ``tiles`` is left as it is and the caller goes on with the
+    return value.
+
+    tiles:     uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
+               uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    threshold: T, an integer in 0..65535, in counts of the planes' dtype.
+    out:       a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
+               shares no memory with ``tiles``; allocated contiguous when None.
+    counts:    optional contiguous int64 device tensor with one element per plane: the number of pixels replaced in each plane
+               is ADDED to it.
+    Returns ``out``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)) or \
+            not 0 <= int(threshold) <= SQ_DESPECKLE_MAX_THRESHOLD:
+        raise ValueError(f"despeckle threshold must be an integer in 0..{SQ_DESPECKLE_MAX_THRESHOLD}, got {threshold!r}")
+    if not isinstance(mode, str) or mode not in DESPECKLE_MODES:
+        raise ValueError(f"despeckle mode must be 'hot' or 'both', got {mode!r}")
+    n_images, h, w, src_plane_stride, src_pitch = _plane_layout(tiles, 'tiles')
+    if out is None:
+        out = torch.empty(tuple(tiles.shape), dtype=tiles.dtype, device=tiles.device)
+        if stream is not None:
+            out.record_stream(stream)
+    elif not torch.is_tensor(out) or tuple(out.shape) != tuple(tiles.shape) or out.dtype != tiles.dtype or \
+            out.device != tiles.device:
+        raise ValueError(f"out must be a {tiles.dtype} tensor of shape {tuple(tiles.shape)} on the tiles' device")
+    n_out, _, _, dst_plane_stride, dst_pitch = _plane_layout(out, 'out')
+    assert n_out == n_images
+    if counts is not None:
+        if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.device != tiles.device or \
+                counts.numel() != n_images or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int64 tensor of {n_images} elements on the tiles' device")
+    if n_images == 0:
+        return out
+    es = tiles.element_size()
+    s0, d0 = tiles.data_ptr(), out.data_ptr()
+    s1 = s0 + ((n_images - 1) * src_plane_stride + (h - 1) * src_pitch + w) * es
+    d1 = d0 + ((n_images - 1) * dst_plane_stride + (h - 1) * dst_pitch + w) * es
+    if s0 < d1 and d0 < s1:
+        raise ValueError("out shares memory with tiles: the filter is out of place")
+    _check(lib().sq_despeckle_tiles(s0, d0, n_images, h, w, src_plane_stride, src_pitch, dst_plane_stride, dst_pitch,
+                                    sq_dtype_of(np_dtype_of_torch(tiles.dtype)), DESPECKLE_MODES[mode], int(threshold),
+                                    None if counts is None else counts.data_ptr(), _stream_ptr(stream)),
+           'sq_despeckle_tiles')
+    return out
 
 
 _COPY_STREAMS = {}

@@ -72,7 +72,8 @@ class Stitcher:
                  focus_radius: int = 3, pyramid_method: str = 'nearest', contrast_limits: str = 'dtype',
                  contrast_percentiles=(0.1, 99.9), focus_guide_channel: Optional[str] = None, focus_depth_map: bool = False,
                  composite: bool = False, composite_max_side: int = 4096, composite_z: Optional[int] = None,
-                 composite_channels=None, background_subtract: str = 'none', background_radius: int = 50):
+                 composite_channels=None, background_subtract: str = 'none', background_radius: int = 50,
+                 despeckle: str = 'none', despeckle_threshold: int = 1000):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -161,6 +162,27 @@ class Stitcher:
             raise ValueError(f"background_radius must be an integer in 1..{native.SQ_TOPHAT_MAX_RADIUS}, got {background_radius!r}")
         self.background_subtract = background_subtract
         self.background_radius = int(background_radius)
+        # Extension: despeckle='hot' / 'both' replaces single-pixel outliers (hot pixels, cosmic hits; 'both': dead pixels too)
+        # of every staged tile plane on the device before anything else touches it (sq_despeckle_tiles): a pixel that differs
+        # from the median m of its edge-replicated 3 x 3 window by more than despeckle_threshold counts of the tile's own dtype
+        # ('hot': I - m > T, 'both': |I - m| > T) becomes m -- what filtering the files beforehand gives.  It runs right after
+        # the copy to the device, before the background removal and the flatfield divide; registration and the flatfield
+        # estimate keep reading raw tiles.  'none': nothing is launched, allocated or written.  A threshold without a mode is
+        # accepted and unused; one at or above the dtype's maximum could never fire and is refused once the dtype is known
+        # (_check_despeckle_dtype).
+        if despeckle not in ('none', 'hot', 'both'):
+            raise ValueError(f"despeckle must be 'none', 'hot' or 'both', got {despeckle!r}")
+        if isinstance(despeckle_threshold, bool) or not isinstance(despeckle_threshold, (int, np.integer)) or \
+                not 0 <= int(despeckle_threshold) <= native.SQ_DESPECKLE_MAX_THRESHOLD:
+            raise ValueError(f"despeckle_threshold must be an integer in 0..{native.SQ_DESPECKLE_MAX_THRESHOLD}, "
+                             f"got {despeckle_threshold!r}")
+        self.despeckle = despeckle
+        self.despeckle_threshold = int(despeckle_threshold)
+        # {channel name: staged pixels replaced / staged pixels filtered by this process}.  They count STAGED pixels: a tile
+        # that is staged for two row bands (or by two calls) counts twice.
+        self.despeckle_replaced: Dict[str, int] = {}
+        self.despeckle_staged: Dict[str, int] = {}
+        self._despeckle_pending = []     # (timepoint, region, device counts [num_c], staged pixels [num_c]) not read back yet
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -318,6 +340,7 @@ class Stitcher:
         first = self.acquisition_metadata[first_key]
         first_image = read_image(first['filepath'])
         self.dtype = first_image.dtype.type
+        self._check_despeckle_dtype()
         if first_image.ndim in (2, 3):
             self.input_height, self.input_width = first_image.shape[:2]
         else:
@@ -938,6 +961,11 @@ class Stitcher:
         print(f"Beginning stitching of {total_tiles} tiles for region {region} timepoint {timepoint}")
         if self.background_subtract == 'tophat':
             self._write_background_note(timepoint, region)
+        despeckle = self.despeckle != 'none'
+        despeckle_counts = despeckle_staged = None
+        if despeckle:
+            self._check_despeckle_dtype()
+            self._write_despeckle_note(timepoint, region)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1060,7 +1088,8 @@ class Stitcher:
                 staged_budget = budget - (0 if focus_scratch is None else focus_scratch.numel())
                 # the top-hat's scratch (the erosion of a batch: as many bytes as its tiles) counts against the budget too
                 tophat = self.background_subtract == 'tophat'
-                batch = max(1, min(len(plist), staged_budget // max(1, per_plane * (2 if tophat else 1))))
+                # and so does the despeckle's destination (one more copy of a batch's tiles)
+                batch = max(1, min(len(plist), staged_budget // max(1, per_plane * (1 + int(despeckle) + int(tophat)))))
                 if writer is not None:
                     batch = min(batch, writer.batch)
                 chunks = [plist[b0:b0 + batch] for b0 in range(0, len(plist), batch)]
@@ -1086,7 +1115,25 @@ class Stitcher:
                         tophat_scratch = torch.empty(native.tophat_scratch_bytes(batch * n, th, tw, self.dtype), dtype=torch.uint8,
                                                      device=self.device)
                         self._keep_buffers(tkey, tophat_scratch)
+                clean = None
+                if despeckle:
+                    # ONE destination for both ingest slots: despeckle, top-hat and the fusion that reads `clean` are launches
+                    # of one stream, so the next chunk's despeckle (which overwrites it) runs after this chunk's fusion has
+                    # read it; only the H2D copy into the OTHER slot's raw tiles overlaps, and nothing reads those but the
+                    # despeckle of their own chunk
+                    ckey = ('despeckle', batch, n, th, tw, np.dtype(self.dtype).str)
+                    clean = self._buffer_cache.get(ckey)
+                    if clean is None:
+                        clean = torch.empty((batch, n, th, tw), dtype=tdtype, device=self.device)
+                        self._keep_buffers(ckey, clean)
+                    if despeckle_counts is None:
+                        despeckle_counts = torch.zeros(self.num_c, dtype=torch.int64, device=self.device)
+                        despeckle_staged = [0] * self.num_c
+                    # the kernel's per-plane counts of this list's planes (plane of plist, tile): every chunk adds into its own
+                    # run of it, and it is folded per channel once, behind the last chunk
+                    list_counts = torch.zeros((len(plist), n), dtype=torch.int64, device=self.device)
                 for k, chunk in enumerate(chunks):
+                    b0 = k * batch      # the chunk is plist[b0:b0 + m]
                     slot = turn[0] % n_slots      # (the turn goes on across calls: the next region starts on the other slot)
                     turn[0] += 1
                     if done[slot] is not None:
@@ -1114,6 +1161,9 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
+                    if despeckle:   # out of place: everything below reads the filtered planes in `clean`
+                        tiles = native.despeckle_tiles(tiles, self.despeckle_threshold, self.despeckle, out=clean[:m],
+                                                       counts=list_counts[b0:b0 + m].view(-1))
                     if tophat:      # in place on the staged tiles: everything below reads the filtered planes
                         native.tophat_tiles(tiles, self.background_radius, tophat_scratch)
                     flats = [flats_dev.get(p // self.num_z) for p in chunk] if self.apply_flatfield else None
@@ -1154,6 +1204,13 @@ class Stitcher:
                                                None if flats is None else flats[pi:pi + 1])
                     done[slot] = torch.cuda.Event()
                     done[slot].record()
+                if despeckle:      # folded per channel on the device: nothing is read back here
+                    of_channel: Dict[int, List[int]] = {}
+                    for pi, p in enumerate(plist):
+                        of_channel.setdefault(p // self.num_z, []).append(pi)
+                    for c, pis in of_channel.items():      # (consecutive: plist is in ascending plane order)
+                        despeckle_counts[c] += list_counts[pis[0]:pis[-1] + 1].sum()
+                        despeckle_staged[c] += len(pis) * n * th * tw
         finally:
             stream_ctx.__exit__(None, None, None)
             if side is not None and project_to is not None:
@@ -1161,8 +1218,11 @@ class Stitcher:
             pool.shutdown(wait=True)
             if writer is not None and not self._defer_drain:
                 writer.drain()      # everything of this region is on disk when the call returns (run() defers it to its end)
+        if despeckle_counts is not None:
+            self._despeckle_pending.append((timepoint, region, despeckle_counts, despeckle_staged))
         if not (writer is not None and self._defer_drain):      # (run(): the writer's events order everything; it is drained at the end)
             torch.cuda.synchronize(self.device)
+            self._finish_despeckle()
         print(f"Time to stitch region {region} timepoint {timepoint}: {time.time() - start_time}")
         return flat_canvas, plane_ids
 
@@ -1178,6 +1238,46 @@ class Stitcher:
         with open(tmp, 'w') as fh:
             json.dump(note, fh, indent=1)
         os.replace(tmp, path)
+
+    def _check_despeckle_dtype(self) -> None:
+        """A threshold at or above the dtype's maximum can never fire (the default on uint8 data): a message, not a silent
+        no-op."""
+        if self.despeckle != 'none' and self.despeckle_threshold >= int(np.iinfo(self.dtype).max):
+            raise ValueError(f"despeckle_threshold {self.despeckle_threshold} can never fire on {np.dtype(self.dtype).name} tiles "
+                             f"(maximum {int(np.iinfo(self.dtype).max)}): give a threshold in counts of the tiles' own dtype")
+
+    def _write_despeckle_note(self, timepoint, region) -> None:
+        """``<t>_stitched/<region>_stitched_despeckle.json``: what was replaced in the tiles of every store of this region --
+        the static facts only (the same bytes from every rank and call, put in place atomically); the counts are in
+        ``despeckle_replaced``."""
+        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"{region}_stitched_despeckle.json")
+        note = {'mode': self.despeckle, 'threshold': self.despeckle_threshold, 'window': 3,
+                'applies_to': 'every staged tile plane, before background removal and the flatfield divide'}
+        tmp = f"{path}.{os.getpid()}.tmp"
+        with open(tmp, 'w') as fh:
+            json.dump(note, fh, indent=1)
+        os.replace(tmp, path)
+
+    def _finish_despeckle(self) -> None:
+        """Read the pending per-channel counts back (the device has been synchronised: stitch_planes' own synchronise, or the
+        writer's final drain in run()), add them to ``despeckle_replaced`` / ``despeckle_staged`` and print them."""
+        pending, self._despeckle_pending = self._despeckle_pending, []
+        regions: Dict[tuple, list] = {}      # one line per (timepoint, region), whatever number of calls fused it
+        for timepoint, region, counts, staged in pending:
+            entry = regions.setdefault((timepoint, region), [np.zeros(self.num_c, np.int64), np.zeros(self.num_c, np.int64)])
+            entry[0] += counts.cpu().numpy()
+            entry[1] += np.asarray(staged, dtype=np.int64)
+        for (timepoint, region), (host, staged) in regions.items():
+            parts = []
+            for c, name in enumerate(self.monochrome_channels):
+                if staged[c]:
+                    self.despeckle_replaced[name] = self.despeckle_replaced.get(name, 0) + int(host[c])
+                    self.despeckle_staged[name] = self.despeckle_staged.get(name, 0) + int(staged[c])
+                    parts.append(f"{name}: {int(host[c])} of {int(staged[c])}")
+            print(f"[despeckle] region {region} timepoint {timepoint}: staged pixels replaced ({self.despeckle}, threshold "
+                  f"{self.despeckle_threshold}) -- " + ", ".join(parts))
 
     # ------------------------------------------------------------------ output
     # ------------------------------------------------------------------ contrast windows
@@ -1806,6 +1906,10 @@ class Stitcher:
         finally:
             self._defer_drain = False
             self._close_stream_writer()
+        if self._despeckle_pending:      # the writer has been drained: every region's fusion (and its despeckle) has finished
+            import torch
+            torch.cuda.synchronize(self.device)
+            self._finish_despeckle()
         self._finish_contrast(wait=True)
         self._finish_composites(wait=True)
         sharding.barrier()

@@ -5,7 +5,8 @@ plus eighteen switches for what this build adds (``--fusion-mode``, ``--normaliz
 ``--global-registration``, ``--z-projection``, ``--focus-radius``, ``--pyramid-method``, ``--contrast-limits``,
 ``--contrast-percentiles``, ``--focus-guide-channel``, ``--focus-depth-map``, ``--composite``, ``--composite-max-side``,
 ``--composite-z``, ``--composite-channels``).  Two more select the background removal of the staged tiles:
-``--background-subtract`` and ``--background-radius``.
+``--background-subtract`` and ``--background-radius``.  ``--despeckle`` and ``--despeckle-threshold`` select the hot-pixel
+removal that runs on the staged tiles before it.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -102,6 +103,19 @@ FLAGS = (
     (('--background-radius',), dict(type=int, default=50, metavar='R',
                                     help="with --background-subtract tophat: radius of the window, 1..127 (larger than the "
                                          "structures to keep, smaller than the background's variation)")),
+    (('--despeckle',), dict(choices=['none', 'hot', 'both'], default='none',
+                            help="replace single-pixel outliers of every tile on the device before anything else touches it "
+                                 "(background removal, flatfield divide, projection, fusion): a pixel that differs from the "
+                                 "median of its 3 x 3 window (edges replicated) by more than --despeckle-threshold becomes "
+                                 "that median; hot = pixels above the median only (hot pixels, cosmic hits), both = below it "
+                                 "too (dead pixels).  Registration and the flatfield estimate keep reading raw tiles; writes "
+                                 "<region>_stitched_despeckle.json and prints the number of staged pixels replaced, one line per "
+                                 "region (one per call where a region is fused in several row-band calls; a tile staged for "
+                                 "two bands counts twice)")),
+    (('--despeckle-threshold',), dict(type=int, default=1000, metavar='T',
+                                      help="with --despeckle hot / both: the difference to the median, in counts of the tiles' "
+                                           "own dtype, above which a pixel is replaced, 0..65535 (it must lie below the dtype's "
+                                           "maximum: give one for uint8 tiles)")),
 )
 
 
@@ -168,7 +182,9 @@ def main(argv=None):
                             composite_z=args.composite_z,
                             composite_channels=args.composite_channels,
                             background_subtract=args.background_subtract,
-                            background_radius=args.background_radius)
+                            background_radius=args.background_radius,
+                            despeckle=args.despeckle,
+                            despeckle_threshold=args.despeckle_threshold)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -396,6 +396,30 @@ int sq_tophat_tiles(void *tiles_dev, int32_t n_images, int32_t h, int32_t w, int
                     int32_t dtype, int32_t radius, void *scratch_dev, int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hot-pixel removal (--despeckle; extension: the reference has none).  A thresholded 3 x 3 median per plane I [h, w]
+ * (SQ_U8 / SQ_U16), OUT OF PLACE, with T = threshold in counts of the plane's own dtype:
+ *     m(y, x) = the median (5th smallest) of the nine values I(clamp(y + dy, 0, h - 1), clamp(x + dx, 0, w - 1)), dy, dx in {-1, 0, 1}
+ *     SQ_DESPECKLE_HOT :  out(y, x) = m(y, x) if I(y, x) - m(y, x) >  T   else I(y, x)
+ *     SQ_DESPECKLE_BOTH:  out(y, x) = m(y, x) if |I(y, x) - m(y, x)| > T  else I(y, x)
+ * The differences are taken in a wider signed type; every m comes from the unfiltered plane (the filter is not recursive); the
+ * edges are replicated, so the window has nine values at every pixel, also for h = 1 or w = 1.  SQ_DESPECKLE_BOTH with T = 0 is
+ * the plain 3 x 3 median.  The definition is the numpy restatement in tests/despeckle_ref.py.  n_images planes, the planes a
+ * plane stride and the rows a pitch apart (elements, pitch >= w), src and dst each with their own; no alignment asked of a base
+ * or a pitch beyond the element's own; any h, w >= 1.  src is read once and dst written once (csrc/despeckle.hip); the columns
+ * between w and dst_pitch stay as they are.  counts_dev (optional, [n_images] uint64, 8-byte aligned): the number of pixels
+ * replaced in plane i is ADDED to counts_dev[i] (strict >, so replaced <=> changed), by at most one integer atomic add per
+ * workgroup.  Integers only, no scratch, no allocation; deterministic.  SQ_ERR_INVALID, and nothing is launched, for an unknown
+ * mode or dtype, a threshold outside 0..65535, a pitch below w, a NULL or misaligned pointer, and src and dst extents (first to
+ * last element of all planes) that overlap.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_DESPECKLE_HOT  1
+#define SQ_DESPECKLE_BOTH 2
+int sq_despeckle_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h, int32_t w,
+                       int64_t src_plane_stride, int64_t src_pitch, int64_t dst_plane_stride, int64_t dst_pitch,
+                       int32_t dtype, int32_t mode, int32_t threshold, uint64_t *counts_dev /* [n_images], added to; may be NULL */,
+                       void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
