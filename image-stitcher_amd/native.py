@@ -148,6 +148,7 @@ EXPORTS = {
                                   C.c_void_p, C.c_int64, C.c_void_p]),
     'sq_despeckle_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                      C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'sq_tile_stats': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1272,6 +1273,39 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
                                     sq_dtype_of(np_dtype_of_torch(tiles.dtype)), DESPECKLE_MODES[mode], int(threshold),
                                     None if counts is None else counts.data_ptr(), _stream_ptr(stream)),
            'sq_despeckle_tiles')
+    return out
+
+
+SQ_TILE_STATS_WORDS = 8
+SQ_TILE_STATS_ROWS_PER_THREAD = 64      # rows one thread of the kernel walks down (include/squidstitch.h): the tests' sizes
+
+
+def tile_stats(tiles, out=None, stream=None):
+    """The eight quality words of every H x W plane of ``tiles`` (sq_tile_stats; an extension, the reference has none): min,
+    max, sum, sum of squares, pixels at the dtype's maximum, pixels at 0 and the Brenner sums with step 2 along x and along y
+    -- ``tests/tile_qc_ref.tile_words``; ``tileqc.derive`` makes mean, std, focus and the saturated fraction of them.
+
+    tiles: uint8 / uint16 device tensor [n, H, W] or [b, n, H, W] with unit-stride rows (any row pitch, any base offset) whose
+           leading dimensions collapse to one plane stride (at least a plane); anything else raises ValueError.
+    out:   int64 device tensor [planes, 8]; its words are overwritten.  Allocated when None.
+    Returns ``out``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() not in (3, 4):
+        raise ValueError("tiles must be a [n, H, W] or [b, n, H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    n_images, h, w, plane_stride, pitch = _plane_layout(tiles, 'tiles')
+    if out is None:
+        out = torch.empty((n_images, SQ_TILE_STATS_WORDS), dtype=torch.int64, device=tiles.device)
+        if stream is not None:
+            out.record_stream(stream)
+    elif not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != tiles.device or \
+            tuple(out.shape) != (n_images, SQ_TILE_STATS_WORDS) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int64 tensor of shape ({n_images}, {SQ_TILE_STATS_WORDS}) on the tiles' device")
+    if n_images == 0:
+        return out
+    _check(lib().sq_tile_stats(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
+                               out.data_ptr(), _stream_ptr(stream)), 'sq_tile_stats')
     return out
 
 

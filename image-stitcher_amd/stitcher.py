@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import alignment, composite as composite_mod, native, placement, registration, sharding
+from . import alignment, composite as composite_mod, native, placement, registration, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -73,7 +73,8 @@ class Stitcher:
                  contrast_percentiles=(0.1, 99.9), focus_guide_channel: Optional[str] = None, focus_depth_map: bool = False,
                  composite: bool = False, composite_max_side: int = 4096, composite_z: Optional[int] = None,
                  composite_channels=None, background_subtract: str = 'none', background_radius: int = 50,
-                 despeckle: str = 'none', despeckle_threshold: int = 1000):
+                 despeckle: str = 'none', despeckle_threshold: int = 1000, tile_qc: bool = False,
+                 tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -183,6 +184,18 @@ class Stitcher:
         self.despeckle_replaced: Dict[str, int] = {}
         self.despeckle_staged: Dict[str, int] = {}
         self._despeckle_pending = []     # (timepoint, region, device counts [num_c], staged pixels [num_c]) not read back yet
+        # Extension: tile_qc=True reports on every tile plane as it is in its file: the eight words of sq_tile_stats (min, max,
+        # sum, sum of squares, pixels at the dtype's maximum and at 0, the Brenner sums along x and y) of every staged plane,
+        # taken right after the copy to the device and before the despeckle, and what tileqc.py derives of them (mean, std,
+        # focus, best z, the flags 'saturated' above tile_qc_saturation of the pixels, 'constant', 'low_focus' below
+        # tile_qc_focus_ratio of the plane's median focus) as <region>_stitched_tile_qc.csv / .json.  It changes no pixel of
+        # any output.  False: nothing is launched, allocated, written or synchronised; the two values are accepted and unused.
+        self.tile_qc, self.tile_qc_saturation, self.tile_qc_focus_ratio = \
+            tileqc.check_options(tile_qc, tile_qc_saturation, tile_qc_focus_ratio)
+        self.tile_qc_table: Dict[tuple, List[dict]] = {}      # (timepoint, region) -> the rows of its CSV
+        self._tile_qc_words: Dict[tuple, Dict[tuple, tuple]] = {}      # (timepoint, region) -> {(plane, fov): the eight words}
+        self._tile_qc_pending = []       # (timepoint, region, device words [planes, tiles, 8], [(plane, fov)]) not read back yet
+        self._tile_qc_shared = False     # the ranks share this region: the words are combined before anything is written
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -985,7 +998,7 @@ class Stitcher:
                            for i, color in enumerate('RGB')]
             for p, rgb in targets:
                 if p in slot_of:
-                    planes.setdefault(p, []).append((info, rgb, rect))
+                    planes.setdefault(p, []).append((info, rgb, rect, fov))
 
         mode = native.SQ_FUSE_OVERWRITE if self.fusion_mode == 'overwrite' else native.SQ_FUSE_FEATHER
         # planes no file touches still have to come out as zeros
@@ -1132,6 +1145,12 @@ class Stitcher:
                     # the kernel's per-plane counts of this list's planes (plane of plist, tile): every chunk adds into its own
                     # run of it, and it is folded per channel once, behind the last chunk
                     list_counts = torch.zeros((len(plist), n), dtype=torch.int64, device=self.device)
+                qc_words = None
+                if self.tile_qc:
+                    # the words of this list's staged planes (plane of plist, tile): every chunk's launch overwrites its own run
+                    # of them; they are read back with the despeckle counts, behind the call's synchronise
+                    qc_words = torch.empty((len(plist), n, native.SQ_TILE_STATS_WORDS), dtype=torch.int64, device=self.device)
+                    self._tile_qc_pending.append((timepoint, region, qc_words, [(p, it[3]) for p in plist for it in planes[p]]))
                 for k, chunk in enumerate(chunks):
                     b0 = k * batch      # the chunk is plist[b0:b0 + m]
                     slot = turn[0] % n_slots      # (the turn goes on across calls: the next region starts on the other slot)
@@ -1141,7 +1160,7 @@ class Stitcher:
                     host = staging[slot].numpy()
 
                     def load(job, host=host):
-                        pi, ti, (info, rgb, _) = job
+                        pi, ti, (info, rgb, _, _) = job
                         if rgb < 0 and read_image_into(info['filepath'], host[pi, ti]):
                             return      # file -> page-locked staging in one read
                         img = read_image(info['filepath'])
@@ -1161,6 +1180,8 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
+                    if qc_words is not None:      # the tiles as they are in their files: before anything filters them
+                        native.tile_stats(tiles, out=qc_words[b0:b0 + m].view(-1, native.SQ_TILE_STATS_WORDS))
                     if despeckle:   # out of place: everything below reads the filtered planes in `clean`
                         tiles = native.despeckle_tiles(tiles, self.despeckle_threshold, self.despeckle, out=clean[:m],
                                                        counts=list_counts[b0:b0 + m].view(-1))
@@ -1223,6 +1244,7 @@ class Stitcher:
         if not (writer is not None and self._defer_drain):      # (run(): the writer's events order everything; it is drained at the end)
             torch.cuda.synchronize(self.device)
             self._finish_despeckle()
+            self._finish_tile_qc()
         print(f"Time to stitch region {region} timepoint {timepoint}: {time.time() - start_time}")
         return flat_canvas, plane_ids
 
@@ -1278,6 +1300,71 @@ class Stitcher:
                     parts.append(f"{name}: {int(host[c])} of {int(staged[c])}")
             print(f"[despeckle] region {region} timepoint {timepoint}: staged pixels replaced ({self.despeckle}, threshold "
                   f"{self.despeckle_threshold}) -- " + ", ".join(parts))
+
+    # ------------------------------------------------------------------ tile quality report
+    def _finish_tile_qc(self) -> None:
+        """Read the pending words back (the device has been synchronised, as for _finish_despeckle), keep them per (timepoint,
+        region) -- a tile staged more than once (row bands, several calls) gives the same words and is kept once -- and write
+        the report of every region that got new words, from all the words it has so far.  A region the ranks share is written
+        by _finish_tile_qc_shared instead."""
+        pending, self._tile_qc_pending = self._tile_qc_pending, []
+        touched = []
+        for timepoint, region, words, keys in pending:
+            host = words.cpu().numpy().reshape(-1, native.SQ_TILE_STATS_WORDS)
+            have = self._tile_qc_words.setdefault((int(timepoint), region), {})
+            for key, row in zip(keys, host):
+                row = tuple(int(v) for v in row)
+                if have.setdefault(key, row) != row:
+                    raise RuntimeError(f"tile-qc: plane {key[0]}, fov {key[1]} of region {region} was staged twice with different words")
+            if (int(timepoint), region) not in touched:
+                touched.append((int(timepoint), region))
+        if not self._tile_qc_shared:
+            for timepoint, region in touched:
+                self._write_tile_qc(timepoint, region)
+
+    def _write_tile_qc(self, timepoint, region) -> None:
+        """The rows of (timepoint, region) from its words, sorted by (output channel, z, fov), into tile_qc_table and the two
+        files under <t>_stitched/; one printed line with the flag counts."""
+        words = self._tile_qc_words.get((int(timepoint), region), {})
+        th, tw = self.input_height, self.input_width
+        rows = [tileqc.make_row(region, fov, p % self.num_z, self.monochrome_channels[p // self.num_z], words[(p, fov)], th, tw)
+                for p, fov in sorted(words)]
+        tileqc.flag_rows(rows, self.tile_qc_saturation, self.tile_qc_focus_ratio)
+        self.tile_qc_table[(int(timepoint), region)] = rows
+        note = tileqc.write_report(os.path.join(self.output_folder, f"{timepoint}_stitched"), region, rows,
+                                   self.monochrome_channels, self.tile_qc_saturation, self.tile_qc_focus_ratio)
+        print(f"[tile-qc] region {region} timepoint {timepoint}: {len(rows)} tile planes -- " +
+              ", ".join(f"{k}: {v}" for k, v in note['flag_counts'].items()))
+
+    def _finish_tile_qc_shared(self, timepoint, region, rank) -> None:
+        """A region the ranks share by planes or bands: every rank's words go into the region's dense table [num_c * num_z,
+        n_fov, 9] -- the eight words and a 'present' word, the min as dtype_max - min, absent entries all zero -- which is
+        combined with ONE element-wise MAX all-reduce (an entry is absent or identical on every rank that has it, so MAX is
+        exact); rank 0 writes the files."""
+        import torch
+        import torch.distributed as dist
+        torch.cuda.synchronize(self.device)
+        self._finish_tile_qc()
+        top = int(np.iinfo(self.dtype).max)
+        dense = np.zeros((self.num_c * self.num_z, self.num_fovs_per_region, native.SQ_TILE_STATS_WORDS + 1), dtype=np.int64)
+        for (p, fov), w in self._tile_qc_words.get((int(timepoint), region), {}).items():
+            dense[p, fov, :native.SQ_TILE_STATS_WORDS] = w
+            dense[p, fov, 0] = top - w[0]
+            dense[p, fov, native.SQ_TILE_STATS_WORDS] = 1
+        table = torch.from_numpy(dense)
+        coll = sharding.collective_device(self)
+        if coll is not None:
+            table = table.to(coll)
+        dist.all_reduce(table, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            dense = table.cpu().numpy()
+            words = {}
+            for p, fov in zip(*np.nonzero(dense[:, :, native.SQ_TILE_STATS_WORDS])):
+                w = [int(v) for v in dense[p, fov, :native.SQ_TILE_STATS_WORDS]]
+                w[0] = top - w[0]
+                words[(int(p), int(fov))] = tuple(w)
+            self._tile_qc_words[(int(timepoint), region)] = words
+            self._write_tile_qc(timepoint, region)
 
     # ------------------------------------------------------------------ output
     # ------------------------------------------------------------------ contrast windows
@@ -1681,6 +1768,7 @@ class Stitcher:
         units = sharding.plane_band_units(n_planes, bands, rank, world)
         print(f"\nProcessing timepoint {timepoint}, region {region}: (plane, band) units {units} (rank {rank}/{world})")
         stack = self.z_projection not in ('max-only', 'focus-only')
+        self._tile_qc_shared = self.tile_qc
         if rank == 0:
             if stack:
                 self.create_region_store(timepoint, region)
@@ -1713,6 +1801,11 @@ class Stitcher:
         # ... and the counts are summed over the ranks (one that was dealt no unit adds zeros), rank 0 writes the windows
         self._write_contrast(self._zarr_path(timepoint, region), stack_hist, shared=True)
         self._write_contrast(self._mip_path(timepoint, region, self._projection_kind() or 'mip'), proj_hist, shared=True)
+        if self.tile_qc:
+            try:
+                self._finish_tile_qc_shared(timepoint, region, rank)
+            finally:
+                self._tile_qc_shared = False
         sharding.barrier()
         return output_path
 
@@ -1906,10 +1999,11 @@ class Stitcher:
         finally:
             self._defer_drain = False
             self._close_stream_writer()
-        if self._despeckle_pending:      # the writer has been drained: every region's fusion (and its despeckle) has finished
+        if self._despeckle_pending or self._tile_qc_pending:      # the writer has been drained: every region's launches have finished
             import torch
             torch.cuda.synchronize(self.device)
             self._finish_despeckle()
+            self._finish_tile_qc()
         self._finish_contrast(wait=True)
         self._finish_composites(wait=True)
         sharding.barrier()

@@ -6,7 +6,8 @@ plus eighteen switches for what this build adds (``--fusion-mode``, ``--normaliz
 ``--contrast-percentiles``, ``--focus-guide-channel``, ``--focus-depth-map``, ``--composite``, ``--composite-max-side``,
 ``--composite-z``, ``--composite-channels``).  Two more select the background removal of the staged tiles:
 ``--background-subtract`` and ``--background-radius``.  ``--despeckle`` and ``--despeckle-threshold`` select the hot-pixel
-removal that runs on the staged tiles before it.
+removal that runs on the staged tiles before it.  ``--tile-qc``, ``--tile-qc-saturation`` and ``--tile-qc-focus-ratio`` select
+the per-tile quality report (focus, saturation, intensity) of the tiles as they are in their files.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -116,6 +117,18 @@ FLAGS = (
                                       help="with --despeckle hot / both: the difference to the median, in counts of the tiles' "
                                            "own dtype, above which a pixel is replaced, 0..65535 (it must lie below the dtype's "
                                            "maximum: give one for uint8 tiles)")),
+    (('--tile-qc',), dict(action='store_true',
+                          help="report on every tile plane as it is in its file, from the bytes staged on the device (no pixel of "
+                               "any output changes): <region>_stitched_tile_qc.csv with min, max, mean, std, saturated and zero "
+                               "pixels, the Brenner focus sums, an exposure-independent focus score, the best z of every (fov, "
+                               "channel) and the flags saturated / constant / low_focus, a summary in "
+                               "<region>_stitched_tile_qc.json, and one printed line per region")),
+    (('--tile-qc-saturation',), dict(type=float, default=0.01, metavar='F',
+                                     help="with --tile-qc: a tile plane is flagged saturated when more than this fraction of its "
+                                          "pixels is at the dtype's maximum, 0..1")),
+    (('--tile-qc-focus-ratio',), dict(type=float, default=0.5, metavar='F',
+                                      help="with --tile-qc: a tile plane is flagged low_focus when its focus score is below this "
+                                           "fraction of the median over the tiles of its (channel, z) plane, 0..1")),
 )
 
 
@@ -184,7 +197,10 @@ def main(argv=None):
                             background_subtract=args.background_subtract,
                             background_radius=args.background_radius,
                             despeckle=args.despeckle,
-                            despeckle_threshold=args.despeckle_threshold)
+                            despeckle_threshold=args.despeckle_threshold,
+                            tile_qc=args.tile_qc,
+                            tile_qc_saturation=args.tile_qc_saturation,
+                            tile_qc_focus_ratio=args.tile_qc_focus_ratio)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

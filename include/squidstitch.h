@@ -420,6 +420,30 @@ int sq_despeckle_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-tile quality words (--tile-qc; extension: the reference has none).  For each of n_images planes I [h, w] (SQ_U8 / SQ_U16),
+ * the planes a plane stride and the rows a pitch apart (elements, pitch >= w; no alignment asked of the base or the pitch
+ * beyond the element's own -- the conventions of sq_despeckle_tiles), SQ_TILE_STATS_WORDS = 8 uint64 are written to
+ * out_dev[n_images][8] (8-byte aligned).  The words are OVERWRITTEN, not added to:
+ *     0  min I                4  number of pixels equal to the dtype's maximum (255 / 65535)
+ *     1  max I                5  number of pixels equal to 0
+ *     2  S = sum I            6  Bx = sum over y, x < w - 2 of (I(y, x + 2) - I(y, x))^2      (0 when w <= 2)
+ *     3  Q = sum I^2          7  By = sum over y < h - 2, x of (I(y + 2, x) - I(y, x))^2      (0 when h <= 2)
+ * Bx and By are the Brenner focus measure with step 2, one per direction.  The definition is the numpy restatement in
+ * tests/tile_qc_ref.py.  Integers only: every pixel product fits 32 bits and is accumulated in 64; the result is bit for bit
+ * numpy's int64 sums whatever the schedule (per-workgroup partial sums, then one integer atomic min / max / add per word per
+ * workgroup, on words the call itself sets to their identities on `stream` first).  The planes are read once, plus two halo
+ * rows per run of SQ_TILE_STATS_ROWS_PER_THREAD rows, and nothing else is stored (csrc/tilestats.hip); the columns between w
+ * and the pitch and the rows between h and the plane stride are never read into a sum.  No scratch, no allocation.
+ * SQ_ERR_UNSUPPORTED for h * w > 2^31 (or a side above 2^30), so that no word can wrap.  SQ_ERR_INVALID, and nothing is
+ * launched, for a NULL or misaligned pointer, a pitch below w, a plane stride smaller than a plane, n_images < 0, h or w < 1 and
+ * an unknown dtype.  n_images == 0 is SQ_OK.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_TILE_STATS_WORDS 8
+#define SQ_TILE_STATS_ROWS_PER_THREAD 64
+int sq_tile_stats(const void *src_dev, int32_t n_images, int32_t h, int32_t w, int64_t plane_stride, int64_t pitch,
+                  int32_t dtype, uint64_t *out_dev /* [n_images][SQ_TILE_STATS_WORDS], overwritten */, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched

@@ -1,0 +1,368 @@
+"""--tile-qc on the device: sq_tile_stats against the numpy definition (tests/tile_qc_ref.py) word for word, and whole runs whose
+CSV and JSON are the reference's table of the tile FILES.  Every comparison is equality."""
+import dataclasses
+import functools
+import hashlib
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+
+import tile_qc_ref as R
+from image_stitcher_amd import native, omezarr, stitcher_cli, synth, tiffio
+from image_stitcher_amd.ometiff import read_ome_tiff
+from image_stitcher_amd.stitcher import Stitcher
+from image_stitcher_amd.stitcher_parameters import StitchingParameters
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+
+# The kernel's own sizes: a thread owns one 16-byte vector of columns (8 uint16 / 16 uint8) and walks down RPT rows two at a
+# time; a workgroup is 64, 128 or 256 vectors wide and 4, 2 or 1 runs of RPT rows tall.  Widths around one and two vectors and
+# around the step of the x difference; heights around the step of the y difference, one run, and more than one run.
+RPT = native.SQ_TILE_STATS_ROWS_PER_THREAD
+WIDTHS = (1, 2, 3, 7, 8, 9, 15, 16, 17, 63, 64, 65, 255, 257)
+HEIGHTS = (1, 2, 3, RPT - 1, RPT, RPT + 1, RPT + 2, 2 * RPT + 1)
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.array(a)).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _planes(dtype, h, w, n=5):
+    """[n, H, W]: uniform random full-range values, all zero, all at the maximum, a checkerboard of 0 / maximum (the largest
+    Bx, By and Q), sparse extremes on a mid value; more planes are random."""
+    dt = np.dtype(dtype)
+    top = int(np.iinfo(dt).max)
+    rng = np.random.default_rng(h * 10007 + w * 31 + n)
+    out = rng.integers(0, top + 1, (n, h, w)).astype(dt)
+    if n >= 5:
+        out[1] = 0
+        out[2] = top
+        out[3] = ((np.indices((h, w)).sum(axis=0) % 2) * top).astype(dt)
+        pick = rng.integers(0, 4, (h, w))
+        out[4] = np.where(pick == 0, 0, np.where(pick == 1, top, top // 3)).astype(dt)
+    out.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(dtype, h, w, n=5):
+    ref = R.words_of(_planes(dtype, h, w, n))
+    ref.setflags(write=False)
+    return ref
+
+
+@pytest.mark.parametrize('dtype', ['uint8', 'uint16'])
+def test_kernel_equals_the_definition(dtype):
+    import torch
+    for h in HEIGHTS:
+        for w in WIDTHS:
+            planes = _dev(_planes(dtype, h, w))
+            out = torch.full((5, 8), -12345, dtype=torch.int64, device=DEV)      # garbage: the words are overwritten
+            got = native.tile_stats(planes, out=out)
+            assert got.data_ptr() == out.data_ptr()
+            np.testing.assert_array_equal(got.cpu().numpy(), _reference(dtype, h, w), err_msg=f'{h} x {w}')
+    fresh = native.tile_stats(_dev(_planes(dtype, 3, 17)))      # out allocated by the wrapper
+    assert fresh.dtype == torch.int64 and tuple(fresh.shape) == (5, 8)
+    np.testing.assert_array_equal(fresh.cpu().numpy(), _reference(dtype, 3, 17))
+
+
+@pytest.mark.parametrize('dtype', ['uint8', 'uint16'])
+@pytest.mark.parametrize('n', [1, 3, 37])
+def test_plane_counts(n, dtype):
+    for h, w in ((RPT + 1, 65), (3, 257), (2 * RPT + 1, 9)):
+        got = native.tile_stats(_dev(_planes(dtype, h, w, n)))
+        np.testing.assert_array_equal(got.cpu().numpy(), _reference(dtype, h, w, n), err_msg=f'{n} of {h} x {w}')
+
+
+@pytest.mark.parametrize('dtype', ['uint8', 'uint16'])
+def test_views_pitches_offsets_and_repeatability(dtype):
+    import torch
+    top = int(np.iinfo(np.dtype(dtype)).max)
+    for h, w in ((RPT + 2, 65), (3, 17), (5, 255)):
+        planes, want = _planes(dtype, h, w), _reference(dtype, h, w)
+        n = planes.size
+        # a base one element off: every row has another phase than a 16-byte vector
+        buf = torch.full((n + 8,), top, dtype=native.torch_dtype_of(np.dtype(dtype)), device=DEV)
+        buf[1:n + 1] = _dev(planes).reshape(-1)
+        odd = buf[1:n + 1].view(5, h, w)
+        assert (odd.data_ptr() // odd.element_size()) % 2 == 1
+        np.testing.assert_array_equal(native.tile_stats(odd).cpu().numpy(), want)
+        # pitch = w + 3, the padding columns poisoned with the dtype's maximum
+        wide = _dev(np.concatenate([planes, np.full((5, h, 3), top, planes.dtype)], axis=2))
+        np.testing.assert_array_equal(native.tile_stats(wide[:, :, :w]).cpu().numpy(), want)
+        # a plane stride larger than the plane, the padding rows poisoned
+        tall = _dev(np.concatenate([planes, np.full((5, 2, w), top, planes.dtype)], axis=1))
+        np.testing.assert_array_equal(native.tile_stats(tall[:, :h]).cpu().numpy(), want)
+        # both, and every other plane of the stack
+        both = _dev(np.pad(planes, ((0, 0), (0, 2), (0, 3)), constant_values=top))
+        np.testing.assert_array_equal(native.tile_stats(both[::2, :h, :w]).cpu().numpy(), want[::2])
+        # a [b, n, h, w] batch: contiguous, and a view whose leading dimensions collapse to one plane stride
+        six = _dev(np.concatenate([planes, planes[:1]]))
+        np.testing.assert_array_equal(native.tile_stats(six.view(2, 3, h, w)).cpu().numpy(), np.concatenate([want, want[:1]]))
+        np.testing.assert_array_equal(native.tile_stats(both.view(1, 5, h + 2, w + 3)[:, :, :h, :w]).cpu().numpy(), want)
+        # the same call twice: the same words
+        a, b = native.tile_stats(odd).cpu().numpy(), native.tile_stats(odd).cpu().numpy()
+        assert a.tobytes() == b.tobytes() == want.tobytes()
+
+
+def test_four_planes_of_2048_squared():
+    rng = np.random.default_rng(77)
+    planes = rng.integers(0, 65536, (4, 2048, 2048)).astype(np.uint16)
+    planes[1, 100:300, 200:900] = 65535
+    planes[2, ::2] = 0
+    planes[3] = ((np.indices((2048, 2048)).sum(axis=0) % 2) * 65535).astype(np.uint16)
+    got = native.tile_stats(_dev(planes)).cpu().numpy()
+    np.testing.assert_array_equal(got, R.words_of(planes))
+    assert got[3, 3] == 65535 ** 2 * 2048 * 1024 and got[3, 6] == 0 and got[3, 7] == 0
+
+
+def test_refusals():
+    import torch
+    t = _dev(_planes('uint16', 8, 8, 3))
+    out = torch.full((3, 8), 7, dtype=torch.int64, device=DEV)
+    with pytest.raises(ValueError):
+        native.tile_stats(t.to(torch.float32), out=out)                        # a float tensor
+    with pytest.raises(ValueError):
+        native.tile_stats(t.permute(0, 2, 1), out=out)                         # rows that are not contiguous
+    with pytest.raises(ValueError):
+        native.tile_stats(t[0], out=out)                                       # not [n, H, W] or [b, n, H, W]
+    with pytest.raises(ValueError):
+        native.tile_stats(t.view(1, 3, 8, 8).expand(2, 3, 8, 8), out=out)      # leading dimensions that do not collapse
+    with pytest.raises(ValueError):
+        native.tile_stats(t, out=out[:2])
+    with pytest.raises(ValueError):
+        native.tile_stats(t, out=out.to(torch.int32))
+    with pytest.raises(ValueError):
+        native.tile_stats(t, out=torch.zeros((3, 8), dtype=torch.int64))       # another device
+    with pytest.raises(ValueError):
+        native.tile_stats(t.cpu())
+    # the library itself refuses what the wrapper would let through
+    L = native.lib()
+
+    def call(src=t.data_ptr(), n=3, h=8, w=8, ps=64, pitch=8, dtype=native.SQ_U16, dst=out.data_ptr()):
+        return L.sq_tile_stats(src, n, h, w, ps, pitch, dtype, dst, None)
+
+    for bad in (dict(src=None), dict(dst=None), dict(pitch=7), dict(dtype=native.SQ_F32), dict(dtype=0), dict(n=-1), dict(h=0),
+                dict(w=0), dict(src=t.data_ptr() + 1), dict(dst=out.data_ptr() + 4), dict(ps=10)):
+        assert call(**bad) == -1, bad      # SQ_ERR_INVALID
+    # h * w > 2^31: refused on the arguments alone (no such buffer exists)
+    assert call(h=65536, w=32769, pitch=32769, ps=1 << 40) == -3      # SQ_ERR_UNSUPPORTED
+    assert call(n=0) == 0 and call(n=0, src=None, dst=None) == 0
+    torch.cuda.synchronize()
+    assert (out.cpu().numpy() == 7).all()      # nothing was launched
+    assert call() == 0
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(out.cpu().numpy(), _reference('uint16', 8, 8, 3))
+
+
+# ---------------------------------------------------------------------------------------------------- whole runs
+FIXTURE = synth.GridSpec(rows=3, cols=4, tile_h=64, tile_w=96, ov_y=8, ov_x=12, nz=3, channels=tuple(synth.DEFAULT_CHANNELS[:2]),
+                         seed=5, blank_fovs=(7,))
+RGB = synth.GridSpec(rows=2, cols=3, tile_h=64, tile_w=96, ov_y=8, ov_x=12, nz=2, dtype='uint8', seed=9,
+                     channels=('BF LED matrix full_RGB', synth.DEFAULT_CHANNELS[1]), rgb_channels=('BF LED matrix full_RGB',))
+DEFOCUSED, SATURATED = (5, 1, 0), (2, 2, 1)      # (fov, z, channel index) of the planted tiles
+
+
+def _spec(case):
+    return RGB if case == 'rgb' else dataclasses.replace(FIXTURE, dtype=case)
+
+
+def _tile_files(root):
+    """[(path, fov, z, channel name)] of the acquisition's timepoint 0, named as the stitcher names them."""
+    found = []
+    for name in sorted(os.listdir(os.path.join(root, '0'))):
+        if name.lower().endswith(('.tif', '.tiff')):
+            parts = name.split('_', 3)
+            channel = os.path.splitext(parts[3])[0].replace('_', ' ').replace('full ', 'full_')
+            found.append((os.path.join(root, '0', name), int(parts[1]), int(parts[2]), channel))
+    assert found
+    return found
+
+
+def _plant(root, spec):
+    """One tile rewritten as its own 3 x 3 box mean, another given 2 % pixels at the dtype's maximum (monochrome files)."""
+    top = int(np.iinfo(np.dtype(spec.dtype)).max)
+    done = 0
+    for path, fov, z, channel in _tile_files(root):
+        key = (fov, z, list(spec.channels).index(channel))
+        if key == DEFOCUSED:
+            tiffio.write_tiff(path, R.box3(tiffio.read_image(path)))
+            done += 1
+        elif key == SATURATED:
+            img = tiffio.read_image(path).copy()
+            img.reshape(-1)[::50] = top
+            tiffio.write_tiff(path, img)
+            done += 1
+    assert done == 2
+
+
+def _expected(root, saturation=0.01, focus_ratio=0.5):
+    """The reference's table of the FILES, and the output channel order."""
+    entries, outputs = [], {}
+    for path, fov, z, channel in _tile_files(root):
+        img = tiffio.read_image(path)
+        if img.ndim == 3 and img.shape[2] == 3:
+            base = channel.split('_')[0]
+            parts = [(f'{base}_{c}', img[:, :, i]) for i, c in enumerate('RGB')]
+        else:
+            parts = [(channel, img[0] if img.ndim == 3 else img)]
+        outputs[channel] = [name for name, _ in parts]
+        entries += [(fov, z, name, plane) for name, plane in parts]
+    order = [name for channel in sorted(outputs) for name in outputs[channel]]      # sorted file channels, an RGB file expanded
+    h, w = entries[0][3].shape
+    return R.table_of(entries, order, h, w, saturation, focus_ratio), order
+
+
+def _run(root, *extra):
+    random.seed(1234)
+    stitcher_cli.main(['-i', root, '--normalization', 'none', *extra])
+    base = os.path.dirname(root)
+    outs = [d for d in os.listdir(base) if d.startswith(os.path.basename(root) + '_stitched_')]
+    assert len(outs) == 1
+    return os.path.join(base, outs[0], '0_stitched')
+
+
+def _report(out):
+    with open(os.path.join(out, 'R0_stitched_tile_qc.csv')) as fh:
+        text = fh.read()
+    with open(os.path.join(out, 'R0_stitched_tile_qc.json')) as fh:
+        note = json.load(fh)
+    assert text.endswith('\n')
+    return text, [line.split(',') for line in text.splitlines()], note
+
+
+def _qc_files(folder):
+    return sorted(n for _, _, names in os.walk(folder) for n in names if '_tile_qc.' in n)
+
+
+def _check_json(note, rows, order, saturation=0.01, focus_ratio=0.5):
+    """The JSON agrees with the CSV."""
+    head, body = rows[0], rows[1:]
+    col = {k: i for i, k in enumerate(head)}
+    assert note['rows'] == len(body)
+    assert note['settings']['tile_qc_saturation'] == saturation and note['settings']['tile_qc_focus_ratio'] == focus_ratio
+    flagged = [dict(fov=int(r[col['fov']]), z_level=int(r[col['z_level']]), channel=r[col['channel']], flags=r[col['flags']])
+               for r in body if r[col['flags']]]
+    assert note['flagged'] == flagged
+    for f in ('saturated', 'constant', 'low_focus'):
+        assert note['flag_counts'][f] == sum(1 for r in body if f in r[col['flags']].split('|'))
+    assert list(note['median_focus']) == order == list(note['best_z_histogram'])
+    for name in order:
+        zs = sorted({int(r[col['z_level']]) for r in body if r[col['channel']] == name})
+        for z in zs:
+            focus = [float(r[col['focus']]) for r in body if r[col['channel']] == name and int(r[col['z_level']]) == z]
+            assert note['median_focus'][name][str(z)] == float(np.median(focus))
+        best = {int(r[col['fov']]): int(r[col['best_z']]) for r in body if r[col['channel']] == name}
+        assert note['best_z_histogram'][name] == {str(z): sum(1 for b in best.values() if b == z) for z in zs}
+
+
+@pytest.mark.parametrize('case', ['uint16', 'uint8', 'rgb'])
+def test_run_reports_the_files(tmp_path, case, capsys):
+    spec = _spec(case)
+    root = str(tmp_path / 'acq')
+    synth.write_acquisition(spec, root)
+    if case != 'rgb':
+        _plant(root, spec)
+    out = _run(root, '--tile-qc')
+    assert _qc_files(out) == ['R0_stitched_tile_qc.csv', 'R0_stitched_tile_qc.json']
+    text, rows, note = _report(out)
+    want, order = _expected(root)
+    assert rows == want                      # the integer columns are numpy on the files, floats and flags the reference's
+    _check_json(note, rows, order)
+    col = {k: i for i, k in enumerate(rows[0])}
+    flagged = {(int(r[col['fov']]), int(r[col['z_level']]), r[col['channel']]): r[col['flags']] for r in rows[1:] if r[col['flags']]}
+    if case == 'rgb':
+        assert len(rows) == 1 + 6 * 2 * 4 and order == ['BF LED matrix full_R', 'BF LED matrix full_G', 'BF LED matrix full_B',
+                                                        synth.DEFAULT_CHANNELS[1]]
+        assert flagged == {}
+    else:      # the planted tiles and the blank fov are exactly the flagged rows
+        names = list(spec.channels)
+        planted = {(7, z, ch): 'constant' for z in range(3) for ch in names}
+        planted[(DEFOCUSED[0], DEFOCUSED[1], names[DEFOCUSED[2]])] = 'low_focus'
+        planted[(SATURATED[0], SATURATED[1], names[SATURATED[2]])] = 'saturated'
+        assert flagged == planted and len(rows) == 1 + 72
+        assert 'constant: 6' in capsys.readouterr().out
+
+
+def test_run_with_filters_reports_the_raw_tiles(tmp_path):
+    """Despeckle, top-hat and the flatfield divide come after the report: the table is that of the plain run."""
+    roots = [str(tmp_path / k / 'acq') for k in ('plain', 'filtered')]
+    for r in roots:
+        synth.write_acquisition(FIXTURE, r)
+        _plant(r, FIXTURE)
+    a = _report(_run(roots[0], '--tile-qc', '--tile-qc-saturation', '0.005', '--tile-qc-focus-ratio', '0.6'))
+    b = _report(_run(roots[1], '--tile-qc', '--tile-qc-saturation', '0.005', '--tile-qc-focus-ratio', '0.6', '--despeckle', 'both',
+                     '--background-subtract', 'tophat', '--background-radius', '5', '-ff', '--z-projection', 'focus'))
+    assert a[0] == b[0] and a[2] == b[2]
+    want, order = _expected(roots[0], 0.005, 0.6)
+    assert a[1] == want
+    _check_json(a[2], a[1], order, 0.005, 0.6)
+
+
+def _hashes(out):
+    """{relative path: digest} of everything a run wrote but the report itself."""
+    found = {}
+    for folder, _, names in os.walk(out):
+        for name in names:
+            if '_tile_qc.' not in name:
+                with open(os.path.join(folder, name), 'rb') as fh:
+                    found[os.path.relpath(os.path.join(folder, name), out)] = hashlib.sha256(fh.read()).hexdigest()
+    return found
+
+
+@pytest.mark.parametrize('extra', [(), ('-f', '.ome.tiff'), ('--z-projection', 'focus-only')], ids=['zarr', 'tiff', 'focus-only'])
+def test_outputs_are_unchanged_and_default_writes_no_report(tmp_path, extra):
+    roots = [str(tmp_path / k / 'acq') for k in ('with', 'without')]
+    for r in roots:
+        synth.write_acquisition(FIXTURE, r)
+    with_qc, without = _run(roots[0], '--tile-qc', *extra), _run(roots[1], '--tile-qc-saturation', '0.3', *extra)
+    assert _qc_files(with_qc) == ['R0_stitched_tile_qc.csv', 'R0_stitched_tile_qc.json']
+    assert _qc_files(str(tmp_path / 'without')) == []
+    a, b = _hashes(with_qc), _hashes(without)
+    if extra[:1] == ('-f',):      # (the OME-XML names no file of the run; compared plane by plane as well)
+        for name in (n for n in os.listdir(without) if n.endswith('.ome.tiff')):
+            pa, xa = read_ome_tiff(os.path.join(with_qc, name))
+            pb, xb = read_ome_tiff(os.path.join(without, name))
+            assert xa == xb
+            np.testing.assert_array_equal(np.stack(pa), np.stack(pb))
+    assert a and a == b
+    assert _report(with_qc)[1] == _expected(roots[0])[0]
+
+
+def _prepared(root, **kw):
+    st = Stitcher(StitchingParameters(input_folder=root), normalization=None, **kw)
+    st.get_timepoints()
+    st.extract_acquisition_parameters()
+    st.get_pixel_size()
+    st.parse_acquisition_metadata()
+    return st
+
+
+def test_row_bands_list_every_tile_once(tmp_path):
+    """A row band stages whole tiles: the tiles both bands reach are staged twice, give the same words and are listed once."""
+    root = str(tmp_path / 'acq')
+    synth.write_acquisition(FIXTURE, root)
+    st = _prepared(root, tile_qc=True)
+    st.chunks = (1, 1, 1, 64, 64)      # bands are whole chunk rows
+    os.makedirs(os.path.join(st.output_folder, '0_stitched'), exist_ok=True)
+    _, height = st.calculate_output_dimensions(0, 'R0')
+    assert height > 128
+    st.create_region_store(0, 'R0')
+    for band in ((0, 128), (128, height)):
+        st.stream_region_to_zarr(0, 'R0', create=False, row_band=band)
+    rows = st.tile_qc_table[(0, 'R0')]
+    assert len(rows) == 72 == len({(r['fov'], r['z_level'], r['channel']) for r in rows})
+    want, _ = _expected(root)
+    assert _report(os.path.join(st.output_folder, '0_stitched'))[1] == want
+    assert not st._tile_qc_pending
+    # without the option nothing is kept, allocated or written
+    plain = _prepared(root)
+    plain.stitch_region(0, 'R0')
+    assert plain.tile_qc_table == {} and not plain._tile_qc_pending and plain._tile_qc_words == {}
+    assert _qc_files(plain.output_folder) == []
