@@ -183,8 +183,12 @@ __global__ __launch_bounds__(256) void s_linear_kernel(const Scalars *sc, const 
     s_lin[p] = sp + acc / eta;
 }
 
-// One workgroup: X <- C X C^T, shrink, X <- C^T X C.  X and C live in LDS (2 x 64 KB); every thread owns 16 outputs
-// of each of the four products and sums over k in ascending order.
+// One workgroup: X <- C X C^T, shrink, X <- C^T X C.  X and C live in LDS (64 + 64.5 KB); every thread owns 16 outputs
+// of each of the four products and sums over k in ascending order.  The rows of C are CS = 129 floats apart: the second
+// product reads C[c][k] with c running over the lanes, which at a stride of 128 floats puts all 32 lanes of a half-wave
+// on one bank (this kernel is most of a fit's time); the sums and their order are untouched.
+constexpr int CS = WS + 1;
+constexpr int DCT_LDS_BYTES = (NPIX + WS * CS) * 4;
 __global__ __launch_bounds__(1024) void s_dct_shrink_kernel(Scalars *sc, const float *cmat, const float *s_lin, float *s) {
     if (sc->converged) return;
     extern __shared__ float lds[];
@@ -193,7 +197,7 @@ __global__ __launch_bounds__(1024) void s_dct_shrink_kernel(Scalars *sc, const f
     const int tid = threadIdx.x;
     for (int e = tid; e < NPIX; e += 1024) {
         X[e] = s_lin[e];
-        C[e] = cmat[e];
+        C[(e >> 7) * CS + (e & 127)] = cmat[e];
     }
     __syncthreads();
     float out[16];
@@ -210,13 +214,13 @@ __global__ __launch_bounds__(1024) void s_dct_shrink_kernel(Scalars *sc, const f
         for (int q = 0; q < 16; ++q) X[tid + 1024 * q] = out[q];
         __syncthreads();
     };
-    product([&](int r_, int k) { return C[r_ * WS + k]; }, [&](int k, int c_) { return X[k * WS + c_]; });    // C X
-    product([&](int r_, int k) { return X[r_ * WS + k]; }, [&](int k, int c_) { return C[c_ * WS + k]; });    // (C X) C^T
+    product([&](int r_, int k) { return C[r_ * CS + k]; }, [&](int k, int c_) { return X[k * WS + c_]; });    // C X
+    product([&](int r_, int k) { return X[r_ * WS + k]; }, [&](int k, int c_) { return C[c_ * CS + k]; });    // (C X) C^T
     const float thr = sc->thr_s;
     for (int e = tid; e < NPIX; e += 1024) X[e] = shrinkf(X[e], thr);
     __syncthreads();
-    product([&](int r_, int k) { return C[k * WS + r_]; }, [&](int k, int c_) { return X[k * WS + c_]; });    // C^T X
-    product([&](int r_, int k) { return X[r_ * WS + k]; }, [&](int k, int c_) { return C[k * WS + c_]; });    // (C^T X) C
+    product([&](int r_, int k) { return C[k * CS + r_]; }, [&](int k, int c_) { return X[k * WS + c_]; });    // C^T X
+    product([&](int r_, int k) { return X[r_ * WS + k]; }, [&](int k, int c_) { return C[k * CS + c_]; });    // (C^T X) C
     double ds2 = 0.0, s2 = 0.0;
     for (int e = tid; e < NPIX; e += 1024) {
         const float nv = X[e], ov = s[e];
@@ -538,9 +542,9 @@ extern "C" int sq_basic_fit(const void *const *tile_ptrs_dev, const void *tile_b
     const float init_mu = (float)(MU_COEF / spectral);
     hipLaunchKernelGGL(fill_kernel, dim3(256), dim3(256), 0, s, F(L.wt), (int64_t)n * NPIX, 1.0f);
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(s_dct_shrink_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * NPIX * 4) != hipSuccess)
+                            DCT_LDS_BYTES) != hipSuccess)
         return fail(SQ_ERR_HIP, "sq_basic_fit: cannot raise the LDS limit");
-    int reweights = 0, total_iterations = 0;
+    int reweights = 0, total_iterations = 0, capped_rounds = 0;
     Scalars host{};
     for (int rw = 0; rw < MAX_REWEIGHT; ++rw) {
         hipLaunchKernelGGL(median_kernel, dim3(NPIX / 256), dim3(256), 0, s, F(L.im), n, F(L.s));
@@ -548,7 +552,7 @@ extern "C" int sq_basic_fit(const void *const *tile_ptrs_dev, const void *tile_b
         for (int it = 0; it < MAX_ITER; ++it) {
             hipLaunchKernelGGL(iter_begin_kernel, dim3(1), dim3(1), 0, s, sc, F(L.b), n);
             hipLaunchKernelGGL(s_linear_kernel, dim3(NPIX / 256), dim3(256), 0, s, sc, F(L.im), F(L.r), F(L.y), F(L.b), n, F(L.s), F(L.s_lin));
-            hipLaunchKernelGGL(s_dct_shrink_kernel, dim3(1), dim3(1024), 2 * NPIX * 4, s, sc, F(L.cmat), F(L.s_lin), F(L.s));
+            hipLaunchKernelGGL(s_dct_shrink_kernel, dim3(1), dim3(1024), DCT_LDS_BYTES, s, sc, F(L.cmat), F(L.s_lin), F(L.s));
             hipLaunchKernelGGL(residual_kernel, dim3(n), dim3(256), 0, s, sc, F(L.im), F(L.r), F(L.y), F(L.wt), F(L.s), F(L.b));
             hipLaunchKernelGGL(multiplier_kernel, dim3(n), dim3(256), 0, s, sc, F(L.im), F(L.r), F(L.y), F(L.s), F(L.b));
             hipLaunchKernelGGL(step_kernel, dim3(1), dim3(1), 0, s, sc);
@@ -559,6 +563,7 @@ extern "C" int sq_basic_fit(const void *const *tile_ptrs_dev, const void *tile_b
             }
         }
         total_iterations += host.iterations;
+        if (host.iterations >= MAX_ITER) ++capped_rounds;   // the solve stopped at the cap, settled or not
         ++reweights;
         hipLaunchKernelGGL(reweight_s_kernel, dim3(1), dim3(1024), 0, s, sc, F(L.s), F(L.b), n, F(L.last), rw > 0 ? 1 : 0);
         hipLaunchKernelGGL(reweight_w_kernel, dim3(n), dim3(256), 0, s, sc, F(L.r), F(L.s), F(L.b), F(L.wt));
@@ -568,14 +573,38 @@ extern "C" int sq_basic_fit(const void *const *tile_ptrs_dev, const void *tile_b
         if (rw > 0 && host.mad_den > 0.0 && host.mad_num / host.mad_den <= REWEIGHT_TOL) break;
         SQ_HIP(hipMemcpyAsync(F(L.last), F(L.s), NPIX * 4, hipMemcpyDeviceToDevice, s));
     }
-    hipLaunchKernelGGL(resample_up_kernel, dim3(tile_h), dim3(256), 0, s, F(L.s), tile_h, tile_w, duy, dux, flatfield_dev);
+    // A solve that ran into the iteration cap hands back whatever S holds (step_kernel), and a smoothness weight that
+    // shrinks every DCT coefficient away leaves S = 0 and 0 / 0 behind it: the gains go to the fusion divide, so a fit
+    // whose S is not finite and positive is an error, not a result.  The up-sampling weights are non-negative and every
+    // row of them sums to 1, so S > 0 at the working size carries over to every full-size gain.
+    std::vector<float> s_host((size_t)NPIX);
+    SQ_HIP(hipMemcpyAsync(s_host.data(), F(L.s), s_host.size() * 4, hipMemcpyDeviceToHost, s));
     SQ_HIP(hipGetLastError());
     SQ_HIP(hipStreamSynchronize(s));
     if (info) {
         info->reweight_iterations = reweights;
         info->ladmap_iterations = total_iterations;
         info->working_size = WS;
+        info->capped_rounds = capped_rounds;
     }
+    int not_finite = 0;
+    float s_min = INFINITY;
+    for (const float v : s_host) {
+        if (!std::isfinite(v)) ++not_finite;
+        else s_min = std::min(s_min, v);
+    }
+    if (not_finite || !(s_min > 0.0f)) {
+        char least[64] = "none is finite";
+        if (not_finite < NPIX) snprintf(least, sizeof least, "the smallest finite one is %g", (double)s_min);
+        return fail(SQ_ERR_NUMERIC,
+                    "sq_basic_fit: the fit gave no usable flatfield: %d of %d gains at the working size are not finite, %s (all "
+                    "must be > 0); %d of %d re-weighting rounds stopped at the cap of %d iterations%s",
+                    not_finite, NPIX, least, capped_rounds, reweights, MAX_ITER,
+                    capped_rounds ? " without settling (images too dim or too few, or a smoothness weight that removes the flatfield)" : "");
+    }
+    hipLaunchKernelGGL(resample_up_kernel, dim3(tile_h), dim3(256), 0, s, F(L.s), tile_h, tile_w, duy, dux, flatfield_dev);
+    SQ_HIP(hipGetLastError());
+    SQ_HIP(hipStreamSynchronize(s));
 #undef SQ_HIP
     return SQ_OK;
 }

@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SQ_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libsquidstitch.so')
 
 SQ_U8, SQ_U16, SQ_F32, SQ_F64 = 1, 2, 4, 8
+SQ_ERR_INVALID, SQ_ERR_HIP, SQ_ERR_UNSUPPORTED, SQ_ERR_WORKSPACE, SQ_ERR_NUMERIC = -1, -2, -3, -4, -5
 SQ_FUSE_OVERWRITE, SQ_FUSE_FEATHER = 0, 1
 SQ_NORM_NONE, SQ_NORM_PHASE = 0, 1
 SQ_FUSE_FORCE_QUEUES, SQ_FUSE_FORCE_STATIC, SQ_FUSE_NO_PLANE_GROUPS, SQ_FUSE_NO_SEAM_OWNERS, SQ_FUSE_CONSECUTIVE_GROUPS = 1, 2, 4, 8, 16
@@ -44,7 +45,11 @@ OVERLAP_DTYPE = np.dtype([('ref_tile', '<i4'), ('mov_tile', '<i4'), ('ref_y0', '
 
 
 class NativeError(RuntimeError):
-    """A libsquidstitch call returned a negative status."""
+    """A libsquidstitch call returned a negative status (``status``: the sq_status code, when the call gave one)."""
+
+    def __init__(self, message, status=None):
+        super().__init__(message)
+        self.status = status
 
 
 class _FuseArgs(C.Structure):
@@ -105,7 +110,8 @@ class _ArenaInfo(C.Structure):
 
 
 class _BasicInfo(C.Structure):
-    _fields_ = [('reweight_iterations', C.c_int32), ('ladmap_iterations', C.c_int32), ('working_size', C.c_int32)]
+    _fields_ = [('reweight_iterations', C.c_int32), ('ladmap_iterations', C.c_int32), ('working_size', C.c_int32),
+                ('capped_rounds', C.c_int32)]
 
 
 EXPORTS = {
@@ -202,7 +208,7 @@ def lib() -> C.CDLL:
 
 def _check(status: int, what: str) -> None:
     if status < 0:
-        raise NativeError(f"{what} failed ({status}): {lib().sq_last_error().decode()}")
+        raise NativeError(f"{what} failed ({status}): {lib().sq_last_error().decode()}", status)
 
 
 def sq_dtype_of(np_dtype) -> int:
@@ -1485,7 +1491,10 @@ def blosc_encode_planes(planes, chunk_h: int, chunk_w: int, buffers: Optional[Bl
 def basic_fit(tiles, smoothness_flatfield: float = 1.0, stream=None):
     """Flatfield estimate of a device stack [n, H, W] (uint8 / uint16, n <= 80) -> (device float32 [H, W], info dict).
     Replaces ``BaSiC(get_darkfield=False, smoothness_flatfield=...).fit(images).flatfield`` (stitcher.py:374-377);
-    parity with basicpy is UNPINNED (the package is absent offline) -- see include/squidstitch.h.  Synchronises."""
+    parity with basicpy is UNPINNED (the package is absent offline) -- see include/squidstitch.h.  Synchronises.
+    ``info['capped_rounds']`` counts the re-weighting rounds that stopped at the 500-iteration cap (0 for a fit that
+    settled); a fit whose 128 x 128 flatfield is not finite and > 0 everywhere raises NativeError with status
+    SQ_ERR_NUMERIC instead of returning gains that would ruin the fusion divide."""
     import torch
     L = lib()
     if tiles.dim() != 3 or not tiles.is_cuda or not tiles.is_contiguous():
@@ -1501,7 +1510,7 @@ def basic_fit(tiles, smoothness_flatfield: float = 1.0, stream=None):
                           float(smoothness_flatfield), out.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(info),
                           _stream_ptr(stream)), 'sq_basic_fit')
     return out, {'reweight_iterations': info.reweight_iterations, 'ladmap_iterations': info.ladmap_iterations,
-                 'working_size': info.working_size}
+                 'working_size': info.working_size, 'capped_rounds': info.capped_rounds}
 
 
 def selftest_flat_divide(exponent: int, n_binades: int, negative: bool, device) -> int:

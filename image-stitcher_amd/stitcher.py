@@ -679,7 +679,14 @@ class Stitcher:
                 self.flatfields[channel_index] = np.asarray(basic.flatfield)
             elif used == 'basic':
                 stack = torch.from_numpy(np.ascontiguousarray(images)).to(self.device)
-                flat, info = native.basic_fit(stack, 1.0)
+                try:
+                    flat, info = native.basic_fit(stack, 1.0)
+                except native.NativeError as e:       # SQ_ERR_NUMERIC: the fit gave no finite, positive gains
+                    raise native.NativeError(f"flatfield of channel {channel_name} ({len(images)} images): {e}", e.status) from e
+                if info.get('capped_rounds', 0) > 0:
+                    print(f"WARNING: flatfield of channel {channel_name}: {info['capped_rounds']} of "
+                          f"{info['reweight_iterations']} re-weighting rounds of the BaSiC fit stopped at the iteration cap "
+                          f"without settling (dim or few images?); the gains are finite and positive but may be poor")
                 self.flatfields[channel_index] = flat.cpu().numpy()
             else:
                 acc = images.astype(np.float64).mean(axis=0)

@@ -36,7 +36,8 @@ typedef enum sq_status {
     SQ_ERR_INVALID = -1,     /* bad argument (NULL, negative size, unknown enum, misaligned) */
     SQ_ERR_HIP = -2,         /* a HIP runtime call or launch failed                          */
     SQ_ERR_UNSUPPORTED = -3, /* valid request this build cannot serve                        */
-    SQ_ERR_WORKSPACE = -4    /* caller workspace too small                                   */
+    SQ_ERR_WORKSPACE = -4,   /* caller workspace too small                                   */
+    SQ_ERR_NUMERIC = -5      /* the computation ran but its result is unusable (sq_basic_fit) */
 } sq_status;
 
 typedef enum sq_dtype { SQ_U8 = 1, SQ_U16 = 2, SQ_F32 = 4, SQ_F64 = 8 } sq_dtype;
@@ -597,11 +598,17 @@ int sq_write_files(const char *paths, const int64_t *path_offsets, const void *d
  * oracle/basic_oracle.py.  Not on the hot path (the divide by the result is: sq_fuse_planes).
  * Unlike the other entry points this one SYNCHRONISES `stream` (its iteration count is decided by the data).
  * flatfield_dev: tile_h x tile_w float32, dense.  workspace: sq_basic_workspace_bytes(), 256-byte aligned.
+ * The definition does not converge on every input (dim stacks, a handful of images, a huge smoothness weight: see
+ * oracle/basic_oracle.py): a re-weighting round then stops at the cap of 500 iterations with whatever it holds, counted in
+ * info->capped_rounds.  When the 128 x 128 flatfield of the last round is not finite and > 0 everywhere the call returns
+ * SQ_ERR_NUMERIC (the minimum and the capped rounds in sq_last_error), fills `info` and leaves flatfield_dev unwritten;
+ * S > 0 there carries over to every full-size gain (the up-sampling weights are >= 0 and sum to 1 per pixel).
  * ---------------------------------------------------------------------------------------- */
 typedef struct sq_basic_info {
     int32_t reweight_iterations; /* outer re-weighted-L1 rounds run (<= 10)          */
     int32_t ladmap_iterations;   /* inner iterations summed over the rounds          */
     int32_t working_size;        /* 128: the images are resampled to this before the fit */
+    int32_t capped_rounds;       /* rounds whose inner loop reached the 500-iteration cap (0 for a fit that settled) */
 } sq_basic_info;
 
 int64_t sq_basic_workspace_bytes(int32_t n_images, int32_t tile_h, int32_t tile_w);

@@ -16,6 +16,15 @@ the configuration the reference asks for: no darkfield, flatfield smoothness wei
 defaults for everything else (working size 128, epsilon 0.1, rho 1.5, mu_coef 12.5, max_mu_coef 1e7,
 optimization_tol 1e-3, reweighting_tol 1e-2, max_iterations 500, max_reweight_iterations 10).  The device version
 (csrc/basic.hip) is tested against THIS definition and against a planted gain, not against basicpy.
+
+KNOWN LIMIT: the definition does not converge on every input, and nothing in it notices.  With the float32 code below
+on ``planted_stack`` tiles (tests/test_basic_oracle_cpu.py): ``// 300`` (a background of about 10 counts), n = 4 or 8:
+all 10 re-weighting rounds run to the 500-iteration cap and the gains have a minimum of -1.4 to -2.9; ``// 64``
+(background about 47), n = 2: 5 of 10 rounds at the cap, the gains stay positive, gain error 0.11; uint16 tiles with
+``smoothness_flatfield=100``: all 10 rounds at the cap, S shrinks to exactly 0 and the result is NaN.  Non-converged
+runs are chaotic (float32 and float64 evaluations disagree by orders of magnitude).  Whether basicpy behaves the same
+is unknown: parity with it remains unpinned.  The algorithm is left as it is; the device version counts the rounds
+that hit the cap (``capped_rounds``) and refuses gains that are not finite and > 0 (SQ_ERR_NUMERIC).
 """
 from __future__ import annotations
 

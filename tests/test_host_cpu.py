@@ -374,6 +374,52 @@ def test_flatfield_sample_can_reach_80_images_and_the_device_fit_takes_them(tmp_
     assert L.sq_basic_workspace_bytes(81, 32, 48) < 0 and b'1..80' in L.sq_last_error()
 
 
+def test_get_flatfields_reports_capped_rounds_and_names_the_channel_of_a_failed_fit(tmp_path, monkeypatch, capsys):
+    """The device fit's verdict reaches the user (native.basic_fit replaced: no device here): ``capped_rounds`` lands
+    in ``flatfield_info`` for every channel, a channel whose fit ran into the iteration cap gets a WARNING that names
+    it, and SQ_ERR_NUMERIC (no finite, positive gains) propagates with the channel's name and its status."""
+    import sys
+    import torch
+    from image_stitcher_amd import native
+    from image_stitcher_amd.stitcher import Stitcher
+    channels = ('Fluorescence 405 nm Ex', 'Fluorescence 488 nm Ex')
+    spec = synth.GridSpec(rows=2, cols=2, tile_h=32, tile_w=48, ov_y=8, ov_x=8, seed=9, channels=channels)
+    root = str(tmp_path / 'acq')
+    synth.write_acquisition(spec, root)
+    monkeypatch.setitem(sys.modules, 'basicpy', None)            # 'auto' -> the device fit
+
+    def prepared():
+        st = Stitcher(StitchingParameters(input_folder=root, apply_flatfield=True), device=torch.device('cpu'))
+        st.get_timepoints(); st.extract_acquisition_parameters(); st.get_pixel_size(); st.parse_acquisition_metadata()
+        return st
+
+    capped = iter([0, 3])
+
+    def fit(stack, smoothness_flatfield=1.0, stream=None):
+        assert smoothness_flatfield == 1.0 and tuple(stack.shape) == (4, 32, 48)
+        return torch.ones(stack.shape[1:]), {'reweight_iterations': 4, 'ladmap_iterations': 1700, 'working_size': 128,
+                                              'capped_rounds': next(capped)}
+
+    monkeypatch.setattr(native, 'basic_fit', fit)
+    st = prepared()
+    st.get_flatfields()
+    assert st.flatfield_estimator_used == 'basic' and sorted(st.flatfields) == [0, 1]
+    info = st.flatfield_info['channels']
+    assert info[channels[0]]['capped_rounds'] == 0 and info[channels[1]]['capped_rounds'] == 3
+    assert info[channels[1]]['images'] == 4
+    warnings = [line for line in capsys.readouterr().out.splitlines() if line.startswith('WARNING')]
+    assert len(warnings) == 1 and channels[1] in warnings[0] and '3 of 4' in warnings[0]
+
+    def failing(stack, smoothness_flatfield=1.0, stream=None):
+        raise native.NativeError("sq_basic_fit failed (-5): the fit gave no usable flatfield", native.SQ_ERR_NUMERIC)
+
+    monkeypatch.setattr(native, 'basic_fit', failing)
+    st = prepared()
+    with pytest.raises(native.NativeError, match=f'{channels[0]}.*no usable flatfield') as e:
+        st.get_flatfields()
+    assert e.value.status == native.SQ_ERR_NUMERIC == -5 and not st.flatfields
+
+
 @pytest.mark.parametrize('rows,cols', [(1, 3), (3, 1), (1, 1)])
 def test_degenerate_grids_behave_like_the_reference(tmp_path, rows, cols):
     """One row, one column or one tile: coordinate-only placement works; with -r the reference indexes

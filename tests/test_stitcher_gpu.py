@@ -273,6 +273,7 @@ def test_cli_with_ff_estimates_gains_on_the_device_and_says_so(tmp_path, capsys)
         info = json.load(fh)
     assert info['estimator'] == 'basic' and sorted(info['channels']) == sorted(st.channel_names)
     assert all(c['images'] == 12 and c['working_size'] == 128 and c['ladmap_iterations'] >= 1 for c in info['channels'].values())
+    assert all(c['capped_rounds'] == 0 for c in info['channels'].values()) and 'WARNING: flatfield' not in out, info    # the fits settled
     with open(os.path.join(st.output_folder, 'shift_table.json')) as fh:
         assert json.load(fh)['flatfield_estimator'] == 'basic'
     assert sorted(st.flatfields) == [0, 1]
