@@ -155,6 +155,8 @@ EXPORTS = {
     'sq_despeckle_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                      C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_tile_stats': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    'sq_dpc_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                               C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1312,6 +1314,53 @@ def tile_stats(tiles, out=None, stream=None):
         return out
     _check(lib().sq_tile_stats(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
                                out.data_ptr(), _stream_ptr(stream)), 'sq_tile_stats')
+    return out
+
+
+SQ_DPC_MAX_GAIN = 16
+DPC_CHANNEL = 'DPC'      # the derived channel's name (stitcher.py)
+DPC_DEFINITION = 'S = L + R; N = S + 2*gain*(L - R); DPC = 0 if S == 0 else clamp(floor(M*N / (2*S)), 0, M), M = the dtype maximum'
+
+
+def dpc_tiles(left, right, gain: int = 1, out=None, stream=None):
+    """Differential phase contrast of every H x W plane of ``left`` and ``right`` (sq_dpc_tiles; an extension, the reference
+    has none): with S = L + R, N = S + 2 gain (L - R) and M the dtype's maximum, 0 where S == 0 and
+    clamp(floor(M N / (2 S)), 0, M) elsewhere, exact in integers -- ``tests/dpc_ref.dpc_image``.
+
+    left, right: uint8 / uint16 device tensors [..., H, W] of one dtype and shape with unit-stride rows (any row pitch) whose
+                 leading dimensions are one uniform plane stride apart, each with its own.
+    gain:        an integer in 1..16.
+    out:         None: in place over ``left``.  Else a tensor of the same shape, dtype and device under the same rules (its
+                 columns beyond W stay as they are) that is exactly ``left`` or shares no memory with either input.
+    Returns ``out`` (``left`` when None)."""
+    import torch
+    if not torch.is_tensor(left) or not left.is_cuda or left.dim() < 2:
+        raise ValueError("left must be a [..., H, W] device tensor")
+    if left.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"left must be uint8 or uint16, got {left.dtype}")
+    if isinstance(gain, bool) or not isinstance(gain, (int, np.integer)) or not 1 <= int(gain) <= SQ_DPC_MAX_GAIN:
+        raise ValueError(f"dpc gain must be an integer in 1..{SQ_DPC_MAX_GAIN}, got {gain!r}")
+    if out is None:
+        out = left
+    for name, t in (('right', right), ('out', out)):
+        if not torch.is_tensor(t) or tuple(t.shape) != tuple(left.shape) or t.dtype != left.dtype or t.device != left.device:
+            raise ValueError(f"{name} must be a {left.dtype} tensor of shape {tuple(left.shape)} on left's device")
+    n_images, h, w, left_plane_stride, left_pitch = _plane_layout(left, 'left')
+    _, _, _, right_plane_stride, right_pitch = _plane_layout(right, 'right')
+    _, _, _, out_plane_stride, out_pitch = _plane_layout(out, 'out')
+    if n_images == 0:
+        return out
+    es = left.element_size()
+    l0, r0, o0 = left.data_ptr(), right.data_ptr(), out.data_ptr()
+    l1 = l0 + ((n_images - 1) * left_plane_stride + (h - 1) * left_pitch + w) * es
+    r1 = r0 + ((n_images - 1) * right_plane_stride + (h - 1) * right_pitch + w) * es
+    o1 = o0 + ((n_images - 1) * out_plane_stride + (h - 1) * out_pitch + w) * es
+    in_place = o0 == l0 and out_pitch == left_pitch and (n_images == 1 or out_plane_stride == left_plane_stride)
+    if (not in_place and l0 < o1 and o0 < l1) or (r0 < o1 and o0 < r1):
+        raise ValueError("out must be exactly left (in place) or share no memory with left and right")
+    _check(lib().sq_dpc_tiles(l0, r0, o0, n_images, h, w, left_plane_stride, left_pitch, right_plane_stride, right_pitch,
+                              out_plane_stride, out_pitch, sq_dtype_of(np_dtype_of_torch(left.dtype)), int(gain),
+                              _stream_ptr(stream)), 'sq_dpc_tiles')
     return out
 
 

@@ -74,7 +74,8 @@ class Stitcher:
                  composite: bool = False, composite_max_side: int = 4096, composite_z: Optional[int] = None,
                  composite_channels=None, background_subtract: str = 'none', background_radius: int = 50,
                  despeckle: str = 'none', despeckle_threshold: int = 1000, tile_qc: bool = False,
-                 tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5):
+                 tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5, dpc: bool = False,
+                 dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -196,6 +197,35 @@ class Stitcher:
         self._tile_qc_words: Dict[tuple, Dict[tuple, tuple]] = {}      # (timepoint, region) -> {(plane, fov): the eight words}
         self._tile_qc_pending = []       # (timepoint, region, device words [planes, tiles, 8], [(plane, fov)]) not read back yet
         self._tile_qc_shared = False     # the ranks share this region: the words are combined before anything is written
+        # Extension: dpc=True adds one derived channel, 'DPC', the differential phase contrast of the two half-pupil brightfield
+        # channels dpc_channels = (left, right): with S = L + R, N = S + 2 dpc_gain (L - R) and M the dtype's maximum, 0 where
+        # S == 0 and clamp(floor(M N / (2 S)), 0, M) elsewhere (sq_dpc_tiles; tests/dpc_ref.py) -- for gain 1 Squid's
+        # generate_dpc, M (0.5 + (L - R) / (L + R)), without its float rounding.  It is made of the staged tiles on the device,
+        # right after the copy and before anything else touches them, so a run equals a run without the option on a folder
+        # that also holds the files <region>_<fov>_<z>_DPC.tiff: the channel sits where its name sorts, and goes through the
+        # tile report, the despeckle, the background removal, the projections and the fusion like a file channel.  The one
+        # exception is the flatfield: the ratio cancels a multiplicative gain, so the channel is fused without one and the
+        # estimate never samples it.  Registration reads files: it never sees the channel.  False: nothing is parsed
+        # differently, allocated, launched or written; the other two values are checked and unused.
+        if not isinstance(dpc, (bool, np.bool_)):
+            raise ValueError(f"dpc must be True or False, got {dpc!r}")
+        if isinstance(dpc_channels, str) or not isinstance(dpc_channels, (tuple, list)) or len(dpc_channels) != 2 or \
+                not all(isinstance(n, str) and n for n in dpc_channels):
+            raise ValueError(f"dpc_channels must be two channel names (left, right), got {dpc_channels!r}")
+        if isinstance(dpc_gain, bool) or not isinstance(dpc_gain, (int, np.integer)) or \
+                not 1 <= int(dpc_gain) <= native.SQ_DPC_MAX_GAIN:
+            raise ValueError(f"dpc_gain must be an integer in 1..{native.SQ_DPC_MAX_GAIN}, got {dpc_gain!r}")
+        self.dpc = bool(dpc)
+        self.dpc_channels = tuple(dpc_channels)
+        self.dpc_gain = int(dpc_gain)
+        self._dpc_index = None      # the derived channel's index in monochrome_channels, once the metadata is parsed
+        if self.dpc:
+            if self.dpc_channels[0] == self.dpc_channels[1]:
+                raise ValueError(f"dpc_channels names one channel twice: {self.dpc_channels[0]!r}")
+            if native.DPC_CHANNEL in self.dpc_channels:
+                raise ValueError(f"dpc_channels {self.dpc_channels}: {native.DPC_CHANNEL!r} is the derived channel's own name")
+            if params.registration_channel == native.DPC_CHANNEL:
+                raise ValueError(f"registration_channel {native.DPC_CHANNEL!r} is the derived channel: registration reads files")
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -316,6 +346,7 @@ class Stitcher:
         self._region_index = {}
         regions, channels = set(), set()
         max_z = max_fov = 0
+        dpc_unpaired = 0
         for timepoint in self.timepoints:
             image_folder = os.path.join(self.input_folder, str(timepoint))
             print(f"[metadata] timepoint {timepoint}: {image_folder}")
@@ -325,6 +356,11 @@ class Stitcher:
                 print(f"Warning: timepoint {timepoint} has no coordinates.csv, skipped")
                 continue
             files = sorted(f for f in os.listdir(image_folder) if f.endswith(_IMAGE_EXT) and 'focus_camera' not in f)
+            halves = {}      # --dpc: name of a derived tile's would-be file -> (left file, right file)
+            if self.dpc:
+                halves, lone = self._dpc_file_pairs(files)
+                dpc_unpaired += lone
+                files = sorted(files + list(halves))
             for file in files:
                 parts = file.split('_', 3)
                 region, fov, z_level = parts[0], int(parts[1]), int(parts[2])
@@ -334,8 +370,14 @@ class Stitcher:
                     print(f"Warning: {file} has no row in coordinates.csv, skipped")
                     continue
                 key = (int(timepoint), region, fov, z_level, channel)
-                rec = {'filepath': os.path.join(image_folder, file), 'x': pos[0], 'y': pos[1], 'z': pos[2],
+                rec = {'filepath': os.path.join(image_folder, halves[file][0] if file in halves else file),
+                       'x': pos[0], 'y': pos[1], 'z': pos[2],
                        'channel': channel, 'z_level': z_level, 'region': region, 'fov_idx': fov, 't': int(timepoint)}
+                if file in halves:      # a derived tile: both halves, at the place its own file would have
+                    rec['filepath_right'] = os.path.join(image_folder, halves[file][1])
+                    self.acquisition_metadata[key] = rec
+                    self._region_index.setdefault((int(timepoint), region), {})[key] = rec
+                    continue
                 self.acquisition_metadata[key] = rec
                 self._region_index.setdefault((int(timepoint), region), {})[key] = rec
                 regions.add(region)
@@ -349,6 +391,13 @@ class Stitcher:
         self.num_fovs_per_region = max_fov + 1
         if not self.acquisition_metadata:
             raise ValueError(f"No image files with coordinates found under {self.input_folder}")
+        if self.dpc:
+            for half in self.dpc_channels:
+                if half not in channels:
+                    raise ValueError(f"dpc_channels: {half!r} is not a channel of this acquisition: {self.channel_names}")
+            if dpc_unpaired:
+                print(f"Warning: {dpc_unpaired} (fov, z) with only one of the halves {self.dpc_channels}: no "
+                      f"{native.DPC_CHANNEL} tile there")
         first_key = next(iter(self.acquisition_metadata))
         first = self.acquisition_metadata[first_key]
         first_image = read_image(first['filepath'])
@@ -360,7 +409,11 @@ class Stitcher:
             raise ValueError(f"Unexpected image shape: {first_image.shape}")
         self.chunks = (1, 1, 1, 512, 512)
         self.monochrome_channels = []
-        for channel in self.channel_names:
+        # (the derived channel sits where its name sorts among the file channels; channel_names stays the file channels)
+        for channel in sorted(self.channel_names + [native.DPC_CHANNEL]) if self.dpc else self.channel_names:
+            if self.dpc and channel == native.DPC_CHANNEL:
+                self.monochrome_channels.append(channel)
+                continue
             ck = (first['t'], first['region'], first['fov_idx'], first['z_level'], channel)
             img = read_image(self.acquisition_metadata[ck]['filepath'])
             if img.ndim == 3 and img.shape[2] == 3:
@@ -370,6 +423,11 @@ class Stitcher:
                 self.monochrome_channels.append(channel)
         self.num_c = len(self.monochrome_channels)
         self.monochrome_colors = [self.get_channel_color(n) for n in self.monochrome_channels]
+        if self.dpc:
+            for half in self.dpc_channels:
+                if half not in self.monochrome_channels:
+                    raise ValueError(f"dpc_channels: the files of {half!r} are RGB; the halves are monochrome channels")
+            self._dpc_index = self.monochrome_channels.index(native.DPC_CHANNEL)
         if self.focus_guide_channel is not None:
             if self.focus_guide_channel not in self.monochrome_channels:
                 raise ValueError(f"focus_guide_channel {self.focus_guide_channel!r} is not a channel of this acquisition: "
@@ -388,6 +446,26 @@ class Stitcher:
         print(f"[metadata] tile {self.input_height} x {self.input_width} {np.dtype(self.dtype)}")
         print(f"[metadata] {self.num_z} z levels, {self.num_t} timepoints, {self.num_fovs_per_region} fovs per region")
         print(f"[metadata] {self.num_c} output channels: {self.monochrome_channels}")
+
+    def _dpc_file_pairs(self, files):
+        """--dpc: ({name the file of a derived tile would have: (left file, right file)}, number of (region, fov, z) with one
+        half only) of one timepoint's file names.  A file that is already called like that makes 'DPC' a file channel."""
+        left, right = {}, {}
+        for file in files:
+            parts = file.split('_', 3)
+            stem, ext = os.path.splitext(parts[3])
+            channel = stem.replace("_", " ").replace("full ", "full_")
+            if channel == native.DPC_CHANNEL:
+                raise ValueError(f"{file}: the acquisition already has a channel named {native.DPC_CHANNEL!r}, the name of "
+                                 "the channel --dpc derives")
+            for name, table in zip(self.dpc_channels, (left, right)):
+                if channel == name:
+                    table[tuple(parts[:3])] = (file, ext)
+        pairs = {}
+        for at, (file, ext) in left.items():
+            if at in right:
+                pairs['_'.join(at) + '_' + native.DPC_CHANNEL + ext] = (file, right[at][0])
+        return pairs, len(set(left) ^ set(right))
 
     def get_region_data(self, t, region):
         """(stitcher.py:260-280) -- served from an index built once instead of a full scan."""
@@ -986,6 +1064,8 @@ class Stitcher:
         if despeckle:
             self._check_despeckle_dtype()
             self._write_despeckle_note(timepoint, region)
+        if self.dpc:
+            self._write_dpc_note(timepoint, region)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1109,7 +1189,10 @@ class Stitcher:
                 # the top-hat's scratch (the erosion of a batch: as many bytes as its tiles) counts against the budget too
                 tophat = self.background_subtract == 'tophat'
                 # and so does the despeckle's destination (one more copy of a batch's tiles)
-                batch = max(1, min(len(plist), staged_budget // max(1, per_plane * (1 + int(despeckle) + int(tophat)))))
+                # and the right halves of the derived planes (--dpc: counted as one more copy, though only they have one)
+                n_derived = sum(p // self.num_z == self._dpc_index for p in plist) if self.dpc else 0
+                batch = max(1, min(len(plist), staged_budget // max(1, per_plane * (1 + int(despeckle) + int(tophat) +
+                                                                                     int(n_derived > 0)))))
                 if writer is not None:
                     batch = min(batch, writer.batch)
                 chunks = [plist[b0:b0 + batch] for b0 in range(0, len(plist), batch)]
@@ -1152,6 +1235,21 @@ class Stitcher:
                     # the kernel's per-plane counts of this list's planes (plane of plist, tile): every chunk adds into its own
                     # run of it, and it is folded per channel once, behind the last chunk
                     list_counts = torch.zeros((len(plist), n), dtype=torch.int64, device=self.device)
+                right_staging = right_dev = right_done = None
+                if n_derived:
+                    # the right halves: one more staged buffer per ingest slot, pinned and mirrored on the device, as deep as
+                    # a chunk can hold derived planes (they are consecutive: plist is ascending).  Its own events: whatever
+                    # ingest buffers it is used beside, the copy and the launch that read a slot have finished before the
+                    # loader writes to it again
+                    deep = min(batch, n_derived)
+                    rkey = ('dpc', deep, n, th, tw, n_slots, np.dtype(self.dtype).str)
+                    rbufs = self._buffer_cache.get(rkey)
+                    if rbufs is None:
+                        rbufs = ([torch.empty((deep, n, th, tw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
+                                 [torch.empty((deep, n, th, tw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
+                                 [None] * n_slots)
+                        self._keep_buffers(rkey, rbufs)
+                    right_staging, right_dev, right_done = rbufs
                 qc_words = None
                 if self.tile_qc:
                     # the words of this list's staged planes (plane of plist, tile): every chunk's launch overwrites its own run
@@ -1165,19 +1263,31 @@ class Stitcher:
                     if done[slot] is not None:
                         done[slot].synchronize()      # the slot's previous copy and fusion have finished
                     host = staging[slot].numpy()
+                    # the chunk's derived planes (consecutive) and where their right halves go
+                    derived = [pi for pi, p in enumerate(chunk) if p // self.num_z == self._dpc_index] if n_derived else []
+                    right_host = None
+                    if derived:
+                        if right_done[slot] is not None:
+                            right_done[slot].synchronize()
+                        right_host = right_staging[slot].numpy()
 
-                    def load(job, host=host):
-                        pi, ti, (info, rgb, _, _) = job
-                        if rgb < 0 and read_image_into(info['filepath'], host[pi, ti]):
+                    def read_tile(path, rgb, dest):
+                        if rgb < 0 and read_image_into(path, dest):
                             return      # file -> page-locked staging in one read
-                        img = read_image(info['filepath'])
+                        img = read_image(path)
                         if rgb >= 0:
                             img = img[:, :, rgb]
                         elif img.ndim == 3 and img.shape[0] == 1:
                             img = img[0]
                         if img.shape != (th, tw):
                             raise ValueError(f"Unexpected tile shape: {img.shape}")
-                        host[pi, ti] = img
+                        dest[...] = img
+
+                    def load(job, host=host, right_host=right_host, first=derived[0] if derived else 0):
+                        pi, ti, (info, rgb, _, _) = job
+                        read_tile(info['filepath'], rgb, host[pi, ti])
+                        if 'filepath_right' in info:      # a derived tile: its left half above, its right half here
+                            read_tile(info['filepath_right'], -1, right_host[pi - first, ti])
 
                     jobs = [(pi, ti, it) for pi, p in enumerate(chunk) for ti, it in enumerate(planes[p])]
                     for _ in pool.map(load, jobs):
@@ -1187,6 +1297,13 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
+                    if derived:     # in place over the left halves, before anything reads the staged planes
+                        i0, i1 = derived[0], derived[-1] + 1
+                        rights = right_dev[slot][:i1 - i0]
+                        rights.copy_(right_staging[slot][:i1 - i0], non_blocking=True)
+                        native.dpc_tiles(tiles[i0:i1], rights, self.dpc_gain)
+                        right_done[slot] = torch.cuda.Event()
+                        right_done[slot].record()
                     if qc_words is not None:      # the tiles as they are in their files: before anything filters them
                         native.tile_stats(tiles, out=qc_words[b0:b0 + m].view(-1, native.SQ_TILE_STATS_WORDS))
                     if despeckle:   # out of place: everything below reads the filtered planes in `clean`
@@ -1263,6 +1380,19 @@ class Stitcher:
         path = os.path.join(folder, f"{region}_stitched_background.json")
         note = {'method': 'tophat', 'radius': self.background_radius, 'window': 2 * self.background_radius + 1,
                 'applies_to': 'every staged tile plane, before the flatfield divide'}
+        tmp = f"{path}.{os.getpid()}.tmp"
+        with open(tmp, 'w') as fh:
+            json.dump(note, fh, indent=1)
+        os.replace(tmp, path)
+
+    def _write_dpc_note(self, timepoint, region) -> None:
+        """``<t>_stitched/<region>_stitched_dpc.json``: what the derived channel of every store of this region is made of
+        (the same bytes from every rank and call, put in place atomically)."""
+        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"{region}_stitched_dpc.json")
+        note = {'left': self.dpc_channels[0], 'right': self.dpc_channels[1], 'gain': self.dpc_gain,
+                'channel': native.DPC_CHANNEL, 'definition': native.DPC_DEFINITION}
         tmp = f"{path}.{os.getpid()}.tmp"
         with open(tmp, 'w') as fh:
             json.dump(note, fh, indent=1)

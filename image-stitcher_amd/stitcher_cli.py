@@ -7,7 +7,8 @@ plus eighteen switches for what this build adds (``--fusion-mode``, ``--normaliz
 ``--composite-z``, ``--composite-channels``).  Two more select the background removal of the staged tiles:
 ``--background-subtract`` and ``--background-radius``.  ``--despeckle`` and ``--despeckle-threshold`` select the hot-pixel
 removal that runs on the staged tiles before it.  ``--tile-qc``, ``--tile-qc-saturation`` and ``--tile-qc-focus-ratio`` select
-the per-tile quality report (focus, saturation, intensity) of the tiles as they are in their files.
+the per-tile quality report (focus, saturation, intensity) of the tiles as they are in their files.  ``--dpc``,
+``--dpc-channels`` and ``--dpc-gain`` add the differential phase contrast channel made of the two half-pupil brightfield tiles.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -129,6 +130,18 @@ FLAGS = (
     (('--tile-qc-focus-ratio',), dict(type=float, default=0.5, metavar='F',
                                       help="with --tile-qc: a tile plane is flagged low_focus when its focus score is below this "
                                            "fraction of the median over the tiles of its (channel, z) plane, 0..1")),
+    (('--dpc',), dict(action='store_true',
+                      help="add the channel DPC, the differential phase contrast of the two half-pupil brightfield channels of "
+                           "--dpc-channels, made of every pair of tiles on the device before anything else touches them: "
+                           "0.5 + (L - R) / (L + R) of the dtype's range, exact in integers and clipped (0 where both are 0) -- "
+                           "what a run on a folder that also holds the files <region>_<fov>_<z>_DPC.tiff gives.  The channel "
+                           "sits where its name sorts and is fused without a flatfield gain (the ratio cancels it); "
+                           "registration and the flatfield estimate keep reading files; writes <region>_stitched_dpc.json")),
+    (('--dpc-channels',), dict(nargs=2, default=('BF LED matrix left half', 'BF LED matrix right half'), metavar=('LEFT', 'RIGHT'),
+                               help="with --dpc: the names of the left-half and the right-half channel")),
+    (('--dpc-gain',), dict(type=int, default=1, metavar='G',
+                           help="with --dpc: the difference is multiplied by this integer, 1..16, before the clip: "
+                                "0.5 + G (L - R) / (L + R)")),
 )
 
 
@@ -200,7 +213,10 @@ def main(argv=None):
                             despeckle_threshold=args.despeckle_threshold,
                             tile_qc=args.tile_qc,
                             tile_qc_saturation=args.tile_qc_saturation,
-                            tile_qc_focus_ratio=args.tile_qc_focus_ratio)
+                            tile_qc_focus_ratio=args.tile_qc_focus_ratio,
+                            dpc=args.dpc,
+                            dpc_channels=tuple(args.dpc_channels),
+                            dpc_gain=args.dpc_gain)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -445,6 +445,31 @@ int sq_tile_stats(const void *src_dev, int32_t n_images, int32_t h, int32_t w, i
                   int32_t dtype, uint64_t *out_dev /* [n_images][SQ_TILE_STATS_WORDS], overwritten */, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Differential phase contrast (--dpc; extension: the reference has none -- Squid's acquisition software computes it for its
+ * live display, generate_dpc, in floats).  From the two half-pupil brightfield planes L and R [h, w] of one dtype (SQ_U8 /
+ * SQ_U16, maximum M = 255 / 65535) and an integer gain g, exact in integers:
+ *     S = L + R
+ *     N = S + 2 g (L - R)
+ *     out = 0                                 if S == 0
+ *         = clamp(floor(M N / (2 S)), 0, M)   otherwise          (floor of the exact rational)
+ * For g = 1 that is M (0.5 + (L - R) / (L + R)), truncated and clipped.  The definition is the numpy restatement in
+ * tests/dpc_ref.py, and the result is bit for bit that on every input.  n_images planes, the planes a plane stride and the rows
+ * a pitch apart (elements, pitch >= w), left, right and out each with their own -- the conventions of sq_despeckle_tiles: no
+ * alignment asked of a base or a pitch beyond the element's own; any h, w >= 1.  out may be EXACTLY left (same base, plane
+ * stride and pitch: in place); otherwise its extent (first to last element of all planes) must meet neither input's.  left and
+ * right are read once and out is written once (csrc/dpc.hip); the columns between w and out_pitch and the rows between h and
+ * the plane stride are never written, and nothing past w or h is read into a result.  No scratch, no allocation, no atomics;
+ * asynchronous on `stream`; deterministic.  SQ_ERR_INVALID, and nothing is launched, for an unknown dtype, a gain outside
+ * 1..SQ_DPC_MAX_GAIN, a pitch below w, a plane stride smaller than a plane, a NULL or element-misaligned pointer, n_images < 0,
+ * h or w < 1, extents beyond the address space, and an out that overlaps right, or left without being exactly left.
+ * SQ_ERR_UNSUPPORTED for a plane that needs more workgroups than a launch has.  n_images == 0 is SQ_OK.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_DPC_MAX_GAIN 16
+int sq_dpc_tiles(const void *left_dev, const void *right_dev, void *out_dev, int32_t n_images, int32_t h, int32_t w,
+                 int64_t left_plane_stride, int64_t left_pitch, int64_t right_plane_stride, int64_t right_pitch,
+                 int64_t out_plane_stride, int64_t out_pitch, int32_t dtype, int32_t gain, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
