@@ -8,6 +8,7 @@ module raises.  Build with ``python -c "import __graft_entry__ as g; g.build()"`
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Sequence
@@ -238,6 +239,17 @@ def _stream_ptr(stream=None) -> int:
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
     return int(s.cuda_stream)
+
+
+def _on_stream(stream):
+    """Makes ``stream`` the current stream for a wrapper's allocations, zero-fills, uploads and launch: outputs, scratch,
+    workspaces and result buffers are then made, cleared and used on the stream the kernels run on (a buffer taken from
+    another stream's pool could be handed out again while they still run, and a zero-fill on another stream lands whenever
+    that stream gets to it).  None: the current stream is the one the kernels run on already."""
+    if stream is None:
+        return contextlib.nullcontext()
+    import torch
+    return torch.cuda.stream(stream)
 
 
 def as_rects(rects) -> np.ndarray:
@@ -477,13 +489,14 @@ def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, strea
                 (n_planes > 1 and canvas.stride(0) < (hc - 1) * canvas.stride(1) + wc):
             raise ValueError("canvas must be contiguous or a [P, Hc, Wc] tensor with unit-stride rows and non-overlapping planes")
         pitch, plane_stride = int(canvas.stride(1)), int(canvas.stride(0))
-    keep = []
-    a = _fuse_args(plan, tiles, n_planes, canvas, plane_stride, pitch, flats, tile_ptrs, flat_ptrs, keep)
-    a.flags, a.grid_blocks = int(flags), int(grid_blocks)
-    if stream is not None:      # launched on another stream than the one the helpers above allocated for
-        for t in keep:
-            t.record_stream(stream)
-    _check(L.sq_fuse_planes(C.byref(a), _stream_ptr(stream)), 'sq_fuse_planes')
+    with _on_stream(stream):
+        keep = []
+        a = _fuse_args(plan, tiles, n_planes, canvas, plane_stride, pitch, flats, tile_ptrs, flat_ptrs, keep)
+        a.flags, a.grid_blocks = int(flags), int(grid_blocks)
+        if stream is not None:      # launched on another stream than the one the helpers above allocated for
+            for t in keep:
+                t.record_stream(stream)
+        _check(L.sq_fuse_planes(C.byref(a), _stream_ptr(stream)), 'sq_fuse_planes')
 
 
 def fuse_project_max(plan: FusePlan, tiles, out, flats=None, tile_ptrs=None, accumulate: bool = False, flags: int = 0,
@@ -513,14 +526,15 @@ def fuse_project_max(plan: FusePlan, tiles, out, flats=None, tile_ptrs=None, acc
         raise ValueError("tiles or tile_ptrs is required")
     if n_planes < 1:
         raise ValueError("at least one plane to project")
-    keep = []
-    a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
-    a.flags, a.grid_blocks = 0, int(grid_blocks)
-    if stream is not None:
-        for t in keep:
-            t.record_stream(stream)
-    fl = int(flags) | (SQ_PROJECT_ACCUMULATE if accumulate else 0)
-    _check(L.sq_fuse_project_max(C.byref(a), fl, _stream_ptr(stream)), 'sq_fuse_project_max')
+    with _on_stream(stream):
+        keep = []
+        a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
+        a.flags, a.grid_blocks = 0, int(grid_blocks)
+        if stream is not None:
+            for t in keep:
+                t.record_stream(stream)
+        fl = int(flags) | (SQ_PROJECT_ACCUMULATE if accumulate else 0)
+        _check(L.sq_fuse_project_max(C.byref(a), fl, _stream_ptr(stream)), 'sq_fuse_project_max')
 
 
 def focus_scratch_bytes(n_tiles: int, tile_h: int, tile_w: int) -> int:
@@ -575,35 +589,36 @@ def fuse_project_focus(plan: FusePlan, tiles, out, key, z_levels, radius: int = 
         raise ValueError("tiles or tile_ptrs is required")
     if not 1 <= n_planes <= SQ_FOCUS_MAX_PLANES:
         raise ValueError(f"{n_planes} planes: a call projects 1..{SQ_FOCUS_MAX_PLANES}")
-    keep = []
-    if torch.is_tensor(z_levels) and z_levels.is_cuda:
-        zl = z_levels.to(torch.int32)
-    else:
-        zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
-        if any(not 0 <= z < 2 ** 32 for z in zs):
-            raise ValueError("z levels must lie in 0 .. 2^32 - 1")
-        zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
-    if zl.numel() != n_planes:
-        raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
-    keep.append(zl)
-    need = focus_scratch_bytes(plan.n_tiles, plan.tile_h, plan.tile_w)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=out.device)
-    elif scratch.numel() * scratch.element_size() < need or not scratch.is_cuda:
-        raise ValueError(f"focus scratch must be a device tensor of at least {need} bytes")
-    keep.append(scratch)
-    a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
-    a.flags, a.grid_blocks = 0, int(grid_blocks)
-    f = _FocusArgs()
-    f.z_levels_dev = zl.data_ptr()
-    f.radius = int(radius)
-    f.scratch_dev, f.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
-    f.key_dev, f.key_pitch = key.data_ptr(), key_pitch
-    if stream is not None:
-        for t in keep:
-            t.record_stream(stream)
-    fl = int(flags) | (SQ_FOCUS_ACCUMULATE if accumulate else 0)
-    _check(L.sq_fuse_project_focus(C.byref(a), C.byref(f), fl, _stream_ptr(stream)), 'sq_fuse_project_focus')
+    with _on_stream(stream):
+        keep = []
+        if torch.is_tensor(z_levels) and z_levels.is_cuda:
+            zl = z_levels.to(torch.int32)
+        else:
+            zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
+            if any(not 0 <= z < 2 ** 32 for z in zs):
+                raise ValueError("z levels must lie in 0 .. 2^32 - 1")
+            zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
+        if zl.numel() != n_planes:
+            raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
+        keep.append(zl)
+        need = focus_scratch_bytes(plan.n_tiles, plan.tile_h, plan.tile_w)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=out.device)
+        elif scratch.numel() * scratch.element_size() < need or not scratch.is_cuda:
+            raise ValueError(f"focus scratch must be a device tensor of at least {need} bytes")
+        keep.append(scratch)
+        a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
+        a.flags, a.grid_blocks = 0, int(grid_blocks)
+        f = _FocusArgs()
+        f.z_levels_dev = zl.data_ptr()
+        f.radius = int(radius)
+        f.scratch_dev, f.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
+        f.key_dev, f.key_pitch = key.data_ptr(), key_pitch
+        if stream is not None:
+            for t in keep:
+                t.record_stream(stream)
+        fl = int(flags) | (SQ_FOCUS_ACCUMULATE if accumulate else 0)
+        _check(L.sq_fuse_project_focus(C.byref(a), C.byref(f), fl, _stream_ptr(stream)), 'sq_fuse_project_focus')
 
 
 def depth_of_keys(key):
@@ -640,17 +655,18 @@ def focus_depth_plane(key, out=None, dtype=None, stream=None):
         raise ValueError("key must be a [Hc, Wc] int64 device tensor")
     shape = tuple(key.shape)
     _check_plane('key', key, shape)
-    if out is None:
-        out = torch.empty(shape, dtype=torch_dtype_of(np.dtype(dtype or 'uint8')), device=key.device)
-    elif dtype is not None and np_dtype_of_torch(out.dtype) != np.dtype(dtype):
-        raise ValueError(f"out is {out.dtype}, dtype asks for {np.dtype(dtype)}")
-    _check_plane('out', out, shape)
-    if out.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError("the depth plane is uint8 or uint16")
-    h, w = shape
-    _check(lib().sq_focus_depth_plane(key.data_ptr(), int(key.stride(0)) if h > 1 else w, h, w, out.data_ptr(),
-                                      int(out.stride(0)) if h > 1 else w, sq_dtype_of(np_dtype_of_torch(out.dtype)),
-                                      _stream_ptr(stream)), 'sq_focus_depth_plane')
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty(shape, dtype=torch_dtype_of(np.dtype(dtype or 'uint8')), device=key.device)
+        elif dtype is not None and np_dtype_of_torch(out.dtype) != np.dtype(dtype):
+            raise ValueError(f"out is {out.dtype}, dtype asks for {np.dtype(dtype)}")
+        _check_plane('out', out, shape)
+        if out.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError("the depth plane is uint8 or uint16")
+        h, w = shape
+        _check(lib().sq_focus_depth_plane(key.data_ptr(), int(key.stride(0)) if h > 1 else w, h, w, out.data_ptr(),
+                                          int(out.stride(0)) if h > 1 else w, sq_dtype_of(np_dtype_of_torch(out.dtype)),
+                                          _stream_ptr(stream)), 'sq_focus_depth_plane')
     return out
 
 
@@ -686,27 +702,28 @@ def fuse_select_depth(plan: FusePlan, tiles, out, depth, z_levels, flats=None, a
         raise ValueError("tiles or tile_ptrs is required")
     if not 1 <= n_planes <= SQ_FOCUS_MAX_PLANES:
         raise ValueError(f"{n_planes} planes: a call selects among 1..{SQ_FOCUS_MAX_PLANES}")
-    keep = []
-    if torch.is_tensor(z_levels) and z_levels.is_cuda:
-        zl = z_levels.to(torch.int32)
-    else:
-        zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
-        if any(not 0 <= z < 2 ** 32 for z in zs):
-            raise ValueError("z levels must lie in 0 .. 2^32 - 1")
-        if len(set(zs)) != len(zs):
-            raise ValueError("the z levels of a call must be distinct")
-        zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
-    if zl.numel() != n_planes:
-        raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
-    keep.append(zl)
-    a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
-    a.flags, a.grid_blocks = 0, int(grid_blocks)
-    if stream is not None:
-        for t in keep:
-            t.record_stream(stream)
-    fl = int(flags) | (SQ_SELECT_ACCUMULATE if accumulate else 0)
-    _check(L.sq_fuse_select_depth(C.byref(a), depth.data_ptr(), depth_pitch, sq_dtype_of(np_dtype_of_torch(depth.dtype)),
-                                  zl.data_ptr(), fl, _stream_ptr(stream)), 'sq_fuse_select_depth')
+    with _on_stream(stream):
+        keep = []
+        if torch.is_tensor(z_levels) and z_levels.is_cuda:
+            zl = z_levels.to(torch.int32)
+        else:
+            zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
+            if any(not 0 <= z < 2 ** 32 for z in zs):
+                raise ValueError("z levels must lie in 0 .. 2^32 - 1")
+            if len(set(zs)) != len(zs):
+                raise ValueError("the z levels of a call must be distinct")
+            zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
+        if zl.numel() != n_planes:
+            raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
+        keep.append(zl)
+        a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
+        a.flags, a.grid_blocks = 0, int(grid_blocks)
+        if stream is not None:
+            for t in keep:
+                t.record_stream(stream)
+        fl = int(flags) | (SQ_SELECT_ACCUMULATE if accumulate else 0)
+        _check(L.sq_fuse_select_depth(C.byref(a), depth.data_ptr(), depth_pitch, sq_dtype_of(np_dtype_of_torch(depth.dtype)),
+                                      zl.data_ptr(), fl, _stream_ptr(stream)), 'sq_fuse_select_depth')
 
 
 PLANE_ALIGN_BYTES = 128
@@ -860,9 +877,10 @@ def tile_minmax(tiles, stream=None, tile_ptrs=None, shape=None, np_dtype=None):
     L = lib()
     ptrs, base, stride, n, h, w, dt = _tile_table(tiles, tile_ptrs, shape, np_dtype)
     device = tile_ptrs.device if tile_ptrs is not None else tiles.device
-    out = torch.empty((n, 2), dtype=torch.int32, device=device)
-    _check(L.sq_tile_minmax(ptrs, base, stride, n, h, w, w, dt, out.data_ptr(), _stream_ptr(stream)),
-           'sq_tile_minmax')
+    with _on_stream(stream):
+        out = torch.empty((n, 2), dtype=torch.int32, device=device)
+        _check(L.sq_tile_minmax(ptrs, base, stride, n, h, w, w, dt, out.data_ptr(), _stream_ptr(stream)),
+               'sq_tile_minmax')
     return out
 
 
@@ -882,27 +900,28 @@ def pair_overlap_moments(tiles, windows, out=None, stream=None, tile_ptrs=None, 
     if win.dtype != OVERLAP_DTYPE:
         win = np.ascontiguousarray(win, dtype=np.int32).reshape(-1, 8).view(OVERLAP_DTYPE).reshape(-1)
     win = np.ascontiguousarray(win)
-    if out is None:
-        out = torch.empty((len(win), 5), dtype=torch.int64, device=device)
-    if tuple(out.shape) != (len(win), 5) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
-        raise ValueError(f"out must be a contiguous int64 [{len(win)}, 5] tensor on {device}")
-    if len(win) == 0:
-        return out
-    win_dev = upload_small(torch.from_numpy(win.view(np.uint8).reshape(-1)), device)
-    # the C entry point takes up to OVERLAP_BATCH windows per call (the pair is its grid's y dimension); every window is
-    # checked before the first batch is launched, so a bad one still leaves ``out`` untouched
-    bad = ((win['ref_tile'] < 0) | (win['ref_tile'] >= n) | (win['mov_tile'] < 0) | (win['mov_tile'] >= n) | (win['h'] < 0)
-           | (win['w'] < 0) | (win['ref_y0'] < 0) | (win['ref_x0'] < 0) | (win['mov_y0'] < 0) | (win['mov_x0'] < 0)
-           | (win['ref_y0'].astype(np.int64) + win['h'] > h) | (win['mov_y0'].astype(np.int64) + win['h'] > h)
-           | (win['ref_x0'].astype(np.int64) + win['w'] > w) | (win['mov_x0'].astype(np.int64) + win['w'] > w))
-    if len(win) > OVERLAP_BATCH and bad.any():
-        raise NativeError(f"sq_pair_overlap_moments: window {int(np.flatnonzero(bad)[0])} leaves its tile or names no tile")
-    for i in range(0, len(win), OVERLAP_BATCH):
-        k = min(OVERLAP_BATCH, len(win) - i)
-        _check(L.sq_pair_overlap_moments(ptrs, base, stride, n, h, w, w, dt, win_dev.data_ptr() + i * OVERLAP_DTYPE.itemsize, k,
-                                         out.data_ptr() + i * 5 * 8, _stream_ptr(stream)), 'sq_pair_overlap_moments')
-    if stream is not None:
-        win_dev.record_stream(stream)
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty((len(win), 5), dtype=torch.int64, device=device)
+        if tuple(out.shape) != (len(win), 5) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != device:
+            raise ValueError(f"out must be a contiguous int64 [{len(win)}, 5] tensor on {device}")
+        if len(win) == 0:
+            return out
+        win_dev = upload_small(torch.from_numpy(win.view(np.uint8).reshape(-1)), device)
+        # the C entry point takes up to OVERLAP_BATCH windows per call (the pair is its grid's y dimension); every window is
+        # checked before the first batch is launched, so a bad one still leaves ``out`` untouched
+        bad = ((win['ref_tile'] < 0) | (win['ref_tile'] >= n) | (win['mov_tile'] < 0) | (win['mov_tile'] >= n) | (win['h'] < 0)
+               | (win['w'] < 0) | (win['ref_y0'] < 0) | (win['ref_x0'] < 0) | (win['mov_y0'] < 0) | (win['mov_x0'] < 0)
+               | (win['ref_y0'].astype(np.int64) + win['h'] > h) | (win['mov_y0'].astype(np.int64) + win['h'] > h)
+               | (win['ref_x0'].astype(np.int64) + win['w'] > w) | (win['mov_x0'].astype(np.int64) + win['w'] > w))
+        if len(win) > OVERLAP_BATCH and bad.any():
+            raise NativeError(f"sq_pair_overlap_moments: window {int(np.flatnonzero(bad)[0])} leaves its tile or names no tile")
+        for i in range(0, len(win), OVERLAP_BATCH):
+            k = min(OVERLAP_BATCH, len(win) - i)
+            _check(L.sq_pair_overlap_moments(ptrs, base, stride, n, h, w, w, dt, win_dev.data_ptr() + i * OVERLAP_DTYPE.itemsize, k,
+                                             out.data_ptr() + i * 5 * 8, _stream_ptr(stream)), 'sq_pair_overlap_moments')
+        if stream is not None:
+            win_dev.record_stream(stream)
     return out
 
 
@@ -911,11 +930,12 @@ def normalize_tiles(tiles, minmax=None, stream=None):
     import torch
     L = lib()
     n, h, w = (int(v) for v in tiles.shape)
-    if minmax is None:
-        minmax = tile_minmax(tiles, stream)
-    out = torch.empty_like(tiles)
-    _check(L.sq_normalize_tiles(None, tiles.data_ptr(), h * w, n, h, w, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
-                                minmax.data_ptr(), out.data_ptr(), _stream_ptr(stream)), 'sq_normalize_tiles')
+    with _on_stream(stream):
+        if minmax is None:
+            minmax = tile_minmax(tiles, stream)
+        out = torch.empty_like(tiles)
+        _check(L.sq_normalize_tiles(None, tiles.data_ptr(), h * w, n, h, w, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
+                                    minmax.data_ptr(), out.data_ptr(), _stream_ptr(stream)), 'sq_normalize_tiles')
     return out
 
 
@@ -930,17 +950,18 @@ def downsample2(planes, out=None, stream=None):
     if planes.stride(2) != 1 and planes.shape[2] > 1:
         raise ValueError("planes rows must be contiguous")
     n, h, w = (int(v) for v in planes.shape)
-    if out is None:
-        out = torch.empty((n, h // 2, w // 2), dtype=planes.dtype, device=planes.device)
-    if tuple(out.shape) != (n, h // 2, w // 2) or out.dtype != planes.dtype or out.device != planes.device:
-        raise ValueError(f"out must be a {(n, h // 2, w // 2)} tensor of the input's dtype and device")
-    if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
-        raise ValueError("out rows must be contiguous")
-    if out.numel() == 0:
-        return out
-    _check(L.sq_downsample2(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), out.data_ptr(), out.stride(0),
-                            out.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)), _stream_ptr(stream)),
-           'sq_downsample2')
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty((n, h // 2, w // 2), dtype=planes.dtype, device=planes.device)
+        if tuple(out.shape) != (n, h // 2, w // 2) or out.dtype != planes.dtype or out.device != planes.device:
+            raise ValueError(f"out must be a {(n, h // 2, w // 2)} tensor of the input's dtype and device")
+        if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
+            raise ValueError("out rows must be contiguous")
+        if out.numel() == 0:
+            return out
+        _check(L.sq_downsample2(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), out.data_ptr(), out.stride(0),
+                                out.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)), _stream_ptr(stream)),
+               'sq_downsample2')
     return out
 
 
@@ -969,24 +990,25 @@ def pyramid_mean(planes, n_levels, out=None, stream=None):
     shapes = []
     while len(shapes) < n_levels and (h >> (len(shapes) + 1)) > 0 and (w >> (len(shapes) + 1)) > 0:
         shapes.append((n, h >> (len(shapes) + 1), w >> (len(shapes) + 1)))
-    if out is None:
-        out = [torch.empty(s, dtype=planes.dtype, device=planes.device) for s in shapes]
-    out = list(out)
-    if len(out) != len(shapes):
-        raise ValueError(f"out must hold {len(shapes)} tensors (the levels of a {(n, h, w)} stack that exist), got {len(out)}")
-    for s, o in zip(shapes, out):
-        if tuple(o.shape) != s or o.dtype != planes.dtype or o.device != planes.device:
-            raise ValueError(f"out must be {shapes} tensors of the input's dtype and device")
-        if o.stride(2) != 1 and o.shape[2] > 1:
-            raise ValueError("out rows must be contiguous")
-    if not shapes or n == 0:
-        return out
-    k = len(shapes)
-    ptrs = (C.c_void_p * k)(*[o.data_ptr() for o in out])
-    strides = (C.c_int64 * k)(*[o.stride(0) for o in out])
-    pitches = (C.c_int64 * k)(*[o.stride(1) for o in out])
-    _check(L.sq_pyramid_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), ptrs, strides, pitches, k, n, dtype,
-                             _stream_ptr(stream)), 'sq_pyramid_mean')
+    with _on_stream(stream):
+        if out is None:
+            out = [torch.empty(s, dtype=planes.dtype, device=planes.device) for s in shapes]
+        out = list(out)
+        if len(out) != len(shapes):
+            raise ValueError(f"out must hold {len(shapes)} tensors (the levels of a {(n, h, w)} stack that exist), got {len(out)}")
+        for s, o in zip(shapes, out):
+            if tuple(o.shape) != s or o.dtype != planes.dtype or o.device != planes.device:
+                raise ValueError(f"out must be {shapes} tensors of the input's dtype and device")
+            if o.stride(2) != 1 and o.shape[2] > 1:
+                raise ValueError("out rows must be contiguous")
+        if not shapes or n == 0:
+            return out
+        k = len(shapes)
+        ptrs = (C.c_void_p * k)(*[o.data_ptr() for o in out])
+        strides = (C.c_int64 * k)(*[o.stride(0) for o in out])
+        pitches = (C.c_int64 * k)(*[o.stride(1) for o in out])
+        _check(L.sq_pyramid_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), ptrs, strides, pitches, k, n, dtype,
+                                 _stream_ptr(stream)), 'sq_pyramid_mean')
     return out
 
 
@@ -1018,24 +1040,25 @@ def histogram_planes(planes, rows, hist=None, n_rows=None, stream=None):
     rows = [int(r) for r in rows]
     if len(rows) != n:
         raise ValueError(f"{n} planes, {len(rows)} rows given")
-    if hist is None:
-        if n_rows is None:
-            n_rows = max(rows) + 1 if rows else 1
-        hist = torch.zeros((int(n_rows), bins), dtype=torch.int64, device=planes.device)
-    if hist.dim() != 2 or hist.shape[1] != bins or hist.dtype != torch.int64 or hist.device != planes.device or \
-            not hist.is_contiguous():
-        raise ValueError(f"hist must be a contiguous int64 [n_rows, {bins}] tensor on the planes' device")
-    if n_rows is not None and int(n_rows) != hist.shape[0]:
-        raise ValueError(f"hist has {hist.shape[0]} rows, n_rows = {n_rows}")
-    if n == 0 or h == 0 or w == 0:
-        if any(not 0 <= r < hist.shape[0] for r in rows):
+    with _on_stream(stream):
+        if hist is None:
+            if n_rows is None:
+                n_rows = max(rows) + 1 if rows else 1
+            hist = torch.zeros((int(n_rows), bins), dtype=torch.int64, device=planes.device)
+        if hist.dim() != 2 or hist.shape[1] != bins or hist.dtype != torch.int64 or hist.device != planes.device or \
+                not hist.is_contiguous():
+            raise ValueError(f"hist must be a contiguous int64 [n_rows, {bins}] tensor on the planes' device")
+        if n_rows is not None and int(n_rows) != hist.shape[0]:
+            raise ValueError(f"hist has {hist.shape[0]} rows, n_rows = {n_rows}")
+        if n == 0 or h == 0 or w == 0:
+            if any(not 0 <= r < hist.shape[0] for r in rows):
+                raise ValueError(f"rows must lie in [0, {hist.shape[0]})")
+            return hist
+        table = (C.c_int32 * n)(*rows) if all(-2 ** 31 <= r < 2 ** 31 for r in rows) else None
+        if table is None:
             raise ValueError(f"rows must lie in [0, {hist.shape[0]})")
-        return hist
-    table = (C.c_int32 * n)(*rows) if all(-2 ** 31 <= r < 2 ** 31 for r in rows) else None
-    if table is None:
-        raise ValueError(f"rows must lie in [0, {hist.shape[0]})")
-    _check(L.sq_histogram_planes(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype), table,
-                                 int(hist.shape[0]), hist.data_ptr(), _stream_ptr(stream)), 'sq_histogram_planes')
+        _check(L.sq_histogram_planes(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype), table,
+                                     int(hist.shape[0]), hist.data_ptr(), _stream_ptr(stream)), 'sq_histogram_planes')
     return hist
 
 
@@ -1068,16 +1091,17 @@ def block_mean(planes, k, out=None, rows=None, stream=None):
     y0, y1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
     if not (0 <= y0 <= y1 <= h) or y0 % f or ((y1 - y0) % f and y1 != h):
         raise ValueError(f"rows {rows} of {h}: a band starts on a multiple of {f} and is a multiple of it long, or runs to the last row")
-    if out is None:
-        out = (torch.empty if (y0, y1) == (0, h) else torch.zeros)(shape, dtype=planes.dtype, device=planes.device)
-    if tuple(out.shape) != shape or out.dtype != planes.dtype or out.device != planes.device:
-        raise ValueError(f"out must be a {shape} tensor of the input's dtype and device")
-    if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
-        raise ValueError("out rows must be contiguous")
-    if n == 0 or h == 0 or w == 0 or y1 == y0:
-        return out
-    _check(L.sq_block_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)),
-                           k, y0, y1 - y0, out.data_ptr(), out.stride(0), out.stride(1), _stream_ptr(stream)), 'sq_block_mean')
+    with _on_stream(stream):
+        if out is None:
+            out = (torch.empty if (y0, y1) == (0, h) else torch.zeros)(shape, dtype=planes.dtype, device=planes.device)
+        if tuple(out.shape) != shape or out.dtype != planes.dtype or out.device != planes.device:
+            raise ValueError(f"out must be a {shape} tensor of the input's dtype and device")
+        if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
+            raise ValueError("out rows must be contiguous")
+        if n == 0 or h == 0 or w == 0 or y1 == y0:
+            return out
+        _check(L.sq_block_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)),
+                               k, y0, y1 - y0, out.data_ptr(), out.stride(0), out.stride(1), _stream_ptr(stream)), 'sq_block_mean')
     return out
 
 
@@ -1107,19 +1131,20 @@ def composite_render(means, windows, colors, out=None, stream=None):
         raise ValueError(f"windows must satisfy 0 <= start < end <= 65535, got {windows}")
     if any(not 0 <= c <= 0xFFFFFF for c in colors):
         raise ValueError(f"colours are 0xRRGGBB, got {colors}")
-    if out is None:
-        out = torch.empty((h, w, 3), dtype=torch.uint8, device=means.device)
-    if tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != means.device:
-        raise ValueError(f"out must be a uint8 {(h, w, 3)} tensor on the planes' device")
-    if out.numel() and (out.stride(2) != 1 or out.stride(1) != 3):
-        raise ValueError("out pixels must be contiguous (strides (pitch, 3, 1))")
-    if h == 0 or w == 0:
-        return out
-    win = (C.c_int32 * (2 * n))(*[v for ab in windows for v in ab])
-    col = (C.c_uint32 * n)(*colors)
-    _check(L.sq_composite_render(means.data_ptr(), means.stride(0), h, w, means.stride(1), n,
-                                 sq_dtype_of(np_dtype_of_torch(means.dtype)), win, col, out.data_ptr(), out.stride(0),
-                                 _stream_ptr(stream)), 'sq_composite_render')
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.uint8, device=means.device)
+        if tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or out.device != means.device:
+            raise ValueError(f"out must be a uint8 {(h, w, 3)} tensor on the planes' device")
+        if out.numel() and (out.stride(2) != 1 or out.stride(1) != 3):
+            raise ValueError("out pixels must be contiguous (strides (pitch, 3, 1))")
+        if h == 0 or w == 0:
+            return out
+        win = (C.c_int32 * (2 * n))(*[v for ab in windows for v in ab])
+        col = (C.c_uint32 * n)(*colors)
+        _check(L.sq_composite_render(means.data_ptr(), means.stride(0), h, w, means.stride(1), n,
+                                     sq_dtype_of(np_dtype_of_torch(means.dtype)), win, col, out.data_ptr(), out.stride(0),
+                                     _stream_ptr(stream)), 'sq_composite_render')
     return out
 
 
@@ -1180,20 +1205,21 @@ def tophat_tiles(tiles, radius: int, scratch=None, stream=None):
             raise ValueError("the planes of tiles overlap")
     np_dtype = np_dtype_of_torch(tiles.dtype)
     need = tophat_scratch_bytes(n_images, h, w, np_dtype)
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=tiles.device)
-        if stream is not None:
-            scratch.record_stream(stream)
-    elif not torch.is_tensor(scratch) or not scratch.is_cuda or not scratch.is_contiguous() or \
-            scratch.numel() * scratch.element_size() < need:
-        raise ValueError(f"top-hat scratch must be a contiguous device tensor of at least {need} bytes")
-    if scratch.data_ptr() % 16:
-        raise ValueError("top-hat scratch must be aligned to 16 bytes")
-    if n_images == 0:
-        return tiles
-    _check(lib().sq_tophat_tiles(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype), int(radius),
-                                 scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream_ptr(stream)),
-           'sq_tophat_tiles')
+    with _on_stream(stream):
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.uint8, device=tiles.device)
+            if stream is not None:
+                scratch.record_stream(stream)
+        elif not torch.is_tensor(scratch) or not scratch.is_cuda or not scratch.is_contiguous() or \
+                scratch.numel() * scratch.element_size() < need:
+            raise ValueError(f"top-hat scratch must be a contiguous device tensor of at least {need} bytes")
+        if scratch.data_ptr() % 16:
+            raise ValueError("top-hat scratch must be aligned to 16 bytes")
+        if n_images == 0:
+            return tiles
+        _check(lib().sq_tophat_tiles(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype), int(radius),
+                                     scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream_ptr(stream)),
+               'sq_tophat_tiles')
     return tiles
 
 
@@ -1256,31 +1282,32 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
     if not isinstance(mode, str) or mode not in DESPECKLE_MODES:
         raise ValueError(f"despeckle mode must be 'hot' or 'both', got {mode!r}")
     n_images, h, w, src_plane_stride, src_pitch = _plane_layout(tiles, 'tiles')
-    if out is None:
-        out = torch.empty(tuple(tiles.shape), dtype=tiles.dtype, device=tiles.device)
-        if stream is not None:
-            out.record_stream(stream)
-    elif not torch.is_tensor(out) or tuple(out.shape) != tuple(tiles.shape) or out.dtype != tiles.dtype or \
-            out.device != tiles.device:
-        raise ValueError(f"out must be a {tiles.dtype} tensor of shape {tuple(tiles.shape)} on the tiles' device")
-    n_out, _, _, dst_plane_stride, dst_pitch = _plane_layout(out, 'out')
-    assert n_out == n_images
-    if counts is not None:
-        if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.device != tiles.device or \
-                counts.numel() != n_images or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous int64 tensor of {n_images} elements on the tiles' device")
-    if n_images == 0:
-        return out
-    es = tiles.element_size()
-    s0, d0 = tiles.data_ptr(), out.data_ptr()
-    s1 = s0 + ((n_images - 1) * src_plane_stride + (h - 1) * src_pitch + w) * es
-    d1 = d0 + ((n_images - 1) * dst_plane_stride + (h - 1) * dst_pitch + w) * es
-    if s0 < d1 and d0 < s1:
-        raise ValueError("out shares memory with tiles: the filter is out of place")
-    _check(lib().sq_despeckle_tiles(s0, d0, n_images, h, w, src_plane_stride, src_pitch, dst_plane_stride, dst_pitch,
-                                    sq_dtype_of(np_dtype_of_torch(tiles.dtype)), DESPECKLE_MODES[mode], int(threshold),
-                                    None if counts is None else counts.data_ptr(), _stream_ptr(stream)),
-           'sq_despeckle_tiles')
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty(tuple(tiles.shape), dtype=tiles.dtype, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or tuple(out.shape) != tuple(tiles.shape) or out.dtype != tiles.dtype or \
+                out.device != tiles.device:
+            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {tuple(tiles.shape)} on the tiles' device")
+        n_out, _, _, dst_plane_stride, dst_pitch = _plane_layout(out, 'out')
+        assert n_out == n_images
+        if counts is not None:
+            if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.device != tiles.device or \
+                    counts.numel() != n_images or not counts.is_contiguous():
+                raise ValueError(f"counts must be a contiguous int64 tensor of {n_images} elements on the tiles' device")
+        if n_images == 0:
+            return out
+        es = tiles.element_size()
+        s0, d0 = tiles.data_ptr(), out.data_ptr()
+        s1 = s0 + ((n_images - 1) * src_plane_stride + (h - 1) * src_pitch + w) * es
+        d1 = d0 + ((n_images - 1) * dst_plane_stride + (h - 1) * dst_pitch + w) * es
+        if s0 < d1 and d0 < s1:
+            raise ValueError("out shares memory with tiles: the filter is out of place")
+        _check(lib().sq_despeckle_tiles(s0, d0, n_images, h, w, src_plane_stride, src_pitch, dst_plane_stride, dst_pitch,
+                                        sq_dtype_of(np_dtype_of_torch(tiles.dtype)), DESPECKLE_MODES[mode], int(threshold),
+                                        None if counts is None else counts.data_ptr(), _stream_ptr(stream)),
+               'sq_despeckle_tiles')
     return out
 
 
@@ -1303,17 +1330,18 @@ def tile_stats(tiles, out=None, stream=None):
     if tiles.dtype not in (torch.uint8, torch.uint16):
         raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
     n_images, h, w, plane_stride, pitch = _plane_layout(tiles, 'tiles')
-    if out is None:
-        out = torch.empty((n_images, SQ_TILE_STATS_WORDS), dtype=torch.int64, device=tiles.device)
-        if stream is not None:
-            out.record_stream(stream)
-    elif not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != tiles.device or \
-            tuple(out.shape) != (n_images, SQ_TILE_STATS_WORDS) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous int64 tensor of shape ({n_images}, {SQ_TILE_STATS_WORDS}) on the tiles' device")
-    if n_images == 0:
-        return out
-    _check(lib().sq_tile_stats(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
-                               out.data_ptr(), _stream_ptr(stream)), 'sq_tile_stats')
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty((n_images, SQ_TILE_STATS_WORDS), dtype=torch.int64, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != tiles.device or \
+                tuple(out.shape) != (n_images, SQ_TILE_STATS_WORDS) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 tensor of shape ({n_images}, {SQ_TILE_STATS_WORDS}) on the tiles' device")
+        if n_images == 0:
+            return out
+        _check(lib().sq_tile_stats(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
+                                   out.data_ptr(), _stream_ptr(stream)), 'sq_tile_stats')
     return out
 
 
@@ -1425,27 +1453,28 @@ def register_pairs_async(tiles, minmax, pairs: np.ndarray, n0: int, n1: int, ups
             or (pairs['mov_y0'] + n0 > h).any() or (pairs['ref_x0'] + n1 > w).any()
             or (pairs['mov_x0'] + n1 > w).any()):
         raise ValueError("crop reaches outside its tile")
-    ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=device)
-    pairs_dev = upload_small(torch.from_numpy(pairs.view(np.uint8).reshape(-1)), device)
-    res_dev = torch.zeros(npairs * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
-    a = _RegisterArgs()
-    a.tile_ptrs_dev = ptrs
-    a.tile_base_dev = base
-    a.tile_stride = stride
-    a.n_tiles, a.tile_h, a.tile_w, a.tile_pitch = n, h, w, w
-    a.tile_dtype = dt
-    a.minmax_dev = minmax.data_ptr()
-    a.pairs_dev = pairs_dev.data_ptr()
-    a.n_pairs = npairs
-    a.n0, a.n1 = int(n0), int(n1)
-    a.upsample_factor = int(upsample_factor)
-    a.normalization = int(normalization)
-    a.results_dev = res_dev.data_ptr()
-    a.workspace_dev = ws.data_ptr()
-    a.workspace_bytes = ws.numel()
-    _check(L.sq_register_pairs(C.byref(a), _stream_ptr(stream)), 'sq_register_pairs')
-    done = torch.cuda.Event()
-    done.record(stream if stream is not None else torch.cuda.current_stream())
+    with _on_stream(stream):
+        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=device)
+        pairs_dev = upload_small(torch.from_numpy(pairs.view(np.uint8).reshape(-1)), device)
+        res_dev = torch.zeros(npairs * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        a = _RegisterArgs()
+        a.tile_ptrs_dev = ptrs
+        a.tile_base_dev = base
+        a.tile_stride = stride
+        a.n_tiles, a.tile_h, a.tile_w, a.tile_pitch = n, h, w, w
+        a.tile_dtype = dt
+        a.minmax_dev = minmax.data_ptr()
+        a.pairs_dev = pairs_dev.data_ptr()
+        a.n_pairs = npairs
+        a.n0, a.n1 = int(n0), int(n1)
+        a.upsample_factor = int(upsample_factor)
+        a.normalization = int(normalization)
+        a.results_dev = res_dev.data_ptr()
+        a.workspace_dev = ws.data_ptr()
+        a.workspace_bytes = ws.numel()
+        _check(L.sq_register_pairs(C.byref(a), _stream_ptr(stream)), 'sq_register_pairs')
+        done = torch.cuda.Event()
+        done.record(stream if stream is not None else torch.cuda.current_stream())
     return PendingRegistration(res_dev, (ws, pairs_dev, minmax, tiles, tile_ptrs), npairs, done)
 
 
@@ -1528,12 +1557,13 @@ def blosc_encode_planes(planes, chunk_h: int, chunk_w: int, buffers: Optional[Bl
         raise ValueError("planes must be a [n, H, W] device tensor with unit-stride rows")
     n, h, w = (int(v) for v in planes.shape)
     npdt = np_dtype_of_torch(planes.dtype)
-    if buffers is None or buffers.geometry != (n, h, w, sq_dtype_of(npdt), int(chunk_h), int(chunk_w)):
-        buffers = BloscBuffers(n, h, w, npdt, chunk_h, chunk_w, planes.device)
-    _check(L.sq_blosc_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h, w,
-                                    sq_dtype_of(npdt), int(chunk_h), int(chunk_w), buffers.scratch.data_ptr(),
-                                    buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(), buffers.out.numel(),
-                                    buffers.status.data_ptr(), _stream_ptr(stream)), 'sq_blosc_encode_planes')
+    with _on_stream(stream):
+        if buffers is None or buffers.geometry != (n, h, w, sq_dtype_of(npdt), int(chunk_h), int(chunk_w)):
+            buffers = BloscBuffers(n, h, w, npdt, chunk_h, chunk_w, planes.device)
+        _check(L.sq_blosc_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h, w,
+                                        sq_dtype_of(npdt), int(chunk_h), int(chunk_w), buffers.scratch.data_ptr(),
+                                        buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(), buffers.out.numel(),
+                                        buffers.status.data_ptr(), _stream_ptr(stream)), 'sq_blosc_encode_planes')
     return buffers
 
 
@@ -1552,12 +1582,13 @@ def basic_fit(tiles, smoothness_flatfield: float = 1.0, stream=None):
     need = L.sq_basic_workspace_bytes(n, h, w)
     if need < 0:
         raise NativeError(f"sq_basic_workspace_bytes failed: {L.sq_last_error().decode()}")
-    ws = torch.empty(int(need), dtype=torch.uint8, device=tiles.device)
-    out = torch.empty((h, w), dtype=torch.float32, device=tiles.device)
-    info = _BasicInfo()
-    _check(L.sq_basic_fit(None, tiles.data_ptr(), h * w, n, h, w, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
-                          float(smoothness_flatfield), out.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(info),
-                          _stream_ptr(stream)), 'sq_basic_fit')
+    with _on_stream(stream):
+        ws = torch.empty(int(need), dtype=torch.uint8, device=tiles.device)
+        out = torch.empty((h, w), dtype=torch.float32, device=tiles.device)
+        info = _BasicInfo()
+        _check(L.sq_basic_fit(None, tiles.data_ptr(), h * w, n, h, w, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
+                              float(smoothness_flatfield), out.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(info),
+                              _stream_ptr(stream)), 'sq_basic_fit')
     return out, {'reweight_iterations': info.reweight_iterations, 'ladmap_iterations': info.ladmap_iterations,
                  'working_size': info.working_size, 'capped_rounds': info.capped_rounds}
 
@@ -1604,11 +1635,12 @@ def synth_tiles(desc: np.ndarray, tile_h: int, tile_w: int, noise_amp: int, np_d
     L = lib()
     desc = np.ascontiguousarray(desc, dtype=SYNTH_DTYPE)
     n = len(desc)
-    if out is None:
-        out = torch.empty((n, tile_h, tile_w), dtype=torch_dtype_of(np_dtype), device=device)
-    d = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(device)
-    for i0 in range(0, n, 32768):   # grid.z limit
-        i1 = min(n, i0 + 32768)
-        _check(L.sq_synth_tiles(d.data_ptr() + i0 * SYNTH_DTYPE.itemsize, i1 - i0, tile_h, tile_w, noise_amp,
-                                sq_dtype_of(np_dtype), out[i0:].data_ptr(), _stream_ptr(stream)), 'sq_synth_tiles')
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty((n, tile_h, tile_w), dtype=torch_dtype_of(np_dtype), device=device)
+        d = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(device)
+        for i0 in range(0, n, 32768):   # grid.z limit
+            i1 = min(n, i0 + 32768)
+            _check(L.sq_synth_tiles(d.data_ptr() + i0 * SYNTH_DTYPE.itemsize, i1 - i0, tile_h, tile_w, noise_amp,
+                                    sq_dtype_of(np_dtype), out[i0:].data_ptr(), _stream_ptr(stream)), 'sq_synth_tiles')
     return out
