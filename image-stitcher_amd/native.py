@@ -214,6 +214,20 @@ def _check(status: int, what: str) -> None:
         raise NativeError(f"{what} failed ({status}): {lib().sq_last_error().decode()}", status)
 
 
+def _size(n, what: str) -> int:
+    """The result of a size query (sq_*_bytes and their like): a negative one is the status of a query that failed."""
+    n = int(n)
+    _check(n, what)
+    return n
+
+
+def _int_in(value, lo: int, hi: int, what: str) -> int:
+    """``value`` as an int when it is a Python or numpy integer (no bool, no float) in lo..hi; ValueError otherwise."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(f"{what} must be an integer in {lo}..{hi}, got {value!r}")
+    return int(value)
+
+
 def sq_dtype_of(np_dtype) -> int:
     dt = np.dtype(np_dtype)
     table = {np.dtype('uint8'): SQ_U8, np.dtype('uint16'): SQ_U16, np.dtype('float32'): SQ_F32,
@@ -339,9 +353,7 @@ class FusePlan:
             with torch.cuda.device(dev.device):
                 side = _copy_stream(dev.device)
                 if self.expand_on_device:
-                    need = int(lib().sq_fuse_plan_expand_scratch_bytes(self._h))
-                    if need < 0:
-                        raise NativeError(f"sq_fuse_plan_expand_scratch_bytes failed: {lib().sq_last_error().decode()}")
+                    need = _size(lib().sq_fuse_plan_expand_scratch_bytes(self._h), 'sq_fuse_plan_expand_scratch_bytes')
                     with torch.cuda.stream(side):      # written and read on the side stream only, dropped on return
                         scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev.device)
                     _check(lib().sq_fuse_plan_expand(self._h, dev.data_ptr(), dev.numel(), scratch.data_ptr(), scratch.numel(),
@@ -466,6 +478,59 @@ def _fuse_args(plan: FusePlan, tiles, n_planes: int, out, plane_stride: int, pit
     return a
 
 
+def _fuse_launch(name: str, stream, keep, plan: FusePlan, tiles, n_planes: int, out, plane_stride: int, pitch: int, flats, tile_ptrs,
+                 flat_ptrs, *rest, flags: int = 0, grid_blocks: int = 0) -> None:
+    """The launch every fuse wrapper ends with, called inside its ``_on_stream(stream)``: the sq_fuse_args (``_fuse_args``) with
+    ``flags`` and ``grid_blocks``, everything in ``keep`` (the wrapper's own buffers and the ones made here) recorded on
+    ``stream``, then entry point ``name``(args, *rest, stream)."""
+    a = _fuse_args(plan, tiles, n_planes, out, plane_stride, pitch, flats, tile_ptrs, flat_ptrs, keep)
+    a.flags, a.grid_blocks = int(flags), int(grid_blocks)
+    if stream is not None:      # launched on another stream than the one the helpers above allocated for
+        for t in keep:
+            t.record_stream(stream)
+    _check(getattr(lib(), name)(C.byref(a), *rest, _stream_ptr(stream)), name)
+
+
+def _check_plane(name, t, shape) -> int:
+    """The row pitch of ``t``, a [Hc, Wc] device tensor of this shape with unit-stride rows; ValueError otherwise."""
+    if not t.is_cuda or t.dim() != 2 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a [{shape[0]}, {shape[1]}] device tensor")
+    if (shape[1] > 1 and t.stride(1) != 1) or (shape[0] > 1 and t.stride(0) < shape[1]):
+        raise ValueError(f"{name} must have unit-stride rows")
+    return int(t.stride(0)) if shape[0] > 1 else int(shape[1])
+
+
+def _projected_planes(plan, tiles, tile_ptrs, flats) -> int:
+    """The number of z planes a projection call was given: tiles.shape[0], or what the pointer table holds per tile."""
+    if tile_ptrs is not None:
+        return int(tile_ptrs.numel()) // plan.n_tiles if plan.n_tiles else (len(flats) if flats is not None else 1)
+    if tiles is not None:
+        return int(tiles.shape[0]) if tiles.dim() == 4 else 1
+    raise ValueError("tiles or tile_ptrs is required")
+
+
+def _z_level_words(z_levels, distinct: bool) -> np.ndarray:
+    """Host z levels (a sequence or a host tensor), each in 0 .. 2^32 - 1, as the int32 words the device reads as uint32."""
+    zs = [int(z) for z in (z_levels.tolist() if hasattr(z_levels, 'tolist') else z_levels)]
+    if any(not 0 <= z < 2 ** 32 for z in zs):
+        raise ValueError("z levels must lie in 0 .. 2^32 - 1")
+    if distinct and len(set(zs)) != len(zs):
+        raise ValueError("the z levels of a call must be distinct")
+    return np.array(zs, dtype=np.uint32).view(np.int32)
+
+
+def _z_levels_dev(z_levels, n_planes: int, device, distinct: bool = False):
+    """Device int32 tensor of the z levels of a call's ``n_planes`` planes (a device tensor is converted, not checked)."""
+    import torch
+    if torch.is_tensor(z_levels) and z_levels.is_cuda:
+        zl = z_levels.to(torch.int32)
+    else:
+        zl = upload_small(torch.tensor(_z_level_words(z_levels, distinct)), device)
+    if zl.numel() != n_planes:
+        raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
+    return zl
+
+
 def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, stream=None, flat_ptrs=None,
                 flags: int = 0, grid_blocks: int = 0) -> None:
     """Fuse all planes of ``canvas`` ([P, Hc, Wc] or [..., Hc, Wc] contiguous) from ``tiles``.
@@ -477,7 +542,6 @@ def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, strea
     flat_ptrs: optionally ``pointer_table(flats, device)`` made earlier, for callers that fuse with the same
                gains again and again (saves a small blocking upload per call).
     """
-    L = lib()
     hc, wc = int(canvas.shape[-2]), int(canvas.shape[-1])
     n_planes = int(canvas.numel() // (hc * wc)) if hc * wc else 0
     # contiguous, or [P, Hc, Wc] with dense rows and any row pitch / plane stride (empty_canvas pads the plane stride)
@@ -490,13 +554,8 @@ def fuse_planes(plan: FusePlan, tiles, canvas, flats=None, tile_ptrs=None, strea
             raise ValueError("canvas must be contiguous or a [P, Hc, Wc] tensor with unit-stride rows and non-overlapping planes")
         pitch, plane_stride = int(canvas.stride(1)), int(canvas.stride(0))
     with _on_stream(stream):
-        keep = []
-        a = _fuse_args(plan, tiles, n_planes, canvas, plane_stride, pitch, flats, tile_ptrs, flat_ptrs, keep)
-        a.flags, a.grid_blocks = int(flags), int(grid_blocks)
-        if stream is not None:      # launched on another stream than the one the helpers above allocated for
-            for t in keep:
-                t.record_stream(stream)
-        _check(L.sq_fuse_planes(C.byref(a), _stream_ptr(stream)), 'sq_fuse_planes')
+        _fuse_launch('sq_fuse_planes', stream, [], plan, tiles, n_planes, canvas, plane_stride, pitch, flats, tile_ptrs, flat_ptrs,
+                     flags=flags, grid_blocks=grid_blocks)
 
 
 def fuse_project_max(plan: FusePlan, tiles, out, flats=None, tile_ptrs=None, accumulate: bool = False, flags: int = 0,
@@ -509,41 +568,21 @@ def fuse_project_max(plan: FusePlan, tiles, out, flats=None, tile_ptrs=None, acc
     tile_ptrs.numel() // plan.n_tiles).  The plan must be an overwrite plan.
     accumulate: ``out`` = max(out, projection) on the plan's covered voxels, the uncovered ones untouched (a channel's z planes
     that come in several calls or under different plans); otherwise every voxel of ``out`` is written, uncovered ones 0."""
-    L = lib()
     if plan.mode != SQ_FUSE_OVERWRITE:
         raise ValueError("fuse_project_max projects overwrite plans only")
-    if not out.is_cuda or out.dim() != 2 or tuple(out.shape) != (plan.canvas_h, plan.canvas_w):
-        raise ValueError(f"out must be a [{plan.canvas_h}, {plan.canvas_w}] device tensor")
-    hc, wc = int(out.shape[0]), int(out.shape[1])
-    if (wc > 1 and out.stride(1) != 1) or (hc > 1 and out.stride(0) < wc):
-        raise ValueError("out must have unit-stride rows")
-    pitch = int(out.stride(0)) if hc > 1 else wc
-    if tile_ptrs is not None:
-        n_planes = int(tile_ptrs.numel()) // max(plan.n_tiles, 1) if plan.n_tiles else (len(flats) if flats is not None else 1)
-    elif tiles is not None:
-        n_planes = int(tiles.shape[0]) if tiles.dim() == 4 else 1
-    else:
-        raise ValueError("tiles or tile_ptrs is required")
+    pitch = _check_plane('out', out, (plan.canvas_h, plan.canvas_w))
+    n_planes = _projected_planes(plan, tiles, tile_ptrs, flats)
     if n_planes < 1:
         raise ValueError("at least one plane to project")
     with _on_stream(stream):
-        keep = []
-        a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
-        a.flags, a.grid_blocks = 0, int(grid_blocks)
-        if stream is not None:
-            for t in keep:
-                t.record_stream(stream)
-        fl = int(flags) | (SQ_PROJECT_ACCUMULATE if accumulate else 0)
-        _check(L.sq_fuse_project_max(C.byref(a), fl, _stream_ptr(stream)), 'sq_fuse_project_max')
+        _fuse_launch('sq_fuse_project_max', stream, [], plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs,
+                     int(flags) | (SQ_PROJECT_ACCUMULATE if accumulate else 0), grid_blocks=grid_blocks)
 
 
 def focus_scratch_bytes(n_tiles: int, tile_h: int, tile_w: int) -> int:
     """Bytes of the caller-owned scratch of ``fuse_project_focus`` for a plan of ``n_tiles`` tiles of tile_h x tile_w: the
     per-tile-pixel winner (uint32 score + uint8 plane index), about 5 B per tile pixel whatever the number of planes."""
-    n = int(lib().sq_focus_scratch_bytes(int(n_tiles), int(tile_h), int(tile_w)))
-    if n < 0:
-        _check(n, 'sq_focus_scratch_bytes')
-    return n
+    return _size(lib().sq_focus_scratch_bytes(int(n_tiles), int(tile_h), int(tile_w)), 'sq_focus_scratch_bytes')
 
 
 def fuse_project_focus(plan: FusePlan, tiles, out, key, z_levels, radius: int = 3, flats=None, scratch=None,
@@ -565,60 +604,32 @@ def fuse_project_focus(plan: FusePlan, tiles, out, key, z_levels, radius: int = 
     accumulate: voxels whose new key exceeds ``key`` take the new value and key, the others (and uncovered voxels) stay --
               the z planes of a channel that come in several calls, in any z order, or under different plans."""
     import torch
-    L = lib()
     if plan.mode != SQ_FUSE_OVERWRITE:
         raise ValueError("fuse_project_focus projects overwrite plans only")
     if not 0 <= int(radius) <= SQ_FOCUS_MAX_RADIUS:
         raise ValueError(f"focus radius {radius} outside 0..{SQ_FOCUS_MAX_RADIUS}")
     shape = (plan.canvas_h, plan.canvas_w)
-    for name, t in (('out', out), ('key', key)):
-        if not t.is_cuda or t.dim() != 2 or tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be a [{shape[0]}, {shape[1]}] device tensor")
-        if (shape[1] > 1 and t.stride(1) != 1) or (shape[0] > 1 and t.stride(0) < shape[1]):
-            raise ValueError(f"{name} must have unit-stride rows")
+    pitch = _check_plane('out', out, shape)
+    key_pitch = _check_plane('key', key, shape)
     if key.dtype != torch.int64:
         raise ValueError("key must be an int64 tensor")
-    hc, wc = shape
-    pitch = int(out.stride(0)) if hc > 1 else wc
-    key_pitch = int(key.stride(0)) if hc > 1 else wc
-    if tile_ptrs is not None:
-        n_planes = int(tile_ptrs.numel()) // max(plan.n_tiles, 1) if plan.n_tiles else (len(flats) if flats is not None else 1)
-    elif tiles is not None:
-        n_planes = int(tiles.shape[0]) if tiles.dim() == 4 else 1
-    else:
-        raise ValueError("tiles or tile_ptrs is required")
+    n_planes = _projected_planes(plan, tiles, tile_ptrs, flats)
     if not 1 <= n_planes <= SQ_FOCUS_MAX_PLANES:
         raise ValueError(f"{n_planes} planes: a call projects 1..{SQ_FOCUS_MAX_PLANES}")
     with _on_stream(stream):
-        keep = []
-        if torch.is_tensor(z_levels) and z_levels.is_cuda:
-            zl = z_levels.to(torch.int32)
-        else:
-            zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
-            if any(not 0 <= z < 2 ** 32 for z in zs):
-                raise ValueError("z levels must lie in 0 .. 2^32 - 1")
-            zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
-        if zl.numel() != n_planes:
-            raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
-        keep.append(zl)
+        zl = _z_levels_dev(z_levels, n_planes, out.device)
         need = focus_scratch_bytes(plan.n_tiles, plan.tile_h, plan.tile_w)
         if scratch is None:
             scratch = torch.empty(need, dtype=torch.uint8, device=out.device)
         elif scratch.numel() * scratch.element_size() < need or not scratch.is_cuda:
             raise ValueError(f"focus scratch must be a device tensor of at least {need} bytes")
-        keep.append(scratch)
-        a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
-        a.flags, a.grid_blocks = 0, int(grid_blocks)
         f = _FocusArgs()
         f.z_levels_dev = zl.data_ptr()
         f.radius = int(radius)
         f.scratch_dev, f.scratch_bytes = scratch.data_ptr(), scratch.numel() * scratch.element_size()
         f.key_dev, f.key_pitch = key.data_ptr(), key_pitch
-        if stream is not None:
-            for t in keep:
-                t.record_stream(stream)
-        fl = int(flags) | (SQ_FOCUS_ACCUMULATE if accumulate else 0)
-        _check(L.sq_fuse_project_focus(C.byref(a), C.byref(f), fl, _stream_ptr(stream)), 'sq_fuse_project_focus')
+        _fuse_launch('sq_fuse_project_focus', stream, [zl, scratch], plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs,
+                     flat_ptrs, C.byref(f), int(flags) | (SQ_FOCUS_ACCUMULATE if accumulate else 0), grid_blocks=grid_blocks)
 
 
 def depth_of_keys(key):
@@ -638,13 +649,6 @@ def depth_dtype_for(num_z: int) -> np.dtype:
     return np.dtype('uint8') if int(num_z) <= 255 else np.dtype('uint16')
 
 
-def _check_plane(name, t, shape):
-    if not t.is_cuda or t.dim() != 2 or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must be a [{shape[0]}, {shape[1]}] device tensor")
-    if (shape[1] > 1 and t.stride(1) != 1) or (shape[0] > 1 and t.stride(0) < shape[1]):
-        raise ValueError(f"{name} must have unit-stride rows")
-
-
 def focus_depth_plane(key, out=None, dtype=None, stream=None):
     """The unsigned depth plane of a key plane of ``fuse_project_focus`` (sq_focus_depth_plane): z* + 1 per voxel, 0 where the
     key is 0 (no plane covers the voxel).  key: [Hc, Wc] device int64 tensor with unit-stride rows.  out: [Hc, Wc] device uint8 /
@@ -654,19 +658,18 @@ def focus_depth_plane(key, out=None, dtype=None, stream=None):
     if not torch.is_tensor(key) or key.dtype != torch.int64 or key.dim() != 2:
         raise ValueError("key must be a [Hc, Wc] int64 device tensor")
     shape = tuple(key.shape)
-    _check_plane('key', key, shape)
+    key_pitch = _check_plane('key', key, shape)
     with _on_stream(stream):
         if out is None:
             out = torch.empty(shape, dtype=torch_dtype_of(np.dtype(dtype or 'uint8')), device=key.device)
         elif dtype is not None and np_dtype_of_torch(out.dtype) != np.dtype(dtype):
             raise ValueError(f"out is {out.dtype}, dtype asks for {np.dtype(dtype)}")
-        _check_plane('out', out, shape)
+        out_pitch = _check_plane('out', out, shape)
         if out.dtype not in (torch.uint8, torch.uint16):
             raise ValueError("the depth plane is uint8 or uint16")
         h, w = shape
-        _check(lib().sq_focus_depth_plane(key.data_ptr(), int(key.stride(0)) if h > 1 else w, h, w, out.data_ptr(),
-                                          int(out.stride(0)) if h > 1 else w, sq_dtype_of(np_dtype_of_torch(out.dtype)),
-                                          _stream_ptr(stream)), 'sq_focus_depth_plane')
+        _check(lib().sq_focus_depth_plane(key.data_ptr(), key_pitch, h, w, out.data_ptr(), out_pitch,
+                                          sq_dtype_of(np_dtype_of_torch(out.dtype)), _stream_ptr(stream)), 'sq_focus_depth_plane')
     return out
 
 
@@ -683,47 +686,21 @@ def fuse_select_depth(plan: FusePlan, tiles, out, depth, z_levels, flats=None, a
     accumulate: voxels whose depth is not among ``z_levels`` are left untouched (the z planes of a channel that come in several
               calls, in any z order, or under different plans); otherwise they are written 0, so every voxel is written."""
     import torch
-    L = lib()
     if plan.mode != SQ_FUSE_OVERWRITE:
         raise ValueError("fuse_select_depth selects from overwrite plans only")
     shape = (plan.canvas_h, plan.canvas_w)
-    _check_plane('out', out, shape)
-    _check_plane('depth', depth, shape)
+    pitch = _check_plane('out', out, shape)
+    depth_pitch = _check_plane('depth', depth, shape)
     if depth.dtype not in (torch.uint8, torch.uint16):
         raise ValueError("depth must be a uint8 or uint16 tensor")
-    hc, wc = shape
-    pitch = int(out.stride(0)) if hc > 1 else wc
-    depth_pitch = int(depth.stride(0)) if hc > 1 else wc
-    if tile_ptrs is not None:
-        n_planes = int(tile_ptrs.numel()) // max(plan.n_tiles, 1) if plan.n_tiles else (len(flats) if flats is not None else 1)
-    elif tiles is not None:
-        n_planes = int(tiles.shape[0]) if tiles.dim() == 4 else 1
-    else:
-        raise ValueError("tiles or tile_ptrs is required")
+    n_planes = _projected_planes(plan, tiles, tile_ptrs, flats)
     if not 1 <= n_planes <= SQ_FOCUS_MAX_PLANES:
         raise ValueError(f"{n_planes} planes: a call selects among 1..{SQ_FOCUS_MAX_PLANES}")
     with _on_stream(stream):
-        keep = []
-        if torch.is_tensor(z_levels) and z_levels.is_cuda:
-            zl = z_levels.to(torch.int32)
-        else:
-            zs = [int(z) for z in (z_levels.tolist() if torch.is_tensor(z_levels) else z_levels)]
-            if any(not 0 <= z < 2 ** 32 for z in zs):
-                raise ValueError("z levels must lie in 0 .. 2^32 - 1")
-            if len(set(zs)) != len(zs):
-                raise ValueError("the z levels of a call must be distinct")
-            zl = upload_small(torch.tensor(np.array(zs, dtype=np.uint32).view(np.int32)), out.device)
-        if zl.numel() != n_planes:
-            raise ValueError(f"{zl.numel()} z levels for {n_planes} planes")
-        keep.append(zl)
-        a = _fuse_args(plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs, keep)
-        a.flags, a.grid_blocks = 0, int(grid_blocks)
-        if stream is not None:
-            for t in keep:
-                t.record_stream(stream)
-        fl = int(flags) | (SQ_SELECT_ACCUMULATE if accumulate else 0)
-        _check(L.sq_fuse_select_depth(C.byref(a), depth.data_ptr(), depth_pitch, sq_dtype_of(np_dtype_of_torch(depth.dtype)),
-                                      zl.data_ptr(), fl, _stream_ptr(stream)), 'sq_fuse_select_depth')
+        zl = _z_levels_dev(z_levels, n_planes, out.device, distinct=True)
+        _fuse_launch('sq_fuse_select_depth', stream, [zl], plan, tiles, n_planes, out, 0, pitch, flats, tile_ptrs, flat_ptrs,
+                     depth.data_ptr(), depth_pitch, sq_dtype_of(np_dtype_of_torch(depth.dtype)), zl.data_ptr(),
+                     int(flags) | (SQ_SELECT_ACCUMULATE if accumulate else 0), grid_blocks=grid_blocks)
 
 
 PLANE_ALIGN_BYTES = 128
@@ -860,13 +837,13 @@ def planes_to_host(canvas):
 
 
 def _tile_table(tiles, tile_ptrs, shape, np_dtype):
-    """(ptrs_dev, base_dev, stride, n, h, w, sq dtype) for a stack [N, H, W] or a pointer table."""
+    """(ptrs_dev, base_dev, stride, n, h, w, sq dtype, device) for a stack [N, H, W] or a pointer table."""
     if tile_ptrs is not None:
         n = int(tile_ptrs.numel())
         h, w = (int(v) for v in shape)
-        return tile_ptrs.data_ptr(), None, 0, n, h, w, sq_dtype_of(np_dtype)
+        return tile_ptrs.data_ptr(), None, 0, n, h, w, sq_dtype_of(np_dtype), tile_ptrs.device
     n, h, w = (int(v) for v in tiles.shape)
-    return None, tiles.data_ptr(), h * w, n, h, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype))
+    return None, tiles.data_ptr(), h * w, n, h, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), tiles.device
 
 
 def tile_minmax(tiles, stream=None, tile_ptrs=None, shape=None, np_dtype=None):
@@ -875,8 +852,7 @@ def tile_minmax(tiles, stream=None, tile_ptrs=None, shape=None, np_dtype=None):
     values fit int32 for uint8/uint16 tiles)."""
     import torch
     L = lib()
-    ptrs, base, stride, n, h, w, dt = _tile_table(tiles, tile_ptrs, shape, np_dtype)
-    device = tile_ptrs.device if tile_ptrs is not None else tiles.device
+    ptrs, base, stride, n, h, w, dt, device = _tile_table(tiles, tile_ptrs, shape, np_dtype)
     with _on_stream(stream):
         out = torch.empty((n, 2), dtype=torch.int32, device=device)
         _check(L.sq_tile_minmax(ptrs, base, stride, n, h, w, w, dt, out.data_ptr(), _stream_ptr(stream)),
@@ -894,8 +870,7 @@ def pair_overlap_moments(tiles, windows, out=None, stream=None, tile_ptrs=None, 
     OVERLAP_BATCH windows go to the device in batches of that many."""
     import torch
     L = lib()
-    ptrs, base, stride, n, h, w, dt = _tile_table(tiles, tile_ptrs, shape, np_dtype)
-    device = tile_ptrs.device if tile_ptrs is not None else tiles.device
+    ptrs, base, stride, n, h, w, dt, device = _tile_table(tiles, tile_ptrs, shape, np_dtype)
     win = np.asarray(windows)
     if win.dtype != OVERLAP_DTYPE:
         win = np.ascontiguousarray(win, dtype=np.int32).reshape(-1, 8).view(OVERLAP_DTYPE).reshape(-1)
@@ -939,24 +914,39 @@ def normalize_tiles(tiles, minmax=None, stream=None):
     return out
 
 
+def _plane_stack(planes, what: str, integer_only: bool):
+    """(n, h, w) of a [n, h, w] device tensor with unit-stride rows (any row pitch and plane stride); ValueError otherwise.
+    ``integer_only``: uint8 / uint16 only (without it the dtype is left to the entry point, which refuses with NativeError)."""
+    import torch
+    if planes.dim() != 3 or planes.device.type != 'cuda':
+        raise ValueError(f"{what} must be a [n, h, w] device tensor")
+    if planes.stride(2) != 1 and planes.shape[2] > 1:
+        raise ValueError(f"{what} rows must be contiguous")
+    if integer_only and planes.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"{what} must be uint8 or uint16, got {planes.dtype}")
+    n, h, w = (int(v) for v in planes.shape)
+    return n, h, w
+
+
+def _check_out_stack(out, shape, like) -> None:
+    """``out`` is a stack of this shape with the dtype and device of ``like`` and unit-stride rows; ValueError otherwise."""
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device:
+        raise ValueError(f"out must be a {tuple(shape)} tensor of the input's dtype and device")
+    if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
+        raise ValueError("out rows must be contiguous")
+
+
 def downsample2(planes, out=None, stream=None):
     """Next pyramid level of ``planes`` [n, h, w] (uint8 / uint16 device tensor, any row pitch) ->
     [n, h // 2, w // 2]: out[p, y, x] = planes[p, 2y+1, 2x+1], what ome_zarr's Scaler.nearest computes per
     level (stitcher.py:797-798).  ``out`` may be a preallocated tensor (any row pitch)."""
     import torch
     L = lib()
-    if planes.dim() != 3 or planes.device.type != 'cuda':
-        raise ValueError("planes must be a [n, h, w] device tensor")
-    if planes.stride(2) != 1 and planes.shape[2] > 1:
-        raise ValueError("planes rows must be contiguous")
-    n, h, w = (int(v) for v in planes.shape)
+    n, h, w = _plane_stack(planes, 'planes', integer_only=False)
     with _on_stream(stream):
         if out is None:
             out = torch.empty((n, h // 2, w // 2), dtype=planes.dtype, device=planes.device)
-        if tuple(out.shape) != (n, h // 2, w // 2) or out.dtype != planes.dtype or out.device != planes.device:
-            raise ValueError(f"out must be a {(n, h // 2, w // 2)} tensor of the input's dtype and device")
-        if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
-            raise ValueError("out rows must be contiguous")
+        _check_out_stack(out, (n, h // 2, w // 2), planes)
         if out.numel() == 0:
             return out
         _check(L.sq_downsample2(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), out.data_ptr(), out.stride(0),
@@ -976,17 +966,11 @@ def pyramid_mean(planes, n_levels, out=None, stream=None):
     ``out`` may be a list of preallocated tensors (any row pitch), one per level that exists."""
     import torch
     L = lib()
-    if planes.dim() != 3 or planes.device.type != 'cuda':
-        raise ValueError("planes must be a [n, h, w] device tensor")
-    if planes.stride(2) != 1 and planes.shape[2] > 1:
-        raise ValueError("planes rows must be contiguous")
-    if planes.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"planes must be uint8 or uint16, got {planes.dtype}")
+    n, h, w = _plane_stack(planes, 'planes', integer_only=True)
     dtype = sq_dtype_of(np_dtype_of_torch(planes.dtype))
     n_levels = int(n_levels)
     if n_levels < 0:
         raise ValueError(f"n_levels must be >= 0, got {n_levels}")
-    n, h, w = (int(v) for v in planes.shape)
     shapes = []
     while len(shapes) < n_levels and (h >> (len(shapes) + 1)) > 0 and (w >> (len(shapes) + 1)) > 0:
         shapes.append((n, h >> (len(shapes) + 1), w >> (len(shapes) + 1)))
@@ -997,10 +981,7 @@ def pyramid_mean(planes, n_levels, out=None, stream=None):
         if len(out) != len(shapes):
             raise ValueError(f"out must hold {len(shapes)} tensors (the levels of a {(n, h, w)} stack that exist), got {len(out)}")
         for s, o in zip(shapes, out):
-            if tuple(o.shape) != s or o.dtype != planes.dtype or o.device != planes.device:
-                raise ValueError(f"out must be {shapes} tensors of the input's dtype and device")
-            if o.stride(2) != 1 and o.shape[2] > 1:
-                raise ValueError("out rows must be contiguous")
+            _check_out_stack(o, s, planes)
         if not shapes or n == 0:
             return out
         k = len(shapes)
@@ -1028,15 +1009,9 @@ def histogram_planes(planes, rows, hist=None, n_rows=None, stream=None):
     np.iinfo(dtype).max, stitcher.py:846-850); the definition is numpy.bincount."""
     import torch
     L = lib()
-    if planes.dim() != 3 or planes.device.type != 'cuda':
-        raise ValueError("planes must be a [n, h, w] device tensor")
-    if planes.stride(2) != 1 and planes.shape[2] > 1:
-        raise ValueError("planes rows must be contiguous")
-    if planes.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"planes must be uint8 or uint16, got {planes.dtype}")
+    n, h, w = _plane_stack(planes, 'planes', integer_only=True)
     np_dtype = np_dtype_of_torch(planes.dtype)
     bins = histogram_bins(np_dtype)
-    n, h, w = (int(v) for v in planes.shape)
     rows = [int(r) for r in rows]
     if len(rows) != n:
         raise ValueError(f"{n} planes, {len(rows)} rows given")
@@ -1076,17 +1051,11 @@ def block_mean(planes, k, out=None, rows=None, stream=None):
     part of it unwritten)."""
     import torch
     L = lib()
-    if planes.dim() != 3 or planes.device.type != 'cuda':
-        raise ValueError("planes must be a [n, h, w] device tensor")
-    if planes.stride(2) != 1 and planes.shape[2] > 1:
-        raise ValueError("planes rows must be contiguous")
-    if planes.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"planes must be uint8 or uint16, got {planes.dtype}")
+    n, h, w = _plane_stack(planes, 'planes', integer_only=True)
     k = int(k)
     if not 0 <= k <= SQ_BLOCK_MEAN_MAX_K:
         raise ValueError(f"k must lie in 0..{SQ_BLOCK_MEAN_MAX_K}, got {k}")
     f = 1 << k
-    n, h, w = (int(v) for v in planes.shape)
     shape = (n, -(-h // f), -(-w // f))
     y0, y1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
     if not (0 <= y0 <= y1 <= h) or y0 % f or ((y1 - y0) % f and y1 != h):
@@ -1094,10 +1063,7 @@ def block_mean(planes, k, out=None, rows=None, stream=None):
     with _on_stream(stream):
         if out is None:
             out = (torch.empty if (y0, y1) == (0, h) else torch.zeros)(shape, dtype=planes.dtype, device=planes.device)
-        if tuple(out.shape) != shape or out.dtype != planes.dtype or out.device != planes.device:
-            raise ValueError(f"out must be a {shape} tensor of the input's dtype and device")
-        if out.numel() and out.stride(2) != 1 and out.shape[2] > 1:
-            raise ValueError("out rows must be contiguous")
+        _check_out_stack(out, shape, planes)
         if n == 0 or h == 0 or w == 0 or y1 == y0:
             return out
         _check(L.sq_block_mean(planes.data_ptr(), planes.stride(0), h, w, planes.stride(1), n, sq_dtype_of(np_dtype_of_torch(planes.dtype)),
@@ -1114,13 +1080,7 @@ def composite_render(means, windows, colors, out=None, stream=None):
     [h, w, 3] tensor whose pixels are contiguous (any row pitch)."""
     import torch
     L = lib()
-    if means.dim() != 3 or means.device.type != 'cuda':
-        raise ValueError("means must be a [n, h, w] device tensor")
-    if means.stride(2) != 1 and means.shape[2] > 1:
-        raise ValueError("means rows must be contiguous")
-    if means.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"means must be uint8 or uint16, got {means.dtype}")
-    n, h, w = (int(v) for v in means.shape)
+    n, h, w = _plane_stack(means, 'means', integer_only=True)
     if not 1 <= n <= SQ_COMPOSITE_MAX_PLANES:
         raise ValueError(f"1..{SQ_COMPOSITE_MAX_PLANES} planes, got {n}")
     windows = [(int(a), int(b)) for a, b in windows]
@@ -1159,10 +1119,7 @@ def tophat_scratch_bytes(n_images: int, h: int, w: int, dtype) -> int:
         raise ValueError(f"the top-hat filters uint8 and uint16 planes, got {dt}")
     if int(n_images) < 0 or int(h) < 1 or int(w) < 1:
         raise ValueError(f"bad sizes: {n_images} planes of {h} x {w}")
-    n = int(lib().sq_tophat_scratch_bytes(int(n_images), int(h), int(w), sq_dtype_of(dt)))
-    if n < 0:
-        _check(n, 'sq_tophat_scratch_bytes')
-    return n
+    return _size(lib().sq_tophat_scratch_bytes(int(n_images), int(h), int(w), sq_dtype_of(dt)), 'sq_tophat_scratch_bytes')
 
 
 def tophat_tiles(tiles, radius: int, scratch=None, stream=None):
@@ -1180,29 +1137,8 @@ def tophat_tiles(tiles, radius: int, scratch=None, stream=None):
         raise ValueError("tiles must be a [..., H, W] device tensor")
     if tiles.dtype not in (torch.uint8, torch.uint16):
         raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= SQ_TOPHAT_MAX_RADIUS:
-        raise ValueError(f"top-hat radius must be an integer in 1..{SQ_TOPHAT_MAX_RADIUS}, got {radius!r}")
-    h, w = int(tiles.shape[-2]), int(tiles.shape[-1])
-    if h < 1 or w < 1:
-        raise ValueError(f"planes of {h} x {w}")
-    if w > 1 and tiles.stride(-1) != 1:
-        raise ValueError("tiles rows must be contiguous")
-    pitch = int(tiles.stride(-2)) if h > 1 else w
-    if pitch < w:
-        raise ValueError("tiles rows overlap")
-    # the leading dimensions as one run of planes a uniform stride apart
-    lead = [(int(n), int(s)) for n, s in zip(tiles.shape[:-2], tiles.stride()[:-2]) if n != 1]
-    n_images = 1
-    for n, _ in lead:
-        n_images *= n
-    plane_stride = (h - 1) * pitch + w
-    if n_images > 1:
-        for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
-            if s0 != n1 * s1:
-                raise ValueError("the planes of tiles must be a uniform stride apart (a contiguous stack or a regular view of one)")
-        plane_stride = lead[-1][1]
-        if plane_stride < (h - 1) * pitch + w:
-            raise ValueError("the planes of tiles overlap")
+    radius = _int_in(radius, 1, SQ_TOPHAT_MAX_RADIUS, 'top-hat radius')
+    n_images, h, w, plane_stride, pitch = _plane_layout(tiles, 'tiles')
     np_dtype = np_dtype_of_torch(tiles.dtype)
     need = tophat_scratch_bytes(n_images, h, w, np_dtype)
     with _on_stream(stream):
@@ -1256,6 +1192,19 @@ def _plane_layout(t, what):
     return n_images, h, w, plane_stride, pitch
 
 
+def _byte_extent(t, layout):
+    """(first byte, one past the last byte) of the planes of ``t``, ``layout`` its ``_plane_layout`` with at least one plane:
+    the whole range the run spans, the gaps between its rows and planes included."""
+    n_images, h, w, plane_stride, pitch = layout
+    first = t.data_ptr()
+    return first, first + ((n_images - 1) * plane_stride + (h - 1) * pitch + w) * t.element_size()
+
+
+def _overlap(a, b) -> bool:
+    """Two byte extents share memory (interleaved views such as t[::2] and t[1::2] count: their ranges do)."""
+    return a[0] < b[1] and b[0] < a[1]
+
+
 def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=None, stream=None):
     """Hot-pixel removal of every H x W plane of ``tiles`` into ``out`` (sq_despeckle_tiles; an extension, the reference has
     none): a pixel that differs from the median m of its edge-replicated 3 x 3 window by more than ``threshold`` -- mode 'hot':
@@ -1276,12 +1225,11 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
         raise ValueError("tiles must be a [..., H, W] device tensor")
     if tiles.dtype not in (torch.uint8, torch.uint16):
         raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)) or \
-            not 0 <= int(threshold) <= SQ_DESPECKLE_MAX_THRESHOLD:
-        raise ValueError(f"despeckle threshold must be an integer in 0..{SQ_DESPECKLE_MAX_THRESHOLD}, got {threshold!r}")
+    threshold = _int_in(threshold, 0, SQ_DESPECKLE_MAX_THRESHOLD, 'despeckle threshold')
     if not isinstance(mode, str) or mode not in DESPECKLE_MODES:
         raise ValueError(f"despeckle mode must be 'hot' or 'both', got {mode!r}")
-    n_images, h, w, src_plane_stride, src_pitch = _plane_layout(tiles, 'tiles')
+    src = _plane_layout(tiles, 'tiles')
+    n_images, h, w, src_plane_stride, src_pitch = src
     with _on_stream(stream):
         if out is None:
             out = torch.empty(tuple(tiles.shape), dtype=tiles.dtype, device=tiles.device)
@@ -1290,7 +1238,8 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
         elif not torch.is_tensor(out) or tuple(out.shape) != tuple(tiles.shape) or out.dtype != tiles.dtype or \
                 out.device != tiles.device:
             raise ValueError(f"out must be a {tiles.dtype} tensor of shape {tuple(tiles.shape)} on the tiles' device")
-        n_out, _, _, dst_plane_stride, dst_pitch = _plane_layout(out, 'out')
+        dst = _plane_layout(out, 'out')
+        n_out, _, _, dst_plane_stride, dst_pitch = dst
         assert n_out == n_images
         if counts is not None:
             if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.device != tiles.device or \
@@ -1298,14 +1247,11 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
                 raise ValueError(f"counts must be a contiguous int64 tensor of {n_images} elements on the tiles' device")
         if n_images == 0:
             return out
-        es = tiles.element_size()
-        s0, d0 = tiles.data_ptr(), out.data_ptr()
-        s1 = s0 + ((n_images - 1) * src_plane_stride + (h - 1) * src_pitch + w) * es
-        d1 = d0 + ((n_images - 1) * dst_plane_stride + (h - 1) * dst_pitch + w) * es
-        if s0 < d1 and d0 < s1:
+        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
             raise ValueError("out shares memory with tiles: the filter is out of place")
-        _check(lib().sq_despeckle_tiles(s0, d0, n_images, h, w, src_plane_stride, src_pitch, dst_plane_stride, dst_pitch,
-                                        sq_dtype_of(np_dtype_of_torch(tiles.dtype)), DESPECKLE_MODES[mode], int(threshold),
+        _check(lib().sq_despeckle_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
+                                        dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
+                                        DESPECKLE_MODES[mode], threshold,
                                         None if counts is None else counts.data_ptr(), _stream_ptr(stream)),
                'sq_despeckle_tiles')
     return out
@@ -1366,29 +1312,24 @@ def dpc_tiles(left, right, gain: int = 1, out=None, stream=None):
         raise ValueError("left must be a [..., H, W] device tensor")
     if left.dtype not in (torch.uint8, torch.uint16):
         raise ValueError(f"left must be uint8 or uint16, got {left.dtype}")
-    if isinstance(gain, bool) or not isinstance(gain, (int, np.integer)) or not 1 <= int(gain) <= SQ_DPC_MAX_GAIN:
-        raise ValueError(f"dpc gain must be an integer in 1..{SQ_DPC_MAX_GAIN}, got {gain!r}")
+    gain = _int_in(gain, 1, SQ_DPC_MAX_GAIN, 'dpc gain')
     if out is None:
         out = left
     for name, t in (('right', right), ('out', out)):
         if not torch.is_tensor(t) or tuple(t.shape) != tuple(left.shape) or t.dtype != left.dtype or t.device != left.device:
             raise ValueError(f"{name} must be a {left.dtype} tensor of shape {tuple(left.shape)} on left's device")
-    n_images, h, w, left_plane_stride, left_pitch = _plane_layout(left, 'left')
-    _, _, _, right_plane_stride, right_pitch = _plane_layout(right, 'right')
-    _, _, _, out_plane_stride, out_pitch = _plane_layout(out, 'out')
+    lay_l, lay_r, lay_o = _plane_layout(left, 'left'), _plane_layout(right, 'right'), _plane_layout(out, 'out')
+    n_images, h, w, left_plane_stride, left_pitch = lay_l
+    (right_plane_stride, right_pitch), (out_plane_stride, out_pitch) = lay_r[3:], lay_o[3:]
     if n_images == 0:
         return out
-    es = left.element_size()
-    l0, r0, o0 = left.data_ptr(), right.data_ptr(), out.data_ptr()
-    l1 = l0 + ((n_images - 1) * left_plane_stride + (h - 1) * left_pitch + w) * es
-    r1 = r0 + ((n_images - 1) * right_plane_stride + (h - 1) * right_pitch + w) * es
-    o1 = o0 + ((n_images - 1) * out_plane_stride + (h - 1) * out_pitch + w) * es
-    in_place = o0 == l0 and out_pitch == left_pitch and (n_images == 1 or out_plane_stride == left_plane_stride)
-    if (not in_place and l0 < o1 and o0 < l1) or (r0 < o1 and o0 < r1):
+    ext_l, ext_r, ext_o = _byte_extent(left, lay_l), _byte_extent(right, lay_r), _byte_extent(out, lay_o)
+    in_place = ext_o[0] == ext_l[0] and out_pitch == left_pitch and (n_images == 1 or out_plane_stride == left_plane_stride)
+    if (not in_place and _overlap(ext_l, ext_o)) or _overlap(ext_r, ext_o):
         raise ValueError("out must be exactly left (in place) or share no memory with left and right")
-    _check(lib().sq_dpc_tiles(l0, r0, o0, n_images, h, w, left_plane_stride, left_pitch, right_plane_stride, right_pitch,
-                              out_plane_stride, out_pitch, sq_dtype_of(np_dtype_of_torch(left.dtype)), int(gain),
-                              _stream_ptr(stream)), 'sq_dpc_tiles')
+    _check(lib().sq_dpc_tiles(left.data_ptr(), right.data_ptr(), out.data_ptr(), n_images, h, w, left_plane_stride, left_pitch,
+                              right_plane_stride, right_pitch, out_plane_stride, out_pitch,
+                              sq_dtype_of(np_dtype_of_torch(left.dtype)), gain, _stream_ptr(stream)), 'sq_dpc_tiles')
     return out
 
 
@@ -1436,15 +1377,12 @@ def register_pairs_async(tiles, minmax, pairs: np.ndarray, n0: int, n1: int, ups
     ``tiles`` [N, H, W] device stack (or a pointer table + shape + dtype), ``pairs`` PAIR_DTYPE."""
     import torch
     L = lib()
-    ptrs, base, stride, n, h, w, dt = _tile_table(tiles, tile_ptrs, shape, np_dtype)
-    device = tile_ptrs.device if tile_ptrs is not None else tiles.device
+    ptrs, base, stride, n, h, w, dt, device = _tile_table(tiles, tile_ptrs, shape, np_dtype)
     pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
     npairs = len(pairs)
     if npairs == 0:
         return PendingRegistration(None, None, 0)
-    ws_bytes = L.sq_register_workspace_bytes(npairs, n0, n1, upsample_factor)
-    if ws_bytes < 0:
-        raise NativeError(f"sq_register_workspace_bytes failed: {L.sq_last_error().decode()}")
+    ws_bytes = _size(L.sq_register_workspace_bytes(npairs, n0, n1, upsample_factor), 'sq_register_workspace_bytes')
     if min(pairs['ref_tile'].min(), pairs['mov_tile'].min()) < 0 or \
             max(pairs['ref_tile'].max(), pairs['mov_tile'].max()) >= n:
         raise ValueError("pair refers to a tile outside the table")
@@ -1454,7 +1392,7 @@ def register_pairs_async(tiles, minmax, pairs: np.ndarray, n0: int, n1: int, ups
             or (pairs['mov_x0'] + n1 > w).any()):
         raise ValueError("crop reaches outside its tile")
     with _on_stream(stream):
-        ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=device)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device)
         pairs_dev = upload_small(torch.from_numpy(pairs.view(np.uint8).reshape(-1)), device)
         res_dev = torch.zeros(npairs * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
         a = _RegisterArgs()
@@ -1539,8 +1477,7 @@ class BloscBuffers:
         self.n_chunks = int(L.sq_blosc_chunk_count(n_planes, h, w, chunk_h, chunk_w))
         self.bound = int(L.sq_blosc_out_bound(*self.geometry))
         need = int(L.sq_blosc_scratch_bytes(*self.geometry))
-        if min(self.n_chunks, self.bound, need) < 0:
-            raise NativeError(f"sq_blosc geometry: {L.sq_last_error().decode()}")
+        _size(min(self.n_chunks, self.bound, need), 'sq_blosc geometry')
         self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
         self.offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=device)
         self.out = torch.empty(max(self.bound, 1), dtype=torch.uint8, device=device)
@@ -1553,9 +1490,7 @@ def blosc_encode_planes(planes, chunk_h: int, chunk_w: int, buffers: Optional[Bl
     chunk row, chunk column) is ``buffers.out[offsets[i]:offsets[i + 1]]`` with ``offsets = buffers.offsets``
     (size 0 = all-zero chunk).  Nothing is synchronised or copied here."""
     L = lib()
-    if planes.dim() != 3 or not planes.is_cuda or (planes.shape[2] > 1 and planes.stride(2) != 1):
-        raise ValueError("planes must be a [n, H, W] device tensor with unit-stride rows")
-    n, h, w = (int(v) for v in planes.shape)
+    n, h, w = _plane_stack(planes, 'planes', integer_only=False)
     npdt = np_dtype_of_torch(planes.dtype)
     with _on_stream(stream):
         if buffers is None or buffers.geometry != (n, h, w, sq_dtype_of(npdt), int(chunk_h), int(chunk_w)):
@@ -1579,11 +1514,9 @@ def basic_fit(tiles, smoothness_flatfield: float = 1.0, stream=None):
     if tiles.dim() != 3 or not tiles.is_cuda or not tiles.is_contiguous():
         raise ValueError("tiles must be a contiguous [n, H, W] device tensor")
     n, h, w = (int(v) for v in tiles.shape)
-    need = L.sq_basic_workspace_bytes(n, h, w)
-    if need < 0:
-        raise NativeError(f"sq_basic_workspace_bytes failed: {L.sq_last_error().decode()}")
+    need = _size(L.sq_basic_workspace_bytes(n, h, w), 'sq_basic_workspace_bytes')
     with _on_stream(stream):
-        ws = torch.empty(int(need), dtype=torch.uint8, device=tiles.device)
+        ws = torch.empty(need, dtype=torch.uint8, device=tiles.device)
         out = torch.empty((h, w), dtype=torch.float32, device=tiles.device)
         info = _BasicInfo()
         _check(L.sq_basic_fit(None, tiles.data_ptr(), h * w, n, h, w, w, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
@@ -1593,40 +1526,34 @@ def basic_fit(tiles, smoothness_flatfield: float = 1.0, stream=None):
                  'working_size': info.working_size, 'capped_rounds': info.capped_rounds}
 
 
-def selftest_flat_divide(exponent: int, n_binades: int, negative: bool, device) -> int:
-    """Mismatches between the fast and the IEEE flatfield divide over whole binades of gains (tests)."""
+def _selftest(name: str, device, *args) -> int:
+    """The mismatch count of self-test ``name``(*args, count, stream), whose kernels add into a zeroed device counter."""
     import torch
     out = torch.zeros(1, dtype=torch.int64, device=device)
-    _check(lib().sq_selftest_flat_divide(int(exponent), int(n_binades), int(bool(negative)), out.data_ptr(),
-                                         _stream_ptr()), 'sq_selftest_flat_divide')
+    _check(getattr(lib(), name)(*args, out.data_ptr(), _stream_ptr()), name)
     return int(out.item())
+
+
+def selftest_flat_divide(exponent: int, n_binades: int, negative: bool, device) -> int:
+    """Mismatches between the fast and the IEEE flatfield divide over whole binades of gains (tests)."""
+    return _selftest('sq_selftest_flat_divide', device, int(exponent), int(n_binades), int(bool(negative)))
 
 
 def selftest_flat_divide_f64(exponent: int, n_binades: int, negative: bool, seed: int, device) -> int:
     """Mismatches between the shortened and the IEEE float64 flatfield divide on random gains (tests)."""
-    import torch
-    out = torch.zeros(1, dtype=torch.int64, device=device)
-    _check(lib().sq_selftest_flat_divide_f64(int(exponent), int(n_binades), int(bool(negative)), int(seed) & (2 ** 64 - 1),
-                                             out.data_ptr(), _stream_ptr()), 'sq_selftest_flat_divide_f64')
-    return int(out.item())
+    return _selftest('sq_selftest_flat_divide_f64', device, int(exponent), int(n_binades), int(bool(negative)),
+                     int(seed) & (2 ** 64 - 1))
 
 
 def selftest_normalise_divide(device) -> int:
     """Mismatches between the registration kernels' shortened normalisation quotient and the IEEE float64 division over
     every (numerator, range) pair of 16-bit integers (tests)."""
-    import torch
-    out = torch.zeros(1, dtype=torch.int64, device=device)
-    _check(lib().sq_selftest_normalise_divide(out.data_ptr(), _stream_ptr()), 'sq_selftest_normalise_divide')
-    return int(out.item())
+    return _selftest('sq_selftest_normalise_divide', device)
 
 
 def selftest_blend_divide(exponent: int, n_binades: int, negative: bool, device) -> int:
     """Mismatches between the grouped feather blend's final division and the IEEE one over whole binades (tests)."""
-    import torch
-    out = torch.zeros(1, dtype=torch.int64, device=device)
-    _check(lib().sq_selftest_blend_divide(int(exponent), int(n_binades), int(bool(negative)), out.data_ptr(),
-                                          _stream_ptr()), 'sq_selftest_blend_divide')
-    return int(out.item())
+    return _selftest('sq_selftest_blend_divide', device, int(exponent), int(n_binades), int(bool(negative)))
 
 
 def synth_tiles(desc: np.ndarray, tile_h: int, tile_w: int, noise_amp: int, np_dtype, device, out=None, stream=None):

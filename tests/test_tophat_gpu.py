@@ -77,6 +77,10 @@ def test_refusals():
         native.tophat_tiles(t, 3, scratch=torch.empty(16, dtype=torch.uint8, device=DEV))
     with pytest.raises(ValueError):
         native.tophat_tiles(t.permute(0, 2, 1), 3)          # rows that are not contiguous
+    with pytest.raises(ValueError):
+        native.tophat_tiles(t[:1].expand(3, 8, 8), 3)       # planes on top of each other
+    with pytest.raises(ValueError):
+        native.tophat_tiles(torch.zeros((2, 4, 8, 8), dtype=torch.uint16, device=DEV)[:, :3], 3)      # no uniform plane stride
     assert not t.cpu().numpy().any()      # nothing was launched
 
 
