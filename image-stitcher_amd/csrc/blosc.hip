@@ -269,8 +269,9 @@ int64_t up256(int64_t v) { return (v + 255) & ~int64_t(255); }
 }  // namespace
 
 extern "C" int64_t sq_blosc_chunk_count(int32_t n_planes, int32_t h, int32_t w, int32_t cy, int32_t cx) {
-    BloscParams P{};
-    if (geometry(P, h, w, n_planes, SQ_U16, cy, cx) != SQ_OK) return SQ_ERR_INVALID;
+    BloscParams P{};   // the count does not depend on the element size: refuse only what no dtype could encode
+    const int rc = geometry(P, h, w, n_planes, SQ_U8, cy, cx);
+    if (rc != SQ_OK) return rc;
     return P.n_chunks;
 }
 

@@ -594,6 +594,8 @@ int sq_pair_overlap_moments(const void *const *tile_ptrs_dev, const void *tile_b
  * out_dev[offsets_dev[i] .. offsets_dev[i + 1]) (n_chunks + 1 offsets; an all-zero chunk has size 0: the store's
  * fill_value stands for it).  *status_dev != 0 afterwards: out_capacity was too small (sq_blosc_out_bound() never is).
  * Strides in elements; dtype SQ_U8 or SQ_U16.  Asynchronous on `stream` like the other entry points.
+ * The three size queries return a negative sq_status for a geometry the encode call refuses (a chunk may hold at most
+ * 32 MiB); sq_blosc_chunk_count is not told the dtype and refuses only what no dtype could encode.
  * ---------------------------------------------------------------------------------------- */
 int64_t sq_blosc_chunk_count(int32_t n_planes, int32_t h, int32_t w, int32_t chunk_h, int32_t chunk_w);
 int64_t sq_blosc_out_bound(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t chunk_h, int32_t chunk_w);

@@ -63,6 +63,123 @@ def lz4_decompress_block(data: memoryview, expected: int) -> bytes:
     return bytes(dst)
 
 
+def lz4_sequences(data, expected: int) -> list:
+    """The sequences of an LZ4 block of `expected` decoded bytes, under the conditions liblz4's LZ4_decompress_safe
+    succeeds with (lz4_Block_format.md, "End of block restrictions"), which lz4_decompress_block above does not hold a
+    block to.  Returns [(literals, match_len | None, offset | None, out_pos)]: the literal count, the match length and
+    offset (None for the last sequence) and the output position after the literals, where the match starts.
+    ValueError unless, with n = expected:
+      every offset is in 1..out_pos; every match starts at out_pos <= n - 12 and ends at <= n - 5;
+      the last sequence has no match part, a zero low nibble in its token, and ends the input exactly;
+      the output is exactly n bytes."""
+    data = bytes(data)
+    n, end = int(expected), len(data)
+    ip = op = 0
+    seqs = []
+
+    def length(base):
+        nonlocal ip
+        while True:
+            if ip >= end:
+                raise ValueError("LZ4 strict: a length runs past the input")
+            s = data[ip]
+            ip += 1
+            base += s
+            if s < 255:
+                return base
+
+    while True:
+        if ip >= end:
+            raise ValueError("LZ4 strict: the input ends where a token is due (the last sequence must be literals only)")
+        token = data[ip]
+        ip += 1
+        run = token >> 4
+        if run == 15:
+            run = length(run)
+        if ip + run > end:
+            raise ValueError("LZ4 strict: literals run past the input")
+        if op + run > n:
+            raise ValueError(f"LZ4 strict: literals run past the {n} output bytes")
+        ip += run
+        op += run
+        if ip == end:
+            if token & 15:
+                raise ValueError("LZ4 strict: the last token announces a match")
+            if op != n:
+                raise ValueError(f"LZ4 strict: the block ends at {op}, expected {n}")
+            seqs.append((run, None, None, op))
+            return seqs
+        if ip + 2 > end:
+            raise ValueError("LZ4 strict: the input ends inside an offset")
+        offset = data[ip] | (data[ip + 1] << 8)
+        ip += 2
+        if not 1 <= offset <= op:
+            raise ValueError(f"LZ4 strict: offset {offset} at output position {op}")
+        mlen = token & 15
+        if mlen == 15:
+            mlen = length(mlen)
+        mlen += 4
+        if op > n - 12:
+            raise ValueError(f"LZ4 strict: a match starts at {op}, in the last 12 of {n} bytes")
+        if op + mlen > n - 5:
+            raise ValueError(f"LZ4 strict: a match ends at {op + mlen}, in the last 5 of {n} bytes")
+        seqs.append((run, mlen, offset, op))
+        op += mlen
+
+
+def lz4_decode_strict(data, expected: int) -> bytes:
+    """The bytes of a block that lz4_sequences accepts.  An overlapping copy (offset < length) is laid down by
+    doubling, so a block that is one long run costs a few numpy copies, not one Python step per byte."""
+    data = bytes(data)
+    dst = np.empty(expected, dtype=np.uint8)
+    src = np.frombuffer(data, dtype=np.uint8)
+    ip = op = 0
+    for run, mlen, offset, _ in lz4_sequences(data, expected):
+        ip += 1 + (0 if run < 15 else (run - 15) // 255 + 1)
+        dst[op:op + run] = src[ip:ip + run]
+        ip += run
+        op += run
+        if mlen is None:
+            break
+        ip += 2 + (0 if mlen - 4 < 15 else (mlen - 4 - 15) // 255 + 1)
+        ref, done = op - offset, 0
+        while done < mlen:              # [ref, op + done) is periodic with period `offset`: copy as much of it as fits
+            step = min(mlen - done, offset + done)
+            dst[op + done:op + done + step] = dst[ref:ref + step]
+            done += step
+        op += mlen
+    return dst.tobytes()
+
+
+def blosc_block_streams(frame):
+    """Walks an LZ4 Blosc-1 frame: yields (block_index, raw_size, stored_raw, stream_bytes) for every stream -- one per
+    block, or `typesize` per split block, each with its own raw size; stored_raw says that the stream is the raw bytes
+    themselves (cbytes == raw size).  A memcpy'd frame has no streams."""
+    mv = memoryview(frame)
+    h = parse_header(mv)
+    if h['version'] != 2 or h['cbytes'] != len(frame):
+        raise ValueError("not a whole Blosc-1 frame")
+    if h['memcpyed']:
+        return
+    if h['codec'] != 1 or h['versionlz'] != 1:
+        raise ValueError("not an LZ4 frame")
+    nbytes, typesize, blocksize = h['nbytes'], h['typesize'], h['blocksize']
+    nblocks = (nbytes + blocksize - 1) // blocksize if nbytes else 0
+    bstarts = struct.unpack_from(f'<{nblocks}i', mv, 16)
+    for b in range(nblocks):
+        bsize = min(blocksize, nbytes - b * blocksize)
+        split = (not h['dont_split']) and typesize <= BLOSC_MAX_SPLITS and blocksize // typesize >= BLOSC_MIN_BUFFERSIZE and bsize == blocksize
+        nsplits = typesize if split else 1
+        at = bstarts[b]
+        for _ in range(nsplits):
+            (cb,) = struct.unpack_from('<i', mv, at)
+            at += 4
+            if cb < 0 or at + cb > len(frame):
+                raise ValueError(f"block {b}: a stream of {cb} bytes leaves the frame")
+            yield b, bsize // nsplits, cb == bsize // nsplits, bytes(mv[at:at + cb])
+            at += cb
+
+
 def parse_header(frame) -> dict:
     version, versionlz, flags, typesize, nbytes, blocksize, cbytes = struct.unpack_from('<BBBBIII', frame, 0)
     return dict(version=version, versionlz=versionlz, flags=flags, typesize=typesize, nbytes=nbytes, blocksize=blocksize,
