@@ -156,6 +156,8 @@ EXPORTS = {
     'sq_despeckle_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                      C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_tile_stats': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    'sq_seam_stats': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_dpc_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
@@ -1288,6 +1290,92 @@ def tile_stats(tiles, out=None, stream=None):
             return out
         _check(lib().sq_tile_stats(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
                                    out.data_ptr(), _stream_ptr(stream)), 'sq_tile_stats')
+    return out
+
+
+SQ_SEAM_MAX_RADIUS = 3
+
+
+def seam_words(radius: int) -> int:
+    """Words per (plane, seam) of sq_seam_stats at search radius R: Sa, Saa, Sad and (Sb, Sbb, Sab) of (2R + 1)^2 offsets."""
+    radius = _int_in(radius, 0, SQ_SEAM_MAX_RADIUS, 'seam radius')
+    return 3 + 3 * (2 * radius + 1) ** 2
+
+
+def as_overlaps(pairs) -> np.ndarray:
+    """OVERLAP_DTYPE records, or [n, 8] ints (ref_tile, mov_tile, ref_y0, ref_x0, mov_y0, mov_x0, h, w) -> contiguous
+    OVERLAP_DTYPE [n]; ValueError for anything else."""
+    win = np.asarray(pairs)
+    if win.dtype != OVERLAP_DTYPE:
+        if win.dtype.kind not in 'iu' or (win.size and (win.ndim != 2 or win.shape[1] != 8)):
+            raise ValueError("pairs must be OVERLAP_DTYPE records or an [n, 8] integer array")
+        if win.size and (np.abs(win.astype(np.int64)) >= 2 ** 31).any():
+            raise ValueError("a pair's coordinate does not fit int32")
+        win = np.ascontiguousarray(win, dtype=np.int32).reshape(-1, 8).view(OVERLAP_DTYPE)
+    return np.ascontiguousarray(win.reshape(-1))
+
+
+def seam_pairs_to_device(pairs, device):
+    """The device copy of a pair table that ``seam_stats`` takes as ``pairs_dev`` (a caller with one table for many calls
+    uploads it once)."""
+    import torch
+    return upload_small(torch.from_numpy(as_overlaps(pairs).view(np.uint8).reshape(-1).copy()), device)
+
+
+def seam_stats(tiles, pairs, radius, out=None, stream=None, pairs_dev=None):
+    """The alignment words of every (plane, pair) of ``tiles`` (sq_seam_stats; an extension, the reference has none): for the
+    core windows a(y, x) of the ref tile and b_e(y, x) = mov[my + y - ey, mx + x - ex] of the mov tile, Sa, Saa, Sad = sum
+    |a - b_0| and then, row-major over e = (ey, ex) in [-R, R]^2, Sb_e, Sbb_e, Sab_e -- ``tests/seam_qc_ref.pair_words``;
+    ``seamqc.derive`` makes the ncc at the placement, the best residual displacement and the flags of them.
+
+    tiles:  uint8 / uint16 device tensor [m, n, H, W]: m planes of n tiles with unit-stride rows (any row pitch, any base
+            offset), the tiles one stride apart and the planes another; anything else raises ValueError.
+    pairs:  host array of OVERLAP_DTYPE records (or [k, 8] ints): the core windows at e = 0, the same for every plane.  A
+            tile index outside 0..n-1, a ref window outside its tile or a mov window nearer than R to an edge of its tile raises
+            NativeError, and nothing is launched.
+    radius: R, an integer in 0..SQ_SEAM_MAX_RADIUS.
+    out:    contiguous int64 device tensor [m, k, seam_words(R)]; its words are overwritten.  Allocated when None.
+    pairs_dev: ``seam_pairs_to_device(pairs, device)`` kept from an earlier call with the same table; uploaded here when None.
+    Returns ``out``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() != 4:
+        raise ValueError("tiles must be a [m, n, H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    words = seam_words(radius)
+    win = as_overlaps(pairs)
+    m, n = int(tiles.shape[0]), int(tiles.shape[1])
+    if m and n:
+        _, h, w, tile_stride, pitch = _plane_layout(tiles[0], 'tiles')
+        plane_stride = int(tiles.stride(0)) if m > 1 else (n - 1) * tile_stride + (h - 1) * pitch + w
+        if plane_stride < (n - 1) * tile_stride + (h - 1) * pitch + w:
+            raise ValueError("the planes of tiles overlap")
+    else:
+        h, w = int(tiles.shape[2]), int(tiles.shape[3])
+        if h < 1 or w < 1:
+            raise ValueError(f"tiles: planes of {h} x {w}")
+        tile_stride, pitch, plane_stride = h * w, w, n * h * w
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty((m, len(win), words), dtype=torch.int64, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or out.dtype != torch.int64 or out.device != tiles.device or \
+                tuple(out.shape) != (m, len(win), words) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int64 tensor of shape ({m}, {len(win)}, {words}) on the tiles' device")
+        if m == 0 or len(win) == 0:
+            return out
+        if n == 0:
+            raise NativeError(f"sq_seam_stats: {len(win)} pairs of no tiles")
+        if pairs_dev is None:
+            pairs_dev = seam_pairs_to_device(win, tiles.device)
+        elif not torch.is_tensor(pairs_dev) or pairs_dev.device != tiles.device or pairs_dev.dtype != torch.uint8 or \
+                pairs_dev.numel() != win.nbytes or not pairs_dev.is_contiguous():
+            raise ValueError("pairs_dev must be seam_pairs_to_device(pairs, device) of the same table")
+        _check(lib().sq_seam_stats(tiles.data_ptr(), m, n, h, w, plane_stride, tile_stride, pitch,
+                                   sq_dtype_of(np_dtype_of_torch(tiles.dtype)), win.ctypes.data, pairs_dev.data_ptr(), len(win),
+                                   radius, out.data_ptr(), _stream_ptr(stream)), 'sq_seam_stats')
+        pairs_dev.record_stream(torch.cuda.current_stream(tiles.device))      # (the stream of the launch, inside _on_stream)
     return out
 
 

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import alignment, composite as composite_mod, native, placement, registration, sharding, tileqc
+from . import alignment, composite as composite_mod, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -75,7 +75,8 @@ class Stitcher:
                  composite_channels=None, background_subtract: str = 'none', background_radius: int = 50,
                  despeckle: str = 'none', despeckle_threshold: int = 1000, tile_qc: bool = False,
                  tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5, dpc: bool = False,
-                 dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1):
+                 dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
+                 seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -197,6 +198,23 @@ class Stitcher:
         self._tile_qc_words: Dict[tuple, Dict[tuple, tuple]] = {}      # (timepoint, region) -> {(plane, fov): the eight words}
         self._tile_qc_pending = []       # (timepoint, region, device words [planes, tiles, 8], [(plane, fov)]) not read back yet
         self._tile_qc_shared = False     # the ranks share this region: the words are combined before anything is written
+        # Extension: seam_qc=True reports on every pair of overlapping tiles of every (channel, z) plane: how well the two
+        # agree where they are placed, and the integer residual displacement within +-seam_qc_radius at which they would
+        # agree best (sq_seam_stats' exact sums over the overlap inset by the radius; seamqc.py for the definition, the ncc,
+        # the flags 'unmeasured', 'featureless', 'low_ncc' below seam_qc_min_ncc and 'shifted') as
+        # <region>_stitched_seam_qc.csv / .json.  A pair is a seam when its inset overlap has seam_qc_min_pixels pixels.  The
+        # sums are taken of the staged planes as the fusion reads them: after dpc, despeckle and background removal, before the
+        # flatfield divide.  The three defaults are design choices, not measurements.  It changes no pixel of any output.
+        # False: nothing is launched, allocated, written or synchronised; the three values are checked and unused.
+        self.seam_qc, self.seam_qc_radius, self.seam_qc_min_pixels, self.seam_qc_min_ncc = \
+            seamqc.check_options(seam_qc, seam_qc_radius, seam_qc_min_pixels, seam_qc_min_ncc)
+        self.seam_qc_table: Dict[tuple, List[dict]] = {}      # (timepoint, region) -> the rows of its CSV
+        self._seam_qc_words: Dict[tuple, Dict[tuple, tuple]] = {}     # (timepoint, region) -> {(plane, ref fov, mov fov): words}
+        self._seam_qc_pending = []       # (timepoint, region, device words [planes, seams, words], plane ids, [(ref, mov)])
+        self._seam_qc_tables: Dict[tuple, tuple] = {}      # (rectangle list, fovs) -> (seams, host table, device table)
+        self._seam_qc_layouts: Dict[tuple, tuple] = {}     # (timepoint, region) -> (its seams, {plane: fovs with a file}), as staged
+        self._seam_qc_planes: Dict[tuple, set] = {}        # (timepoint, region) -> the planes staged so far
+        self._seam_qc_shared = False     # the ranks share this region: the words are combined before anything is written
         # Extension: dpc=True adds one derived channel, 'DPC', the differential phase contrast of the two half-pupil brightfield
         # channels dpc_channels = (left, right): with S = L + R, N = S + 2 dpc_gain (L - R) and M the dtype's maximum, 0 where
         # S == 0 and clamp(floor(M N / (2 S)), 0, M) elsewhere (sq_dpc_tiles; tests/dpc_ref.py) -- for gain 1 Squid's
@@ -1256,6 +1274,20 @@ class Stitcher:
                     # of them; they are read back with the despeckle counts, behind the call's synchronise
                     qc_words = torch.empty((len(plist), n, native.SQ_TILE_STATS_WORDS), dtype=torch.int64, device=self.device)
                     self._tile_qc_pending.append((timepoint, region, qc_words, [(p, it[3]) for p in plist for it in planes[p]]))
+                seam_table = seam_words = None
+                if self.seam_qc:
+                    # the seams among this list's tiles and their words (plane of plist, seam): every chunk's launch overwrites
+                    # its own run of them; they are read back with the tile-qc words, behind the call's synchronise
+                    seam_table = self._seam_qc_table_of(sig, rects, [tuple(it[3] for it in planes[p]) for p in plist], th, tw)
+                    if (int(timepoint), region) not in self._seam_qc_layouts:      # at the placement these launches see
+                        self._seam_qc_layouts[(int(timepoint), region)] = self._seam_qc_layout(timepoint, region)
+                    if seam_table is None:      # no seam among these tiles: the planes are still reported
+                        self._seam_qc_pending.append((timepoint, region, None, list(plist), []))
+                    else:
+                        seam_words = torch.empty((len(plist), len(seam_table[1]), native.seam_words(self.seam_qc_radius)),
+                                                 dtype=torch.int64, device=self.device)
+                        self._seam_qc_pending.append((timepoint, region, seam_words, list(plist),
+                                                      [(s['ref_fov'], s['mov_fov']) for s in seam_table[0]]))
                 for k, chunk in enumerate(chunks):
                     b0 = k * batch      # the chunk is plist[b0:b0 + m]
                     slot = turn[0] % n_slots      # (the turn goes on across calls: the next region starts on the other slot)
@@ -1311,6 +1343,9 @@ class Stitcher:
                                                        counts=list_counts[b0:b0 + m].view(-1))
                     if tophat:      # in place on the staged tiles: everything below reads the filtered planes
                         native.tophat_tiles(tiles, self.background_radius, tophat_scratch)
+                    if seam_words is not None:      # the planes as the fusion reads them: behind the last filter
+                        native.seam_stats(tiles, seam_table[1], self.seam_qc_radius, out=seam_words[b0:b0 + m],
+                                          pairs_dev=seam_table[2])
                     flats = [flats_dev.get(p // self.num_z) for p in chunk] if self.apply_flatfield else None
                     slots = [slot_of[p] for p in chunk]
                     if project_to is not None:
@@ -1369,6 +1404,7 @@ class Stitcher:
             torch.cuda.synchronize(self.device)
             self._finish_despeckle()
             self._finish_tile_qc()
+            self._finish_seam_qc()
         print(f"Time to stitch region {region} timepoint {timepoint}: {time.time() - start_time}")
         return flat_canvas, plane_ids
 
@@ -1502,6 +1538,115 @@ class Stitcher:
                 words[(int(p), int(fov))] = tuple(w)
             self._tile_qc_words[(int(timepoint), region)] = words
             self._write_tile_qc(timepoint, region)
+
+    # ------------------------------------------------------------------ seam alignment report
+    def _seam_qc_table_of(self, sig, rects, fov_lists, th, tw):
+        """(seams, host pair table, device pair table) of the rectangle list ``rects`` whose i-th tile is fov ``fovs[i]`` --
+        the seams both of whose tiles are in the list -- cached per list; None when the list holds no seam."""
+        fovs = fov_lists[0]
+        if any(f != fovs for f in fov_lists[1:]):
+            raise RuntimeError("seam-qc: planes that share one rectangle list name different fovs")
+        key = (sig, fovs, th, tw, self.seam_qc_radius, self.seam_qc_min_pixels)
+        if key not in self._seam_qc_tables:
+            seams = seamqc.region_seams({f: rects[i] for i, f in enumerate(fovs)}, th, tw, self.seam_qc_radius,
+                                        self.seam_qc_min_pixels)
+            entry = None
+            if seams:
+                table = native.as_overlaps(seamqc.pair_table(seams, {f: i for i, f in enumerate(fovs)}))
+                entry = (seams, table, native.seam_pairs_to_device(table, self.device))
+            if len(self._seam_qc_tables) >= 64:
+                self._seam_qc_tables.clear()
+            self._seam_qc_tables[key] = entry
+        return self._seam_qc_tables[key]
+
+    def _finish_seam_qc(self) -> None:
+        """Read the pending words back (the device has been synchronised, as for _finish_tile_qc), keep them per (timepoint,
+        region) -- a seam measured more than once (row bands, several calls) must give the same words and is kept once -- and
+        write the report of every region that got new words, from all the words it has so far.  A region the ranks share is
+        written by _finish_seam_qc_shared instead."""
+        pending, self._seam_qc_pending = self._seam_qc_pending, []
+        touched = []
+        for timepoint, region, words, plist, keys in pending:
+            have = self._seam_qc_words.setdefault((int(timepoint), region), {})
+            self._seam_qc_planes.setdefault((int(timepoint), region), set()).update(int(p) for p in plist)
+            host = words.cpu().numpy() if words is not None else None
+            for pi, p in enumerate(plist):
+                for (ref, mov), row in zip(keys, host[pi] if keys else ()):
+                    row = tuple(int(v) for v in row)
+                    if have.setdefault((int(p), ref, mov), row) != row:
+                        raise RuntimeError(f"seam-qc: the seam of fovs {ref} and {mov} in plane {p} of region {region} was "
+                                           "measured twice with different words")
+            if (int(timepoint), region) not in touched:
+                touched.append((int(timepoint), region))
+        if not self._seam_qc_shared:
+            for timepoint, region in touched:
+                self._write_seam_qc(timepoint, region)
+
+    def _seam_qc_layout(self, timepoint, region):
+        """(seams of the whole region, {plane: the fovs that have a file of it}) from the region's files and rectangles."""
+        rects, fovs_of = {}, {}
+        for key, info in self.get_region_data(int(timepoint), region).items():
+            _, _, fov, z_level, channel = key
+            rects.setdefault(int(fov), self._tile_rect(info))
+            if channel in self.monochrome_channels:
+                ids = [self.monochrome_channels.index(channel) * self.num_z + z_level]
+            else:
+                base = channel.split('_')[0]
+                ids = [self.monochrome_channels.index(f"{base}_{color}") * self.num_z + z_level for color in 'RGB']
+            for p in ids:
+                fovs_of.setdefault(p, set()).add(int(fov))
+        seams = seamqc.region_seams(rects, self.input_height, self.input_width, self.seam_qc_radius, self.seam_qc_min_pixels)
+        return seams, fovs_of
+
+    def _write_seam_qc(self, timepoint, region) -> None:
+        """The rows of (timepoint, region) -- for every plane that has words, the region's seams both of whose files exist,
+        sorted by (output channel, z, ref fov, mov fov); a seam without words is 'unmeasured' -- into seam_qc_table and the two
+        files under <t>_stitched/; one printed line with the flag counts."""
+        words = self._seam_qc_words.get((int(timepoint), region), {})
+        seams, fovs_of = self._seam_qc_layouts.get((int(timepoint), region)) or self._seam_qc_layout(timepoint, region)
+        rows = []
+        for p in sorted(self._seam_qc_planes.get((int(timepoint), region), ())):
+            have = fovs_of.get(p, ())
+            for s in seams:
+                if s['ref_fov'] in have and s['mov_fov'] in have:
+                    rows.append(seamqc.make_row(region, self.monochrome_channels[p // self.num_z], p % self.num_z, s,
+                                                words.get((p, s['ref_fov'], s['mov_fov'])), self.seam_qc_radius))
+        seamqc.flag_rows(rows, self.seam_qc_min_ncc)
+        self.seam_qc_table[(int(timepoint), region)] = rows
+        note = seamqc.write_report(os.path.join(self.output_folder, f"{timepoint}_stitched"), region, rows,
+                                   self.monochrome_channels, self.seam_qc_radius, self.seam_qc_min_pixels, self.seam_qc_min_ncc)
+        print(f"[seam-qc] region {region} timepoint {timepoint}: {len(rows)} seams of planes -- " +
+              ", ".join(f"{k}: {v}" for k, v in note['flag_counts'].items()))
+
+    def _finish_seam_qc_shared(self, timepoint, region, rank) -> None:
+        """A region the ranks share by planes or bands: every rank's words go into the region's dense table [num_c * num_z,
+        seams of the region, words + 1] -- the words and a 'present' word, absent entries all zero -- which is combined with
+        ONE element-wise MAX all-reduce (every word is >= 0, and an entry is absent or identical on every rank that has it, so
+        MAX is exact); rank 0 writes the files."""
+        import torch
+        import torch.distributed as dist
+        torch.cuda.synchronize(self.device)
+        self._finish_seam_qc()
+        seams, fovs_of = self._seam_qc_layouts.get((int(timepoint), region)) or self._seam_qc_layout(timepoint, region)
+        index = {(s['ref_fov'], s['mov_fov']): i for i, s in enumerate(seams)}
+        nw = native.seam_words(self.seam_qc_radius)
+        dense = np.zeros((self.num_c * self.num_z, len(seams), nw + 1), dtype=np.int64)
+        for (p, ref, mov), w in self._seam_qc_words.get((int(timepoint), region), {}).items():
+            dense[p, index[(ref, mov)], :nw] = w
+            dense[p, index[(ref, mov)], nw] = 1
+        table = torch.from_numpy(dense)
+        coll = sharding.collective_device(self)
+        if coll is not None:
+            table = table.to(coll)
+        dist.all_reduce(table, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            dense = table.cpu().numpy()
+            words = {}
+            for p, i in zip(*np.nonzero(dense[:, :, nw])):
+                words[(int(p), seams[i]['ref_fov'], seams[i]['mov_fov'])] = tuple(int(v) for v in dense[p, i, :nw])
+            self._seam_qc_words[(int(timepoint), region)] = words
+            self._seam_qc_planes[(int(timepoint), region)] = set(fovs_of)      # the ranks staged every plane between them
+            self._write_seam_qc(timepoint, region)
 
     # ------------------------------------------------------------------ output
     # ------------------------------------------------------------------ contrast windows
@@ -1906,6 +2051,7 @@ class Stitcher:
         print(f"\nProcessing timepoint {timepoint}, region {region}: (plane, band) units {units} (rank {rank}/{world})")
         stack = self.z_projection not in ('max-only', 'focus-only')
         self._tile_qc_shared = self.tile_qc
+        self._seam_qc_shared = self.seam_qc
         if rank == 0:
             if stack:
                 self.create_region_store(timepoint, region)
@@ -1943,6 +2089,11 @@ class Stitcher:
                 self._finish_tile_qc_shared(timepoint, region, rank)
             finally:
                 self._tile_qc_shared = False
+        if self.seam_qc:
+            try:
+                self._finish_seam_qc_shared(timepoint, region, rank)
+            finally:
+                self._seam_qc_shared = False
         sharding.barrier()
         return output_path
 
@@ -2136,11 +2287,12 @@ class Stitcher:
         finally:
             self._defer_drain = False
             self._close_stream_writer()
-        if self._despeckle_pending or self._tile_qc_pending:      # the writer has been drained: every region's launches have finished
+        if self._despeckle_pending or self._tile_qc_pending or self._seam_qc_pending:      # the writer has been drained: every region's launches have finished
             import torch
             torch.cuda.synchronize(self.device)
             self._finish_despeckle()
             self._finish_tile_qc()
+            self._finish_seam_qc()
         self._finish_contrast(wait=True)
         self._finish_composites(wait=True)
         sharding.barrier()

@@ -9,6 +9,9 @@ plus eighteen switches for what this build adds (``--fusion-mode``, ``--normaliz
 removal that runs on the staged tiles before it.  ``--tile-qc``, ``--tile-qc-saturation`` and ``--tile-qc-focus-ratio`` select
 the per-tile quality report (focus, saturation, intensity) of the tiles as they are in their files.  ``--dpc``,
 ``--dpc-channels`` and ``--dpc-gain`` add the differential phase contrast channel made of the two half-pupil brightfield tiles.
+``--seam-qc``, ``--seam-qc-radius``, ``--seam-qc-min-pixels`` and ``--seam-qc-min-ncc`` select the per-seam alignment report: how
+well every pair of overlapping tiles agrees where it is placed, on every (channel, z) plane, and the integer residual displacement
+at which it would agree best.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -142,6 +145,25 @@ FLAGS = (
     (('--dpc-gain',), dict(type=int, default=1, metavar='G',
                            help="with --dpc: the difference is multiplied by this integer, 1..16, before the clip: "
                                 "0.5 + G (L - R) / (L + R)")),
+    (('--seam-qc',), dict(action='store_true',
+                          help="report on every pair of overlapping tiles of every (channel, z) plane, from the planes staged on "
+                               "the device as the fusion reads them -- after --dpc, --despeckle and --background-subtract, before "
+                               "the flatfield divide (no pixel of any output changes): <region>_stitched_seam_qc.csv with the "
+                               "pair's placement offset (dy, dx), the pixels compared (the overlap inset by the radius), the mean "
+                               "of each side and the mean absolute difference in raw counts, the zero-normalised "
+                               "cross-correlation ncc at the placement, the integer residual displacement (best_dy, best_dx) "
+                               "within the radius at which the ncc is largest, and the flags unmeasured / featureless / low_ncc "
+                               "/ shifted; a summary in <region>_stitched_seam_qc.json (per channel the median ncc per z and a "
+                               "histogram of the residuals), and one printed line per region")),
+    (('--seam-qc-radius',), dict(type=int, default=2, metavar='R',
+                                 help="with --seam-qc: residual displacements up to this many pixels along each axis are tried, "
+                                      "0..3")),
+    (('--seam-qc-min-pixels',), dict(type=int, default=256, metavar='N',
+                                     help="with --seam-qc: two tiles form a seam when their overlap, inset by the radius, has at "
+                                          "least this many pixels")),
+    (('--seam-qc-min-ncc',), dict(type=float, default=0.5, metavar='C',
+                                  help="with --seam-qc: a seam is flagged low_ncc when its ncc at the placement is below this, "
+                                       "-1..1")),
 )
 
 
@@ -214,6 +236,10 @@ def main(argv=None):
                             tile_qc=args.tile_qc,
                             tile_qc_saturation=args.tile_qc_saturation,
                             tile_qc_focus_ratio=args.tile_qc_focus_ratio,
+                            seam_qc=args.seam_qc,
+                            seam_qc_radius=args.seam_qc_radius,
+                            seam_qc_min_pixels=args.seam_qc_min_pixels,
+                            seam_qc_min_ncc=args.seam_qc_min_ncc,
                             dpc=args.dpc,
                             dpc_channels=tuple(args.dpc_channels),
                             dpc_gain=args.dpc_gain)

@@ -587,6 +587,38 @@ int sq_pair_overlap_moments(const void *const *tile_ptrs_dev, const void *tile_b
                             const sq_overlap *pairs_dev, int32_t n_pairs, uint64_t *out_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-seam alignment words (--seam-qc; extension: the reference has none): how well two overlapping tiles agree where they are
+ * placed, and at every integer residual displacement e = (ey, ex) in [-R, R]^2 around that placement, R = radius in
+ * 0..SQ_SEAM_MAX_RADIUS.  tiles_dev holds n_planes planes of n_tiles tiles [h, w] (SQ_U8 / SQ_U16), the planes a plane stride,
+ * the tiles a tile stride and the rows a pitch apart (elements, pitch >= w; no alignment asked beyond the element's own).  ONE
+ * pair table applies to every plane: record i is the CORE window pair at e = 0 -- for tiles whose full-tile canvas origins
+ * differ by d = o_mov - o_ref, with the overlap (ry0, rx0, my0, mx0, ho, wo) of the two full tiles at d, the core is the overlap
+ * inset by R on all four sides: h = ho - 2R, w = wo - 2R, ref window at (ry0 + R, rx0 + R), mov window at (my0 + R, mx0 + R).
+ * With a(y, x) = ref[ref_y0 + y, ref_x0 + x] and b_e(y, x) = mov[mov_y0 + y - ey, mov_x0 + x - ex] over the core,
+ * out_dev[plane][pair][...] receives 3 + 3 (2R + 1)^2 words:
+ *     0  Sa = sum a      1  Saa = sum a^2      2  Sad = sum |a - b_0|
+ *     then, row-major over (ey, ex) from (-R, -R):  Sb_e = sum b_e,  Sbb_e = sum b_e^2,  Sab_e = sum a b_e
+ * When the tiles agree at e, their true displacement is d + e.  The definition is the numpy restatement in
+ * tests/seam_qc_ref.py.  Integers only, 64-bit from the first add of a product; the words are bit for bit numpy's int64 sums
+ * whatever the schedule (per-workgroup partial sums, then one 64-bit integer atomic add per word per workgroup into words the
+ * call zeroes on `stream` first: out_dev needs no preparation and is OVERWRITTEN).  Every piece of a window is read from global
+ * memory once -- the mov piece with its R-pixel halo into LDS, a thread's ref column into registers -- and the offsets are
+ * evaluated from there (csrc/seam.hip).
+ * pairs_host is the table on the host and is what the call validates -- tile indices, the ref window inside its tile, the mov
+ * window at least R inside its tile on every side; pairs_dev is the same table on the device and is what the kernel reads (the
+ * caller keeps the two equal).  Asynchronous on `stream`: no host read-back, no allocation, no other stream.  SQ_ERR_INVALID,
+ * and nothing is launched, for a bad record, an unknown dtype, a radius outside 0..SQ_SEAM_MAX_RADIUS, negative counts, h or
+ * w < 1, a pitch below w, strides smaller than what they step over, and a NULL or misaligned pointer.  SQ_ERR_UNSUPPORTED for a
+ * core of more than 2^31 pixels (below that no word can reach 2^63).  n_pairs == 0 or n_planes == 0 is SQ_OK.  A record with
+ * h == 0 or w == 0 gives zeros.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_SEAM_MAX_RADIUS 3
+int sq_seam_stats(const void *tiles_dev, int32_t n_planes, int32_t n_tiles, int32_t h, int32_t w, int64_t plane_stride,
+                  int64_t tile_stride, int64_t pitch, int32_t dtype, const sq_overlap *pairs_host, const sq_overlap *pairs_dev,
+                  int32_t n_pairs, int32_t radius, uint64_t *out_dev /* [n_planes][n_pairs][3 + 3 (2R+1)^2], overwritten */,
+                  void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Chunk encoding on the device: the chunks of n_planes (t, c, z) planes (chunk_h x chunk_w elements,
  * zero-padded past the plane's edge like zarr pads edge chunks) as Blosc-1 frames -- byte shuffle + LZ4, the
  * default codec of the store the reference writes (zarr.storage.default_compressor, stitcher.py:814-818) -- packed
