@@ -160,6 +160,8 @@ EXPORTS = {
                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'sq_dpc_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    'sq_bin_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1418,6 +1420,59 @@ def dpc_tiles(left, right, gain: int = 1, out=None, stream=None):
     _check(lib().sq_dpc_tiles(left.data_ptr(), right.data_ptr(), out.data_ptr(), n_images, h, w, left_plane_stride, left_pitch,
                               right_plane_stride, right_pitch, out_plane_stride, out_pitch,
                               sq_dtype_of(np_dtype_of_torch(left.dtype)), gain, _stream_ptr(stream)), 'sq_dpc_tiles')
+    return out
+
+
+SQ_BIN_MEAN = 1
+SQ_BIN_SUM = 2
+SQ_BIN_MAX_FACTOR = 8
+BIN_METHODS = {'mean': SQ_BIN_MEAN, 'sum': SQ_BIN_SUM}
+
+
+def bin_tiles(tiles, factor: int, method: str = 'mean', out=None, stream=None):
+    """K x K binning of every H x W plane of ``tiles`` into ``out`` (sq_bin_tiles; an extension, the reference has nothing
+    like it): with hb = H // K and wb = W // K -- the last H - K hb rows and W - K wb columns are dropped -- and S the sum of
+    a K x K block, 'mean' gives floor(S / K^2) and 'sum' gives min(S, M), M the dtype's maximum, exact in integers --
+    ``tests/bin_ref.bin_image``.  The binning is out of place: ``tiles`` is left as it is.
+
+    tiles:  uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
+            uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    factor: K, an integer in 2..8 no larger than H or W.
+    method: 'mean' or 'sum'.
+    out:    a tensor [..., hb, wb] with the same leading dimensions, dtype and device under the same rules (its columns beyond
+            wb stay as they are) that shares no memory with ``tiles``; allocated contiguous when None.
+    Returns ``out``."""
+    import torch
+    factor = _int_in(factor, 2, SQ_BIN_MAX_FACTOR, 'binning factor')
+    if not isinstance(method, str) or method not in BIN_METHODS:
+        raise ValueError(f"binning method must be 'mean' or 'sum', got {method!r}")
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    src = _plane_layout(tiles, 'tiles')
+    n_images, h, w, src_plane_stride, src_pitch = src
+    hb, wb = h // factor, w // factor
+    if hb < 1 or wb < 1:
+        raise ValueError(f"planes of {h} x {w} have no {factor} x {factor} block")
+    shape = tuple(tiles.shape[:-2]) + (hb, wb)
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
+            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
+        dst = _plane_layout(out, 'out')
+        n_out, _, _, dst_plane_stride, dst_pitch = dst
+        assert n_out == n_images
+        if n_images == 0:
+            return out
+        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
+            raise ValueError("out shares memory with tiles: the binning is out of place")
+        _check(lib().sq_bin_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
+                                  dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), factor,
+                                  BIN_METHODS[method], _stream_ptr(stream)), 'sq_bin_tiles')
     return out
 
 

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import alignment, composite as composite_mod, native, placement, registration, seamqc, sharding, tileqc
+from . import alignment, binning, composite as composite_mod, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -76,7 +76,8 @@ class Stitcher:
                  despeckle: str = 'none', despeckle_threshold: int = 1000, tile_qc: bool = False,
                  tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5, dpc: bool = False,
                  dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
-                 seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5):
+                 seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
+                 tile_binning: int = 1, tile_binning_method: str = 'mean'):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -244,6 +245,18 @@ class Stitcher:
                 raise ValueError(f"dpc_channels {self.dpc_channels}: {native.DPC_CHANNEL!r} is the derived channel's own name")
             if params.registration_channel == native.DPC_CHANNEL:
                 raise ValueError(f"registration_channel {native.DPC_CHANNEL!r} is the derived channel: registration reads files")
+        # Extension: tile_binning=K (1..8) stitches K x K binned tiles: with hb = h // K and wb = w // K (the last rows and columns
+        # are dropped) and S the sum of a K x K block, tile_binning_method 'mean' gives floor(S / K^2) -- the truncated mean of
+        # pyramid_method='mean' -- and 'sum' gives min(S, M), M the dtype's maximum: camera binning (binning.py;
+        # tests/bin_ref.py).  A run equals a run without the option on a folder that holds the binned files, the same
+        # coordinates.csv and an 'acquisition parameters.json' whose sensor_pixel_size_um is multiplied by K, byte for byte
+        # in every store, sidecar and picture: the staged tiles are binned on the device as the first launch after the copy
+        # (sq_bin_tiles), the all-pairs stack likewise, and the readers of single files (the metadata probe, get_tile and the
+        # centre-pair registration, the flatfield estimate's samples) bin on the host -- placement, registration, the
+        # flatfield estimate and every tile filter see binned tiles only.  input_height / input_width are the binned size
+        # (file_height / file_width the files'), pixel_size_um the binned pixel's.  1: nothing is launched, allocated, written
+        # or parsed differently; the method is checked and unused.
+        self.tile_binning, self.tile_binning_method = binning.check_options(tile_binning, tile_binning_method)
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -296,7 +309,9 @@ class Stitcher:
         self.monochrome_channels = []
         self.monochrome_colors = []
         self.num_z = self.num_c = self.num_t = 1
-        self.input_height = self.input_width = 0
+        self.input_height = self.input_width = 0      # the tiles as everything downstream sees them (binned with tile_binning)
+        self.file_height = self.file_width = 0        # the tiles as they are in their files
+        self.file_pixel_size_um = None
         self.num_pyramid_levels = 5
         self.flatfields = {}
         self.acquisition_metadata = {}
@@ -338,7 +353,10 @@ class Stitcher:
         obj_focal_length_mm = ap['objective']['tube_lens_f_mm'] / ap['objective']['magnification']
         actual_mag = ap['tube_lens_mm'] / obj_focal_length_mm
         self.pixel_binning = ap.get('pixel_binning', 1)
-        self.pixel_size_um = ap['sensor_pixel_size_um'] / actual_mag
+        self.file_pixel_size_um = ap['sensor_pixel_size_um'] / actual_mag
+        # (in this order: bit for bit what a folder of binned files, whose sensor pixel is K times as large, gives)
+        self.pixel_size_um = (ap['sensor_pixel_size_um'] * self.tile_binning) / actual_mag if self.tile_binning > 1 \
+            else self.file_pixel_size_um
         print(f"[metadata] pixel size {self.pixel_size_um} um")
 
     @staticmethod
@@ -422,9 +440,17 @@ class Stitcher:
         self.dtype = first_image.dtype.type
         self._check_despeckle_dtype()
         if first_image.ndim in (2, 3):
-            self.input_height, self.input_width = first_image.shape[:2]
+            self.file_height, self.file_width = first_image.shape[:2]
+            self.input_height, self.input_width = self.file_height, self.file_width
         else:
             raise ValueError(f"Unexpected image shape: {first_image.shape}")
+        if self.tile_binning > 1:      # (refused here when K is larger than a side of the tiles)
+            self.input_height, self.input_width = binning.binned_shape(self.file_height, self.file_width, self.tile_binning)
+            print(f"[binning] {self.tile_binning} x {self.tile_binning} {self.tile_binning_method}: tiles of "
+                  f"{self.file_height} x {self.file_width} stitched as {self.input_height} x {self.input_width} "
+                  f"({self.file_height - self.tile_binning * self.input_height} rows, "
+                  f"{self.file_width - self.tile_binning * self.input_width} columns dropped), pixel size "
+                  f"{self.file_pixel_size_um} -> {self.pixel_size_um} um")
         self.chunks = (1, 1, 1, 512, 512)
         self.monochrome_channels = []
         # (the derived channel sits where its name sorts among the file channels; channel_names stays the file channels)
@@ -509,7 +535,7 @@ class Stitcher:
         for value in self.get_region_data(int(t), str(region)).values():
             if value['x'] == x and value['y'] == y and value['channel'] == channel and value['z_level'] == z_level:
                 try:
-                    return read_image(value['filepath'])
+                    return binning.read_binned(value['filepath'], self.tile_binning, self.tile_binning_method)
                 except FileNotFoundError:
                     print(f"Warning: cannot open {value['filepath']}")
                     return None
@@ -688,7 +714,10 @@ class Stitcher:
                 return img if img.ndim == 2 else img[..., 0]
             with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as pool:
                 images = list(pool.map(one, cells))
-            return torch.from_numpy(np.ascontiguousarray(np.stack(images))).to(self.device)
+            stack = torch.from_numpy(np.ascontiguousarray(np.stack(images))).to(self.device)
+            if self.tile_binning > 1:      # the raw stack, binned by the launch the staged tiles go through
+                stack = native.bin_tiles(stack, self.tile_binning, self.tile_binning_method)
+            return stack
 
         table = registration.register_all_pairs_sharded(
             pairs, load_cells, self.input_height, self.input_width, max_x_overlap, max_y_overlap, self.normalization,
@@ -812,7 +841,7 @@ class Stitcher:
             if not paths:
                 print(f"WARNING: No images found for channel {channel} across all timepoints")
                 continue
-            images = np.array([read_image(p) for p in paths])
+            images = np.array([binning.read_binned(p, self.tile_binning, self.tile_binning_method) for p in paths])
             if images.ndim == 4 and images.shape[1] == 1:       # (N, 1, Y, X) page stacks
                 images = images[:, 0]
             if images.ndim == 3:
@@ -1073,8 +1102,14 @@ class Stitcher:
         flat_canvas = None if (stream_to is not None or not stack) else \
             self._empty_canvas(len(plane_ids), hc, wc, native.torch_dtype_of(self.dtype))
         th, tw = self.input_height, self.input_width
+        # --tile-binning: the files (and so the pinned staging and its device mirror) are fh x fw; everything behind the
+        # binning launch is th x tw
+        binned = self.tile_binning > 1
+        fh, fw = (self.file_height, self.file_width) if binned else (th, tw)
         total_tiles = len(region_data)
         print(f"Beginning stitching of {total_tiles} tiles for region {region} timepoint {timepoint}")
+        if binned:
+            self._write_binning_note(timepoint, region)
         if self.background_subtract == 'tophat':
             self._write_background_note(timepoint, region)
         despeckle = self.despeckle != 'none'
@@ -1152,9 +1187,16 @@ class Stitcher:
             flats_dev = {}
             if self.apply_flatfield:
                 for ci, ff in self.flatfields.items():
+                    if binned and tuple(np.shape(ff)) != (th, tw):
+                        raise ValueError(f"the flatfield of channel {ci} is {tuple(np.shape(ff))}: with tile_binning "
+                                         f"{self.tile_binning} the gains divide the binned tiles of {(th, tw)}, not the files' "
+                                         f"{(fh, fw)}")
                     flats_dev[ci] = torch.from_numpy(np.ascontiguousarray(ff)).to(self.device)
             if stream_to is not None and groups:
-                widest = max(len(rect_of[sig]) for sig in groups) * th * tw * np.dtype(self.dtype).itemsize
+                # (one staged plane of the longest list: its raw tiles and, with --tile-binning, their binned copy -- the
+                # batch budget below counts the same two)
+                widest = max(len(rect_of[sig]) for sig in groups) * (fh * fw + (th * tw if binned else 0)) * \
+                    np.dtype(self.dtype).itemsize
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
             def parts_of(t):      # the tensors of a target that this call writes
                 return t if isinstance(t, tuple) else ((t.out,) if isinstance(t, FocusFollower) else (t,))
@@ -1209,8 +1251,14 @@ class Stitcher:
                 # and so does the despeckle's destination (one more copy of a batch's tiles)
                 # and the right halves of the derived planes (--dpc: counted as one more copy, though only they have one)
                 n_derived = sum(p // self.num_z == self._dpc_index for p in plist) if self.dpc else 0
-                batch = max(1, min(len(plist), staged_budget // max(1, per_plane * (1 + int(despeckle) + int(tophat) +
-                                                                                     int(n_derived > 0)))))
+                copies = 1 + int(despeckle) + int(tophat) + int(n_derived > 0)
+                staged_per_plane = per_plane * copies
+                if binned:
+                    # the staged planes (and the right halves) keep the files' size; the binned copy of both -- 1 / K^2 of
+                    # them -- and everything behind it is per_plane
+                    raw_per_plane = n * fh * fw * np.dtype(self.dtype).itemsize
+                    staged_per_plane = raw_per_plane * (1 + int(n_derived > 0)) + per_plane * copies
+                batch = max(1, min(len(plist), staged_budget // max(1, staged_per_plane)))
                 if writer is not None:
                     batch = min(batch, writer.batch)
                 chunks = [plist[b0:b0 + batch] for b0 in range(0, len(plist), batch)]
@@ -1218,11 +1266,11 @@ class Stitcher:
                 # the next region's files are then read while this region's copy and fusion are still under way
                 pipelined = writer is not None and self._defer_drain
                 n_slots = 2 if (len(chunks) > 1 or pipelined) else 1
-                key = ('ingest', batch, n, th, tw, n_slots, np.dtype(self.dtype).str)
+                key = ('ingest', batch, n, fh, fw, n_slots, np.dtype(self.dtype).str)
                 bufs = self._buffer_cache.get(key)
                 if bufs is None:   # pinned staging + device mirrors, kept for the next region of the same shape
-                    bufs = ([torch.empty((batch, n, th, tw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
-                            [torch.empty((batch, n, th, tw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
+                    bufs = ([torch.empty((batch, n, fh, fw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
+                            [torch.empty((batch, n, fh, fw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
                             [None] * n_slots, [0])
                     self._keep_buffers(key, bufs)
                 # the slots' "copy and fusion finished" events live with the buffers: another group (or the next
@@ -1236,6 +1284,17 @@ class Stitcher:
                         tophat_scratch = torch.empty(native.tophat_scratch_bytes(batch * n, th, tw, self.dtype), dtype=torch.uint8,
                                                      device=self.device)
                         self._keep_buffers(tkey, tophat_scratch)
+                binned_tiles = None
+                if binned:
+                    # ONE binned buffer for both ingest slots, by the argument for the despeckle's `clean` below: the binning
+                    # and everything that reads its result are launches of one stream, so the next chunk's binning (which
+                    # overwrites it) runs after this chunk's fusion has read it; only the H2D copy into the OTHER slot's raw
+                    # tiles overlaps, and nothing reads those but the binning of their own chunk
+                    bkey = ('binning', batch, n, th, tw, np.dtype(self.dtype).str)
+                    binned_tiles = self._buffer_cache.get(bkey)
+                    if binned_tiles is None:
+                        binned_tiles = torch.empty((batch, n, th, tw), dtype=tdtype, device=self.device)
+                        self._keep_buffers(bkey, binned_tiles)
                 clean = None
                 if despeckle:
                     # ONE destination for both ingest slots: despeckle, top-hat and the fusion that reads `clean` are launches
@@ -1253,21 +1312,27 @@ class Stitcher:
                     # the kernel's per-plane counts of this list's planes (plane of plist, tile): every chunk adds into its own
                     # run of it, and it is folded per channel once, behind the last chunk
                     list_counts = torch.zeros((len(plist), n), dtype=torch.int64, device=self.device)
-                right_staging = right_dev = right_done = None
+                right_staging = right_dev = right_done = binned_rights = None
                 if n_derived:
                     # the right halves: one more staged buffer per ingest slot, pinned and mirrored on the device, as deep as
                     # a chunk can hold derived planes (they are consecutive: plist is ascending).  Its own events: whatever
                     # ingest buffers it is used beside, the copy and the launch that read a slot have finished before the
                     # loader writes to it again
                     deep = min(batch, n_derived)
-                    rkey = ('dpc', deep, n, th, tw, n_slots, np.dtype(self.dtype).str)
+                    rkey = ('dpc', deep, n, fh, fw, n_slots, np.dtype(self.dtype).str)
                     rbufs = self._buffer_cache.get(rkey)
                     if rbufs is None:
-                        rbufs = ([torch.empty((deep, n, th, tw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
-                                 [torch.empty((deep, n, th, tw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
+                        rbufs = ([torch.empty((deep, n, fh, fw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
+                                 [torch.empty((deep, n, fh, fw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
                                  [None] * n_slots)
                         self._keep_buffers(rkey, rbufs)
                     right_staging, right_dev, right_done = rbufs
+                    if binned:      # the binned right halves: one small buffer for both slots, like `binned_tiles`
+                        rbkey = ('binning-dpc', deep, n, th, tw, np.dtype(self.dtype).str)
+                        binned_rights = self._buffer_cache.get(rbkey)
+                        if binned_rights is None:
+                            binned_rights = torch.empty((deep, n, th, tw), dtype=tdtype, device=self.device)
+                            self._keep_buffers(rbkey, binned_rights)
                 qc_words = None
                 if self.tile_qc:
                     # the words of this list's staged planes (plane of plist, tile): every chunk's launch overwrites its own run
@@ -1311,7 +1376,7 @@ class Stitcher:
                             img = img[:, :, rgb]
                         elif img.ndim == 3 and img.shape[0] == 1:
                             img = img[0]
-                        if img.shape != (th, tw):
+                        if img.shape != (fh, fw):
                             raise ValueError(f"Unexpected tile shape: {img.shape}")
                         dest[...] = img
 
@@ -1329,10 +1394,15 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
+                    if binned:      # the first launch after the copy: everything below reads the binned planes
+                        tiles = native.bin_tiles(tiles, self.tile_binning, self.tile_binning_method, out=binned_tiles[:m])
                     if derived:     # in place over the left halves, before anything reads the staged planes
                         i0, i1 = derived[0], derived[-1] + 1
                         rights = right_dev[slot][:i1 - i0]
                         rights.copy_(right_staging[slot][:i1 - i0], non_blocking=True)
+                        if binned:
+                            rights = native.bin_tiles(rights, self.tile_binning, self.tile_binning_method,
+                                                      out=binned_rights[:i1 - i0])
                         native.dpc_tiles(tiles[i0:i1], rights, self.dpc_gain)
                         right_done[slot] = torch.cuda.Event()
                         right_done[slot].record()
@@ -1416,6 +1486,25 @@ class Stitcher:
         path = os.path.join(folder, f"{region}_stitched_background.json")
         note = {'method': 'tophat', 'radius': self.background_radius, 'window': 2 * self.background_radius + 1,
                 'applies_to': 'every staged tile plane, before the flatfield divide'}
+        tmp = f"{path}.{os.getpid()}.tmp"
+        with open(tmp, 'w') as fh:
+            json.dump(note, fh, indent=1)
+        os.replace(tmp, path)
+
+    def _write_binning_note(self, timepoint, region) -> None:
+        """``<t>_stitched/<region>_stitched_binning.json``: how the tiles of every store of this region were binned (the same
+        bytes from every rank and call, put in place atomically)."""
+        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"{region}_stitched_binning.json")
+        k = self.tile_binning
+        note = {'factor': k, 'method': self.tile_binning_method,
+                'file_tile_shape': [self.file_height, self.file_width],
+                'binned_tile_shape': [self.input_height, self.input_width],
+                'rows_dropped': self.file_height - k * self.input_height,
+                'columns_dropped': self.file_width - k * self.input_width,
+                'file_pixel_size_um': self.file_pixel_size_um, 'pixel_size_um': self.pixel_size_um,
+                'applies_to': 'every tile, before placement, registration, the flatfield estimate and every tile filter'}
         tmp = f"{path}.{os.getpid()}.tmp"
         with open(tmp, 'w') as fh:
             json.dump(note, fh, indent=1)

@@ -11,7 +11,8 @@ the per-tile quality report (focus, saturation, intensity) of the tiles as they 
 ``--dpc-channels`` and ``--dpc-gain`` add the differential phase contrast channel made of the two half-pupil brightfield tiles.
 ``--seam-qc``, ``--seam-qc-radius``, ``--seam-qc-min-pixels`` and ``--seam-qc-min-ncc`` select the per-seam alignment report: how
 well every pair of overlapping tiles agrees where it is placed, on every (channel, z) plane, and the integer residual displacement
-at which it would agree best.
+at which it would agree best.  ``--tile-binning`` and ``--tile-binning-method`` stitch K x K binned tiles, binned on the device
+before anything else sees them.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -164,6 +165,17 @@ FLAGS = (
     (('--seam-qc-min-ncc',), dict(type=float, default=0.5, metavar='C',
                                   help="with --seam-qc: a seam is flagged low_ncc when its ncc at the placement is below this, "
                                        "-1..1")),
+    (('--tile-binning',), dict(type=int, choices=range(1, 9), default=1, metavar='K',
+                               help="stitch K x K binned tiles, 1..8: a run equals a run without the flag on a folder that holds "
+                                    "the binned files, the same coordinates.csv and an acquisition parameters.json whose "
+                                    "sensor_pixel_size_um is multiplied by K, byte for byte in every store, sidecar and picture.  "
+                                    "The tiles are binned on the device right after the copy (the last h mod K rows and w mod K "
+                                    "columns are dropped), before placement, registration, the flatfield estimate and every tile "
+                                    "filter see them; writes <region>_stitched_binning.json.  1 = off")),
+    (('--tile-binning-method',), dict(choices=['mean', 'sum'], default='mean',
+                                      help="with --tile-binning: mean = the truncated mean of the K x K block, floor(S / K^2) (the "
+                                           "rule of --pyramid-method mean); sum = min(S, dtype maximum), what camera binning does: "
+                                           "counts add, and the result saturates")),
 )
 
 
@@ -242,7 +254,9 @@ def main(argv=None):
                             seam_qc_min_ncc=args.seam_qc_min_ncc,
                             dpc=args.dpc,
                             dpc_channels=tuple(args.dpc_channels),
-                            dpc_gain=args.dpc_gain)
+                            dpc_gain=args.dpc_gain,
+                            tile_binning=args.tile_binning,
+                            tile_binning_method=args.tile_binning_method)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

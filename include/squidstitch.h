@@ -470,6 +470,33 @@ int sq_dpc_tiles(const void *left_dev, const void *right_dev, void *out_dev, int
                  int64_t out_plane_stride, int64_t out_pitch, int32_t dtype, int32_t gain, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K x K binning of tile planes (--tile-binning; extension: the reference has nothing like it).  For each of n_images planes
+ * I [h, w] (SQ_U8 / SQ_U16, maximum M = 255 / 65535) and an integer factor K in 2..SQ_BIN_MAX_FACTOR, OUT OF PLACE, with
+ * hb = h / K and wb = w / K (integer division: the last h - K hb rows and the last w - K wb columns are dropped):
+ *     S(y, x) = the sum of I over the K x K block at (K y, K x)          (it fits 32 bits)
+ *     SQ_BIN_MEAN:  out(y, x) = floor(S(y, x) / K^2)     (the truncated mean, the rule of sq_pyramid_mean: for K = 2 on even
+ *                                                          sizes a binned plane is that function's level 1 of the plane)
+ *     SQ_BIN_SUM :  out(y, x) = min(S(y, x), M)          (what camera binning does: counts add, and the result saturates)
+ * The definition is the numpy restatement in tests/bin_ref.py, and the result is bit for bit that on every input.  n_images
+ * planes, the planes a plane stride and the rows a pitch apart (elements; src_pitch >= w, dst_pitch >= wb), src and dst each
+ * with their own -- the conventions of sq_despeckle_tiles: no alignment asked of a base or a pitch beyond the element's own.
+ * dst [n_images][hb][wb] must not meet src.  Every source element inside the K hb x K wb area is read exactly once, nothing of
+ * the dropped rows and columns reaches a result, and nothing outside hb x wb of a destination plane is written
+ * (csrc/bin.hip).  No scratch, no allocation, no atomics; asynchronous on `stream`; deterministic.  SQ_ERR_INVALID, and
+ * nothing is launched, for an unknown dtype or method, a factor outside 2..8, hb or wb < 1, a pitch below the width, a plane
+ * stride smaller than a plane, a NULL or element-misaligned pointer, n_images < 0, extents beyond the address space, and src
+ * and dst extents (first to last element of all planes) that overlap.  SQ_ERR_UNSUPPORTED for a plane that needs more
+ * workgroups than a launch has.  n_images == 0 is SQ_OK.  (Added without a change of SQ_VERSION: every caller built against
+ * 108 still links and runs.)
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_BIN_MEAN 1
+#define SQ_BIN_SUM  2
+#define SQ_BIN_MAX_FACTOR 8
+int sq_bin_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h, int32_t w,
+                 int64_t src_plane_stride, int64_t src_pitch, int64_t dst_plane_stride, int64_t dst_pitch,
+                 int32_t dtype, int32_t factor, int32_t method, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
