@@ -162,6 +162,8 @@ EXPORTS = {
                                C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_bin_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    'sq_warp_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                C.c_int32, C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1473,6 +1475,56 @@ def bin_tiles(tiles, factor: int, method: str = 'mean', out=None, stream=None):
         _check(lib().sq_bin_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                   dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), factor,
                                   BIN_METHODS[method], _stream_ptr(stream)), 'sq_bin_tiles')
+    return out
+
+
+SQ_WARP_MAX_PPM = 50000
+SQ_WARP_MAX_SIDE = 65535
+SQ_WARP_PLANES_PER_THREAD = 16
+
+
+def warp_tiles(tiles, ppm: int, out=None, stream=None):
+    """Radial lens correction of every H x W plane of ``tiles`` into ``out`` (sq_warp_tiles; an extension, the reference has
+    nothing like it): the output at radius r takes the input at radius r (1 + ppm 10^-6 r^2 / R^2), R the plane's half
+    diagonal, bilinearly with 8 fractional bits and replicated edges, exact in integers -- ``tests/warp_ref.warp_image``; the
+    formula stands in include/squidstitch.h.  The correction is out of place: ``tiles`` is left as it is.
+
+    tiles:  uint8 / uint16 device tensor [..., H, W], H and W at most 65535, with unit-stride rows (any row pitch) whose
+            leading dimensions are one uniform plane stride apart: a contiguous stack, or a view such as every other plane of
+            one.
+    ppm:    an integer in -50000..50000, the relative displacement at the plane's corner in parts per million; positive
+            undoes pincushion, negative barrel distortion, 0 gives an exact copy.
+    out:    a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
+            shares no memory with ``tiles``; allocated contiguous when None.
+    Returns ``out``."""
+    import torch
+    ppm = _int_in(ppm, -SQ_WARP_MAX_PPM, SQ_WARP_MAX_PPM, 'distortion ppm')
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    src = _plane_layout(tiles, 'tiles')
+    n_images, h, w, src_plane_stride, src_pitch = src
+    if h > SQ_WARP_MAX_SIDE or w > SQ_WARP_MAX_SIDE:
+        raise ValueError(f"planes of {h} x {w} have a side above {SQ_WARP_MAX_SIDE}")
+    shape = tuple(tiles.shape)
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
+            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
+        dst = _plane_layout(out, 'out')
+        n_out, _, _, dst_plane_stride, dst_pitch = dst
+        assert n_out == n_images
+        if n_images == 0:
+            return out
+        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
+            raise ValueError("out shares memory with tiles: the correction is out of place")
+        _check(lib().sq_warp_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
+                                   dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), ppm,
+                                   _stream_ptr(stream)), 'sq_warp_tiles')
     return out
 
 

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import alignment, binning, composite as composite_mod, native, placement, registration, seamqc, sharding, tileqc
+from . import alignment, binning, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -77,7 +77,7 @@ class Stitcher:
                  tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5, dpc: bool = False,
                  dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
                  seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
-                 tile_binning: int = 1, tile_binning_method: str = 'mean'):
+                 tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -257,6 +257,18 @@ class Stitcher:
         # (file_height / file_width the files'), pixel_size_um the binned pixel's.  1: nothing is launched, allocated, written
         # or parsed differently; the method is checked and unused.
         self.tile_binning, self.tile_binning_method = binning.check_options(tile_binning, tile_binning_method)
+        # Extension: distortion_correction=D (an integer in parts per million, -50000..50000) removes radial lens distortion
+        # from every tile: the output at radius r takes the input at radius r (1 + D 10^-6 r^2 / R^2), R the tile's half
+        # diagonal, bilinearly with 8 fractional bits and replicated edges, exact in integers (distortion.py;
+        # tests/warp_ref.py); D > 0 undoes pincushion, D < 0 barrel distortion.  A run equals a run without the option on a
+        # folder whose tile files were corrected beforehand, byte for byte in every store, sidecar and picture: the staged
+        # tiles are corrected on the device as the first launch after the copy (sq_warp_tiles), the all-pairs stack
+        # likewise, and the readers of single files (get_tile and the centre-pair registration, the flatfield estimate's
+        # samples) correct on the host -- placement, registration, the flatfield estimate and every tile filter see corrected
+        # tiles only.  With tile_binning the tiles are corrected first, in sensor pixels, and binned second.  A supplied
+        # flatfield is taken to be in corrected geometry.  0: nothing is launched, allocated, written, synchronised or parsed
+        # differently.
+        self.distortion_correction = distortion.check_option(distortion_correction)
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -451,6 +463,11 @@ class Stitcher:
                   f"({self.file_height - self.tile_binning * self.input_height} rows, "
                   f"{self.file_width - self.tile_binning * self.input_width} columns dropped), pixel size "
                   f"{self.file_pixel_size_um} -> {self.pixel_size_um} um")
+        if self.distortion_correction:
+            du, dv = distortion.max_displacement(self.file_height, self.file_width, self.distortion_correction)
+            print(f"[distortion] {self.distortion_correction} ppm: tiles of {self.file_height} x {self.file_width} corrected "
+                  f"before anything else reads them, samples moved by up to {du / 256:.2f} px along x and {dv / 256:.2f} px "
+                  f"along y (bilinear, 8 fractional bits, edges replicated)")
         self.chunks = (1, 1, 1, 512, 512)
         self.monochrome_channels = []
         # (the derived channel sits where its name sorts among the file channels; channel_names stays the file channels)
@@ -530,12 +547,20 @@ class Stitcher:
         """(stitcher.py:1220-1223)"""
         return sorted(set(r[0] for r in self.regions)), sorted(set(r[1:] for r in self.regions))
 
+    def _read_tile_file(self, path):
+        """One tile file as the run sees it: corrected (--distortion-correction) first, binned (--tile-binning) second, on the
+        host with the integer arithmetic of the device launches; the file itself without the options."""
+        if not self.distortion_correction:
+            return binning.read_binned(path, self.tile_binning, self.tile_binning_method)
+        img = distortion.read_warped(path, self.distortion_correction)
+        return img if self.tile_binning == 1 else binning.bin_image(img, self.tile_binning, self.tile_binning_method)
+
     def get_tile(self, t, region, x, y, channel, z_level):
         """(stitcher.py:526-542) -> numpy image or None."""
         for value in self.get_region_data(int(t), str(region)).values():
             if value['x'] == x and value['y'] == y and value['channel'] == channel and value['z_level'] == z_level:
                 try:
-                    return binning.read_binned(value['filepath'], self.tile_binning, self.tile_binning_method)
+                    return self._read_tile_file(value['filepath'])
                 except FileNotFoundError:
                     print(f"Warning: cannot open {value['filepath']}")
                     return None
@@ -715,7 +740,9 @@ class Stitcher:
             with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as pool:
                 images = list(pool.map(one, cells))
             stack = torch.from_numpy(np.ascontiguousarray(np.stack(images))).to(self.device)
-            if self.tile_binning > 1:      # the raw stack, binned by the launch the staged tiles go through
+            if self.distortion_correction:      # the raw stack, corrected by the launch the staged tiles go through ...
+                stack = native.warp_tiles(stack, self.distortion_correction)
+            if self.tile_binning > 1:      # ... and binned by theirs
                 stack = native.bin_tiles(stack, self.tile_binning, self.tile_binning_method)
             return stack
 
@@ -841,7 +868,7 @@ class Stitcher:
             if not paths:
                 print(f"WARNING: No images found for channel {channel} across all timepoints")
                 continue
-            images = np.array([binning.read_binned(p, self.tile_binning, self.tile_binning_method) for p in paths])
+            images = np.array([self._read_tile_file(p) for p in paths])
             if images.ndim == 4 and images.shape[1] == 1:       # (N, 1, Y, X) page stacks
                 images = images[:, 0]
             if images.ndim == 3:
@@ -1108,6 +1135,10 @@ class Stitcher:
         fh, fw = (self.file_height, self.file_width) if binned else (th, tw)
         total_tiles = len(region_data)
         print(f"Beginning stitching of {total_tiles} tiles for region {region} timepoint {timepoint}")
+        # --distortion-correction: the staged tiles are corrected into one buffer of the files' shape, in front of the binning
+        warped = self.distortion_correction != 0
+        if warped:
+            self._write_distortion_note(timepoint, region)
         if binned:
             self._write_binning_note(timepoint, region)
         if self.background_subtract == 'tophat':
@@ -1195,8 +1226,9 @@ class Stitcher:
             if stream_to is not None and groups:
                 # (one staged plane of the longest list: its raw tiles and, with --tile-binning, their binned copy -- the
                 # batch budget below counts the same two)
-                widest = max(len(rect_of[sig]) for sig in groups) * (fh * fw + (th * tw if binned else 0)) * \
-                    np.dtype(self.dtype).itemsize
+                # (and with --distortion-correction their corrected copy)
+                widest = max(len(rect_of[sig]) for sig in groups) * \
+                    (fh * fw + (th * tw if binned else 0) + (fh * fw if warped else 0)) * np.dtype(self.dtype).itemsize
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
             def parts_of(t):      # the tensors of a target that this call writes
                 return t if isinstance(t, tuple) else ((t.out,) if isinstance(t, FocusFollower) else (t,))
@@ -1252,12 +1284,14 @@ class Stitcher:
                 # and the right halves of the derived planes (--dpc: counted as one more copy, though only they have one)
                 n_derived = sum(p // self.num_z == self._dpc_index for p in plist) if self.dpc else 0
                 copies = 1 + int(despeckle) + int(tophat) + int(n_derived > 0)
-                staged_per_plane = per_plane * copies
+                # the corrected copy of the staged planes (--distortion-correction; of the right halves too): one more raw copy
+                raw_copies = (1 + int(n_derived > 0)) * (1 + int(warped))
+                staged_per_plane = per_plane * (copies + raw_copies - 1 - int(n_derived > 0))
                 if binned:
-                    # the staged planes (and the right halves) keep the files' size; the binned copy of both -- 1 / K^2 of
-                    # them -- and everything behind it is per_plane
+                    # the staged planes (and the right halves) keep the files' size, and so do their corrected copies; the
+                    # binned copy of both -- 1 / K^2 of them -- and everything behind it is per_plane
                     raw_per_plane = n * fh * fw * np.dtype(self.dtype).itemsize
-                    staged_per_plane = raw_per_plane * (1 + int(n_derived > 0)) + per_plane * copies
+                    staged_per_plane = raw_per_plane * raw_copies + per_plane * copies
                 batch = max(1, min(len(plist), staged_budget // max(1, staged_per_plane)))
                 if writer is not None:
                     batch = min(batch, writer.batch)
@@ -1284,6 +1318,18 @@ class Stitcher:
                         tophat_scratch = torch.empty(native.tophat_scratch_bytes(batch * n, th, tw, self.dtype), dtype=torch.uint8,
                                                      device=self.device)
                         self._keep_buffers(tkey, tophat_scratch)
+                warped_tiles = None
+                if warped:
+                    # ONE corrected buffer of the files' shape for both ingest slots, by the argument for `binned_tiles` and
+                    # the despeckle's `clean` below: the correction and everything that reads its result are launches of one
+                    # stream, so the next chunk's correction (which overwrites it) runs after this chunk's fusion has read it;
+                    # only the H2D copy into the OTHER slot's raw tiles overlaps, and nothing reads those but the correction
+                    # of their own chunk
+                    wkey = ('distortion', batch, n, fh, fw, np.dtype(self.dtype).str)
+                    warped_tiles = self._buffer_cache.get(wkey)
+                    if warped_tiles is None:
+                        warped_tiles = torch.empty((batch, n, fh, fw), dtype=tdtype, device=self.device)
+                        self._keep_buffers(wkey, warped_tiles)
                 binned_tiles = None
                 if binned:
                     # ONE binned buffer for both ingest slots, by the argument for the despeckle's `clean` below: the binning
@@ -1312,7 +1358,7 @@ class Stitcher:
                     # the kernel's per-plane counts of this list's planes (plane of plist, tile): every chunk adds into its own
                     # run of it, and it is folded per channel once, behind the last chunk
                     list_counts = torch.zeros((len(plist), n), dtype=torch.int64, device=self.device)
-                right_staging = right_dev = right_done = binned_rights = None
+                right_staging = right_dev = right_done = binned_rights = warped_rights = None
                 if n_derived:
                     # the right halves: one more staged buffer per ingest slot, pinned and mirrored on the device, as deep as
                     # a chunk can hold derived planes (they are consecutive: plist is ascending).  Its own events: whatever
@@ -1327,6 +1373,12 @@ class Stitcher:
                                  [None] * n_slots)
                         self._keep_buffers(rkey, rbufs)
                     right_staging, right_dev, right_done = rbufs
+                    if warped:      # the corrected right halves: one small buffer for both slots, like `warped_tiles`
+                        rwkey = ('distortion-dpc', deep, n, fh, fw, np.dtype(self.dtype).str)
+                        warped_rights = self._buffer_cache.get(rwkey)
+                        if warped_rights is None:
+                            warped_rights = torch.empty((deep, n, fh, fw), dtype=tdtype, device=self.device)
+                            self._keep_buffers(rwkey, warped_rights)
                     if binned:      # the binned right halves: one small buffer for both slots, like `binned_tiles`
                         rbkey = ('binning-dpc', deep, n, th, tw, np.dtype(self.dtype).str)
                         binned_rights = self._buffer_cache.get(rbkey)
@@ -1394,12 +1446,16 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
-                    if binned:      # the first launch after the copy: everything below reads the binned planes
+                    if warped:      # the first launch after the copy: everything below reads the corrected planes
+                        tiles = native.warp_tiles(tiles, self.distortion_correction, out=warped_tiles[:m])
+                    if binned:      # the next (without the correction, the first): everything below reads the binned planes
                         tiles = native.bin_tiles(tiles, self.tile_binning, self.tile_binning_method, out=binned_tiles[:m])
                     if derived:     # in place over the left halves, before anything reads the staged planes
                         i0, i1 = derived[0], derived[-1] + 1
                         rights = right_dev[slot][:i1 - i0]
                         rights.copy_(right_staging[slot][:i1 - i0], non_blocking=True)
+                        if warped:
+                            rights = native.warp_tiles(rights, self.distortion_correction, out=warped_rights[:i1 - i0])
                         if binned:
                             rights = native.bin_tiles(rights, self.tile_binning, self.tile_binning_method,
                                                       out=binned_rights[:i1 - i0])
@@ -1486,6 +1542,22 @@ class Stitcher:
         path = os.path.join(folder, f"{region}_stitched_background.json")
         note = {'method': 'tophat', 'radius': self.background_radius, 'window': 2 * self.background_radius + 1,
                 'applies_to': 'every staged tile plane, before the flatfield divide'}
+        tmp = f"{path}.{os.getpid()}.tmp"
+        with open(tmp, 'w') as fh:
+            json.dump(note, fh, indent=1)
+        os.replace(tmp, path)
+
+    def _write_distortion_note(self, timepoint, region) -> None:
+        """``<t>_stitched/<region>_stitched_distortion.json``: how the tiles of every store of this region were corrected (the
+        same bytes from every rank and call, put in place atomically)."""
+        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"{region}_stitched_distortion.json")
+        du, dv = distortion.max_displacement(self.file_height, self.file_width, self.distortion_correction)
+        note = {'ppm': self.distortion_correction, 'tile_shape': [self.file_height, self.file_width],
+                'max_abs_du_256': du, 'max_abs_dv_256': dv, 'edges': 'replicated',
+                'interpolation': 'bilinear, 8 fractional bits',
+                'applies_to': 'every tile, before binning, placement, registration, the flatfield estimate and every tile filter'}
         tmp = f"{path}.{os.getpid()}.tmp"
         with open(tmp, 'w') as fh:
             json.dump(note, fh, indent=1)

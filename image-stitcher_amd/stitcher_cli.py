@@ -12,7 +12,8 @@ the per-tile quality report (focus, saturation, intensity) of the tiles as they 
 ``--seam-qc``, ``--seam-qc-radius``, ``--seam-qc-min-pixels`` and ``--seam-qc-min-ncc`` select the per-seam alignment report: how
 well every pair of overlapping tiles agrees where it is placed, on every (channel, z) plane, and the integer residual displacement
 at which it would agree best.  ``--tile-binning`` and ``--tile-binning-method`` stitch K x K binned tiles, binned on the device
-before anything else sees them.
+before anything else sees them.  ``--distortion-correction`` removes radial lens distortion from every tile, on the device, in
+front of all of that.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
@@ -21,6 +22,17 @@ import sys
 
 from .stitcher import Stitcher
 from .stitcher_parameters import StitchingParameters
+
+
+def _ppm(text):
+    """--distortion-correction: an integer in -50000..50000 (no float, no exponent)."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"an integer in -50000..50000 (parts per million), got {text!r}")
+    if not -50000 <= value <= 50000:
+        raise argparse.ArgumentTypeError(f"an integer in -50000..50000 (parts per million), got {text!r}")
+    return value
 
 
 FLAGS = (
@@ -176,6 +188,18 @@ FLAGS = (
                                       help="with --tile-binning: mean = the truncated mean of the K x K block, floor(S / K^2) (the "
                                            "rule of --pyramid-method mean); sum = min(S, dtype maximum), what camera binning does: "
                                            "counts add, and the result saturates")),
+    (('--distortion-correction',), dict(type=_ppm, default=0, metavar='D',
+                                        help="remove radial lens distortion from every tile: the output at radius r takes the "
+                                             "input at radius r (1 + D 1e-6 r^2 / R^2), R the tile's half diagonal, bilinearly with "
+                                             "8 fractional bits and replicated edges, exact in integers; D in parts per million, "
+                                             "-50000..50000, is the relative displacement at the tile's corner: positive undoes "
+                                             "pincushion, negative barrel distortion (find it with tools/distortion_scan.py).  A run "
+                                             "equals a run without the flag on a folder whose tile files were corrected beforehand, "
+                                             "byte for byte in every store, sidecar and picture.  The tiles are corrected on the "
+                                             "device right after the copy, in sensor pixels, before --tile-binning, placement, "
+                                             "registration, the flatfield estimate and every tile filter see them; a supplied "
+                                             "flatfield is taken to be in corrected geometry; writes "
+                                             "<region>_stitched_distortion.json.  0 = off")),
 )
 
 
@@ -256,7 +280,8 @@ def main(argv=None):
                             dpc_channels=tuple(args.dpc_channels),
                             dpc_gain=args.dpc_gain,
                             tile_binning=args.tile_binning,
-                            tile_binning_method=args.tile_binning_method)
+                            tile_binning_method=args.tile_binning_method,
+                            distortion_correction=args.distortion_correction)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

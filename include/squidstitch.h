@@ -497,6 +497,43 @@ int sq_bin_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h
                  int32_t dtype, int32_t factor, int32_t method, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Radial lens correction of tile planes (--distortion-correction; extension: the reference has nothing like it -- ASHLAR, which
+ * its ashlar_stitcher.py wraps, has --barrel-correction).  For each of n_images planes I [h, w] (SQ_U8 / SQ_U16; h, w <=
+ * SQ_WARP_MAX_SIDE) and an integer D = ppm in -SQ_WARP_MAX_PPM..SQ_WARP_MAX_PPM (parts per million: the relative displacement
+ * at the plane's corner), OUT OF PLACE, with // the floor division (also of negative numerators):
+ *     U = w - 1, V = h - 1                         R2 = max(1, U*U + V*V)
+ *     for the output pixel (y, x):
+ *       u = 2*x - U,  v = 2*y - V                  (half-pixels from the plane's centre)
+ *       rho = ((u*u + v*v) << 24) // R2            (0 .. 2^24: squared radius, 1.0 at the corners)
+ *       s   = D * rho
+ *       du  = (u*s + H) // (2*H),  dv = (v*s + H) // (2*H),   H = 10^6 * 2^16      (1/256 pixel, rounded half up)
+ *       X = clamp(256*x + du, 0, 256*U),  Y = clamp(256*y + dv, 0, 256*V)           (edges replicated)
+ *       x0 = X >> 8, fx = X & 255, x1 = min(x0 + 1, U);   y0, fy, y1 likewise
+ *       out(y, x) = ( I[y0,x0]*(256-fx)*(256-fy) + I[y0,x1]*fx*(256-fy)
+ *                   + I[y1,x0]*(256-fx)*fy       + I[y1,x1]*fx*fy + 32768 ) >> 16
+ * i.e. the output at radius r takes the input at radius r (1 + D 10^-6 r^2 / R^2), bilinearly with 8 fractional bits: D > 0
+ * samples farther out (it undoes pincushion distortion), D < 0 undoes barrel distortion, D = 0 is an exact copy.  The map fits
+ * 64 bits and the blend unsigned 32 bits up to the largest side and |D|.  The definition is the numpy restatement in
+ * tests/warp_ref.py, and the result is bit for bit that on every input.  n_images planes, the planes a plane stride and the
+ * rows a pitch apart (elements; both pitches >= w), src and dst each with their own -- the conventions of sq_bin_tiles: no
+ * alignment asked of a base or a pitch beyond the element's own.  dst [n_images][h][w] must not meet src.  Every output element
+ * is written exactly once, nothing outside h x w of a destination plane is written, and every tap lies inside its source plane
+ * (csrc/warp.hip: a thread works the map of its positions out once and walks over SQ_WARP_PLANES_PER_THREAD planes with it; a
+ * launch takes 65535 such runs of planes, longer batches are split).  No scratch, no allocation, no atomics; asynchronous on
+ * `stream`; deterministic.  SQ_ERR_INVALID, and nothing is launched, for an unknown dtype, ppm outside its range, h or w < 1, a
+ * pitch below the width, a plane stride smaller than a plane, a NULL or element-misaligned pointer, n_images < 0, extents beyond
+ * the address space, and src and dst extents (first to last element of all planes) that overlap.  SQ_ERR_UNSUPPORTED for a side
+ * above SQ_WARP_MAX_SIDE.  n_images == 0 is SQ_OK.  (Added without a change of SQ_VERSION: every caller built against 108 still
+ * links and runs.)
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_WARP_MAX_PPM 50000
+#define SQ_WARP_MAX_SIDE 65535
+#define SQ_WARP_PLANES_PER_THREAD 16
+int sq_warp_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h, int32_t w,
+                  int64_t src_plane_stride, int64_t src_pitch, int64_t dst_plane_stride, int64_t dst_pitch,
+                  int32_t dtype, int32_t ppm, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched

@@ -1,0 +1,107 @@
+"""Time sq_warp_tiles on the staged tiles of one config-3 plane (256 tiles of 2048 x 2048 uint16 from the device generator; HIP
+events after warm-up, one process, a time limit of its own) at D = 1500 ppm (a real lens: samples move by up to 1.5 px) and at
+D = 50000 (the option's limit: up to 51 px, the clamp active on every border), against
+
+    (a) sq_warp_tiles                          one launch for the batch, out of place: it reads the batch once (the four taps of
+                                               neighbouring outputs share their lines) and writes it once
+    (b) a device copy of the same batch        dst.copy_(src): one read and one write of the same bytes, the yardstick of
+                                               tools/despeckle_probe.py
+    (c) the same definition with torch         the map in int64 tensors (floor divisions), four gathers through flat indices,
+                                               the blend in int64, back to uint16; on the first B_TILES tiles (its time is per
+                                               tile), equality with (a) checked there
+
+    python tools/warp_probe.py [tiles [reps]]      -> profiles/warp_probe_kernel.json
+"""
+import json
+import os
+import signal
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, '.')
+from image_stitcher_amd import native
+
+OUT = os.environ.get('SQ_PROBE_OUT', 'profiles')
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+H = W = 2048
+B_TILES = min(n, 8)
+HALF = 10 ** 6 * 2 ** 16
+signal.alarm(int(os.environ.get('SQ_PROBE_LIMIT_S', 300)))      # the probe ends itself: nothing here should take minutes
+dev = torch.device('cuda:0')
+
+desc = np.zeros(n, dtype=native.SYNTH_DTYPE)      # a 16 x 16 grid of overlapping views of one scene, a noise seed per tile
+for i in range(n):
+    desc[i] = (4242, 977 + i, (i // 16) * 1804, (i % 16) * 1804)
+src = native.synth_tiles(desc, H, W, 300, np.uint16, dev)
+dst = torch.empty_like(src)
+nbytes = src.numel() * 2
+
+
+def timed(fn, reps):
+    times = []
+    for i in range(reps + 3):      # three warm-up rounds
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= 3:
+            times.append(e0.elapsed_time(e1))
+    return {'ms': round(sorted(times)[len(times) // 2], 3), 'ms_min': round(min(times), 3), 'ms_max': round(max(times), 3)}
+
+
+def torch_warp(x, ppm):
+    U, V = W - 1, H - 1
+    r2 = max(1, U * U + V * V)
+    xs = torch.arange(W, dtype=torch.int64, device=dev)[None, :]
+    ys = torch.arange(H, dtype=torch.int64, device=dev)[:, None]
+    u, v = 2 * xs - U, 2 * ys - V
+    s = ppm * torch.div(torch.bitwise_left_shift(u * u + v * v, 24), r2, rounding_mode='floor')
+    du = torch.div(u * s + HALF, 2 * HALF, rounding_mode='floor')
+    dv = torch.div(v * s + HALF, 2 * HALF, rounding_mode='floor')
+    X, Y = (256 * xs + du).clamp(0, 256 * U), (256 * ys + dv).clamp(0, 256 * V)
+    x0, fx, y0, fy = X >> 8, X & 255, Y >> 8, Y & 255
+    x1, y1 = (x0 + 1).clamp(max=U), (y0 + 1).clamp(max=V)
+    flat = x.to(torch.int32).view(x.shape[0], -1)
+    tap = lambda yy, xx: flat[:, (yy * W + xx).view(-1)].view(x.shape).to(torch.int64)
+    acc = tap(y0, x0) * ((256 - fx) * (256 - fy)) + tap(y0, x1) * (fx * (256 - fy)) + tap(y1, x0) * ((256 - fx) * fy) + \
+        tap(y1, x1) * (fx * fy) + 32768
+    return (acc >> 16).to(torch.int16).view(torch.uint16), int(du.abs().max()), int(dv.abs().max())
+
+
+result = {'tiles': n, 'shape': [H, W], 'dtype': 'uint16', 'reps': reps, 'bytes': nbytes, 'torch_tiles': B_TILES}
+cases = (1500, 50000)
+copies = []
+for ppm in cases:      # the copy before every case: the two alternate
+    copy = timed(lambda: dst.copy_(src), reps)
+    copies.append(copy['ms'])
+    row = {'b_device_copy': copy}
+    row['a_warp_tiles'] = timed(lambda: native.warp_tiles(src, ppm, out=dst), reps)
+    row['a_gb_per_s_read_and_written'] = round(2 * nbytes / row['a_warp_tiles']['ms'] / 1e6, 1)
+    got = dst[:B_TILES].clone()
+    keep = {}
+    row['c_torch'] = timed(lambda: keep.__setitem__('out', torch_warp(src[:B_TILES], ppm)), 2)
+    out, du, dv = keep['out']
+    row['equal'] = bool(torch.equal(out.view(torch.int16), got.view(torch.int16)))
+    row['changed_fraction'] = round(float((got.view(torch.int16) != src[:B_TILES].view(torch.int16)).float().mean()), 4)
+    row['max_abs_du_256'], row['max_abs_dv_256'] = du, dv
+    keep.clear()
+    del out
+    a_tile = row['a_warp_tiles']['ms'] / n
+    c_tile = row['c_torch']['ms'] / B_TILES
+    row['a_ms_per_tile'], row['c_ms_per_tile'] = round(a_tile, 4), round(c_tile, 4)
+    row['a_over_copy'] = round(row['a_warp_tiles']['ms'] / copy['ms'], 2)
+    row['c_over_a'] = round(c_tile / a_tile, 2)
+    result[f'D{ppm}'] = row
+    print(f"D={ppm:6d} equal {row['equal']}  copy {copy['ms']:.3f} ms  (a) {row['a_warp_tiles']['ms']:8.3f} ms = "
+          f"{a_tile:.4f} ms/tile = {row['a_over_copy']:.2f} x copy   (c) {c_tile:.4f} ms/tile = {row['c_over_a']:.1f} x (a)",
+          flush=True)
+result['copy_gb_per_s'] = round(2 * nbytes / min(copies) / 1e6, 1)
+result['all_equal'] = all(result[f'D{ppm}']['equal'] for ppm in cases)
+print(json.dumps(result))
+os.makedirs(OUT, exist_ok=True)
+with open(os.path.join(OUT, 'warp_probe_kernel.json'), 'w') as fh:
+    json.dump(result, fh, indent=1)
