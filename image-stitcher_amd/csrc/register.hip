@@ -290,13 +290,14 @@ __device__ __forceinline__ int put_pos(const Axis &X, int p) { return X.rev_bits
 
 // A pair whose tile index or crop origin would read outside its tile never touches memory: its crops
 // are taken as zero and its result carries coarse = INT32_MIN (the pair table lives in device memory,
-// so the host cannot validate it before the launch).
+// so the host cannot validate it before the launch).  Nothing is added to an origin -- one near INT32_MAX would wrap
+// and pass: the host has refused n0 > tile_h and n1 > tile_w, so the differences on the right cannot overflow.
 __device__ __forceinline__ bool pair_ok(const RegParams &P, const sq_pair &pr) {
     const Layout &L = P.L;
     return pr.ref_tile >= 0 && pr.ref_tile < P.n_tiles && pr.mov_tile >= 0 && pr.mov_tile < P.n_tiles &&
            pr.ref_y0 >= 0 && pr.ref_x0 >= 0 && pr.mov_y0 >= 0 && pr.mov_x0 >= 0 &&
-           pr.ref_y0 + L.n0 <= P.tile_h && pr.mov_y0 + L.n0 <= P.tile_h && pr.ref_x0 + L.n1 <= P.tile_w &&
-           pr.mov_x0 + L.n1 <= P.tile_w;
+           pr.ref_y0 <= P.tile_h - L.n0 && pr.mov_y0 <= P.tile_h - L.n0 && pr.ref_x0 <= P.tile_w - L.n1 &&
+           pr.mov_x0 <= P.tile_w - L.n1;
 }
 
 // ---------------------------------------------------------------------------------------------

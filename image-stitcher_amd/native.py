@@ -1565,27 +1565,35 @@ class PendingRegistration:
         return out
 
 
+def _check_pairs(pairs, n_tiles: int, h: int, w: int, n0: int, n1: int) -> np.ndarray:
+    """``pairs`` as contiguous PAIR_DTYPE records, every tile index in 0..n_tiles-1 and every n0 x n1 crop inside its h x w
+    tile; ValueError otherwise.  The origins are int32 and may sit anywhere up to 2^31 - 1, where origin + side wraps in int32:
+    they are compared in int64, with the room a crop has in its tile."""
+    pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE).reshape(-1)
+    if len(pairs) == 0:
+        return pairs
+    fields = pairs.view(np.int32).reshape(-1, 6).astype(np.int64)      # (ref_tile, mov_tile, ref_y0, ref_x0, mov_y0, mov_x0)
+    if fields[:, :2].min() < 0 or fields[:, :2].max() >= n_tiles:
+        raise ValueError("pair refers to a tile outside the table")
+    room_y, room_x = int(h) - int(n0), int(w) - int(n1)                # Python integers: the last origin inside the tile
+    if fields[:, 2:].min() < 0 or (fields[:, 2:] > np.array([room_y, room_x, room_y, room_x], dtype=np.int64)).any():
+        raise ValueError("crop reaches outside its tile")
+    return pairs
+
+
 def register_pairs_async(tiles, minmax, pairs: np.ndarray, n0: int, n1: int, upsample_factor: int = 10,
                          normalization: int = SQ_NORM_PHASE, stream=None, tile_ptrs=None, shape=None,
                          np_dtype=None) -> PendingRegistration:
     """Enqueue batched phase cross-correlation of crop pairs and return without synchronising.
     ``tiles`` [N, H, W] device stack (or a pointer table + shape + dtype), ``pairs`` PAIR_DTYPE."""
     import torch
-    L = lib()
     ptrs, base, stride, n, h, w, dt, device = _tile_table(tiles, tile_ptrs, shape, np_dtype)
-    pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+    pairs = _check_pairs(pairs, n, h, w, n0, n1)
     npairs = len(pairs)
     if npairs == 0:
         return PendingRegistration(None, None, 0)
+    L = lib()
     ws_bytes = _size(L.sq_register_workspace_bytes(npairs, n0, n1, upsample_factor), 'sq_register_workspace_bytes')
-    if min(pairs['ref_tile'].min(), pairs['mov_tile'].min()) < 0 or \
-            max(pairs['ref_tile'].max(), pairs['mov_tile'].max()) >= n:
-        raise ValueError("pair refers to a tile outside the table")
-    if ((pairs['ref_y0'] < 0).any() or (pairs['ref_x0'] < 0).any() or (pairs['mov_y0'] < 0).any()
-            or (pairs['mov_x0'] < 0).any() or (pairs['ref_y0'] + n0 > h).any()
-            or (pairs['mov_y0'] + n0 > h).any() or (pairs['ref_x0'] + n1 > w).any()
-            or (pairs['mov_x0'] + n1 > w).any()):
-        raise ValueError("crop reaches outside its tile")
     with _on_stream(stream):
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device)
         pairs_dev = upload_small(torch.from_numpy(pairs.view(np.uint8).reshape(-1)), device)

@@ -236,6 +236,15 @@ def test_out_of_range_pairs_are_flagged_not_read():
     mm = native.tile_minmax(tiles)
     pairs = np.array([(0, 1, 0, 0, 0, 0), (0, 5, 0, 0, 0, 0), (0, 1, 40, 0, 0, 0), (0, 1, 0, 0, 0, -1), (1, 0, 16, 16, 16, 16)],
                      dtype=native.PAIR_DTYPE)
+    # an origin so large that origin + crop side wraps in 32 bits (to a negative sum, "inside" any tile): each origin field
+    # at 2^31 - 16 and at 2^31 - 1, and a good pair behind them
+    huge = np.zeros(9, dtype=native.PAIR_DTYPE)
+    huge['mov_tile'] = 1
+    for k, name in enumerate(('ref_y0', 'ref_x0', 'mov_y0', 'mov_x0')):
+        huge[name][2 * k] = 2 ** 31 - 16
+        huge[name][2 * k + 1] = 2 ** 31 - 1
+    huge[8] = (1, 0, 32, 32, 32, 32)
+    pairs = np.concatenate([pairs, huge])
     L = native.lib()
     n0 = n1 = 32
     ws = torch.empty(int(L.sq_register_workspace_bytes(len(pairs), n0, n1, 10)), dtype=torch.uint8, device=dev)
@@ -249,7 +258,7 @@ def test_out_of_range_pairs_are_flagged_not_read():
     assert L.sq_register_pairs(C.byref(a), native._stream_ptr()) == 0
     out = res.cpu().numpy().view(native.RESULT_DTYPE)
     bad = np.iinfo(np.int32).min
-    assert [tuple(r['coarse']) == (bad, bad) for r in out] == [False, True, True, True, False]
+    assert [tuple(r['coarse']) == (bad, bad) for r in out] == [False, True, True, True, False] + [True] * 8 + [False]
 
 
 def test_normalize_tiles_equals_reference_golden_and_oracle():
