@@ -17,6 +17,7 @@ Qt is not required: signals are plain callback lists with ``emit``/``connect``.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import os
@@ -26,6 +27,10 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
+try:
+    import psutil
+except Exception:   # pragma: no cover
+    psutil = None      # stitch_planes then assumes 8 GiB of free host memory
 
 from . import alignment, binning, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
@@ -34,6 +39,7 @@ from .ometiff import write_ome_tiff
 from .placement import Shifts
 from .stitcher_parameters import StitchingParameters
 from .tiffio import read_image, read_image_into
+from .tilechain import TileChain, warp_and_bin
 
 _IMAGE_EXT = ('.bmp', '.tiff', 'tif', 'jpg', 'jpeg', 'png')   # as the reference spells them (stitcher.py:169)
 
@@ -740,11 +746,8 @@ class Stitcher:
             with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as pool:
                 images = list(pool.map(one, cells))
             stack = torch.from_numpy(np.ascontiguousarray(np.stack(images))).to(self.device)
-            if self.distortion_correction:      # the raw stack, corrected by the launch the staged tiles go through ...
-                stack = native.warp_tiles(stack, self.distortion_correction)
-            if self.tile_binning > 1:      # ... and binned by theirs
-                stack = native.bin_tiles(stack, self.tile_binning, self.tile_binning_method)
-            return stack
+            # the raw stack, corrected and binned by the launches the staged tiles go through
+            return warp_and_bin(stack, self.distortion_correction, self.tile_binning, self.tile_binning_method)
 
         table = registration.register_all_pairs_sharded(
             pairs, load_cells, self.input_height, self.input_width, max_x_overlap, max_y_overlap, self.normalization,
@@ -887,6 +890,14 @@ class Stitcher:
         for k in [k for k in self._buffer_cache if k[0] == key[0] and k != key]:
             del self._buffer_cache[k]
         self._buffer_cache[key] = bufs
+
+    def _cached_buffers(self, key, make):
+        """The buffers kept under ``key``, made by ``make()`` and kept when there are none."""
+        bufs = self._buffer_cache.get(key)
+        if bufs is None:
+            bufs = make()
+            self._keep_buffers(key, bufs)
+        return bufs
 
     def _plan_for(self, rects, tile_h, tile_w, canvas_h, canvas_w, mode) -> native.FusePlan:
         rects = np.asarray(rects, dtype=np.int64).reshape(-1, 6)
@@ -1135,21 +1146,16 @@ class Stitcher:
         fh, fw = (self.file_height, self.file_width) if binned else (th, tw)
         total_tiles = len(region_data)
         print(f"Beginning stitching of {total_tiles} tiles for region {region} timepoint {timepoint}")
-        # --distortion-correction: the staged tiles are corrected into one buffer of the files' shape, in front of the binning
-        warped = self.distortion_correction != 0
-        if warped:
-            self._write_distortion_note(timepoint, region)
-        if binned:
-            self._write_binning_note(timepoint, region)
-        if self.background_subtract == 'tophat':
-            self._write_background_note(timepoint, region)
         despeckle = self.despeckle != 'none'
         despeckle_counts = despeckle_staged = None
-        if despeckle:
-            self._check_despeckle_dtype()
-            self._write_despeckle_note(timepoint, region)
-        if self.dpc:
-            self._write_dpc_note(timepoint, region)
+        self._write_option_notes(timepoint, region)
+        # everything between a chunk's copy to the device and its fusion: what it allocates, costs and launches
+        chain = TileChain(distortion_ppm=self.distortion_correction, binning=self.tile_binning,
+                          binning_method=self.tile_binning_method,
+                          dpc_planes=range(self._dpc_index * self.num_z, (self._dpc_index + 1) * self.num_z) if self.dpc else (),
+                          dpc_gain=self.dpc_gain, despeckle=self.despeckle, despeckle_threshold=self.despeckle_threshold,
+                          tophat_radius=self.background_radius if self.background_subtract == 'tophat' else None,
+                          seam_qc_radius=self.seam_qc_radius, file_shape=(fh, fw), tile_shape=(th, tw), dtype=self.dtype)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1188,7 +1194,6 @@ class Stitcher:
                 self._ingest_stream = torch.cuda.Stream(device=self.device)
             side = self._ingest_stream
             side.wait_stream(torch.cuda.current_stream(self.device))      # whatever the caller enqueued (flatfields, shifts) first
-        import contextlib
         stream_ctx = torch.cuda.stream(side) if side is not None else contextlib.nullcontext()
 
         # batch planes that share one rectangle list (normally: all of them)
@@ -1203,12 +1208,10 @@ class Stitcher:
         # few planes: bounded by free HBM, by host memory and by what is sensible to pin.
         free_bytes = torch.cuda.mem_get_info(self.device)[0]
         try:
-            import psutil
             host_free = psutil.virtual_memory().available
         except Exception:   # pragma: no cover
             host_free = 8 << 30
         budget = max(1, min(int(free_bytes * 0.2), int(host_free * 0.1), int(self.batch_bytes_limit)))
-        tdtype = native.torch_dtype_of(self.dtype)
         processed = 0
         projected = set()      # channels whose projection has been written once: later batches accumulate
         pool = ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4))
@@ -1224,11 +1227,7 @@ class Stitcher:
                                          f"{(fh, fw)}")
                     flats_dev[ci] = torch.from_numpy(np.ascontiguousarray(ff)).to(self.device)
             if stream_to is not None and groups:
-                # (one staged plane of the longest list: its raw tiles and, with --tile-binning, their binned copy -- the
-                # batch budget below counts the same two)
-                # (and with --distortion-correction their corrected copy)
-                widest = max(len(rect_of[sig]) for sig in groups) * \
-                    (fh * fw + (th * tw if binned else 0) + (fh * fw if warped else 0)) * np.dtype(self.dtype).itemsize
+                widest = chain.writer_plane_bytes(max(len(rect_of[sig]) for sig in groups))      # of the longest list
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
             def parts_of(t):      # the tensors of a target that this call writes
                 return t if isinstance(t, tuple) else ((t.out,) if isinstance(t, FocusFollower) else (t,))
@@ -1273,26 +1272,13 @@ class Stitcher:
                 focus = project_to is not None and any(isinstance(project_to.get(p // self.num_z), tuple) for p in plist)
                 n = len(rects)
                 plan = self._plan_for(rects, th, tw, hc, wc, mode)
-                per_plane = n * th * tw * np.dtype(self.dtype).itemsize
                 # the best-focus projection's per-tile-pixel winners (5 B per tile pixel, one buffer for the group's calls)
                 focus_scratch = torch.empty(native.focus_scratch_bytes(n, th, tw), dtype=torch.uint8, device=self.device) \
                     if focus else None
                 staged_budget = budget - (0 if focus_scratch is None else focus_scratch.numel())
-                # the top-hat's scratch (the erosion of a batch: as many bytes as its tiles) counts against the budget too
-                tophat = self.background_subtract == 'tophat'
-                # and so does the despeckle's destination (one more copy of a batch's tiles)
-                # and the right halves of the derived planes (--dpc: counted as one more copy, though only they have one)
-                n_derived = sum(p // self.num_z == self._dpc_index for p in plist) if self.dpc else 0
-                copies = 1 + int(despeckle) + int(tophat) + int(n_derived > 0)
-                # the corrected copy of the staged planes (--distortion-correction; of the right halves too): one more raw copy
-                raw_copies = (1 + int(n_derived > 0)) * (1 + int(warped))
-                staged_per_plane = per_plane * (copies + raw_copies - 1 - int(n_derived > 0))
-                if binned:
-                    # the staged planes (and the right halves) keep the files' size, and so do their corrected copies; the
-                    # binned copy of both -- 1 / K^2 of them -- and everything behind it is per_plane
-                    raw_per_plane = n * fh * fw * np.dtype(self.dtype).itemsize
-                    staged_per_plane = raw_per_plane * raw_copies + per_plane * copies
-                batch = max(1, min(len(plist), staged_budget // max(1, staged_per_plane)))
+                # every buffer of the chain counts against the budget (TileChain.plane_bytes)
+                derived_in_list = chain.derived(plist)
+                batch = max(1, min(len(plist), staged_budget // max(1, chain.plane_bytes(n, bool(derived_in_list)))))
                 if writer is not None:
                     batch = min(batch, writer.batch)
                 chunks = [plist[b0:b0 + batch] for b0 in range(0, len(plist), batch)]
@@ -1300,91 +1286,20 @@ class Stitcher:
                 # the next region's files are then read while this region's copy and fusion are still under way
                 pipelined = writer is not None and self._defer_drain
                 n_slots = 2 if (len(chunks) > 1 or pipelined) else 1
-                key = ('ingest', batch, n, fh, fw, n_slots, np.dtype(self.dtype).str)
-                bufs = self._buffer_cache.get(key)
-                if bufs is None:   # pinned staging + device mirrors, kept for the next region of the same shape
-                    bufs = ([torch.empty((batch, n, fh, fw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
-                            [torch.empty((batch, n, fh, fw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
-                            [None] * n_slots, [0])
-                    self._keep_buffers(key, bufs)
-                # the slots' "copy and fusion finished" events live with the buffers: another group (or the next
-                # region) that gets the same cached staging must wait for the H2D copy still reading it
-                staging, on_dev, done, turn = bufs
-                tophat_scratch = None
-                if tophat:      # one scratch beside the ingest buffers: the launches of one stream follow each other
-                    tkey = ('tophat', batch, n, th, tw, np.dtype(self.dtype).str)
-                    tophat_scratch = self._buffer_cache.get(tkey)
-                    if tophat_scratch is None:
-                        tophat_scratch = torch.empty(native.tophat_scratch_bytes(batch * n, th, tw, self.dtype), dtype=torch.uint8,
-                                                     device=self.device)
-                        self._keep_buffers(tkey, tophat_scratch)
-                warped_tiles = None
-                if warped:
-                    # ONE corrected buffer of the files' shape for both ingest slots, by the argument for `binned_tiles` and
-                    # the despeckle's `clean` below: the correction and everything that reads its result are launches of one
-                    # stream, so the next chunk's correction (which overwrites it) runs after this chunk's fusion has read it;
-                    # only the H2D copy into the OTHER slot's raw tiles overlaps, and nothing reads those but the correction
-                    # of their own chunk
-                    wkey = ('distortion', batch, n, fh, fw, np.dtype(self.dtype).str)
-                    warped_tiles = self._buffer_cache.get(wkey)
-                    if warped_tiles is None:
-                        warped_tiles = torch.empty((batch, n, fh, fw), dtype=tdtype, device=self.device)
-                        self._keep_buffers(wkey, warped_tiles)
-                binned_tiles = None
-                if binned:
-                    # ONE binned buffer for both ingest slots, by the argument for the despeckle's `clean` below: the binning
-                    # and everything that reads its result are launches of one stream, so the next chunk's binning (which
-                    # overwrites it) runs after this chunk's fusion has read it; only the H2D copy into the OTHER slot's raw
-                    # tiles overlaps, and nothing reads those but the binning of their own chunk
-                    bkey = ('binning', batch, n, th, tw, np.dtype(self.dtype).str)
-                    binned_tiles = self._buffer_cache.get(bkey)
-                    if binned_tiles is None:
-                        binned_tiles = torch.empty((batch, n, th, tw), dtype=tdtype, device=self.device)
-                        self._keep_buffers(bkey, binned_tiles)
-                clean = None
+                # as deep as a chunk can hold derived planes (they are consecutive: plist is ascending)
+                deep = min(batch, len(derived_in_list))
+                bufs = chain.allocate(self._cached_buffers, self.device, batch, n, deep, n_slots)
+                staging, on_dev, done, turn = bufs['ingest']
+                # the right halves: one more staged buffer per ingest slot, with events of its own
+                right_staging, _, right_done, _ = bufs.get('dpc', (None,) * 4)
+                list_counts = None
                 if despeckle:
-                    # ONE destination for both ingest slots: despeckle, top-hat and the fusion that reads `clean` are launches
-                    # of one stream, so the next chunk's despeckle (which overwrites it) runs after this chunk's fusion has
-                    # read it; only the H2D copy into the OTHER slot's raw tiles overlaps, and nothing reads those but the
-                    # despeckle of their own chunk
-                    ckey = ('despeckle', batch, n, th, tw, np.dtype(self.dtype).str)
-                    clean = self._buffer_cache.get(ckey)
-                    if clean is None:
-                        clean = torch.empty((batch, n, th, tw), dtype=tdtype, device=self.device)
-                        self._keep_buffers(ckey, clean)
                     if despeckle_counts is None:
                         despeckle_counts = torch.zeros(self.num_c, dtype=torch.int64, device=self.device)
                         despeckle_staged = [0] * self.num_c
                     # the kernel's per-plane counts of this list's planes (plane of plist, tile): every chunk adds into its own
                     # run of it, and it is folded per channel once, behind the last chunk
                     list_counts = torch.zeros((len(plist), n), dtype=torch.int64, device=self.device)
-                right_staging = right_dev = right_done = binned_rights = warped_rights = None
-                if n_derived:
-                    # the right halves: one more staged buffer per ingest slot, pinned and mirrored on the device, as deep as
-                    # a chunk can hold derived planes (they are consecutive: plist is ascending).  Its own events: whatever
-                    # ingest buffers it is used beside, the copy and the launch that read a slot have finished before the
-                    # loader writes to it again
-                    deep = min(batch, n_derived)
-                    rkey = ('dpc', deep, n, fh, fw, n_slots, np.dtype(self.dtype).str)
-                    rbufs = self._buffer_cache.get(rkey)
-                    if rbufs is None:
-                        rbufs = ([torch.empty((deep, n, fh, fw), dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
-                                 [torch.empty((deep, n, fh, fw), dtype=tdtype, device=self.device) for _ in range(n_slots)],
-                                 [None] * n_slots)
-                        self._keep_buffers(rkey, rbufs)
-                    right_staging, right_dev, right_done = rbufs
-                    if warped:      # the corrected right halves: one small buffer for both slots, like `warped_tiles`
-                        rwkey = ('distortion-dpc', deep, n, fh, fw, np.dtype(self.dtype).str)
-                        warped_rights = self._buffer_cache.get(rwkey)
-                        if warped_rights is None:
-                            warped_rights = torch.empty((deep, n, fh, fw), dtype=tdtype, device=self.device)
-                            self._keep_buffers(rwkey, warped_rights)
-                    if binned:      # the binned right halves: one small buffer for both slots, like `binned_tiles`
-                        rbkey = ('binning-dpc', deep, n, th, tw, np.dtype(self.dtype).str)
-                        binned_rights = self._buffer_cache.get(rbkey)
-                        if binned_rights is None:
-                            binned_rights = torch.empty((deep, n, th, tw), dtype=tdtype, device=self.device)
-                            self._keep_buffers(rbkey, binned_rights)
                 qc_words = None
                 if self.tile_qc:
                     # the words of this list's staged planes (plane of plist, tile): every chunk's launch overwrites its own run
@@ -1412,8 +1327,7 @@ class Stitcher:
                     if done[slot] is not None:
                         done[slot].synchronize()      # the slot's previous copy and fusion have finished
                     host = staging[slot].numpy()
-                    # the chunk's derived planes (consecutive) and where their right halves go
-                    derived = [pi for pi, p in enumerate(chunk) if p // self.num_z == self._dpc_index] if n_derived else []
+                    derived = chain.derived(chunk)      # (consecutive) -- and where their right halves go
                     right_host = None
                     if derived:
                         if right_done[slot] is not None:
@@ -1446,32 +1360,7 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
-                    if warped:      # the first launch after the copy: everything below reads the corrected planes
-                        tiles = native.warp_tiles(tiles, self.distortion_correction, out=warped_tiles[:m])
-                    if binned:      # the next (without the correction, the first): everything below reads the binned planes
-                        tiles = native.bin_tiles(tiles, self.tile_binning, self.tile_binning_method, out=binned_tiles[:m])
-                    if derived:     # in place over the left halves, before anything reads the staged planes
-                        i0, i1 = derived[0], derived[-1] + 1
-                        rights = right_dev[slot][:i1 - i0]
-                        rights.copy_(right_staging[slot][:i1 - i0], non_blocking=True)
-                        if warped:
-                            rights = native.warp_tiles(rights, self.distortion_correction, out=warped_rights[:i1 - i0])
-                        if binned:
-                            rights = native.bin_tiles(rights, self.tile_binning, self.tile_binning_method,
-                                                      out=binned_rights[:i1 - i0])
-                        native.dpc_tiles(tiles[i0:i1], rights, self.dpc_gain)
-                        right_done[slot] = torch.cuda.Event()
-                        right_done[slot].record()
-                    if qc_words is not None:      # the tiles as they are in their files: before anything filters them
-                        native.tile_stats(tiles, out=qc_words[b0:b0 + m].view(-1, native.SQ_TILE_STATS_WORDS))
-                    if despeckle:   # out of place: everything below reads the filtered planes in `clean`
-                        tiles = native.despeckle_tiles(tiles, self.despeckle_threshold, self.despeckle, out=clean[:m],
-                                                       counts=list_counts[b0:b0 + m].view(-1))
-                    if tophat:      # in place on the staged tiles: everything below reads the filtered planes
-                        native.tophat_tiles(tiles, self.background_radius, tophat_scratch)
-                    if seam_words is not None:      # the planes as the fusion reads them: behind the last filter
-                        native.seam_stats(tiles, seam_table[1], self.seam_qc_radius, out=seam_words[b0:b0 + m],
-                                          pairs_dev=seam_table[2])
+                    tiles = chain.run(tiles, slot, derived, b0, bufs, list_counts, qc_words, seam_table, seam_words)
                     flats = [flats_dev.get(p // self.num_z) for p in chunk] if self.apply_flatfield else None
                     slots = [slot_of[p] for p in chunk]
                     if project_to is not None:
@@ -1534,66 +1423,49 @@ class Stitcher:
         print(f"Time to stitch region {region} timepoint {timepoint}: {time.time() - start_time}")
         return flat_canvas, plane_ids
 
-    def _write_background_note(self, timepoint, region) -> None:
-        """``<t>_stitched/<region>_stitched_background.json``: what was removed from the tiles of every store of this region
-        (the same bytes from every rank and call, put in place atomically)."""
+    def _write_note(self, timepoint, region, suffix, note) -> None:
+        """``<t>_stitched/<region>_stitched_<suffix>.json``: the same bytes from every rank and call, put in place atomically."""
         folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
         os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, f"{region}_stitched_background.json")
-        note = {'method': 'tophat', 'radius': self.background_radius, 'window': 2 * self.background_radius + 1,
-                'applies_to': 'every staged tile plane, before the flatfield divide'}
+        path = os.path.join(folder, f"{region}_stitched_{suffix}.json")
         tmp = f"{path}.{os.getpid()}.tmp"
         with open(tmp, 'w') as fh:
             json.dump(note, fh, indent=1)
         os.replace(tmp, path)
 
-    def _write_distortion_note(self, timepoint, region) -> None:
-        """``<t>_stitched/<region>_stitched_distortion.json``: how the tiles of every store of this region were corrected (the
-        same bytes from every rank and call, put in place atomically)."""
-        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
-        os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, f"{region}_stitched_distortion.json")
-        du, dv = distortion.max_displacement(self.file_height, self.file_width, self.distortion_correction)
-        note = {'ppm': self.distortion_correction, 'tile_shape': [self.file_height, self.file_width],
+    def _write_option_notes(self, timepoint, region) -> None:
+        """One note per per-tile option that is on: what was done to the tiles of every store of this region -- the static
+        facts only (the despeckle's counts are in ``despeckle_replaced``)."""
+        if self.distortion_correction != 0:
+            du, dv = distortion.max_displacement(self.file_height, self.file_width, self.distortion_correction)
+            self._write_note(timepoint, region, 'distortion', {
+                'ppm': self.distortion_correction, 'tile_shape': [self.file_height, self.file_width],
                 'max_abs_du_256': du, 'max_abs_dv_256': dv, 'edges': 'replicated',
                 'interpolation': 'bilinear, 8 fractional bits',
-                'applies_to': 'every tile, before binning, placement, registration, the flatfield estimate and every tile filter'}
-        tmp = f"{path}.{os.getpid()}.tmp"
-        with open(tmp, 'w') as fh:
-            json.dump(note, fh, indent=1)
-        os.replace(tmp, path)
-
-    def _write_binning_note(self, timepoint, region) -> None:
-        """``<t>_stitched/<region>_stitched_binning.json``: how the tiles of every store of this region were binned (the same
-        bytes from every rank and call, put in place atomically)."""
-        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
-        os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, f"{region}_stitched_binning.json")
-        k = self.tile_binning
-        note = {'factor': k, 'method': self.tile_binning_method,
+                'applies_to': 'every tile, before binning, placement, registration, the flatfield estimate and every tile filter'})
+        if self.tile_binning > 1:
+            k = self.tile_binning
+            self._write_note(timepoint, region, 'binning', {
+                'factor': k, 'method': self.tile_binning_method,
                 'file_tile_shape': [self.file_height, self.file_width],
                 'binned_tile_shape': [self.input_height, self.input_width],
                 'rows_dropped': self.file_height - k * self.input_height,
                 'columns_dropped': self.file_width - k * self.input_width,
                 'file_pixel_size_um': self.file_pixel_size_um, 'pixel_size_um': self.pixel_size_um,
-                'applies_to': 'every tile, before placement, registration, the flatfield estimate and every tile filter'}
-        tmp = f"{path}.{os.getpid()}.tmp"
-        with open(tmp, 'w') as fh:
-            json.dump(note, fh, indent=1)
-        os.replace(tmp, path)
-
-    def _write_dpc_note(self, timepoint, region) -> None:
-        """``<t>_stitched/<region>_stitched_dpc.json``: what the derived channel of every store of this region is made of
-        (the same bytes from every rank and call, put in place atomically)."""
-        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
-        os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, f"{region}_stitched_dpc.json")
-        note = {'left': self.dpc_channels[0], 'right': self.dpc_channels[1], 'gain': self.dpc_gain,
-                'channel': native.DPC_CHANNEL, 'definition': native.DPC_DEFINITION}
-        tmp = f"{path}.{os.getpid()}.tmp"
-        with open(tmp, 'w') as fh:
-            json.dump(note, fh, indent=1)
-        os.replace(tmp, path)
+                'applies_to': 'every tile, before placement, registration, the flatfield estimate and every tile filter'})
+        if self.background_subtract == 'tophat':
+            self._write_note(timepoint, region, 'background', {
+                'method': 'tophat', 'radius': self.background_radius, 'window': 2 * self.background_radius + 1,
+                'applies_to': 'every staged tile plane, before the flatfield divide'})
+        if self.despeckle != 'none':
+            self._check_despeckle_dtype()
+            self._write_note(timepoint, region, 'despeckle', {
+                'mode': self.despeckle, 'threshold': self.despeckle_threshold, 'window': 3,
+                'applies_to': 'every staged tile plane, before background removal and the flatfield divide'})
+        if self.dpc:
+            self._write_note(timepoint, region, 'dpc', {
+                'left': self.dpc_channels[0], 'right': self.dpc_channels[1], 'gain': self.dpc_gain,
+                'channel': native.DPC_CHANNEL, 'definition': native.DPC_DEFINITION})
 
     def _check_despeckle_dtype(self) -> None:
         """A threshold at or above the dtype's maximum can never fire (the default on uint8 data): a message, not a silent
@@ -1601,20 +1473,6 @@ class Stitcher:
         if self.despeckle != 'none' and self.despeckle_threshold >= int(np.iinfo(self.dtype).max):
             raise ValueError(f"despeckle_threshold {self.despeckle_threshold} can never fire on {np.dtype(self.dtype).name} tiles "
                              f"(maximum {int(np.iinfo(self.dtype).max)}): give a threshold in counts of the tiles' own dtype")
-
-    def _write_despeckle_note(self, timepoint, region) -> None:
-        """``<t>_stitched/<region>_stitched_despeckle.json``: what was replaced in the tiles of every store of this region --
-        the static facts only (the same bytes from every rank and call, put in place atomically); the counts are in
-        ``despeckle_replaced``."""
-        folder = os.path.join(self.output_folder, f"{timepoint}_stitched")
-        os.makedirs(folder, exist_ok=True)
-        path = os.path.join(folder, f"{region}_stitched_despeckle.json")
-        note = {'mode': self.despeckle, 'threshold': self.despeckle_threshold, 'window': 3,
-                'applies_to': 'every staged tile plane, before background removal and the flatfield divide'}
-        tmp = f"{path}.{os.getpid()}.tmp"
-        with open(tmp, 'w') as fh:
-            json.dump(note, fh, indent=1)
-        os.replace(tmp, path)
 
     def _finish_despeckle(self) -> None:
         """Read the pending per-channel counts back (the device has been synchronised: stitch_planes' own synchronise, or the

@@ -1,0 +1,127 @@
+"""The per-tile filter chain between the staged tiles' copy to the device and their fusion (host side: what it allocates,
+what that costs per staged plane, and the order of its launches).  ``Stitcher.stitch_planes`` builds one ``TileChain`` per call."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import native
+
+# Every device buffer of the chain, once: (cache key name, planes of the files' or the tiles' shape, as deep as a chunk or as
+# a chunk's derived planes, the option that allocates it).  Both byte counts and the allocation are read off this table.
+BUFFERS = (('ingest', 'file', 'chunk', None),                  # the raw tiles: the ring's slots, see RING
+           ('dpc', 'file', 'derived', None),                   # the raw right halves: the ring's, too
+           ('distortion', 'file', 'chunk', 'warped'),          # the corrected copy of the staged planes
+           ('distortion-dpc', 'file', 'derived', 'warped'),    # ... and of the right halves
+           ('binning', 'tile', 'chunk', 'binned'),             # the binned copy of the staged planes
+           ('binning-dpc', 'tile', 'derived', 'binned'),       # ... and of the right halves
+           ('despeckle', 'tile', 'chunk', 'despeckled'),       # the despeckle's destination
+           ('tophat', 'tile', 'chunk', 'tophat'))              # the top-hat's scratch: the erosion, as many bytes as the planes
+RING = ('ingest', 'dpc')      # per ingest slot: (pinned staging, device mirrors, the events behind each slot's last reader, turn)
+WRITER = ('ingest', 'distortion', 'binning')                   # what the stream writer's batch is sized by
+
+
+def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None):
+    """The head of every way tiles reach the device -- the staged planes, the right halves, registration's stack: corrected
+    first (in sensor pixels), binned second, into the first planes of ``warped`` / ``binned`` where they are given."""
+    m = len(tiles)
+    if ppm:
+        tiles = native.warp_tiles(tiles, ppm, out=None if warped is None else warped[:m])
+    if factor > 1:
+        tiles = native.bin_tiles(tiles, factor, method, out=None if binned is None else binned[:m])
+    return tiles
+
+
+class TileChain:
+    def __init__(self, *, distortion_ppm, binning, binning_method, dpc_planes, dpc_gain, despeckle, despeckle_threshold,
+                 tophat_radius, seam_qc_radius, file_shape, tile_shape, dtype):
+        """``dpc_planes``: the derived channel's plane ids (empty without --dpc); ``tophat_radius``: None without the top-hat;
+        ``file_shape`` / ``tile_shape``: (fh, fw) of the files and (th, tw) behind the binning (the same without it)."""
+        self.ppm, self.factor, self.method = distortion_ppm, binning, binning_method
+        self.dpc_planes, self.dpc_gain = dpc_planes, dpc_gain
+        self.despeckle, self.despeckle_threshold = despeckle, despeckle_threshold
+        self.tophat_radius, self.seam_qc_radius = tophat_radius, seam_qc_radius
+        self.shapes = {'file': tuple(file_shape), 'tile': tuple(tile_shape)}
+        self.dtype = np.dtype(dtype)
+        on = {None: True, 'warped': distortion_ppm != 0, 'binned': binning > 1, 'despeckled': despeckle != 'none',
+              'tophat': tophat_radius is not None}
+        self.buffers = [b[:3] for b in BUFFERS if on[b[3]]]
+
+    # ------------------------------------------------------------------ byte accounting (integers only)
+    def derived(self, plane_ids):
+        """The positions of the derived planes among ``plane_ids`` (consecutive: the ids ascend)."""
+        return [i for i, p in enumerate(plane_ids) if p in self.dpc_planes]
+
+    def _plane_bytes(self, n, names):
+        return sum(n * self.shapes[shape][0] * self.shapes[shape][1] * self.dtype.itemsize
+                   for name, shape, _ in self.buffers if name in names)
+
+    def plane_bytes(self, n, derived: bool) -> int:
+        """Device bytes per staged plane of ``n`` tiles, which the batch budget is divided by: every buffer of the chain; with
+        derived planes in the list the right halves' buffers count as whole copies, though only those planes have one."""
+        return self._plane_bytes(n, [name for name, _, deep in self.buffers if derived or deep == 'chunk'])
+
+    def writer_plane_bytes(self, n) -> int:
+        """One staged plane as the stream writer's batch counts it: the raw tiles, their corrected and their binned copy."""
+        return self._plane_bytes(n, WRITER)
+
+    # ------------------------------------------------------------------ allocation
+    def key(self, name, depth, n, n_slots=None):
+        """The buffer-cache key of buffer ``name``, ``depth`` planes of ``n`` tiles deep (the ring's: of ``n_slots`` slots)."""
+        shape = next(b[1] for b in BUFFERS if b[0] == name)
+        return (name, depth, n) + self.shapes[shape] + (() if n_slots is None else (n_slots,)) + (self.dtype.str,)
+
+    def allocate(self, cached, device, batch, n, deep, n_slots):
+        """{name: buffer} for chunks of ``batch`` planes of ``n`` tiles, ``deep`` of them derived at most, through
+        ``cached(key, make)``: kept for the next region of the same shape (page-locking host memory is slow).  The ring's
+        events live with its buffers: whoever gets the same cached staging must wait for the copy and the launch still
+        reading a slot before the loader writes to it again; its turn goes on across calls.
+
+        ONE buffer of every other kind serves both ingest slots: every launch of the chain and the fusion that reads its result are launches of
+        one stream, so the next chunk's launch that overwrites a buffer runs after this chunk's fusion has read it; only the
+        H2D copy into the OTHER slot's raw tiles overlaps, and nothing reads those but the first launch of their own chunk."""
+        import torch
+        bufs = {}
+        for name, shape, deep_as in self.buffers:
+            depth = batch if deep_as == 'chunk' else deep
+            if not depth:
+                continue
+            dims, tdtype = (depth, n) + self.shapes[shape], native.torch_dtype_of(self.dtype)
+            if name in RING:
+                make = lambda: ([torch.empty(dims, dtype=tdtype, pin_memory=True) for _ in range(n_slots)],
+                                [torch.empty(dims, dtype=tdtype, device=device) for _ in range(n_slots)], [None] * n_slots, [0])
+            elif name == 'tophat':
+                make = lambda: torch.empty(native.tophat_scratch_bytes(depth * n, *self.shapes[shape], self.dtype),
+                                           dtype=torch.uint8, device=device)
+            else:
+                make = lambda: torch.empty(dims, dtype=tdtype, device=device)
+            bufs[name] = cached(self.key(name, depth, n, n_slots if name in RING else None), make)
+        return bufs
+
+    # ------------------------------------------------------------------ the launches of one chunk
+    def run(self, tiles, slot, derived, b0, bufs, list_counts=None, qc_words=None, seam_table=None, seam_words=None):
+        """The staged planes ``tiles`` [m, n, fh, fw] of the chunk in ring slot ``slot`` (their copy enqueued) -> the planes
+        the fusion reads.  ``derived``: the positions of the chunk's derived planes, whose right halves are in the slot's
+        pinned 'dpc' buffer; ``b0``: the chunk's first row in the list-wide outputs ``list_counts``, ``qc_words`` and
+        ``seam_words`` (each None when its option is off).  The order is fixed."""
+        import torch
+        m = len(tiles)
+        tiles = warp_and_bin(tiles, self.ppm, self.factor, self.method, bufs.get('distortion'), bufs.get('binning'))
+        if derived:     # in place over the left halves, before anything reads the staged planes
+            i0, i1 = derived[0], derived[-1] + 1
+            staging, on_dev, read, _ = bufs['dpc']
+            halves = on_dev[slot][:i1 - i0]
+            halves.copy_(staging[slot][:i1 - i0], non_blocking=True)
+            halves = warp_and_bin(halves, self.ppm, self.factor, self.method, bufs.get('distortion-dpc'), bufs.get('binning-dpc'))
+            native.dpc_tiles(tiles[i0:i1], halves, self.dpc_gain)
+            read[slot] = torch.cuda.Event()
+            read[slot].record()
+        if qc_words is not None:      # the tiles as they are in their files: before anything filters them
+            native.tile_stats(tiles, out=qc_words[b0:b0 + m].view(-1, native.SQ_TILE_STATS_WORDS))
+        if 'despeckle' in bufs:       # out of place: everything below reads the filtered planes
+            tiles = native.despeckle_tiles(tiles, self.despeckle_threshold, self.despeckle, out=bufs['despeckle'][:m],
+                                           counts=list_counts[b0:b0 + m].view(-1))
+        if 'tophat' in bufs:          # in place: everything below reads the filtered planes
+            native.tophat_tiles(tiles, self.tophat_radius, bufs['tophat'])
+        if seam_words is not None:    # the planes as the fusion reads them: behind the last filter
+            native.seam_stats(tiles, seam_table[1], self.seam_qc_radius, out=seam_words[b0:b0 + m], pairs_dev=seam_table[2])
+        return tiles
