@@ -164,6 +164,8 @@ EXPORTS = {
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'sq_warp_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                 C.c_int32, C.c_int32, C.c_void_p]),
+    'sq_shift_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                 C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1525,6 +1527,71 @@ def warp_tiles(tiles, ppm: int, out=None, stream=None):
         _check(lib().sq_warp_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                    dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), ppm,
                                    _stream_ptr(stream)), 'sq_warp_tiles')
+    return out
+
+
+SQ_SHIFT_MAX = 16384
+SQ_SHIFT_MAX_SIDE = 65535
+SQ_SHIFT_ROWS_PER_THREAD = 32
+
+
+def shift_tiles(tiles, shifts, out=None, stream=None):
+    """Constant sub-pixel translation of every H x W plane of ``tiles`` into ``out`` (sq_shift_tiles; an extension, the
+    reference has nothing like it): the output at (y, x) takes the input at (y + Sy/256, x + Sx/256), bilinearly with 8
+    fractional bits and replicated edges, exact in integers -- ``tests/shift_ref.shift_image``; the formula stands in
+    include/squidstitch.h.  The shift is out of place: ``tiles`` is left as it is.
+
+    tiles:  uint8 / uint16 device tensor [..., H, W], H and W at most 65535, with unit-stride rows (any row pitch) whose
+            leading dimensions are one uniform plane stride apart: a contiguous stack, or a view such as every other plane of
+            one.
+    shifts: one pair (Sy, Sx) of integers in 1/256 pixel, each in -16384..16384, for every plane, or a sequence of one pair per
+            index of the leading dimension (all planes under that index take it).  (0, 0) gives an exact copy.
+    out:    a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
+            shares no memory with ``tiles``; allocated contiguous when None.
+    Returns ``out``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    try:
+        pairs = list(shifts)
+    except TypeError:
+        raise ValueError(f"shifts must be a pair (Sy, Sx) or a sequence of pairs, got {shifts!r}")
+    if len(pairs) == 2 and not any(isinstance(v, (list, tuple, np.ndarray)) for v in pairs):
+        pairs = [pairs]      # one pair for every plane
+    elif tiles.dim() < 3 or len(pairs) != tiles.shape[0]:
+        raise ValueError(f"shifts must be one pair, or one pair per index of the leading dimension "
+                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(pairs)}")
+    table = []
+    for pair in pairs:
+        if len(pair) != 2:
+            raise ValueError(f"a shift is a pair (Sy, Sx), got {pair!r}")
+        table += [_int_in(pair[0], -SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)'),
+                  _int_in(pair[1], -SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)')]
+    src = _plane_layout(tiles, 'tiles')
+    n_images, h, w, src_plane_stride, src_pitch = src
+    if h > SQ_SHIFT_MAX_SIDE or w > SQ_SHIFT_MAX_SIDE:
+        raise ValueError(f"planes of {h} x {w} have a side above {SQ_SHIFT_MAX_SIDE}")
+    shape = tuple(tiles.shape)
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
+            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
+        dst = _plane_layout(out, 'out')
+        n_out, _, _, dst_plane_stride, dst_pitch = dst
+        assert n_out == n_images
+        if n_images == 0:
+            return out
+        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
+            raise ValueError("out shares memory with tiles: the shift is out of place")
+        host = (C.c_int32 * len(table))(*table)
+        _check(lib().sq_shift_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
+                                    dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), host,
+                                    n_images // len(pairs), _stream_ptr(stream)), 'sq_shift_tiles')
     return out
 
 

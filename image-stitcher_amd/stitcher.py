@@ -32,7 +32,7 @@ try:
 except Exception:   # pragma: no cover
     psutil = None      # stitch_planes then assumes 8 GiB of free host memory
 
-from . import alignment, binning, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
+from . import alignment, binning, channelshift, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -83,7 +83,8 @@ class Stitcher:
                  tile_qc_saturation: float = 0.01, tile_qc_focus_ratio: float = 0.5, dpc: bool = False,
                  dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
                  seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
-                 tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0):
+                 tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0,
+                 channel_shifts=None):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -275,6 +276,19 @@ class Stitcher:
         # flatfield is taken to be in corrected geometry.  0: nothing is launched, allocated, written, synchronised or parsed
         # differently.
         self.distortion_correction = distortion.check_option(distortion_correction)
+        # Extension: channel_shifts={output channel name: (Sy, Sx)}, Python ints in 1/256 pixel within -16384..16384, moves
+        # every tile of a channel by a constant sub-pixel translation: the output at (y, x) takes the input at (y + Sy/256,
+        # x + Sx/256), bilinearly with 8 fractional bits and replicated edges, exact in integers (channelshift.py;
+        # tests/shift_ref.py) -- a point imaged at (y, x) in the reference channel and at (y + DY, x + DX) in the named one is
+        # put right by (256 DY, 256 DX).  A run equals a run without the option on a folder whose files of the shifted channels
+        # were translated beforehand, byte for byte in every store, sidecar and picture: the staged tiles are shifted on the
+        # device (sq_shift_tiles) behind the distortion correction and in front of the binning, all in sensor pixels, and the
+        # readers of single files (get_tile, the flatfield estimate's samples) shift on the host.  The registration channel
+        # is the frame the others are moved into and takes no shift; nor do the channels --dpc reads or derives.  A supplied
+        # flatfield is taken to be in shifted geometry.  None, empty or all zero: nothing is launched, allocated, written,
+        # synchronised or parsed differently.
+        self.channel_shifts = channelshift.check_option(channel_shifts)
+        self._channel_shift_index: Dict[int, Tuple[int, int]] = {}      # output channel index -> pair, once the names are known
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -495,6 +509,8 @@ class Stitcher:
                 if half not in self.monochrome_channels:
                     raise ValueError(f"dpc_channels: the files of {half!r} are RGB; the halves are monochrome channels")
             self._dpc_index = self.monochrome_channels.index(native.DPC_CHANNEL)
+        if self.channel_shifts:
+            self._resolve_channel_shifts()
         if self.focus_guide_channel is not None:
             if self.focus_guide_channel not in self.monochrome_channels:
                 raise ValueError(f"focus_guide_channel {self.focus_guide_channel!r} is not a channel of this acquisition: "
@@ -553,12 +569,56 @@ class Stitcher:
         """(stitcher.py:1220-1223)"""
         return sorted(set(r[0] for r in self.regions)), sorted(set(r[1:] for r in self.regions))
 
-    def _read_tile_file(self, path):
-        """One tile file as the run sees it: corrected (--distortion-correction) first, binned (--tile-binning) second, on the
-        host with the integer arithmetic of the device launches; the file itself without the options."""
-        if not self.distortion_correction:
+    def _colour_planes(self, channel):
+        """The output channels a file channel becomes: itself, or the three colour planes of an RGB file."""
+        if channel in self.monochrome_channels:
+            return [channel]
+        base = channel.split('_')[0]
+        return [f"{base}_{color}" for color in 'RGB']
+
+    def _resolve_channel_shifts(self) -> None:
+        """--channel-shift once the output channels are known: every name is one of them, none is the registration channel's
+        (with registration on) or one --dpc reads or derives; the pairs by channel index, and the run's one printed line."""
+        for name in self.channel_shifts:
+            if name not in self.monochrome_channels:
+                raise ValueError(f"channel_shifts: {name!r} is not a channel of this acquisition: {self.monochrome_channels}")
+        if self.use_registration:
+            # (the channel calculate_shifts will resolve to: the first one when none, or an unknown one, is named)
+            reg = self.registration_channel if self.registration_channel in self.channel_names else self.channel_names[0]
+            for name in self._colour_planes(reg):
+                if name in self.channel_shifts:
+                    raise ValueError(f"channel_shifts: {name!r} is the registration channel {reg!r}, the frame the other "
+                                     f"channels are moved into: it takes no shift")
+        if self.dpc:
+            for name in (native.DPC_CHANNEL,) + tuple(self.dpc_channels):
+                if name in self.channel_shifts:
+                    raise ValueError(f"channel_shifts: {name!r} is a channel --dpc reads or derives; both halves come through "
+                                     f"the same optics and take no shift")
+        self._channel_shift_index = {self.monochrome_channels.index(name): pair for name, pair in self.channel_shifts.items()}
+        print("[channel-shift] tiles of " + ", ".join(
+            f"{name} sampled at (y {sy / 256:+.4f}, x {sx / 256:+.4f}) px" for name, (sy, sx) in sorted(self.channel_shifts.items()))
+            + f" ({self.file_height} x {self.file_width}; bilinear, 8 fractional bits, edges replicated; after the distortion "
+              f"correction, before the binning)")
+
+    def _file_channel_shift(self, channel):
+        """(Sy, Sx) of the files of ``channel`` -- for an RGB file a triple each -- or None when none of its planes is shifted."""
+        if not self.channel_shifts or channel is None:
+            return None
+        pairs = [self.channel_shifts.get(name, (0, 0)) for name in self._colour_planes(channel)]
+        if not any(pair != (0, 0) for pair in pairs):
+            return None
+        return pairs[0] if len(pairs) == 1 else ([p[0] for p in pairs], [p[1] for p in pairs])
+
+    def _read_tile_file(self, path, channel=None):
+        """One tile file of ``channel`` as the run sees it: corrected (--distortion-correction) first, shifted (--channel-shift)
+        second, binned (--tile-binning) third, on the host with the integer arithmetic of the device launches; the file itself
+        without the options."""
+        shift = self._file_channel_shift(channel)
+        if not self.distortion_correction and shift is None:
             return binning.read_binned(path, self.tile_binning, self.tile_binning_method)
         img = distortion.read_warped(path, self.distortion_correction)
+        if shift is not None:
+            img = channelshift.shift_image(img, *shift)
         return img if self.tile_binning == 1 else binning.bin_image(img, self.tile_binning, self.tile_binning_method)
 
     def get_tile(self, t, region, x, y, channel, z_level):
@@ -566,7 +626,7 @@ class Stitcher:
         for value in self.get_region_data(int(t), str(region)).values():
             if value['x'] == x and value['y'] == y and value['channel'] == channel and value['z_level'] == z_level:
                 try:
-                    return self._read_tile_file(value['filepath'])
+                    return self._read_tile_file(value['filepath'], channel)
                 except FileNotFoundError:
                     print(f"Warning: cannot open {value['filepath']}")
                     return None
@@ -871,7 +931,7 @@ class Stitcher:
             if not paths:
                 print(f"WARNING: No images found for channel {channel} across all timepoints")
                 continue
-            images = np.array([self._read_tile_file(p) for p in paths])
+            images = np.array([self._read_tile_file(p, channel) for p in paths])
             if images.ndim == 4 and images.shape[1] == 1:       # (N, 1, Y, X) page stacks
                 images = images[:, 0]
             if images.ndim == 3:
@@ -1155,7 +1215,8 @@ class Stitcher:
                           dpc_planes=range(self._dpc_index * self.num_z, (self._dpc_index + 1) * self.num_z) if self.dpc else (),
                           dpc_gain=self.dpc_gain, despeckle=self.despeckle, despeckle_threshold=self.despeckle_threshold,
                           tophat_radius=self.background_radius if self.background_subtract == 'tophat' else None,
-                          seam_qc_radius=self.seam_qc_radius, file_shape=(fh, fw), tile_shape=(th, tw), dtype=self.dtype)
+                          seam_qc_radius=self.seam_qc_radius, file_shape=(fh, fw), tile_shape=(th, tw), dtype=self.dtype,
+                          channel_shifts=self._channel_shift_index, num_z=self.num_z)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1360,7 +1421,7 @@ class Stitcher:
                     m = len(chunk)
                     tiles = on_dev[slot][:m]
                     tiles.copy_(staging[slot][:m], non_blocking=True)
-                    tiles = chain.run(tiles, slot, derived, b0, bufs, list_counts, qc_words, seam_table, seam_words)
+                    tiles = chain.run(tiles, slot, derived, b0, bufs, list_counts, qc_words, seam_table, seam_words, chunk)
                     flats = [flats_dev.get(p // self.num_z) for p in chunk] if self.apply_flatfield else None
                     slots = [slot_of[p] for p in chunk]
                     if project_to is not None:
@@ -1443,6 +1504,15 @@ class Stitcher:
                 'max_abs_du_256': du, 'max_abs_dv_256': dv, 'edges': 'replicated',
                 'interpolation': 'bilinear, 8 fractional bits',
                 'applies_to': 'every tile, before binning, placement, registration, the flatfield estimate and every tile filter'})
+        if self._channel_shift_index:
+            self._write_note(timepoint, region, 'channel_shift', {
+                'channels': {name: {'shift_256': [sy, sx], 'shift_px': [sy / 256, sx / 256]}
+                             for name, (sy, sx) in sorted(self.channel_shifts.items())},
+                'definition': 'the output at (y, x) takes the input at (y + Sy/256, x + Sx/256)',
+                'tile_shape': [self.file_height, self.file_width], 'edges': 'replicated',
+                'interpolation': 'bilinear, 8 fractional bits',
+                'order': 'after the distortion correction, before the binning',
+                'applies_to': 'every tile of the named channels, before placement, the flatfield estimate and every tile filter'})
         if self.tile_binning > 1:
             k = self.tile_binning
             self._write_note(timepoint, region, 'binning', {

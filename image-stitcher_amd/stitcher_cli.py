@@ -13,13 +13,15 @@ the per-tile quality report (focus, saturation, intensity) of the tiles as they 
 well every pair of overlapping tiles agrees where it is placed, on every (channel, z) plane, and the integer residual displacement
 at which it would agree best.  ``--tile-binning`` and ``--tile-binning-method`` stitch K x K binned tiles, binned on the device
 before anything else sees them.  ``--distortion-correction`` removes radial lens distortion from every tile, on the device, in
-front of all of that.
+front of all of that.  ``--channel-shift NAME DY DX`` (repeatable) moves every tile of one channel by a constant sub-pixel
+translation, on the device, between the two, so that channels that are not registered to each other on the sensor line up.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
 import argparse
 import sys
 
+from . import channelshift
 from .stitcher import Stitcher
 from .stitcher_parameters import StitchingParameters
 
@@ -200,7 +202,32 @@ FLAGS = (
                                              "registration, the flatfield estimate and every tile filter see them; a supplied "
                                              "flatfield is taken to be in corrected geometry; writes "
                                              "<region>_stitched_distortion.json.  0 = off")),
+    (('--channel-shift',), dict(nargs=3, action='append', default=None, metavar=('NAME', 'DY', 'DX'),
+                                help="align the tiles of output channel NAME (an RGB file's are <base>_R, <base>_G, <base>_B) to "
+                                     "the other channels: a point imaged at (y, x) in the reference channel and at (y + DY, "
+                                     "x + DX) in channel NAME is put right by --channel-shift NAME DY DX -- the output at (y, x) "
+                                     "takes the input at (y + DY, x + DX), bilinearly with 8 fractional bits and replicated "
+                                     "edges, exact in integers.  DY and DX are plain decimal numbers of pixels in -64..64, "
+                                     "rounded to 1/256 pixel (find them with tools/channel_shift_scan.py); repeatable, a name "
+                                     "once.  A run equals a run without the flag on a folder whose files of the shifted channels "
+                                     "were translated beforehand, byte for byte in every store, sidecar and picture.  The tiles "
+                                     "are shifted on the device after --distortion-correction and before --tile-binning, in "
+                                     "sensor pixels; with -r the registration channel takes no shift, with --dpc neither DPC "
+                                     "nor its half-pupil channels do; a supplied flatfield is taken to be in shifted geometry; "
+                                     "writes <region>_stitched_channel_shift.json")),
 )
+
+
+def channel_shifts_of(entries):
+    """--channel-shift NAME DY DX, as often as given -> {NAME: (Sy, Sx)} in 1/256 pixel (None when the flag is absent)."""
+    if not entries:
+        return None
+    shifts = {}
+    for name, dy, dx in entries:
+        if name in shifts:
+            raise ValueError(f"--channel-shift: channel {name!r} is given twice")
+        shifts[name] = (channelshift.parse_pixels(dy), channelshift.parse_pixels(dx))
+    return shifts
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -281,7 +308,8 @@ def main(argv=None):
                             dpc_gain=args.dpc_gain,
                             tile_binning=args.tile_binning,
                             tile_binning_method=args.tile_binning_method,
-                            distortion_correction=args.distortion_correction)
+                            distortion_correction=args.distortion_correction,
+                            channel_shifts=channel_shifts_of(args.channel_shift))
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

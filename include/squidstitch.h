@@ -534,6 +534,40 @@ int sq_warp_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t 
                   int32_t dtype, int32_t ppm, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Constant sub-pixel translation of tile planes (--channel-shift; extension: the reference has nothing like it).  For each of
+ * n_images planes I [h, w] (SQ_U8 / SQ_U16; h, w <= SQ_SHIFT_MAX_SIDE) and a pair S = (Sy, Sx) of integers in 1/256 pixel, each
+ * in -SQ_SHIFT_MAX..SQ_SHIFT_MAX (+-64 pixels), OUT OF PLACE:
+ *     U = w - 1, V = h - 1, for the output pixel (y, x):
+ *       Y = clamp(256*y + Sy, 0, 256*V),  X = clamp(256*x + Sx, 0, 256*U)           (edges replicated)
+ *       y0 = Y >> 8, fy = Y & 255, y1 = min(y0 + 1, V);   x0, fx, x1 likewise
+ *       out(y, x) = ( I[y0,x0]*(256-fx)*(256-fy) + I[y0,x1]*fx*(256-fy)
+ *                   + I[y1,x0]*(256-fx)*fy       + I[y1,x1]*fx*fy + 32768 ) >> 16
+ * i.e. the output at (y, x) takes the input at (y + Sy/256, x + Sx/256), bilinearly with 8 fractional bits: the blend of
+ * sq_warp_tiles under another map.  S = (0, 0) is an exact copy, a shift by whole pixels a copy with replicated edges.  The
+ * definition is the numpy restatement in tests/shift_ref.py, and the result is bit for bit that on every input.
+ * shifts_host is a HOST table of n_images / images_per_shift pairs (Sy, Sx), read before the call returns: images
+ * [k * images_per_shift, (k + 1) * images_per_shift) take pair k, and n_images must be a multiple of images_per_shift >= 1.
+ * One grid is issued per maximal run of consecutive equal pairs (a run of (0, 0) goes through the same kernel as a copy), each
+ * split at 65535 planes, so no table goes to the device.  The planes a plane stride and the rows a pitch apart (elements; both
+ * pitches >= w), src and dst each with their own -- the conventions of sq_despeckle_tiles: no alignment asked of a base or a
+ * pitch beyond the element's own.  dst [n_images][h][w] must not meet src.  Every output element is written exactly once,
+ * nothing outside h x w of a destination plane is written, and every tap lies inside its source plane (csrc/shift.hip: a
+ * thread owns 16 bytes of dst columns and walks down SQ_SHIFT_ROWS_PER_THREAD rows, every source row is read once per run).
+ * No scratch, no allocation, no atomics; asynchronous on `stream`; deterministic.  SQ_ERR_INVALID, and nothing is launched,
+ * for an unknown dtype, a shift outside its range, h or w < 1, a pitch below the width, a plane stride smaller than a plane,
+ * a NULL or element-misaligned pointer, a NULL table, n_images < 0 or no multiple of images_per_shift, extents beyond the
+ * address space, and src and dst extents (first to last element of all planes) that overlap.  SQ_ERR_UNSUPPORTED for a side
+ * above SQ_SHIFT_MAX_SIDE.  n_images == 0 is SQ_OK, also with a NULL table.  (Added without a change of SQ_VERSION: every
+ * caller built against 108 still links and runs.)
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_SHIFT_MAX 16384
+#define SQ_SHIFT_MAX_SIDE 65535
+#define SQ_SHIFT_ROWS_PER_THREAD 32
+int sq_shift_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h, int32_t w,
+                   int64_t src_plane_stride, int64_t src_pitch, int64_t dst_plane_stride, int64_t dst_pitch,
+                   int32_t dtype, const int32_t *shifts_host, int32_t images_per_shift, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
