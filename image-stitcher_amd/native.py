@@ -166,6 +166,8 @@ EXPORTS = {
                                 C.c_int32, C.c_int32, C.c_void_p]),
     'sq_shift_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
+    'sq_affine_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1592,6 +1594,73 @@ def shift_tiles(tiles, shifts, out=None, stream=None):
         _check(lib().sq_shift_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                     dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), host,
                                     n_images // len(pairs), _stream_ptr(stream)), 'sq_shift_tiles')
+    return out
+
+
+SQ_AFFINE_MAX_PPM = 50000
+SQ_AFFINE_MAX_SIDE = 65535
+SQ_AFFINE_PLANES_PER_THREAD = 16
+
+
+def affine_tiles(tiles, params, out=None, stream=None):
+    """Affine map about the plane's centre, composed with a constant shift, of every H x W plane of ``tiles`` into ``out``
+    (sq_affine_tiles; an extension, the reference has nothing like it): the output at centre + p takes the input at centre +
+    (1 + A 10^-6) p + S/256, bilinearly with 8 fractional bits and replicated edges, exact in integers --
+    ``tests/affine_ref.affine_image``; the formula stands in include/squidstitch.h.  With A = 0 it is ``shift_tiles``.  The map is
+    out of place: ``tiles`` is left as it is.
+
+    tiles:  uint8 / uint16 device tensor [..., H, W], H and W at most 65535, with unit-stride rows (any row pitch) whose
+            leading dimensions are one uniform plane stride apart: a contiguous stack, or a view such as every other plane of
+            one.
+    params: one six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx) of integers -- S in 1/256 pixel, each in -16384..16384, A in parts per
+            million, each in -50000..50000 -- for every plane, or a sequence of one six-tuple per index of the leading dimension
+            (all planes under that index take it).  All zero gives an exact copy.
+    out:    a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
+            shares no memory with ``tiles``; allocated contiguous when None.
+    Returns ``out``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    try:
+        tuples = list(params)
+    except TypeError:
+        raise ValueError(f"params must be a six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx) or a sequence of them, got {params!r}")
+    if len(tuples) == 6 and not any(isinstance(v, (list, tuple, np.ndarray)) for v in tuples):
+        tuples = [tuples]      # one tuple for every plane
+    elif tiles.dim() < 3 or len(tuples) != tiles.shape[0]:
+        raise ValueError(f"params must be one six-tuple, or one per index of the leading dimension "
+                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(tuples)}")
+    table = []
+    for entry in tuples:
+        if isinstance(entry, (str, bytes)) or not hasattr(entry, '__len__') or len(entry) != 6:
+            raise ValueError(f"a parameter set is a six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx), got {entry!r}")
+        table += [_int_in(v, -SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)') for v in entry[:2]]
+        table += [_int_in(v, -SQ_AFFINE_MAX_PPM, SQ_AFFINE_MAX_PPM, 'channel affine coefficient (ppm)') for v in entry[2:]]
+    src = _plane_layout(tiles, 'tiles')
+    n_images, h, w, src_plane_stride, src_pitch = src
+    if h > SQ_AFFINE_MAX_SIDE or w > SQ_AFFINE_MAX_SIDE:
+        raise ValueError(f"planes of {h} x {w} have a side above {SQ_AFFINE_MAX_SIDE}")
+    shape = tuple(tiles.shape)
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
+            if stream is not None:
+                out.record_stream(stream)
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
+            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
+        dst = _plane_layout(out, 'out')
+        n_out, _, _, dst_plane_stride, dst_pitch = dst
+        assert n_out == n_images
+        if n_images == 0:
+            return out
+        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
+            raise ValueError("out shares memory with tiles: the map is out of place")
+        host = (C.c_int32 * len(table))(*table)
+        _check(lib().sq_affine_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
+                                     dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), host,
+                                     n_images // len(tuples), _stream_ptr(stream)), 'sq_affine_tiles')
     return out
 
 

@@ -32,7 +32,7 @@ try:
 except Exception:   # pragma: no cover
     psutil = None      # stitch_planes then assumes 8 GiB of free host memory
 
-from . import alignment, binning, channelshift, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
+from . import alignment, binning, channelaffine, channelshift, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -84,7 +84,7 @@ class Stitcher:
                  dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
                  seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
                  tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0,
-                 channel_shifts=None):
+                 channel_shifts=None, channel_affines=None):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -289,6 +289,17 @@ class Stitcher:
         # synchronised or parsed differently.
         self.channel_shifts = channelshift.check_option(channel_shifts)
         self._channel_shift_index: Dict[int, Tuple[int, int]] = {}      # output channel index -> pair, once the names are known
+        # Extension: channel_affines={output channel name: (Ayy, Ayx, Axy, Axx)}, Python ints in parts per million within
+        # -50000..50000, adds the linear term to the channel's shift: the output at centre + p takes the input at centre +
+        # (1 + A 10^-6) p + S/256, one map, with the shift's blend, exact in integers (channelaffine.py; tests/affine_ref.py) --
+        # a second camera that is not mounted square (rotation by t: Ayy = Axx = (cos t - 1) 10^6, Ayx = -Axy = sin t 10^6) or a
+        # channel that is magnified differently (m: Ayy = Axx = (m - 1) 10^6).  The contract, the order (correct, shift + affine,
+        # bin), the channels that take none and the readers that map on the host are those of channel_shifts; a channel may have
+        # a shift, an affine, or both.  The staged tiles go through sq_affine_tiles, one launch per chunk that holds a plane with
+        # a non-zero A in the place of the shift's.  None, empty or all zero: nothing is launched, allocated, written,
+        # synchronised or parsed differently.
+        self.channel_affines = channelaffine.check_option(channel_affines)
+        self._channel_affine_index: Dict[int, Tuple[int, int, int, int]] = {}
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -511,6 +522,8 @@ class Stitcher:
             self._dpc_index = self.monochrome_channels.index(native.DPC_CHANNEL)
         if self.channel_shifts:
             self._resolve_channel_shifts()
+        if self.channel_affines:
+            self._resolve_channel_affines()
         if self.focus_guide_channel is not None:
             if self.focus_guide_channel not in self.monochrome_channels:
                 raise ValueError(f"focus_guide_channel {self.focus_guide_channel!r} is not a channel of this acquisition: "
@@ -600,6 +613,45 @@ class Stitcher:
             + f" ({self.file_height} x {self.file_width}; bilinear, 8 fractional bits, edges replicated; after the distortion "
               f"correction, before the binning)")
 
+    def _resolve_channel_affines(self) -> None:
+        """--channel-affine once the output channels are known, under the refusals of --channel-shift: every name is an output
+        channel, none is the registration channel's (with registration on) or one --dpc reads or derives; the coefficients by
+        channel index, and the run's one printed line."""
+        for name in self.channel_affines:
+            if name not in self.monochrome_channels:
+                raise ValueError(f"channel_affines: {name!r} is not a channel of this acquisition: {self.monochrome_channels}")
+        if self.use_registration:
+            reg = self.registration_channel if self.registration_channel in self.channel_names else self.channel_names[0]
+            for name in self._colour_planes(reg):
+                if name in self.channel_affines:
+                    raise ValueError(f"channel_affines: {name!r} is the registration channel {reg!r}, the frame the other "
+                                     f"channels are moved into: it takes no map")
+        if self.dpc:
+            for name in (native.DPC_CHANNEL,) + tuple(self.dpc_channels):
+                if name in self.channel_affines:
+                    raise ValueError(f"channel_affines: {name!r} is a channel --dpc reads or derives; both halves come through "
+                                     f"the same optics and take no map")
+        self._channel_affine_index = {self.monochrome_channels.index(name): a for name, a in self.channel_affines.items()}
+        print("[channel-affine] tiles of " + ", ".join(
+            f"{name} sampled at centre + (1 + 1e-6 [[{a[0]}, {a[1]}], [{a[2]}, {a[3]}]]) p" + (
+                " + (y {:+.4f}, x {:+.4f}) px".format(*(v / 256 for v in self.channel_shifts[name]))
+                if name in self.channel_shifts else "")
+            for name, a in sorted(self.channel_affines.items()))
+            + f" ({self.file_height} x {self.file_width}; bilinear, 8 fractional bits, edges replicated; after the distortion "
+              f"correction, before the binning)")
+
+    def _file_channel_affine(self, channel):
+        """(S, A) of the files of ``channel`` -- for an RGB file a triple each -- or None when none of its planes has a non-zero
+        A (then ``_file_channel_shift`` says what happens to the file)."""
+        if not self.channel_affines or channel is None:
+            return None
+        names = self._colour_planes(channel)
+        coeffs = [self.channel_affines.get(name, channelaffine.ZERO) for name in names]
+        if not any(a != channelaffine.ZERO for a in coeffs):
+            return None
+        pairs = [self.channel_shifts.get(name, (0, 0)) for name in names]
+        return (pairs[0], coeffs[0]) if len(names) == 1 else (pairs, coeffs)
+
     def _file_channel_shift(self, channel):
         """(Sy, Sx) of the files of ``channel`` -- for an RGB file a triple each -- or None when none of its planes is shifted."""
         if not self.channel_shifts or channel is None:
@@ -611,12 +663,15 @@ class Stitcher:
 
     def _read_tile_file(self, path, channel=None):
         """One tile file of ``channel`` as the run sees it: corrected (--distortion-correction) first, shifted (--channel-shift)
-        second, binned (--tile-binning) third, on the host with the integer arithmetic of the device launches; the file itself
+        or mapped (--channel-affine, with the shift in one map) second, binned (--tile-binning) third, on the host with the integer arithmetic of the device launches; the file itself
         without the options."""
-        shift = self._file_channel_shift(channel)
-        if not self.distortion_correction and shift is None:
+        affine = self._file_channel_affine(channel)
+        shift = self._file_channel_shift(channel) if affine is None else None
+        if not self.distortion_correction and shift is None and affine is None:
             return binning.read_binned(path, self.tile_binning, self.tile_binning_method)
         img = distortion.read_warped(path, self.distortion_correction)
+        if affine is not None:      # the shift and the linear term are one map
+            img = channelaffine.affine_image(img, *affine)
         if shift is not None:
             img = channelshift.shift_image(img, *shift)
         return img if self.tile_binning == 1 else binning.bin_image(img, self.tile_binning, self.tile_binning_method)
@@ -1216,7 +1271,8 @@ class Stitcher:
                           dpc_gain=self.dpc_gain, despeckle=self.despeckle, despeckle_threshold=self.despeckle_threshold,
                           tophat_radius=self.background_radius if self.background_subtract == 'tophat' else None,
                           seam_qc_radius=self.seam_qc_radius, file_shape=(fh, fw), tile_shape=(th, tw), dtype=self.dtype,
-                          channel_shifts=self._channel_shift_index, num_z=self.num_z)
+                          channel_shifts=self._channel_shift_index, num_z=self.num_z,
+                          channel_affines=self._channel_affine_index)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1512,6 +1568,20 @@ class Stitcher:
                 'tile_shape': [self.file_height, self.file_width], 'edges': 'replicated',
                 'interpolation': 'bilinear, 8 fractional bits',
                 'order': 'after the distortion correction, before the binning',
+                'applies_to': 'every tile of the named channels, before placement, the flatfield estimate and every tile filter'})
+        if self._channel_affine_index:
+            fh, fw = self.file_height, self.file_width
+            channels = {}
+            for name, a in sorted(self.channel_affines.items()):
+                sy, sx = self.channel_shifts.get(name, (0, 0))
+                dv, du = channelaffine.max_displacement(fh, fw, (sy, sx), a)
+                channels[name] = {'affine_ppm': list(a), 'shift_256': [sy, sx], 'max_abs_dv_256': dv, 'max_abs_du_256': du}
+            self._write_note(timepoint, region, 'channel_affine', {
+                'channels': channels,
+                'definition': 'the output at centre + p takes the input at centre + (1 + A 1e-6) p + S/256, '
+                              'A = [[Ayy, Ayx], [Axy, Axx]] in parts per million, p = (y, x)',
+                'tile_shape': [fh, fw], 'edges': 'replicated', 'interpolation': 'bilinear, 8 fractional bits',
+                'order': 'after the distortion correction, before the binning; one map with the channel shift',
                 'applies_to': 'every tile of the named channels, before placement, the flatfield estimate and every tile filter'})
         if self.tile_binning > 1:
             k = self.tile_binning

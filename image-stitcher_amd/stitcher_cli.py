@@ -14,14 +14,15 @@ well every pair of overlapping tiles agrees where it is placed, on every (channe
 at which it would agree best.  ``--tile-binning`` and ``--tile-binning-method`` stitch K x K binned tiles, binned on the device
 before anything else sees them.  ``--distortion-correction`` removes radial lens distortion from every tile, on the device, in
 front of all of that.  ``--channel-shift NAME DY DX`` (repeatable) moves every tile of one channel by a constant sub-pixel
-translation, on the device, between the two, so that channels that are not registered to each other on the sensor line up.
+translation, on the device, between the two, so that channels that are not registered to each other on the sensor line up;
+``--channel-affine NAME AYY AYX AXY AXX`` (repeatable) adds the linear term -- rotation, scale, shear about the tile centre -- to it.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
 import argparse
 import sys
 
-from . import channelshift
+from . import channelaffine, channelshift
 from .stitcher import Stitcher
 from .stitcher_parameters import StitchingParameters
 
@@ -215,6 +216,17 @@ FLAGS = (
                                      "sensor pixels; with -r the registration channel takes no shift, with --dpc neither DPC "
                                      "nor its half-pupil channels do; a supplied flatfield is taken to be in shifted geometry; "
                                      "writes <region>_stitched_channel_shift.json")),
+    (('--channel-affine',), dict(nargs=5, action='append', default=None, metavar=('NAME', 'AYY', 'AYX', 'AXY', 'AXX'),
+                                 help="rotate, scale or shear the tiles of output channel NAME about the tile centre, together "
+                                      "with its --channel-shift: the output at centre + p takes the input at centre + "
+                                      "(1 + A 1e-6) p + (DY, DX), A = [[AYY, AYX], [AXY, AXX]], p = (y, x), bilinearly with 8 "
+                                      "fractional bits and replicated edges, exact in integers.  The four coefficients are plain "
+                                      "integers in parts per million, -50000..50000 (find them with "
+                                      "tools/channel_affine_scan.py): a rotation by t is AYY = AXX = (cos t - 1) 1e6, AYX = -AXY "
+                                      "= sin t 1e6; a magnification m is AYY = AXX = (m - 1) 1e6.  Repeatable, a name once; a "
+                                      "channel may have a shift, an affine, or both.  Everything else is --channel-shift's: the "
+                                      "contract, the order, the channels that take none; writes "
+                                      "<region>_stitched_channel_affine.json")),
 )
 
 
@@ -228,6 +240,19 @@ def channel_shifts_of(entries):
             raise ValueError(f"--channel-shift: channel {name!r} is given twice")
         shifts[name] = (channelshift.parse_pixels(dy), channelshift.parse_pixels(dx))
     return shifts
+
+
+def channel_affines_of(entries):
+    """--channel-affine NAME AYY AYX AXY AXX, as often as given -> {NAME: (Ayy, Ayx, Axy, Axx)} in parts per million (None when
+    the flag is absent)."""
+    if not entries:
+        return None
+    affines = {}
+    for name, *coeffs in entries:
+        if name in affines:
+            raise ValueError(f"--channel-affine: channel {name!r} is given twice")
+        affines[name] = tuple(channelaffine.parse_ppm(c) for c in coeffs)
+    return affines
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -309,7 +334,8 @@ def main(argv=None):
                             tile_binning=args.tile_binning,
                             tile_binning_method=args.tile_binning_method,
                             distortion_correction=args.distortion_correction,
-                            channel_shifts=channel_shifts_of(args.channel_shift))
+                            channel_shifts=channel_shifts_of(args.channel_shift),
+                            channel_affines=channel_affines_of(args.channel_affine))
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -12,7 +12,7 @@ BUFFERS = (('ingest', 'file', 'chunk', None),                  # the raw tiles: 
            ('dpc', 'file', 'derived', None),                   # the raw right halves: the ring's, too
            ('distortion', 'file', 'chunk', 'warped'),          # the corrected copy of the staged planes
            ('distortion-dpc', 'file', 'derived', 'warped'),    # ... and of the right halves
-           ('shift', 'file', 'chunk', 'shifted'),              # the shifted copy of the staged planes (--channel-shift)
+           ('shift', 'file', 'chunk', 'shifted'),              # the shifted copy of the staged planes (--channel-shift, --channel-affine)
            ('binning', 'tile', 'chunk', 'binned'),             # the binned copy of the staged planes
            ('binning-dpc', 'tile', 'derived', 'binned'),       # ... and of the right halves
            ('despeckle', 'tile', 'chunk', 'despeckled'),       # the despeckle's destination
@@ -21,15 +21,19 @@ RING = ('ingest', 'dpc')      # per ingest slot: (pinned staging, device mirrors
 WRITER = ('ingest', 'distortion', 'shift', 'binning')          # what the stream writer's batch is sized by
 
 
-def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None, shifts=None, shifted=None):
+def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None, shifts=None, shifted=None, channel_affines=None):
     """The head of every way tiles reach the device -- the staged planes, the right halves, registration's stack: corrected
     first (in sensor pixels), binned second, into the first planes of ``warped`` / ``binned`` where they are given.  Between
     the two, ``shifts`` (one (Sy, Sx) per plane of ``tiles``, --channel-shift; None: no launch) moves the planes into
-    ``shifted``: the right halves and registration's stack pass none."""
+    ``shifted``, or ``channel_affines`` (one (Sy, Sx, Ayy, Ayx, Axy, Axx) per plane, --channel-affine composed with the plane's
+    shift; None: no launch) maps them there in ONE launch that takes the place of the shift's: the right halves and
+    registration's stack pass neither."""
     m = len(tiles)
     if ppm:
         tiles = native.warp_tiles(tiles, ppm, out=None if warped is None else warped[:m])
-    if shifts is not None:
+    if channel_affines is not None:
+        tiles = native.affine_tiles(tiles, channel_affines, out=None if shifted is None else shifted[:m])
+    elif shifts is not None:
         tiles = native.shift_tiles(tiles, shifts, out=None if shifted is None else shifted[:m])
     if factor > 1:
         tiles = native.bin_tiles(tiles, factor, method, out=None if binned is None else binned[:m])
@@ -38,19 +42,23 @@ def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None, shifts=No
 
 class TileChain:
     def __init__(self, *, distortion_ppm, binning, binning_method, dpc_planes, dpc_gain, despeckle, despeckle_threshold,
-                 tophat_radius, seam_qc_radius, file_shape, tile_shape, dtype, channel_shifts=None, num_z=1):
+                 tophat_radius, seam_qc_radius, file_shape, tile_shape, dtype, channel_shifts=None, num_z=1,
+                 channel_affines=None):
         """``dpc_planes``: the derived channel's plane ids (empty without --dpc); ``tophat_radius``: None without the top-hat;
         ``file_shape`` / ``tile_shape``: (fh, fw) of the files and (th, tw) behind the binning (the same without it);
         ``channel_shifts``: {channel index: (Sy, Sx)} in 1/256 pixel (--channel-shift; None or empty: off), the channel of plane
-        id p being p // ``num_z``."""
+        id p being p // ``num_z``; ``channel_affines``: {channel index: (Ayy, Ayx, Axy, Axx)} in parts per million
+        (--channel-affine; None or empty: off)."""
         self.channel_shifts, self.num_z = dict(channel_shifts or {}), int(num_z)
+        self.channel_affines = dict(channel_affines or {})
         self.ppm, self.factor, self.method = distortion_ppm, binning, binning_method
         self.dpc_planes, self.dpc_gain = dpc_planes, dpc_gain
         self.despeckle, self.despeckle_threshold = despeckle, despeckle_threshold
         self.tophat_radius, self.seam_qc_radius = tophat_radius, seam_qc_radius
         self.shapes = {'file': tuple(file_shape), 'tile': tuple(tile_shape)}
         self.dtype = np.dtype(dtype)
-        on = {None: True, 'warped': distortion_ppm != 0, 'shifted': bool(self.channel_shifts), 'binned': binning > 1,
+        on = {None: True, 'warped': distortion_ppm != 0, 'shifted': bool(self.channel_shifts or self.channel_affines),
+              'binned': binning > 1,
               'despeckled': despeckle != 'none',
               'tophat': tophat_radius is not None}
         self.buffers = [b[:3] for b in BUFFERS if on[b[3]]]
@@ -112,6 +120,15 @@ class TileChain:
         pairs = [self.channel_shifts.get(p // self.num_z, (0, 0)) for p in plane_ids or ()]
         return pairs if any(pair != (0, 0) for pair in pairs) else None
 
+    def plane_affines(self, plane_ids):
+        """One (Sy, Sx, Ayy, Ayx, Axy, Axx) per plane of ``plane_ids`` -- its shift or (0, 0), its A or zeros -- or None when
+        none of them has a non-zero A (then the chunk goes today's way: ``plane_shifts``)."""
+        zero = (0, 0, 0, 0)
+        channels = [p // self.num_z for p in plane_ids or ()]
+        if not any(self.channel_affines.get(c, zero) != zero for c in channels):
+            return None
+        return [tuple(self.channel_shifts.get(c, (0, 0))) + tuple(self.channel_affines.get(c, zero)) for c in channels]
+
     def run(self, tiles, slot, derived, b0, bufs, list_counts=None, qc_words=None, seam_table=None, seam_words=None,
             plane_ids=None):
         """The staged planes ``tiles`` [m, n, fh, fw] of the chunk in ring slot ``slot`` (their copy enqueued) -> the planes
@@ -119,11 +136,14 @@ class TileChain:
         pinned 'dpc' buffer; ``b0``: the chunk's first row in the list-wide outputs ``list_counts``, ``qc_words`` and
         ``seam_words`` (each None when its option is off); ``plane_ids``: the chunk's plane ids (--channel-shift: a chunk with
         a shifted plane is ONE shift launch over the whole chunk, which copies its unshifted planes; a chunk without one
-        launches nothing).  The order is fixed."""
+        launches nothing; --channel-affine: a chunk with a plane whose A is not zero is ONE affine launch over the whole chunk
+        in the shift launch's place, every plane under its shift and its A).  The order is fixed."""
         import torch
         m = len(tiles)
+        affines = self.plane_affines(plane_ids) if self.channel_affines else None
+        shifts = self.plane_shifts(plane_ids) if self.channel_shifts and affines is None else None
         tiles = warp_and_bin(tiles, self.ppm, self.factor, self.method, bufs.get('distortion'), bufs.get('binning'),
-                             self.plane_shifts(plane_ids) if self.channel_shifts else None, bufs.get('shift'))
+                             shifts, bufs.get('shift'), affines)
         if derived:     # in place over the left halves, before anything reads the staged planes
             i0, i1 = derived[0], derived[-1] + 1
             staging, on_dev, read, _ = bufs['dpc']

@@ -568,6 +568,42 @@ int sq_shift_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t
                    int32_t dtype, const int32_t *shifts_host, int32_t images_per_shift, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-channel affine map of tile planes: rotation, scale and shear about the tile centre, composed with a constant shift
+ * (--channel-affine; extension: the reference has nothing like it).  For each of n_images planes I [h, w] (SQ_U8 / SQ_U16; h, w <=
+ * SQ_AFFINE_MAX_SIDE), S = (Sy, Sx) in 1/256 pixel, each in -SQ_SHIFT_MAX..SQ_SHIFT_MAX, and A = (Ayy, Ayx, Axy, Axx), integers in
+ * parts per million, each in -SQ_AFFINE_MAX_PPM..SQ_AFFINE_MAX_PPM, OUT OF PLACE, with // the floor division:
+ *     U = w - 1, V = h - 1, for the output pixel (y, x):
+ *       u = 2*x - U,  v = 2*y - V                                   (half-pixels from the tile centre)
+ *       dv = Sy + (16*(Ayy*v + Ayx*u) + 62500) // 125000            (1/256 pixel, rounded half up: 128/10^6 = 16/125000)
+ *       du = Sx + (16*(Axy*v + Axx*u) + 62500) // 125000
+ *       Y = clamp(256*y + dv, 0, 256*V),  X = clamp(256*x + du, 0, 256*U)        (edges replicated)
+ *       y0 = Y >> 8, fy = Y & 255, y1 = min(y0 + 1, V);   x0, fx, x1 likewise
+ *       out(y, x) = ( I[y0,x0]*(256-fx)*(256-fy) + I[y0,x1]*fx*(256-fy)
+ *                   + I[y1,x0]*(256-fx)*fy       + I[y1,x1]*fx*fy + 32768 ) >> 16
+ * i.e. the output at centre + p takes the input at centre + (1 + A 10^-6) p + S/256, bilinearly with 8 fractional bits: the blend
+ * of sq_shift_tiles under another map, and with A = 0 that function's result.  A rotation by t is Ayy = Axx = (cos t - 1) 10^6,
+ * Ayx = -Axy = sin t 10^6; a magnification m is Ayy = Axx = (m - 1) 10^6.  The numerators need 64 bits (up to 1.05e11 at the
+ * largest side).  The definition is the numpy restatement in tests/affine_ref.py, and the result is bit for bit that on every input.
+ * params_host is a HOST table of n_images / images_per_param six-tuples (Sy, Sx, Ayy, Ayx, Axy, Axx), read before the call
+ * returns: images [k * images_per_param, (k + 1) * images_per_param) take tuple k, and n_images must be a multiple of
+ * images_per_param >= 1.  One grid is issued per maximal run of consecutive equal tuples (a run of zeros goes through the same
+ * kernel as a copy), each split at 65535 * SQ_AFFINE_PLANES_PER_THREAD planes, so no table goes to the device.  Every other
+ * convention is that of sq_shift_tiles: planes a plane stride and rows a pitch apart (elements; both pitches >= w), no alignment
+ * asked of a base or a pitch beyond the element's own; dst must not meet src; every output element is written exactly once,
+ * nothing outside h x w of a destination plane is written, and every tap lies inside its source plane (csrc/affine.hip: a thread
+ * owns 16 bytes of dst columns of one row, steps the map along them without a division per pixel and walks over
+ * SQ_AFFINE_PLANES_PER_THREAD planes with it; the taps of a vector come as 16-byte loads of two or three source rows).  No
+ * scratch, no allocation, no atomics; asynchronous on `stream`; deterministic.  The refusals and return codes of sq_shift_tiles,
+ * plus SQ_ERR_INVALID for a coefficient outside its range.  (Added without a change of SQ_VERSION.)
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_AFFINE_MAX_PPM 50000
+#define SQ_AFFINE_MAX_SIDE 65535
+#define SQ_AFFINE_PLANES_PER_THREAD 16
+int sq_affine_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h, int32_t w,
+                    int64_t src_plane_stride, int64_t src_pitch, int64_t dst_plane_stride, int64_t dst_pitch,
+                    int32_t dtype, const int32_t *params_host, int32_t images_per_param, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
