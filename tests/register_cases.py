@@ -88,6 +88,94 @@ BATCH_PATHS = {
 }
 
 
+def batch_case(n_pairs, n0, n1, path, holds, dtype='uint16', u=10):
+    """A batch of n_pairs crops from batch_inputs (12 tiles, 32 rows and 52 columns of room, real min-max).  `holds`:
+    what the case is there for beyond the `path` keys, as (what, predicate of the describe struct) -- the crossing of a
+    launch choice with the batch, which assert_path checks too."""
+    name = f'{n_pairs}x{n0}x{n1}' + ('-uint8' if dtype == 'uint8' else '') + (f'-u{u}' if u != 10 else '')
+    return dict(name=name, n_pairs=n_pairs, n0=n0, n1=n1, u=u, dtype=dtype, path=path, holds=holds)
+
+
+def _blocks(d):
+    return d['grid_col'][0] * d['grid_col'][1]
+
+
+def _spans(share):
+    """The column-block remap works within spans of 8 * share blocks, which cross pair boundaries."""
+    return [(f'share {share}: a span of {8 * share} column blocks crosses pairs', lambda d: 8 * share > d['grid_col'][0] and _blocks(d) >= 8 * share)]
+
+
+def _tail(share):
+    """... and the blocks after the last whole span are left unmapped."""
+    return _spans(share) + [('a tail of column blocks is left unmapped', lambda d: _blocks(d) % (8 * share) != 0)]
+
+
+def _partial_rows(n0):
+    """The last block of both row kernels has fewer lines than the others; an odd n0's last line repeats its row."""
+    return [('the last forward block is partial', lambda d: d['rl_fwd'] > 1 and n0 % d['rl_fwd'] != 0),
+            ('the last inverse block is partial', lambda d: d['rl_inv'] > 1 and ((n0 + 1) // 2) % d['rl_inv'] != 0)]
+
+
+_ODD = [('odd n0, several row pairs per block', lambda d: d['rl_inv'] > 1)]
+_MIXED = dict(DIRECT, gen0=True, gen1=True)
+_BLUE_BOTH = dict(m0=75, m1=36, long0=False, long1=False, rl_fwd=4, rl_inv=2, columns_single=True, share=8, grid_col=(16, 64))
+
+# Every launch choice that depends on the number of pairs, together with a batch: held to the float64 oracle at TOL by
+# test_batch_paths (tests/test_register_numerics_gpu.py), every pair of every case.  Largest deviation over the pairs
+# of a case measured on an MI355X (the `register-numerics` lines of pytest -s), ccmax as a fraction of its scale under
+# normalisation None and 'phase', the amplitudes relative (the same under both).  The bound stays TOL:
+#   case               ccmax None  ccmax phase  amplitude  |  case               ccmax None  ccmax phase  amplitude
+#   96x45x36            1.4e-15     4.2e-16     9.4e-16    |  5x521x26            9.0e-16     2.9e-16     7.5e-16
+#   64x45x36-uint8      1.8e-15     1.4e-16     6.7e-16    |  40x32x4861          1.3e-14     1.5e-15     5.3e-15
+#   64x34x17            1.6e-15     1.3e-14     9.1e-16    |  16x4862x64          1.9e-15     3.8e-16     1.6e-15
+#   64x34x17-uint8      1.6e-15     1.3e-15     8.2e-16    |  6x16x4861-uint8     6.2e-15     4.7e-16     2.5e-15
+#   130x32x97           2.5e-15     7.3e-16     1.4e-15    |  130x250x36          1.7e-15     4.1e-16     1.0e-15
+#   5x512x16            1.0e-15     2.3e-16     8.1e-16    |  8x64x64-u100        6.5e-16     5.6e-16     8.4e-16
+#   5x256x32            8.3e-16     2.3e-16     1.0e-15    |  24x250x20-u4        1.1e-15     3.6e-16     5.4e-16
+#   5x4620x16           2.2e-15     3.0e-16     6.5e-16    |  24x45x36-u1         1.4e-16     2.3e-16     8.5e-16
+BATCH_CASES = [
+    # lines per block with a partial last block, odd n0
+    batch_case(96, 45, 36, dict(_MIXED, rl_fwd=8, rl_inv=4, radix0=[3, 3, 5], radix1=[4, 3, 3]), _partial_rows(45) + _ODD),
+    batch_case(64, 45, 36, dict(_MIXED, rl_fwd=4, rl_inv=2), _partial_rows(45) + _ODD, dtype='uint8'),
+    # Bluestein rows with several lines per block, Bluestein columns one per block across pairs
+    batch_case(64, 34, 17, _BLUE_BOTH, _partial_rows(34) + _spans(8)),
+    batch_case(64, 34, 17, _BLUE_BOTH, _partial_rows(34) + _spans(8), dtype='uint8'),
+    batch_case(130, 32, 97, dict(m0=0, m1=200, long1=False, rl_fwd=5, rl_inv=4),
+               [('rl_fwd is no power of two and leaves a partial block', lambda d: d['rl_fwd'] & (d['rl_fwd'] - 1) and 32 % d['rl_fwd'] != 0)]),
+    # the remap of the column blocks across pairs, every share, and one column per block
+    batch_case(5, 512, 16, dict(POW2, tc=1, share=8, grid_col=(16, 5)), _tail(8)),
+    batch_case(5, 256, 32, dict(POW2, tc=2, share=4, grid_col=(12, 5)), _tail(4)),
+    batch_case(5, 4620, 16, dict(DIRECT, columns_single=True, tc=0, share=8, gen0=True, grid_col=(16, 5)), _tail(8)),
+    batch_case(5, 521, 26, dict(m0=1152, m1=0, long0=False, columns_single=True, share=8, rl_fwd=4), _tail(8)),
+    # long lines: more lines than scratch lines, so a workgroup takes several, of different pairs
+    batch_case(40, 32, 4861, dict(m0=0, m1=10240, long0=False, long1=True, grid_fwd=(512, 1), grid_inv=(512, 1)),
+               [('more forward lines than workgroups', lambda d: d['grid_fwd'][0] < 40 * 32),
+                ('more inverse lines than workgroups', lambda d: d['grid_inv'][0] < 40 * 16)]),
+    batch_case(16, 4862, 64, dict(m0=10240, m1=0, long0=True, long1=False, columns_single=True, grid_col=(512, 1),
+                                  upsample_rows=(4, 16), grid_up_rows=(38, 16)),
+               [('more columns than workgroups', lambda d: d['grid_col'][0] < 16 * 33),
+                ('several row blocks of the wide upsampling kernel', lambda d: d['grid_up_rows'][0] > 1)]),
+    batch_case(6, 16, 4861, dict(m0=0, m1=10240, long1=True), [], dtype='uint8'),
+    # the wide upsampling kernel with a partial last row block (125 row pairs: 64 + 61)
+    batch_case(130, 250, 36, dict(DIRECT, upsample_rows=(4, 16), grid_up_rows=(2, 130), tc=4, share=2, grid_col=(6, 130)),
+               [('the last row block of the wide upsampling kernel is partial', lambda d: 125 % 64 != 0 and d['grid_up_rows'][0] == 2)]
+               + _tail(2)),
+    # the other upsample factors
+    batch_case(8, 64, 64, dict(POW2, upsample_rows=(1, 32)), [], u=100),
+    batch_case(24, 250, 20, dict(DIRECT, rl_fwd=8, rl_inv=4, upsample_rows=(1, 32)), _partial_rows(250), u=4),
+    batch_case(24, 45, 36, dict(_MIXED, upsample_rows=None), [], u=1),
+]
+# the four whose pair table test_batch_results_do_not_depend_on_the_position runs reversed as well
+REVERSED_CASES = ('64x34x17', '5x512x16', '40x32x4861', '16x4862x64')
+
+
+def batch_case_inputs(c):
+    """(tiles, pairs, planted) of a BATCH_CASES entry."""
+    dtype = np.dtype(c['dtype'])
+    return batch_inputs(12, c['n0'] + 32, c['n1'] + 52, c['n0'], c['n1'], c['n_pairs'], dtype.type,
+                        seed=91 if dtype == np.uint16 else 102)
+
+
 def describe(c):
     return native.register_describe(c['n_pairs'], c['n0'], c['n1'], c['u'], c['dtype'])
 
@@ -100,6 +188,8 @@ def assert_path(c):
     if c.get('bluestein_long'):
         m = d['m0'] if d['long0'] else d['m1']
         assert m > 9728, f"{c.get('name')}: Bluestein length {m} fits the LDS"
+    for what, holds in c.get('holds', ()):
+        assert holds(d), f"{c.get('name')}: not so: {what} ({d})"
     return d
 
 

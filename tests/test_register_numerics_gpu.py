@@ -112,6 +112,44 @@ def test_batch_of_300_uint8_pairs(norm):
     check(tiles, pairs, c['n0'], c['n1'], c['u'], norm, 'real', label='batch300-uint8')
 
 
+_BATCH_INPUTS, _BATCH_RUNS = {}, {}
+
+
+def _batch_run(c, norm):
+    """(tiles, pairs, results) of a BATCH_CASES entry: inputs made once per case, run once per normalisation, shared by
+    the tests below and never modified."""
+    if c['name'] not in _BATCH_INPUTS:
+        _BATCH_INPUTS[c['name']] = R.batch_case_inputs(c)[:2]
+    tiles, pairs = _BATCH_INPUTS[c['name']]
+    if (c['name'], norm) not in _BATCH_RUNS:
+        _BATCH_RUNS[c['name'], norm] = _run(tiles, pairs, c['n0'], c['n1'], c['u'], norm, 'real')
+    return tiles, pairs, _BATCH_RUNS[c['name'], norm]
+
+
+@pytest.mark.parametrize('norm', NORMS)
+@pytest.mark.parametrize('c', R.BATCH_CASES, ids=[c['name'] for c in R.BATCH_CASES])
+def test_batch_paths(c, norm):
+    """Every launch choice that depends on the number of pairs, in a batch with crop origins and a planted shift per pair
+    and the real min-max table: every pair equal to the oracle in its integers and within TOL in ccmax and amplitudes.
+    (The planted shift is not asserted: crops as small as 34 x 17 need not recover it.)"""
+    R.assert_path(c)
+    tiles, pairs, res = _batch_run(c, norm)
+    assert tiles.dtype == np.dtype(c['dtype']) and len(pairs) == c['n_pairs'] > 1
+    assert (pairs['ref_x0'] % 2 == 1).any() and (pairs['mov_x0'] % 2 == 1).any()
+    check(tiles, pairs, c['n0'], c['n1'], c['u'], norm, 'real', res=res, label='batch-' + c['name'])
+
+
+@pytest.mark.parametrize('norm', NORMS)
+@pytest.mark.parametrize('name', R.REVERSED_CASES)
+def test_batch_results_do_not_depend_on_the_position(name, norm):
+    """The pair table reversed (the same plan: n_pairs is what it was): every pair's bytes are those of its old position,
+    whichever pairs share its block, its span of column blocks or its scratch line."""
+    c = next(c for c in R.BATCH_CASES if c['name'] == name)
+    tiles, pairs, res = _batch_run(c, norm)
+    back = _run(tiles, pairs[::-1].copy(), c['n0'], c['n1'], c['u'], norm, 'real')
+    assert back[::-1].tobytes() == res.tobytes()
+
+
 @pytest.mark.parametrize('norm', NORMS)
 def test_pointer_table_and_second_run_give_the_same_bytes(batch257, norm):
     b, c = batch257, batch257['c']

@@ -128,6 +128,50 @@ def test_every_case_runs_where_it_says():
         R.assert_path(c)
 
 
+def test_every_batch_case_runs_where_it_says():
+    assert len({c['name'] for c in R.BATCH_CASES}) == len(R.BATCH_CASES)
+    assert set(R.REVERSED_CASES) <= {c['name'] for c in R.BATCH_CASES}
+    for c in R.BATCH_CASES:
+        R.assert_path(c)
+
+
+def test_the_batch_table_covers_every_crossing():
+    """Every launch choice that make_plan takes from the number of pairs, met by a case of SEVERAL pairs."""
+    cases = [(c, R.describe(c)) for c in R.BATCH_CASES]
+    assert all(c['n_pairs'] > 1 for c, _ in cases)
+
+    def some(holds):
+        return any(holds(c, d) for c, d in cases)
+
+    def nrp(c):
+        return (c['n0'] + 1) // 2
+    short1 = lambda d: not d['long1']
+    # several lines per block: Bluestein rows, a partial last block, the repeated row of an odd n0, a cap of 5 lines
+    assert some(lambda c, d: d['m1'] > 0 and short1(d) and d['rl_fwd'] > 1 and d['rl_inv'] > 1)
+    assert some(lambda c, d: short1(d) and c['n0'] % d['rl_fwd'] != 0)
+    assert some(lambda c, d: short1(d) and c['n0'] % 2 == 1 and d['rl_inv'] > 1 and nrp(c) % d['rl_inv'] != 0)
+    assert some(lambda c, d: d['rl_fwd'] & (d['rl_fwd'] - 1))
+    # the column-block remap with its tail, in the tc-column kernel and in the one-column kernel
+    blocks = lambda d: d['grid_col'][0] * d['grid_col'][1]
+    for share in (2, 4, 8):
+        assert some(lambda c, d: d['share'] == share and not d['long0'] and blocks(d) >= 8 * share
+                    and blocks(d) % (8 * share) != 0), share
+    assert {d['tc'] for c, d in cases if not d['columns_single'] and blocks(d) % (8 * d['share'])} >= {1, 2, 4}
+    assert some(lambda c, d: d['columns_single'] and not d['long0'] and not d['m0'])
+    assert some(lambda c, d: d['columns_single'] and not d['long0'] and d['m0'])
+    # long lines: a workgroup walks over several
+    assert some(lambda c, d: d['long0'] and c['n_pairs'] * (c['n1'] // 2 + 1) > d['grid_col'][0])
+    assert some(lambda c, d: d['long1'] and c['n_pairs'] * c['n0'] > d['grid_fwd'][0] and c['n_pairs'] * nrp(c) > d['grid_inv'][0])
+    # uint8 on each kind of row transform
+    u8 = lambda c: c['dtype'] == 'uint8'
+    assert some(lambda c, d: u8(c) and d['gen1'] and not d['m1'])
+    assert some(lambda c, d: u8(c) and d['m1'] and short1(d))
+    assert some(lambda c, d: u8(c) and d['long1'])
+    # the wide upsampling kernel over several row blocks, the last one partial; every other upsample factor
+    assert some(lambda c, d: d['upsample_rows'] == (4, 16) and d['grid_up_rows'][0] > 1 and nrp(c) % 64 != 0)
+    assert {c['u'] for c, _ in cases} >= {1, 4, 100}
+
+
 def test_the_case_table_covers_every_path():
     plans = [R.describe(c) for c in R.SINGLE_CASES + list(R.BATCH_PATHS.values())]
     tc_kernel = [d for d in plans if not d['columns_single']]
