@@ -168,6 +168,8 @@ EXPORTS = {
                                  C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
     'sq_affine_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                   C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]),
+    'sq_dark_tiles': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p]),
     'sq_register_line_supported': (C.c_int, [C.c_int32]),
     'sq_register_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'sq_register_pairs': (C.c_int, [C.POINTER(_RegisterArgs), C.c_void_p]),
@@ -1662,6 +1664,69 @@ def affine_tiles(tiles, params, out=None, stream=None):
                                      dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), host,
                                      n_images // len(tuples), _stream_ptr(stream)), 'sq_affine_tiles')
     return out
+
+
+SQ_DARK_IMAGES_PER_THREAD = 1
+DARK_DEFINITION = 'out = clamp(I - D + P, 0, M): D the dark frame (or a constant), P the pedestal, M = the dtype maximum'
+
+
+def dark_tiles(tiles, params, frames=None, pedestal: int = 0, stream=None):
+    """Dark-frame subtraction of every H x W plane of ``tiles``, IN PLACE (sq_dark_tiles; an extension, the reference has none):
+    clamp(I - D + P, 0, M) with M the dtype's maximum, exact in integers -- ``tests/dark_ref.dark_image``; the formula stands in
+    include/squidstitch.h.
+
+    tiles:    uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
+              uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    params:   one pair (k, c) of integers for every plane, or a sequence of one pair per index of the leading dimension (all
+              planes under that index take it): k >= 0 names frame k of ``frames`` (with c == 0), k == -1 the constant c in 0..M.
+              A run of pairs that is the identity (k == -1, c == pedestal) launches nothing.
+    frames:   None, or a device tensor [K, H, W] / [H, W] of the tiles' dtype under the same layout rules that shares no memory
+              with ``tiles``.
+    pedestal: P, an integer in 0..M.
+    Returns ``tiles``."""
+    import torch
+    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
+        raise ValueError("tiles must be a [..., H, W] device tensor")
+    if tiles.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    top = 255 if tiles.dtype == torch.uint8 else 65535
+    pedestal = _int_in(pedestal, 0, top, 'dark pedestal')
+    try:
+        pairs = list(params)
+    except TypeError:
+        raise ValueError(f"params must be a pair (k, c) or a sequence of pairs, got {params!r}")
+    if len(pairs) == 2 and not any(isinstance(v, (list, tuple, np.ndarray)) for v in pairs):
+        pairs = [pairs]      # one pair for every plane
+    elif tiles.dim() < 3 or len(pairs) != tiles.shape[0]:
+        raise ValueError(f"params must be one pair, or one pair per index of the leading dimension "
+                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(pairs)}")
+    n_frames = 0
+    lay_f = None
+    if frames is not None:
+        if not torch.is_tensor(frames) or frames.dim() not in (2, 3) or frames.dtype != tiles.dtype or \
+                frames.device != tiles.device or tuple(frames.shape[-2:]) != tuple(tiles.shape[-2:]):
+            raise ValueError(f"frames must be a {tiles.dtype} tensor [K, {tiles.shape[-2]}, {tiles.shape[-1]}] on the tiles' device")
+        lay_f = _plane_layout(frames, 'frames')
+        n_frames = lay_f[0]
+    table = []
+    for pair in pairs:
+        if len(pair) != 2:
+            raise ValueError(f"a dark param is a pair (k, c), got {pair!r}")
+        k = _int_in(pair[0], -1, n_frames - 1, 'dark frame index')
+        c = _int_in(pair[1], 0, 0 if k >= 0 else top, 'dark constant')
+        table += [k, c]
+    lay = _plane_layout(tiles, 'tiles')
+    n_images, h, w, plane_stride, pitch = lay
+    if n_images == 0:
+        return tiles
+    if lay_f is not None and n_frames and _overlap(_byte_extent(tiles, lay), _byte_extent(frames, lay_f)):
+        raise ValueError("frames shares memory with tiles")
+    host = (C.c_int32 * len(table))(*table)
+    _check(lib().sq_dark_tiles(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
+                               frames.data_ptr() if n_frames else None, n_frames, lay_f[3] if n_frames else 0,
+                               lay_f[4] if n_frames else 0, host, n_images // len(pairs), pedestal, _stream_ptr(stream)),
+           'sq_dark_tiles')
+    return tiles
 
 
 _COPY_STREAMS = {}

@@ -32,7 +32,7 @@ try:
 except Exception:   # pragma: no cover
     psutil = None      # stitch_planes then assumes 8 GiB of free host memory
 
-from . import alignment, binning, channelaffine, channelshift, composite as composite_mod, distortion, native, placement, registration, seamqc, sharding, tileqc
+from . import alignment, binning, channelaffine, channelshift, composite as composite_mod, darkframe, distortion, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
 from .ometiff import write_ome_tiff
@@ -84,7 +84,7 @@ class Stitcher:
                  dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
                  seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
                  tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0,
-                 channel_shifts=None, channel_affines=None):
+                 channel_shifts=None, channel_affines=None, dark_frames=None, dark_pedestal=0):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -300,6 +300,23 @@ class Stitcher:
         # synchronised or parsed differently.
         self.channel_affines = channelaffine.check_option(channel_affines)
         self._channel_affine_index: Dict[int, Tuple[int, int, int, int]] = {}
+        # Extension: dark_frames={output channel name, or '*' for every file channel without an entry of its own: a constant
+        # int, a 2-D array or the path of a .tif / .tiff / .npy of exactly the files' shape and dtype} with dark_pedestal=P
+        # subtracts the camera's additive term from every tile: out = clamp(I - D + P, 0, M), exact in integers (darkframe.py;
+        # tests/dark_ref.py) -- the `I - D` of the flatfield correction (I - D) / F.  A run equals a run without the option on
+        # a folder whose every tile file was subtracted beforehand, byte for byte in every store, sidecar and picture: the
+        # staged tiles and the right halves of --dpc are subtracted on the device (sq_dark_tiles, in place, the first launch of
+        # the chain: in front of the distortion correction, the channel shift / affine and the binning, all in sensor pixels),
+        # registration's stack takes the registration channel's frame, and the readers of single files (get_tile, the
+        # centre-pair registration, the flatfield estimate's samples) subtract on the host.  No file channel is exempt; 'DPC'
+        # is read from no file and takes none.  A supplied flatfield is used as given.  A constant equal to P is the identity
+        # and launches nothing.  None or empty: nothing is launched, allocated, written, synchronised or parsed differently.
+        self.dark_frames, self.dark_pedestal = darkframe.check_option(dark_frames, dark_pedestal)
+        self._dark_host: Dict[str, object] = {}               # output channel name -> int or array, the identities left out
+        self._dark_params: Dict[int, Tuple[int, int]] = {}    # output channel index -> (k, c), the identities left out
+        self._dark_right = None                               # the pair of --dpc's right halves
+        self._dark_stack = None                               # the distinct frames [K, fh, fw], host
+        self._dark_note: Dict[str, dict] = {}                 # file channel name -> what the sidecar says of its frame
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
@@ -524,6 +541,8 @@ class Stitcher:
             self._resolve_channel_shifts()
         if self.channel_affines:
             self._resolve_channel_affines()
+        if self.dark_frames or self.dark_pedestal:
+            self._resolve_dark_frames()
         if self.focus_guide_channel is not None:
             if self.focus_guide_channel not in self.monochrome_channels:
                 raise ValueError(f"focus_guide_channel {self.focus_guide_channel!r} is not a channel of this acquisition: "
@@ -640,6 +659,72 @@ class Stitcher:
             + f" ({self.file_height} x {self.file_width}; bilinear, 8 fractional bits, edges replicated; after the distortion "
               f"correction, before the binning)")
 
+    def _resolve_dark_frames(self) -> None:
+        """--dark-frame once the output channels and the files' shape and dtype are known: every name is a file channel's (or
+        '*'), every frame has exactly the files' shape and dtype, every constant and the pedestal lie in 0..M; the pairs by
+        channel index, the distinct frames as one stack, and the run's one printed line."""
+        pedestal = darkframe.check_pedestal(self.dark_pedestal, self.dtype)
+        if not self.dark_frames:      # a pedestal alone: no channel has a frame it would be added back to
+            return
+        shape = (self.file_height, self.file_width)
+        file_channels = [n for n in self.monochrome_channels if not (self.dpc and n == native.DPC_CHANNEL)]
+        for name in self.dark_frames:
+            if name == native.DPC_CHANNEL and name not in file_channels:
+                raise ValueError(f"dark_frames: {name!r} is read from no file (--dpc derives it from its half-pupil channels, "
+                                 f"which take their frames under their own names): it takes no frame")
+            if name != darkframe.WILDCARD and name not in file_channels:
+                raise ValueError(f"dark_frames: {name!r} is not a channel of this acquisition: {file_channels}")
+        loaded = {name: darkframe.load_frame(source, shape, self.dtype, name) for name, source in self.dark_frames.items()}
+        stack, digests, pairs = [], {}, {}
+        for name in file_channels:
+            key = name if name in loaded else (darkframe.WILDCARD if darkframe.WILDCARD in loaded else None)
+            if key is None:
+                continue
+            frame = loaded[key]
+            self._dark_note[name] = darkframe.frame_note(self.dark_frames[key], frame)
+            if darkframe.is_identity(frame, pedestal):
+                continue
+            self._dark_host[name] = frame
+            if isinstance(frame, int):
+                pairs[name] = (-1, frame)
+            else:
+                digest = self._dark_note[name]['sha256']
+                if digest not in digests:
+                    digests[digest] = len(stack)
+                    stack.append(frame)
+                pairs[name] = (digests[digest], 0)
+        self._dark_stack = np.stack(stack) if stack else None
+        self._dark_params = {self.monochrome_channels.index(name): pair for name, pair in pairs.items()}
+        if self.dpc:      # a derived plane is staged as its left half's file; the right halves have a buffer of their own
+            left, right = self.dpc_channels
+            if left in pairs:
+                self._dark_params[self._dpc_index] = pairs[left]
+            self._dark_right = pairs.get(right)
+        print("[dark-frame] tiles of " + (", ".join(
+            f"{name} minus " + (f"the constant {note['constant']}" if 'constant' in note else
+                                f"{note['path'] or 'an array'} (min {note['min']}, max {note['max']}, mean {note['mean']})")
+            for name, note in sorted(self._dark_note.items()))) +
+            f" plus {pedestal}, clamped to 0..{int(np.iinfo(self.dtype).max)} ({shape[0]} x {shape[1]}; "
+            f"{0 if self._dark_stack is None else len(self._dark_stack)} distinct frames on the device; before every other "
+            f"per-tile step)")
+
+    def _file_channel_dark(self, channel):
+        """The frame of the files of ``channel`` -- for an RGB file a list of three -- or None when none of its planes has one."""
+        if not self._dark_host or channel is None:
+            return None
+        frames = [self._dark_host.get(name) for name in self._colour_planes(channel)]
+        if all(f is None for f in frames):
+            return None
+        return frames[0] if len(frames) == 1 else frames
+
+    def _dark_frames_device(self):
+        """The distinct frames [K, fh, fw] on the device, uploaded once and kept with the cached buffers (None without one)."""
+        if self._dark_stack is None:
+            return None
+        import torch
+        key = ('dark-frames',) + tuple(self._dark_stack.shape) + (self._dark_stack.dtype.str,)
+        return self._cached_buffers(key, lambda: torch.from_numpy(self._dark_stack).to(self.device))
+
     def _file_channel_affine(self, channel):
         """(S, A) of the files of ``channel`` -- for an RGB file a triple each -- or None when none of its planes has a non-zero
         A (then ``_file_channel_shift`` says what happens to the file)."""
@@ -667,9 +752,14 @@ class Stitcher:
         without the options."""
         affine = self._file_channel_affine(channel)
         shift = self._file_channel_shift(channel) if affine is None else None
-        if not self.distortion_correction and shift is None and affine is None:
+        dark = self._file_channel_dark(channel)
+        if dark is not None:      # the sensor's own term first; everything behind it as without the option
+            img = darkframe.dark_image(read_image(path), dark, self.dark_pedestal)
+            img = distortion.warp_image(img, self.distortion_correction) if self.distortion_correction else img
+        elif not self.distortion_correction and shift is None and affine is None:
             return binning.read_binned(path, self.tile_binning, self.tile_binning_method)
-        img = distortion.read_warped(path, self.distortion_correction)
+        else:
+            img = distortion.read_warped(path, self.distortion_correction)
         if affine is not None:      # the shift and the linear term are one map
             img = channelaffine.affine_image(img, *affine)
         if shift is not None:
@@ -861,8 +951,13 @@ class Stitcher:
             with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as pool:
                 images = list(pool.map(one, cells))
             stack = torch.from_numpy(np.ascontiguousarray(np.stack(images))).to(self.device)
-            # the raw stack, corrected and binned by the launches the staged tiles go through
-            return warp_and_bin(stack, self.distortion_correction, self.tile_binning, self.tile_binning_method)
+            # the raw stack, corrected and binned by the launches the staged tiles go through; in front of them the registration
+            # channel's dark frame (of an RGB file: its first colour plane's), in place over this fresh upload
+            dark = self._dark_params.get(self.monochrome_channels.index(self._colour_planes(self.registration_channel)[0])) \
+                if self._dark_params else None
+            return warp_and_bin(stack, self.distortion_correction, self.tile_binning, self.tile_binning_method,
+                                darks=dark, dark_frames=self._dark_frames_device() if dark is not None else None,
+                                dark_pedestal=self.dark_pedestal)
 
         table = registration.register_all_pairs_sharded(
             pairs, load_cells, self.input_height, self.input_width, max_x_overlap, max_y_overlap, self.normalization,
@@ -1272,7 +1367,9 @@ class Stitcher:
                           tophat_radius=self.background_radius if self.background_subtract == 'tophat' else None,
                           seam_qc_radius=self.seam_qc_radius, file_shape=(fh, fw), tile_shape=(th, tw), dtype=self.dtype,
                           channel_shifts=self._channel_shift_index, num_z=self.num_z,
-                          channel_affines=self._channel_affine_index)
+                          channel_affines=self._channel_affine_index, dark_params=self._dark_params,
+                          dark_frames=self._dark_frames_device() if self._dark_params or self._dark_right else None,
+                          dark_pedestal=self.dark_pedestal, dark_derived=self._dark_right)
 
         # group the files by (channel, z) plane, keeping the reference's write order inside a plane
         planes: Dict[int, List[Tuple[dict, int, tuple]]] = {}
@@ -1560,6 +1657,16 @@ class Stitcher:
                 'max_abs_du_256': du, 'max_abs_dv_256': dv, 'edges': 'replicated',
                 'interpolation': 'bilinear, 8 fractional bits',
                 'applies_to': 'every tile, before binning, placement, registration, the flatfield estimate and every tile filter'})
+        if self.dark_frames:
+            self._write_note(timepoint, region, 'dark_frame', {
+                'channels': {name: note for name, note in sorted(self._dark_note.items())},
+                'pedestal': self.dark_pedestal, 'definition': native.DARK_DEFINITION,
+                'tile_shape': [self.file_height, self.file_width],
+                'device_frames': 0 if self._dark_stack is None else len(self._dark_stack),
+                'device_frame_bytes': 0 if self._dark_stack is None else int(self._dark_stack.nbytes),
+                'order': darkframe.ORDER,
+                'applies_to': 'every tile file of the named channels, before registration, the flatfield estimate, the tile '
+                              'report and every tile filter'})
         if self._channel_shift_index:
             self._write_note(timepoint, region, 'channel_shift', {
                 'channels': {name: {'shift_256': [sy, sx], 'shift_px': [sy / 256, sx / 256]}

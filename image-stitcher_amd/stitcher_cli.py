@@ -16,13 +16,15 @@ before anything else sees them.  ``--distortion-correction`` removes radial lens
 front of all of that.  ``--channel-shift NAME DY DX`` (repeatable) moves every tile of one channel by a constant sub-pixel
 translation, on the device, between the two, so that channels that are not registered to each other on the sensor line up;
 ``--channel-affine NAME AYY AYX AXY AXX`` (repeatable) adds the linear term -- rotation, scale, shear about the tile centre -- to it.
+``--dark-frame`` (NAME SOURCE, repeatable) and ``--dark-pedestal`` subtract the camera's additive term -- a dark frame or a constant
+-- from every tile of a channel, on the device, in front of all of them.
 
     python -m image_stitcher_amd.stitcher_cli -i /path/to/acquisition -r -ff --registration-channel "488"
 """
 import argparse
 import sys
 
-from . import channelaffine, channelshift
+from . import channelaffine, channelshift, darkframe
 from .stitcher import Stitcher
 from .stitcher_parameters import StitchingParameters
 
@@ -227,6 +229,22 @@ FLAGS = (
                                       "channel may have a shift, an affine, or both.  Everything else is --channel-shift's: the "
                                       "contract, the order, the channels that take none; writes "
                                       "<region>_stitched_channel_affine.json")),
+    (('--dark-frame',), dict(nargs=2, action='append', default=None, metavar=('NAME', 'SOURCE'),
+                             help="subtract the camera's additive term from every tile of output channel NAME (<base>_R/_G/_B "
+                                  "for an RGB file; '*': every file channel without an entry of its own): out = clamp(I - D + P, "
+                                  "0, M), P = --dark-pedestal, M the dtype's maximum, exact in integers.  SOURCE is a plain "
+                                  "non-negative integer (a constant frame) or the path of a 2-D .tif, .tiff or .npy of exactly the "
+                                  "files' shape and dtype (make one with tools/dark_frame_make.py); repeatable, a name once.  A "
+                                  "run equals a run without the flag on a folder whose every tile file was subtracted "
+                                  "beforehand: the tiles are subtracted on the device before --distortion-correction, "
+                                  "--channel-shift / --channel-affine and --tile-binning, in sensor pixels; no file channel is "
+                                  "exempt -- the registration channel takes its frame, with --dpc both half-pupil channels take "
+                                  "theirs, DPC itself is read from no file and takes none; a supplied flatfield is used as "
+                                  "given; a constant equal to the pedestal is the identity; writes "
+                                  "<region>_stitched_dark_frame.json")),
+    (('--dark-pedestal',), dict(type=int, default=0, metavar='P',
+                                help="with --dark-frame: an integer in 0..M added back after the subtraction, so that noise below "
+                                     "the dark level is not clipped at 0 (default 0)")),
 )
 
 
@@ -253,6 +271,18 @@ def channel_affines_of(entries):
             raise ValueError(f"--channel-affine: channel {name!r} is given twice")
         affines[name] = tuple(channelaffine.parse_ppm(c) for c in coeffs)
     return affines
+
+
+def dark_frames_of(entries):
+    """--dark-frame NAME SOURCE, as often as given -> {NAME: int or path} (None when the flag is absent)."""
+    if not entries:
+        return None
+    frames = {}
+    for name, source in entries:
+        if name in frames:
+            raise ValueError(f"--dark-frame: channel {name!r} is given twice")
+        frames[name] = darkframe.parse_source(source)
+    return frames
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -335,7 +365,9 @@ def main(argv=None):
                             tile_binning_method=args.tile_binning_method,
                             distortion_correction=args.distortion_correction,
                             channel_shifts=channel_shifts_of(args.channel_shift),
-                            channel_affines=channel_affines_of(args.channel_affine))
+                            channel_affines=channel_affines_of(args.channel_affine),
+                            dark_frames=dark_frames_of(args.dark_frame),
+                            dark_pedestal=args.dark_pedestal)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -21,14 +21,19 @@ RING = ('ingest', 'dpc')      # per ingest slot: (pinned staging, device mirrors
 WRITER = ('ingest', 'distortion', 'shift', 'binning')          # what the stream writer's batch is sized by
 
 
-def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None, shifts=None, shifted=None, channel_affines=None):
+def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None, shifts=None, shifted=None, channel_affines=None,
+                 darks=None, dark_frames=None, dark_pedestal=0):
     """The head of every way tiles reach the device -- the staged planes, the right halves, registration's stack: corrected
     first (in sensor pixels), binned second, into the first planes of ``warped`` / ``binned`` where they are given.  Between
     the two, ``shifts`` (one (Sy, Sx) per plane of ``tiles``, --channel-shift; None: no launch) moves the planes into
     ``shifted``, or ``channel_affines`` (one (Sy, Sx, Ayy, Ayx, Axy, Axx) per plane, --channel-affine composed with the plane's
     shift; None: no launch) maps them there in ONE launch that takes the place of the shift's: the right halves and
-    registration's stack pass neither."""
+    registration's stack pass neither.  In front of everything, ``darks`` (one (k, c) per plane of ``tiles``, --dark-frame: frame
+    k of the device tensor ``dark_frames``, or the constant c; None: no launch) subtracts the camera's additive term IN PLACE
+    over ``tiles``, under ``dark_pedestal``: a device copy of a plane must pass here exactly once."""
     m = len(tiles)
+    if darks is not None:
+        native.dark_tiles(tiles, darks, dark_frames, dark_pedestal)
     if ppm:
         tiles = native.warp_tiles(tiles, ppm, out=None if warped is None else warped[:m])
     if channel_affines is not None:
@@ -43,12 +48,17 @@ def warp_and_bin(tiles, ppm, factor, method, warped=None, binned=None, shifts=No
 class TileChain:
     def __init__(self, *, distortion_ppm, binning, binning_method, dpc_planes, dpc_gain, despeckle, despeckle_threshold,
                  tophat_radius, seam_qc_radius, file_shape, tile_shape, dtype, channel_shifts=None, num_z=1,
-                 channel_affines=None):
+                 channel_affines=None, dark_params=None, dark_frames=None, dark_pedestal=0, dark_derived=None):
         """``dpc_planes``: the derived channel's plane ids (empty without --dpc); ``tophat_radius``: None without the top-hat;
         ``file_shape`` / ``tile_shape``: (fh, fw) of the files and (th, tw) behind the binning (the same without it);
         ``channel_shifts``: {channel index: (Sy, Sx)} in 1/256 pixel (--channel-shift; None or empty: off), the channel of plane
         id p being p // ``num_z``; ``channel_affines``: {channel index: (Ayy, Ayx, Axy, Axx)} in parts per million
-        (--channel-affine; None or empty: off)."""
+        (--channel-affine; None or empty: off); ``dark_params``: {channel index: (k, c)} (--dark-frame; None or empty: off) --
+        frame k of the device tensor ``dark_frames`` [K, fh, fw], or the constant c -- for the channels whose pair is not the
+        identity (-1, ``dark_pedestal``), the derived channel's being its LEFT half's; ``dark_derived``: the pair of the right
+        halves (None: the identity).  Nothing is allocated for it: the launch works in place over the ring slot's device mirror."""
+        self.dark_params, self.dark_frames, self.dark_pedestal = dict(dark_params or {}), dark_frames, int(dark_pedestal)
+        self.dark_derived = None if dark_derived is None or tuple(dark_derived) == (-1, self.dark_pedestal) else tuple(dark_derived)
         self.channel_shifts, self.num_z = dict(channel_shifts or {}), int(num_z)
         self.channel_affines = dict(channel_affines or {})
         self.ppm, self.factor, self.method = distortion_ppm, binning, binning_method
@@ -120,6 +130,12 @@ class TileChain:
         pairs = [self.channel_shifts.get(p // self.num_z, (0, 0)) for p in plane_ids or ()]
         return pairs if any(pair != (0, 0) for pair in pairs) else None
 
+    def plane_darks(self, plane_ids):
+        """One (k, c) per plane of ``plane_ids``, or None when every one of them is the identity (then nothing is launched)."""
+        same = (-1, self.dark_pedestal)
+        pairs = [tuple(self.dark_params.get(p // self.num_z, same)) for p in plane_ids or ()]
+        return pairs if any(pair != same for pair in pairs) else None
+
     def plane_affines(self, plane_ids):
         """One (Sy, Sx, Ayy, Ayx, Axy, Axx) per plane of ``plane_ids`` -- its shift or (0, 0), its A or zeros -- or None when
         none of them has a non-zero A (then the chunk goes today's way: ``plane_shifts``)."""
@@ -137,19 +153,23 @@ class TileChain:
         ``seam_words`` (each None when its option is off); ``plane_ids``: the chunk's plane ids (--channel-shift: a chunk with
         a shifted plane is ONE shift launch over the whole chunk, which copies its unshifted planes; a chunk without one
         launches nothing; --channel-affine: a chunk with a plane whose A is not zero is ONE affine launch over the whole chunk
-        in the shift launch's place, every plane under its shift and its A).  The order is fixed."""
+        in the shift launch's place, every plane under its shift and its A; --dark-frame: the FIRST launch, in place over the
+        slot's device mirror, which the chunk's copy has just filled -- every copy of a plane passes it once).  The order is fixed."""
         import torch
         m = len(tiles)
         affines = self.plane_affines(plane_ids) if self.channel_affines else None
         shifts = self.plane_shifts(plane_ids) if self.channel_shifts and affines is None else None
+        darks = self.plane_darks(plane_ids) if self.dark_params else None
         tiles = warp_and_bin(tiles, self.ppm, self.factor, self.method, bufs.get('distortion'), bufs.get('binning'),
-                             shifts, bufs.get('shift'), affines)
+                             shifts, bufs.get('shift'), affines, darks, self.dark_frames, self.dark_pedestal)
         if derived:     # in place over the left halves, before anything reads the staged planes
             i0, i1 = derived[0], derived[-1] + 1
             staging, on_dev, read, _ = bufs['dpc']
             halves = on_dev[slot][:i1 - i0]
             halves.copy_(staging[slot][:i1 - i0], non_blocking=True)
-            halves = warp_and_bin(halves, self.ppm, self.factor, self.method, bufs.get('distortion-dpc'), bufs.get('binning-dpc'))
+            halves = warp_and_bin(halves, self.ppm, self.factor, self.method, bufs.get('distortion-dpc'), bufs.get('binning-dpc'),
+                                  darks=None if self.dark_derived is None else self.dark_derived, dark_frames=self.dark_frames,
+                                  dark_pedestal=self.dark_pedestal)
             native.dpc_tiles(tiles[i0:i1], halves, self.dpc_gain)
             read[slot] = torch.cuda.Event()
             read[slot].record()

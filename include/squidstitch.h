@@ -604,6 +604,42 @@ int sq_affine_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_
                     int32_t dtype, const int32_t *params_host, int32_t images_per_param, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dark-frame subtraction of tile planes: the camera's additive term, the other half of the flatfield correction (I - D) / F
+ * (--dark-frame; extension: the reference runs BaSiC with get_darkfield=False and subtracts nothing).  For each of n_images
+ * planes I [h, w] (SQ_U8 / SQ_U16, maximum M = 255 / 65535), a dark frame D [h, w] of the same dtype (or a constant c in 0..M)
+ * and a pedestal P in 0..M, IN PLACE, taken in a wider signed type:
+ *     out(y, x) = clamp(I(y, x) - D(y, x) + P, 0, M)
+ * The definition is the numpy restatement in tests/dark_ref.py, and the result is bit for bit that on every input.  The
+ * operation is elementwise: a thread reads only what it writes.  params_host is a HOST table of n_images / images_per_param
+ * pairs (k, c), read before the call returns: images [j * images_per_param, (j + 1) * images_per_param) take pair j, and n_images
+ * must be a multiple of images_per_param >= 1.  k >= 0 selects frame k of frames_dev [n_frames] (the frames a frame stride and
+ * their rows a frame pitch apart, in elements) and goes with c == 0; k == -1 means the constant c.  One grid is issued per maximal
+ * run of consecutive equal pairs; a run that is the identity (k == -1 and c == pedestal) issues nothing and leaves its planes
+ * untouched; longer runs are split at 65535 * SQ_DARK_IMAGES_PER_THREAD planes.  No table goes to the device.  The layout
+ * conventions are those of sq_dpc_tiles: planes a plane stride and rows a pitch apart (elements; pitch >= w), no alignment asked
+ * of a base or a pitch beyond the element's own; any h, w >= 1; the columns between w and the pitch and the rows beyond h are
+ * never written, and nothing there is read into a result.  The frames must not meet the tiles.  csrc/dark.hip: a thread owns one
+ * 16-byte vector of columns laid at the phase of the tile row, keeps P - D of its (row, columns) in registers and walks
+ * SQ_DARK_IMAGES_PER_THREAD images of the run with it, so a frame is fetched once per that many tiles (image by image where the
+ * plane stride is no whole number of 16-byte vectors); the constant path loads no frame.  The value is 1: measured on an MI355X
+ * the walk over 4 images took 1.12 x the time of the build with 1 (the frame of a run stays in the caches either way), so the
+ * simpler form is the library's; the macro may be set when the file is compiled, which is how tools/dark_probe.py compares.  No scratch, no allocation, no atomics,
+ * no LDS; asynchronous on `stream`; deterministic.  SQ_ERR_INVALID, and nothing is launched, for an unknown dtype, a pedestal or
+ * a constant outside 0..M, a k outside -1..n_frames - 1 (or a k >= 0 with c != 0), a pitch below w, a stride smaller than a
+ * plane, a NULL or element-misaligned pointer (NULL frames are fine when no pair names one), a NULL table, n_images < 0 or no
+ * multiple of images_per_param, h or w < 1, extents beyond the address space, and frames whose extent (first to last element)
+ * overlaps the tiles'.  SQ_ERR_UNSUPPORTED for a plane that needs more workgroups than a launch has.  n_images == 0 is SQ_OK.
+ * (Added without a change of SQ_VERSION: every caller built against 108 still links and runs.)
+ * ---------------------------------------------------------------------------------------- */
+#ifndef SQ_DARK_IMAGES_PER_THREAD
+#define SQ_DARK_IMAGES_PER_THREAD 1
+#endif
+int sq_dark_tiles(void *tiles_dev, int32_t n_images, int32_t h, int32_t w, int64_t plane_stride, int64_t pitch, int32_t dtype,
+                  const void *frames_dev, int32_t n_frames, int64_t frame_stride, int64_t frame_pitch,
+                  const int32_t *params_host /* [n_images / images_per_param][2] */, int32_t images_per_param,
+                  int32_t pedestal, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Registration: replaces normalize_image (stitcher.py:613-617), the crops of
  * calculate_horizontal_shift / calculate_vertical_shift (:504-506, :517-519) and
  * skimage.registration.phase_cross_correlation(upsample_factor=10) (:510, :523), batched
