@@ -188,6 +188,12 @@ EXPORTS = {
     'sq_blosc_scratch_bytes': (C.c_int64, [C.c_int32] * 6),
     'sq_blosc_encode_planes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'sq_deflate_chunk_count': (C.c_int64, [C.c_int32] * 5),
+    'sq_deflate_out_bound': (C.c_int64, [C.c_int32] * 6),
+    'sq_deflate_scratch_bytes': (C.c_int64, [C.c_int32] * 6),
+    'sq_deflate_encode_planes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_void_p]),
     'sq_basic_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'sq_basic_fit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_BasicInfo), C.c_void_p]),
@@ -1903,6 +1909,46 @@ def blosc_encode_planes(planes, chunk_h: int, chunk_w: int, buffers: Optional[Bl
                                         sq_dtype_of(npdt), int(chunk_h), int(chunk_w), buffers.scratch.data_ptr(),
                                         buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(), buffers.out.numel(),
                                         buffers.status.data_ptr(), _stream_ptr(stream)), 'sq_blosc_encode_planes')
+    return buffers
+
+
+class DeflateBuffers:
+    """Device buffers of one sq_deflate_encode_planes geometry: scratch, tile offsets, packed zlib streams, status."""
+
+    def __init__(self, n_planes: int, h: int, w: int, np_dtype, tile_h: int, tile_w: int, device):
+        import torch
+        L = lib()
+        dt = sq_dtype_of(np_dtype)
+        self.geometry = (int(n_planes), int(h), int(w), dt, int(tile_h), int(tile_w))
+        self.n_chunks = int(L.sq_deflate_chunk_count(n_planes, h, w, tile_h, tile_w))
+        self.bound = int(L.sq_deflate_out_bound(*self.geometry))
+        need = int(L.sq_deflate_scratch_bytes(*self.geometry))
+        _size(min(self.n_chunks, self.bound, need), 'sq_deflate geometry')
+        self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        self.offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=device)
+        self.out = torch.empty(max(self.bound, 1), dtype=torch.uint8, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def deflate_encode_planes(planes, tile_h: int, tile_w: int, predictor: int = 2, buffers: Optional[DeflateBuffers] = None,
+                          stream=None) -> DeflateBuffers:
+    """Enqueue the zlib (RFC 1950) encoding of the TIFF tiles of ``planes`` [n, H, W] (uint8 / uint16 device tensor, unit-stride
+    rows, any pitch / plane stride; tiles are full, zero past the plane's edge; ``predictor`` 2 = horizontal differencing, 1 =
+    none).  Returns the buffers: after the stream has run, tile i (plane-major, tile row, tile column) is
+    ``buffers.out[offsets[i]:offsets[i + 1]]`` with ``offsets = buffers.offsets`` (size 0 = all-zero tile).  Nothing is
+    synchronised or copied here."""
+    L = lib()
+    n, h, w = _plane_stack(planes, 'planes', integer_only=False)
+    npdt = np_dtype_of_torch(planes.dtype)
+    predictor = _int_in(predictor, 1, 2, 'predictor')
+    with _on_stream(stream):
+        if buffers is None or buffers.geometry != (n, h, w, sq_dtype_of(npdt), int(tile_h), int(tile_w)):
+            buffers = DeflateBuffers(n, h, w, npdt, tile_h, tile_w, planes.device)
+        _check(L.sq_deflate_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h,
+                                          w, sq_dtype_of(npdt), int(tile_h), int(tile_w), predictor, buffers.scratch.data_ptr(),
+                                          buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(),
+                                          buffers.out.numel(), buffers.status.data_ptr(), _stream_ptr(stream)),
+               'sq_deflate_encode_planes')
     return buffers
 
 

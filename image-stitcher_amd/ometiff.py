@@ -4,11 +4,18 @@ first ImageDescription) for the ``.ome.tiff`` output format.
 The reference writes this format through aicsimageio's OmeTiffWriter (stitcher.py:742-765:
 dim_order TCZYX, channel names, RGB channel colours, physical pixel sizes).  aicsimageio is not on
 the hot path and absent offline; this is the package-free equivalent ("next" row 8(f)1).
+
+``--ome-tiff-layout pyramid`` writes the OME-TIFF 6 pyramid instead: tiled planes, Adobe-deflate tiles with the horizontal
+predictor encoded ON THE DEVICE (csrc/deflate.hip), reduced levels in SubIFDs.  ``PyramidTiff`` is the container (a BigTIFF that
+is appended to while planes stream in, its IFDs written at close), ``PyramidTiffWriter`` streams planes into it with
+``omezarr.PlaneStreamWriter``'s protocol, ``read_pyramid_tiff`` reads it back for the tests.
 """
 from __future__ import annotations
 
+import os
 import struct
-from typing import Sequence
+import zlib
+from typing import Optional, Sequence
 from xml.sax.saxutils import escape
 
 import numpy as np
@@ -115,3 +122,497 @@ def read_ome_tiff(path: str):
             xml = buf[tags[270][2]:tags[270][2] + tags[270][1] - 1].decode('utf-8')
         (off,) = struct.unpack('<Q', buf[off + 8 + 20 * n: off + 16 + 20 * n])
     return planes, xml
+
+
+# ---------------------------------------------------------------------------------------------- the pyramid layout
+TIFF_LAYOUTS = ('planes', 'pyramid')
+TIFF_COMPRESSIONS = ('deflate', 'none')
+PREDICTOR_HORIZONTAL = 2
+
+
+def check_tiff_options(layout: str, compression: str, output_format: str, chunks=None) -> tuple:
+    """-> (layout, compression) validated; the pyramid needs .ome.tiff output and tile sides that are multiples of 16 (TIFF 6)."""
+    if layout not in TIFF_LAYOUTS:
+        raise ValueError(f"ome_tiff_layout must be 'planes' or 'pyramid', got {layout!r}")
+    if compression not in TIFF_COMPRESSIONS:
+        raise ValueError(f"ome_tiff_compression must be 'deflate' or 'none', got {compression!r}")
+    if layout == 'pyramid':
+        if str(output_format).endswith('.zarr'):
+            raise ValueError("ome_tiff_layout='pyramid' needs .ome.tiff output (an .ome.zarr store has its own pyramid)")
+        check_tile_shape((chunks or (1, 1, 1, 512, 512))[3:5])
+    return layout, compression
+
+
+def check_tile_shape(tile) -> tuple:
+    th, tw = (int(v) for v in tile)
+    if th < 16 or tw < 16 or th % 16 or tw % 16:
+        raise ValueError(f"TIFF tile sides must be multiples of 16, got {th} x {tw}")
+    return th, tw
+
+
+class PyramidTiff:
+    """A little-endian BigTIFF that is appended to: the 16-byte header, then the encoded tiles of whatever is appended, in arrival
+    order; ``close`` writes the TileOffsets / TileByteCounts arrays, the IFDs and the OME-XML behind them and patches the header's
+    first-IFD offset.  One top-level IFD per (t, c, z) plane, chained in the order (t C + c) Z + z, the OME-XML in the first one's
+    ImageDescription; the reduced levels of a plane are SubIFDs (tag 330) of its IFD.  Tiles are always full; a tile of zeros (size
+    0 when appended) points at ONE zero-tile stream written when the file is opened -- so does every tile of a plane that is
+    never appended."""
+
+    def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, tile=(512, 512), compression: str = 'deflate', xml: str = ''):
+        self.path = path
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype('uint8'), np.dtype('uint16')):
+            raise ValueError(f"the pyramid layout holds uint8 or uint16 planes, got {self.dtype}")
+        if compression not in TIFF_COMPRESSIONS:
+            raise ValueError(f"compression must be 'deflate' or 'none', got {compression!r}")
+        self.th, self.tw = check_tile_shape(tile)
+        self.compression = compression
+        self.shapes = [tuple(int(v) for v in s) for s in shapes]
+        t, c, z = self.shapes[0][:3]
+        self.n_planes = t * c * z
+        self.xml = xml
+        self.grid = [(-(-s[3] // self.th), -(-s[4] // self.tw)) for s in self.shapes]
+        zero = bytes(self.th * self.tw * self.dtype.itemsize)
+        self.zero_tile = zlib.compress(zero, 1) if compression == 'deflate' else zero
+        self._fh = open(path, 'wb')
+        self._fh.write(struct.pack('<2sHHHQ', b'II', 43, 8, 0, 0))
+        self._zero_at = 16
+        self._fh.write(self.zero_tile)
+        self._pos = 16 + len(self.zero_tile)
+        # every tile points at the zero tile until its bytes arrive
+        self.offsets = [np.full((self.n_planes, gy * gx), self._zero_at, np.uint64) for gy, gx in self.grid]
+        self.counts = [np.full((self.n_planes, gy * gx), len(self.zero_tile), np.uint64) for gy, gx in self.grid]
+        self.tiles_written = 0
+        self.bytes_written = self._pos
+        self.closed = False
+
+    def plane_index(self, t: int, c: int, z: int) -> int:
+        _, nc, nz = self.shapes[0][:3]
+        return (int(t) * nc + int(c)) * nz + int(z)
+
+    def append(self, level: int, planes: Sequence[int], data, sizes) -> int:
+        """The tiles of ``planes`` (indices) at ``level``: ``sizes`` [len(planes) * tiles per plane] byte counts in the order plane,
+        tile row, tile column (0 = a tile of zeros), ``data`` their bytes packed densely in that order.  One write."""
+        sizes = np.asarray(sizes, dtype=np.uint64).reshape(len(planes), -1)
+        if sizes.shape[1] != self.offsets[level].shape[1]:
+            raise ValueError(f"level {level} has {self.offsets[level].shape[1]} tiles per plane, got {sizes.shape[1]}")
+        total = int(sizes.sum())
+        view = memoryview(data).cast('B')[:total]
+        if len(view) != total:
+            raise ValueError("fewer bytes than the sizes add up to")
+        starts = self._pos + np.concatenate([[0], np.cumsum(sizes.reshape(-1))[:-1]]).astype(np.uint64).reshape(sizes.shape)
+        if total:
+            self._fh.write(view)
+        real = sizes > 0
+        for i, p in enumerate(planes):
+            self.offsets[level][p][real[i]] = starts[i][real[i]]
+            self.counts[level][p][real[i]] = sizes[i][real[i]]
+        self._pos += total
+        self.tiles_written += int(real.sum())
+        self.bytes_written += total
+        return total
+
+    def append_planes(self, level: int, planes: Sequence[int], arrays: np.ndarray) -> int:
+        """Host planes [m, y, x] of ``level`` cut into full tiles here (compression 'none', or 'deflate' with host zlib -- the
+        streams the device encoder's stand in for in the CPU tests): zero tiles take no bytes."""
+        gy, gx = self.grid[level]
+        m, y, x = arrays.shape
+        pad = np.zeros((m, gy * self.th, gx * self.tw), self.dtype.newbyteorder('<'))
+        pad[:, :y, :x] = arrays
+        tiles = pad.reshape(m, gy, self.th, gx, self.tw).transpose(0, 1, 3, 2, 4).reshape(m * gy * gx, self.th, self.tw)
+        chunks, sizes = [], np.zeros(len(tiles), np.uint64)
+        for i, tile in enumerate(tiles):
+            if not tile.any():
+                continue
+            if self.compression == 'deflate':
+                pred = tile.copy()
+                pred[:, 1:] = tile[:, 1:] - tile[:, :-1]
+                raw = zlib.compress(pred.tobytes(), 1)
+            else:
+                raw = tile.tobytes()
+            chunks.append(raw)
+            sizes[i] = len(raw)
+        return self.append(level, planes, b''.join(chunks), sizes)
+
+    def _ifd(self, level: int, plane: int, place, sub_offsets, next_off: int, desc) -> bytes:
+        s = self.shapes[level]
+        n_tiles = self.offsets[level].shape[1]
+        ents = [(254, 4, 1, 1 if level else 0), (256, 4, 1, s[4]), (257, 4, 1, s[3]), (258, 3, 1, self.dtype.itemsize * 8),
+                (259, 3, 1, 8 if self.compression == 'deflate' else 1), (262, 3, 1, 1), (277, 3, 1, 1),
+                (322, 4, 1, self.tw), (323, 4, 1, self.th), (339, 3, 1, 1)]
+        if self.compression == 'deflate':
+            ents.append((317, 3, 1, PREDICTOR_HORIZONTAL))
+        if desc is not None:
+            ents.append((270, 2, len(desc), place(desc)))
+        for tag, arr in ((324, self.offsets[level][plane]), (325, self.counts[level][plane])):
+            ents.append((tag, 16, n_tiles, int(arr[0]) if n_tiles == 1 else place(arr.astype('<u8').tobytes())))
+        if sub_offsets:
+            ents.append((330, 18, len(sub_offsets), sub_offsets[0] if len(sub_offsets) == 1 else
+                         place(np.asarray(sub_offsets, '<u8').tobytes())))
+        ents.sort()
+        return struct.pack('<Q', len(ents)) + b''.join(struct.pack('<HHQQ', *e) for e in ents) + struct.pack('<Q', next_off)
+
+    def close(self) -> dict:
+        """Arrays, IFDs, OME-XML, header.  Returns the counts the ``[ome-tiff]`` line prints."""
+        if self.closed:
+            return self.stats
+        base = (self._pos + 15) & ~15
+        tail = bytearray()
+
+        def place(blob: bytes) -> int:      # out-of-line data of an entry, 8-byte aligned
+            tail.extend(b'\0' * (-len(tail) % 8))
+            at = base + len(tail)
+            tail.extend(blob)
+            return at
+
+        desc = self.xml.encode('utf-8') + b'\0'
+        n_levels = len(self.shapes)
+        patches = []                        # position in `tail` of every top-level IFD's next pointer
+        first_ifd = 0
+        for p in range(self.n_planes):
+            subs = []
+            for lv in range(1, n_levels):
+                blob = self._ifd(lv, p, place, None, 0, None)
+                subs.append(place(blob))
+            body = self._ifd(0, p, place, subs, 0, desc if p == 0 else None)
+            at = place(body)        # (behind its out-of-line data; the IFD before it learns the offset now)
+            if p == 0:
+                first_ifd = at
+            else:
+                struct.pack_into('<Q', tail, patches[-1], at)
+            patches.append(at - base + len(body) - 8)
+        self._fh.write(b'\0' * (base - self._pos))
+        self._fh.write(tail)
+        self._fh.seek(8)
+        self._fh.write(struct.pack('<Q', first_ifd))
+        self._fh.close()
+        self.closed = True
+        total_tiles = sum(self.n_planes * gy * gx for gy, gx in self.grid)
+        raw = sum(self.n_planes * s[3] * s[4] * self.dtype.itemsize for s in self.shapes)
+        self.bytes_written = base + len(tail)
+        self.stats = {'levels': n_levels, 'tile': (self.th, self.tw), 'tiles': total_tiles,
+                      'zero_tiles': total_tiles - self.tiles_written, 'raw_bytes': raw, 'written_bytes': self.bytes_written}
+        return self.stats
+
+
+def tiff_summary(path: str, stats: dict) -> str:
+    return (f"[ome-tiff] {os.path.basename(path)}: {stats['levels']} levels, tiles {stats['tile'][0]} x {stats['tile'][1]}, "
+            f"{stats['tiles']} tiles ({stats['zero_tiles']} zero), {stats['raw_bytes']} -> {stats['written_bytes']} bytes")
+
+
+def _parse_ifd(buf, off: int):
+    (n,) = struct.unpack_from('<Q', buf, off)
+    sizes = {1: 1, 2: 1, 3: 2, 4: 4, 16: 8, 18: 8}
+    tags = {}
+    for i in range(n):
+        tag, typ, cnt, val = struct.unpack_from('<HHQQ', buf, off + 8 + 20 * i)
+        width = sizes[typ] * cnt
+        raw = bytes(buf[off + 20 + 20 * i: off + 20 + 20 * i + width]) if width <= 8 else bytes(buf[val:val + width])
+        if typ == 2:
+            value = raw
+        else:
+            value = np.frombuffer(raw, {1: '<u1', 3: '<u2', 4: '<u4', 16: '<u8', 18: '<u8'}[typ]).astype(np.int64)
+        tags[tag] = (typ, cnt, value)
+    (nxt,) = struct.unpack_from('<Q', buf, off + 8 + 20 * n)
+    return tags, nxt
+
+
+def _read_tiled_plane(buf, tags) -> np.ndarray:
+    val = lambda t: int(tags[t][2][0])
+    w, h, bits, comp, tw, th = val(256), val(257), val(258), val(259), val(322), val(323)
+    pred = val(317) if 317 in tags else 1
+    dt = np.dtype(f'<u{bits // 8}')
+    gy, gx = -(-h // th), -(-w // tw)
+    offs, cnts = tags[324][2], tags[325][2]
+    assert len(offs) == len(cnts) == gy * gx
+    full = np.zeros((gy * th, gx * tw), dt)
+    for k in range(gy * gx):
+        raw = bytes(buf[int(offs[k]):int(offs[k]) + int(cnts[k])])
+        if comp == 8:
+            raw = zlib.decompress(raw)
+        elif comp != 1:
+            raise ValueError(f"compression {comp}")
+        tile = np.frombuffer(raw, dt).reshape(th, tw)
+        if pred == 2:
+            tile = np.cumsum(tile, axis=1, dtype=dt)
+        iy, ix = divmod(k, gx)
+        full[iy * th:(iy + 1) * th, ix * tw:(ix + 1) * tw] = tile
+    return full[:h, :w]
+
+
+def read_pyramid_structure(path: str):
+    """-> (file bytes, [top-level IFD tags, each with key 'sub': the tags of its SubIFDs]) of a BigTIFF; a tag's entry is
+    (type, count, values)."""
+    with open(path, 'rb') as fh:
+        buf = fh.read()
+    bo, ver, osz, _, off = struct.unpack('<2sHHHQ', buf[:16])
+    if bo != b'II' or ver != 43 or osz != 8:
+        raise ValueError(f"{path}: not a little-endian BigTIFF")
+    ifds = []
+    while off:
+        tags, off = _parse_ifd(buf, off)
+        tags['sub'] = [_parse_ifd(buf, int(o))[0] for o in tags[330][2]] if 330 in tags else []
+        ifds.append(tags)
+    return buf, ifds
+
+
+def read_pyramid_tiff(path: str):
+    """A file written through ``PyramidTiff`` back into memory (tests): -> (levels, xml) with ``levels[l]`` the list of the planes
+    of level l in IFD order.  Parses the structure, inflates with ``zlib.decompress``, undoes the predictor with numpy."""
+    buf, ifds = read_pyramid_structure(path)
+    n_levels = 1 + len(ifds[0]['sub'])
+    levels = [[] for _ in range(n_levels)]
+    xml = None
+    for tags in ifds:
+        if 270 in tags and xml is None:
+            xml = tags[270][2][:-1].decode('utf-8')
+        for lv, t in enumerate([tags] + tags['sub']):
+            levels[lv].append(_read_tiled_plane(buf, t))
+    return levels, xml
+
+
+class PyramidTiffWriter:
+    """Streams fused planes from the device into a ``PyramidTiff``, with ``omezarr.PlaneStreamWriter``'s protocol (acquire / submit /
+    retarget / matches / drain / close; ``histogram`` and ``composite`` hooks; two slots), so that ``Stitcher.stitch_planes``
+    drives it unchanged.  submit() enqueues the pyramid kernels and, with compression 'deflate', the tile encoder
+    (sq_deflate_encode_planes, predictor 2) behind the fusion; a writer thread fetches exactly the packed streams and appends
+    them with one write per level per batch, straight from the page-locked buffer.  'none': the planes are copied out and cut
+    into tiles on the host.  ``meta``: the keyword arguments of ``ome_xml`` but shape and dtype (pixel_size_um, dz_um,
+    channel_names, channel_colors, name)."""
+
+    def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, meta: dict, chunks=(1, 1, 1, 512, 512), batch: int = 1,
+                 compression: str = 'deflate', device='cuda:0', slots: int = 2, buffers=None, canvas_arena=None,
+                 pyramid_method: str = 'nearest', verbose: bool = True):
+        import queue
+        import threading
+        import torch
+        from . import native, omezarr
+        self.chunks = tuple(chunks)
+        self.tile = check_tile_shape(self.chunks[3:5])
+        if compression not in TIFF_COMPRESSIONS:
+            raise ValueError(f"compression must be 'deflate' or 'none', got {compression!r}")
+        self.compression, self.batch = compression, int(batch)
+        self.pyramid_method = omezarr.check_pyramid_method(pyramid_method)
+        self.shapes = [tuple(int(v) for v in s) for s in shapes]
+        self.dtype = np.dtype(dtype)
+        self.row_offset = 0
+        self.bytes_written = 0
+        self.histogram = None       # as PlaneStreamWriter's: optional device int64 [C, bins] target of level 0's value counts
+        self.composite = None       # as PlaneStreamWriter's: optional composite.CompositeTarget handed every plane
+        self.verbose = verbose
+        tdtype = native.torch_dtype_of(self.dtype.type)
+        yx = [tuple(s[3:]) for s in self.shapes]
+        self._deflate = compression == 'deflate'
+        if buffers is None:
+            dev = [[native.empty_canvas(self.batch, s[0], s[1], tdtype, device, arena=canvas_arena) if lv == 0 else
+                    torch.empty((self.batch,) + s, dtype=tdtype, device=device) for lv, s in enumerate(yx)] for _ in range(slots)]
+            if self._deflate:
+                enc = [[native.DeflateBuffers(self.batch, s[0], s[1], self.dtype, self.tile[0], self.tile[1], device) for s in yx]
+                       for _ in range(slots)]
+                host = [[(torch.empty(e.bound, dtype=torch.uint8, pin_memory=True),
+                          torch.empty(e.n_chunks + 1, dtype=torch.int64, pin_memory=True),
+                          torch.empty(1, dtype=torch.int32, pin_memory=True)) for e in slot_enc] for slot_enc in enc]
+                buffers = (dev, host, enc)
+            else:
+                buffers = (dev, [[torch.empty((self.batch,) + s, dtype=tdtype, pin_memory=True) for s in yx] for _ in range(slots)])
+        self.buffers = buffers
+        if self._deflate != (len(buffers) == 3):
+            raise ValueError("buffers do not match this writer's compression")
+        self._dev, self._host = buffers[0], buffers[1]
+        self._enc = buffers[2] if self._deflate else None
+        if len(self._dev) != slots or [tuple(t.shape) for t in self._dev[0]] != [(self.batch,) + s for s in yx] \
+                or self._dev[0][0].dtype != tdtype:
+            raise ValueError("buffers do not match this writer's geometry")
+        self._copy_stream = torch.cuda.Stream(device=device)
+        self._frame_stream = torch.cuda.Stream(device=device)
+        self._free = [threading.Event() for _ in range(slots)]
+        for e in self._free:
+            e.set()
+        self._slot, self._m, self._error = -1, 0, None
+        self._file = None
+        self._open(path, meta)
+        self._queue: "queue.Queue" = queue.Queue()
+        self._thread = threading.Thread(target=self._dispatch, name='tiff-writer', daemon=True)
+        self._thread.start()
+
+    @property
+    def path(self) -> str:
+        return self._file.path
+
+    def _open(self, path: str, meta: dict) -> None:
+        xml = ome_xml(self.shapes[0], self.dtype, meta.get('channel_names', ()), meta.get('channel_colors', ()),
+                      meta['pixel_size_um'], meta.get('dz_um', 1.0), meta.get('name', 'stitched'))
+        self._file = PyramidTiff(path, self.shapes, self.dtype, tile=self.tile, compression=self.compression, xml=xml)
+
+    def _finish(self, file: PyramidTiff) -> None:
+        if file.closed:
+            return
+        stats = file.close()
+        self.bytes_written += stats['written_bytes']
+        if self.verbose:
+            print(tiff_summary(file.path, stats))
+
+    def _dispatch(self):
+        while True:
+            item = self._queue.get()
+            if item is None:
+                return
+            slot, coords, event, file = item
+            try:
+                if slot is None:          # the file is complete behind everything submitted to it
+                    self._finish(file)
+                    continue
+                event.synchronize()
+                planes = [file.plane_index(*c) for c in coords]
+                if self._deflate:
+                    self._write_streams(slot, planes, file)
+                else:
+                    for lv, h in enumerate(self._host[slot]):
+                        file.append_planes(lv, planes, h.numpy()[:len(planes)])
+            except BaseException as exc:   # surfaced by the next acquire() / drain() / close()
+                self._error = exc
+            finally:
+                if slot is not None:
+                    self._free[slot].set()
+
+    def _write_streams(self, slot: int, planes: Sequence[int], file: PyramidTiff) -> None:
+        """The tile offsets of this slot are on the host; fetch exactly the packed streams (only compressed bytes cross PCIe) and
+        append them, one write per level."""
+        import torch
+        m = len(planes)
+        done = torch.cuda.Event()
+        totals = []
+        with torch.cuda.stream(self._frame_stream):     # the encoder has finished: _dispatch waited for the slot's event
+            for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
+                if int(status[0]):
+                    raise RuntimeError("sq_deflate_encode_planes: output buffer too small")
+                total = int(offsets[m * (enc.n_chunks // self.batch)])
+                totals.append(total)
+                if total:
+                    frames[:total].copy_(enc.out[:total], non_blocking=True)
+            done.record()
+        done.synchronize()
+        for lv, (enc, (frames, offsets, _)) in enumerate(zip(self._enc[slot], self._host[slot])):
+            per_plane = enc.n_chunks // self.batch
+            file.append(lv, planes, frames.numpy()[:totals[lv]], np.diff(offsets.numpy()[:m * per_plane + 1]))
+
+    def _check(self):
+        if self._error is not None:
+            err, self._error = self._error, None
+            raise err
+
+    def acquire(self, m: int):
+        """Device canvas [m, Hc, Wc] of the next slot (contents undefined)."""
+        if not 0 < m <= self.batch:
+            raise ValueError(f"a slot holds 1..{self.batch} planes, asked for {m}")
+        self._slot = (self._slot + 1) % len(self._dev)
+        self._free[self._slot].wait()
+        self._check()
+        self._m = m
+        return self._dev[self._slot][0][:m]
+
+    def submit(self, coords: Sequence[tuple]) -> None:
+        """The canvas handed out by the last ``acquire`` is (being) filled on the current stream."""
+        import torch
+        from . import native, omezarr
+        slot, m = self._slot, self._m
+        if len(coords) != m:
+            raise ValueError(f"{m} planes acquired, {len(coords)} coordinates given")
+        dev = self._dev[slot]
+        if self.histogram is not None:
+            native.histogram_planes(dev[0][:m], [c for _, c, _ in coords], hist=self.histogram)
+        if self.composite is not None:
+            self.composite.add(dev[0][:m], coords, self.row_offset)
+        omezarr.device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
+        if self._deflate:      # encode every level's tiles behind the pyramid, on the caller's stream
+            for lv, enc in enumerate(self._enc[slot]):
+                full = dev[lv]     # the buffers are sized for a full batch: what lies past m is zeroed and costs no bytes
+                native.deflate_encode_planes(full if m == self.batch else omezarr._pad_planes(full, m), self.tile[0], self.tile[1],
+                                             PREDICTOR_HORIZONTAL, enc)
+        fused = torch.cuda.Event()
+        fused.record()
+        event = torch.cuda.Event()
+        with torch.cuda.stream(self._copy_stream):
+            self._copy_stream.wait_event(fused)
+            if self._deflate:
+                for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
+                    offsets.copy_(enc.offsets, non_blocking=True)
+                    status.copy_(enc.status, non_blocking=True)
+            else:
+                for d, h in zip(dev, self._host[slot]):
+                    if d.is_contiguous():
+                        h[:m].copy_(d[:m], non_blocking=True)
+                    else:                       # padded plane stride: every plane is contiguous, the stack is not
+                        for p in range(m):
+                            h[p].copy_(d[p], non_blocking=True)
+            event.record()
+        self._free[slot].clear()
+        self._queue.put((slot, list(coords), event, self._file))
+
+    def retarget(self, path: str, row_offset: int = 0, level_heights=None, meta: Optional[dict] = None) -> None:
+        """The planes submitted FROM NOW ON belong to another file of the same geometry: the current one is finished behind what
+        is still in flight, the next is opened.  (Row bands of one file are not supported: ranks take whole regions.)"""
+        if row_offset or level_heights is not None:
+            raise ValueError("a pyramid TIFF is written whole: no row bands")
+        if meta is None:
+            raise ValueError("retarget needs the next file's metadata")
+        self._queue.put((None, None, None, self._file))
+        self._open(path, meta)
+
+    def matches(self, shapes: Sequence[tuple], dtype, batch: int, compression: str, chunks, pyramid_method: str = 'nearest') -> bool:
+        """Can this writer take planes of these level shapes (its buffers are sized for one geometry)?"""
+        return (self._thread.is_alive() and self.batch == int(batch) and self.compression == compression
+                and self.chunks == tuple(chunks) and self.pyramid_method == pyramid_method
+                and self.shapes == [tuple(int(v) for v in s) for s in shapes] and self.dtype == np.dtype(dtype))
+
+    def drain(self) -> None:
+        """Wait until everything submitted so far is in the file (the writer stays usable; the file is finished by close or
+        retarget)."""
+        for e in self._free:
+            e.wait()
+        self._check()
+
+    def close(self):
+        for e in self._free:
+            e.wait()
+        if self._thread.is_alive():
+            self._queue.put((None, None, None, self._file))
+            self._queue.put(None)
+            self._thread.join()
+        elif self._file is not None and not self._file.closed:
+            self._finish(self._file)
+        self._check()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def write_pyramid_tiff(path: str, image, *, meta: dict, num_levels: int = 1, chunks=(1, 1, 1, 512, 512), compression: str = 'deflate',
+                       device=None, pyramid_method: str = 'nearest', composite=None, verbose: bool = True) -> str:
+    """Write a (T, C, Z, Y, X) uint8 / uint16 array (numpy, or a device tensor) as a pyramid OME-TIFF through
+    ``PyramidTiffWriter``, a batch of planes at a time (what ``omezarr.write_ome_zarr`` is to a store)."""
+    import torch
+    from . import omezarr
+    if image.ndim != 5:
+        raise ValueError(f"expected a 5-D TCZYX array, got {tuple(image.shape)}")
+    on_device = hasattr(image, 'data_ptr')
+    dtype = np.dtype(str(image.dtype).replace('torch.', '')) if on_device else image.dtype
+    shape = tuple(int(v) for v in image.shape)
+    shapes = omezarr.level_shapes(shape, num_levels)
+    coords = [(t, c, z) for t in range(shape[0]) for c in range(shape[1]) for z in range(shape[2])]
+    planes = image.reshape((-1,) + shape[3:])
+    batch = max(1, min(len(coords), (1 << 30) // max(1, shape[3] * shape[4] * dtype.itemsize)))
+    with PyramidTiffWriter(path, shapes, dtype, meta=meta, chunks=chunks, batch=batch, compression=compression,
+                           device=planes.device if on_device else (device if device is not None else 'cuda:0'),
+                           pyramid_method=pyramid_method, verbose=verbose) as writer:
+        writer.composite = composite
+        for b0 in range(0, len(coords), batch):
+            part = planes[b0:b0 + batch]
+            dst = writer.acquire(len(part))
+            dst.copy_(part if on_device else torch.from_numpy(np.ascontiguousarray(part)), non_blocking=False)
+            writer.submit(coords[b0:b0 + batch])
+    return path

@@ -35,6 +35,7 @@ except Exception:   # pragma: no cover
 from . import alignment, binning, channelaffine, channelshift, composite as composite_mod, darkframe, distortion, native, placement, registration, seamqc, sharding, tileqc
 from . import omezarr
 from .omezarr import write_ome_zarr
+from . import ometiff
 from .ometiff import write_ome_tiff
 from .placement import Shifts
 from .stitcher_parameters import StitchingParameters
@@ -84,7 +85,8 @@ class Stitcher:
                  dpc_channels=('BF LED matrix left half', 'BF LED matrix right half'), dpc_gain: int = 1,
                  seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
                  tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0,
-                 channel_shifts=None, channel_affines=None, dark_frames=None, dark_pedestal=0):
+                 channel_shifts=None, channel_affines=None, dark_frames=None, dark_pedestal=0,
+                 ome_tiff_layout: str = 'planes', ome_tiff_compression: str = 'deflate'):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -138,7 +140,8 @@ class Stitcher:
         self._guide = None      # the guide's index in monochrome_channels, once the metadata is parsed
         # Extension: how the OME-Zarr levels above 0 are made.  'nearest' = the reference's Scaler.nearest (stitcher.py:797-798);
         # 'mean' = the truncated 2 x 2 mean its other stitchers store (zarr_stitcher.py:614-719), all levels from one read of
-        # level 0 (sq_pyramid_mean).  Applies to every store a run writes (stack, _mip, _edf); .ome.tiff holds level 0 only.
+        # level 0 (sq_pyramid_mean).  Applies to every store a run writes (stack, _mip, _edf) and to the pyramid layout of
+        # .ome.tiff (ome_tiff_layout below); the planes layout of .ome.tiff holds level 0 only.
         self.pyramid_method = omezarr.check_pyramid_method(pyramid_method)
         # Extension: the channel windows of the omero block.  'dtype' = the reference's 0 ... np.iinfo(dtype).max
         # (stitcher.py:846-850); 'percentile' = contrast_percentiles (lo, hi) of the non-zero voxels of each store's own level 0,
@@ -320,6 +323,13 @@ class Stitcher:
         if zarr_compression not in ('blosc', 'zlib', 'none'):
             raise ValueError("zarr_compression must be 'blosc', 'zlib' or 'none'")
         self.zarr_compression = zarr_compression
+        # Extension: how an .ome.tiff is laid out.  'planes' = one uncompressed strip per (t, c, z) plane, level 0 only (the
+        # file of write_ome_tiff, from the fused region in host memory); 'pyramid' = the OME-TIFF 6 pyramid -- tiled planes
+        # (chunks[3:5], sides multiples of 16), num_pyramid_levels levels in SubIFDs, streamed batch by batch like a store;
+        # ome_tiff_compression 'deflate' = Adobe deflate with the horizontal predictor, encoded on the device
+        # (sq_deflate_encode_planes), 'none' = raw tiles.
+        self.ome_tiff_layout, self.ome_tiff_compression = ometiff.check_tiff_options(ome_tiff_layout, ome_tiff_compression,
+                                                                                     self.output_format)
         if flatfield_estimator not in ('auto', 'basic', 'basicpy', 'mean'):
             raise ValueError("flatfield_estimator must be 'auto', 'basic', 'basicpy' or 'mean'")
         self.flatfield_estimator = flatfield_estimator
@@ -2109,6 +2119,11 @@ class Stitcher:
             self._write_contrast(output_path, hist)
             return output_path
         comp = self._new_composite(timepoint, region) if kind == self._composite_kind() else None
+        if self._tiff_pyramid():
+            self._write_pyramid_tiff(output_path, mip, self.monochrome_channels, self.monochrome_colors,
+                                     f"{region}_t{timepoint}_{kind}", self.pyramid_method, comp)
+            self._finish_composite(comp)
+            return output_path
         if comp is not None:      # the projection buffer, while it is on the device
             import torch
             planes = mip if hasattr(mip, 'data_ptr') else torch.from_numpy(np.ascontiguousarray(mip)).to(self.device)
@@ -2161,6 +2176,9 @@ class Stitcher:
                                              num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                                              name=f"{region}_t{timepoint}_depth", compression=self.zarr_compression,
                                              device=depth.device if hasattr(depth, 'data_ptr') else self._device)
+        if self._tiff_pyramid():      # (levels by nearest: a mean of depths is no depth)
+            return self._write_pyramid_tiff(output_path, depth, labels, [0xFFFFFF] * len(labels), f"{region}_t{timepoint}_depth",
+                                            'nearest', None)
         if hasattr(depth, 'cpu'):
             depth = depth.cpu().numpy()
         print(f"Writing OME-TIFF to: {output_path}")
@@ -2282,6 +2300,72 @@ class Stitcher:
                 self._finish_contrast(wait=False)
             else:
                 self._write_contrast(output_path, histogram)
+        return output_path
+
+    def _tiff_pyramid(self) -> bool:
+        return self.ome_tiff_layout == 'pyramid' and not self.output_format.endswith('.zarr')
+
+    def _tiff_meta(self, channel_names, channel_colors, name: str) -> dict:
+        """What ome_xml needs beside shape and dtype: the arguments write_ome_tiff gets for the same image."""
+        return {'pixel_size_um': self.pixel_size_um, 'dz_um': self._dz_um(), 'channel_names': channel_names,
+                'channel_colors': channel_colors, 'name': name}
+
+    def _write_pyramid_tiff(self, output_path, image, channel_names, channel_colors, name, pyramid_method, composite) -> str:
+        """A (T, C, Z, Y, X) image that exists in one piece (a projection, a depth map, a region fused by stitch_region) as a
+        pyramid OME-TIFF, through the streaming writer."""
+        return ometiff.write_pyramid_tiff(output_path, image, meta=self._tiff_meta(channel_names, channel_colors, name),
+                                          num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
+                                          compression=self.ome_tiff_compression, device=self.device,
+                                          pyramid_method=pyramid_method, composite=composite)
+
+    def stream_region_to_tiff(self, timepoint, region, progress_callback=None, project_to=None):
+        """stream_region_to_zarr's counterpart for ``ome_tiff_layout='pyramid'``: the region streams to
+        ``<region>_stitched.ome.tiff`` batch by batch through an ometiff.PyramidTiffWriter (pyramid kernels, tile encoder, one
+        write per level per batch) and never exists in one piece.  Regions of one geometry share the writer: the file of
+        region k is finished behind its last batch while region k + 1 is read and fused."""
+        composite = self._new_composite(timepoint, region) if self.composite and self._composite_kind() == 'stack' else None
+        output_path = os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched{self.output_format}")
+        os.makedirs(os.path.dirname(output_path), exist_ok=True)
+        width, height = self.calculate_output_dimensions(timepoint, region)
+        shapes = omezarr.level_shapes((1, self.num_c, self.num_z, height, width), self.num_pyramid_levels)
+        chunks = self.chunks or (1, 1, 1, 512, 512)
+        ometiff.check_tile_shape(chunks[3:5])
+        meta = self._tiff_meta(self.monochrome_channels, self.monochrome_colors, f"{region}_t{timepoint}")
+        made = []
+
+        def make_writer(batch):
+            w = self._stream_writer
+            if isinstance(w, ometiff.PyramidTiffWriter) and \
+                    w.matches(shapes, self.dtype, batch, self.ome_tiff_compression, chunks, self.pyramid_method):
+                w.retarget(output_path, meta=meta)      # the same geometry: the next file through the same writer
+            else:
+                self._close_stream_writer()
+                key = ('tiff-writer', tuple(tuple(s[3:]) for s in shapes), batch, np.dtype(self.dtype).str, self.ome_tiff_compression,
+                       tuple(chunks))
+                w = ometiff.PyramidTiffWriter(output_path, shapes, self.dtype, meta=meta, chunks=chunks, batch=batch,
+                                              compression=self.ome_tiff_compression, device=self.device,
+                                              buffers=self._buffer_cache.get(key), pyramid_method=self.pyramid_method)
+                self._keep_buffers(key, w.buffers)
+                self._stream_writer = w
+            w.composite = composite
+            made.append(w)
+            return w
+
+        self.stitch_planes(timepoint, region, None, progress_callback, stream_to=make_writer, project_to=project_to)
+        for w in made:
+            w.composite = None
+        if not made:      # no plane of the region has a tile: a file of zero tiles all the same
+            self._close_stream_writer()
+            ometiff.PyramidTiff(output_path, shapes, self.dtype, tile=chunks[3:5], compression=self.ome_tiff_compression,
+                                xml=ometiff.ome_xml(shapes[0], self.dtype, **{k: meta[k] for k in
+                                                    ('channel_names', 'channel_colors', 'pixel_size_um', 'dz_um', 'name')})).close()
+        if not self._defer_drain:      # (run() keeps the writer for the next region and closes it at its end)
+            self._close_stream_writer()
+        if composite is not None:
+            if self._defer_drain and getattr(self, '_ingest_stream', None) is not None:
+                self._defer_composite(composite)
+            else:
+                self._finish_composite(composite)
         return output_path
 
     def close(self) -> None:
@@ -2431,6 +2515,11 @@ class Stitcher:
         package-free writers: same path template, channel names / colours, physical pixel sizes."""
         if self.output_format.endswith('.zarr'):
             return self.save_region_ome_zarr(timepoint, region, stitched_region)
+        if self._tiff_pyramid():
+            return self._write_pyramid_tiff(os.path.join(self.output_folder, f"{timepoint}_stitched",
+                                                         f"{region}_stitched{self.output_format}"), stitched_region,
+                                            self.monochrome_channels, self.monochrome_colors, f"{region}_t{timepoint}",
+                                            self.pyramid_method, None)
         if hasattr(stitched_region, 'cpu'):
             stitched_region = stitched_region.cpu().numpy()
         output_path = os.path.join(self.output_folder, f"{timepoint}_stitched", f"{region}_stitched{self.output_format}")
@@ -2622,6 +2711,10 @@ class Stitcher:
                 # fused planes stream to the store batch by batch; saving overlaps stitching
                 self.starting_saving.emit(False)
                 output_path = self.stream_region_to_zarr(timepoint, region, progress_callback=self.update_progress.emit,
+                                                         project_to=project_to)
+            elif self._tiff_pyramid():
+                self.starting_saving.emit(False)
+                output_path = self.stream_region_to_tiff(timepoint, region, progress_callback=self.update_progress.emit,
                                                          project_to=project_to)
             else:
                 comp = self._new_composite(timepoint, region) if self._composite_kind() == 'stack' else None

@@ -61,6 +61,12 @@ FLAGS = (
     (('--zarr-compression',), dict(choices=['blosc', 'zlib', 'none'], default='blosc',
                                    help="OME-Zarr chunk codec: blosc = the reference's default (Blosc-1 frames, shuffle + LZ4), encoded "
                                         "on the device; zlib = host threads; none = raw chunks")),
+    (('--ome-tiff-layout',), dict(choices=['planes', 'pyramid'], default='planes',
+                                  help="with -f .ome.tiff: planes = one uncompressed strip per plane, level 0 only; pyramid = tiled "
+                                       "planes with the pyramid levels in SubIFDs (OME-TIFF 6), streamed batch by batch")),
+    (('--ome-tiff-compression',), dict(choices=['deflate', 'none'], default='deflate',
+                                       help="with --ome-tiff-layout pyramid: deflate = Adobe deflate tiles with the horizontal "
+                                            "predictor, encoded on the device; none = raw tiles")),
     (('--per-region-registration',), dict(action='store_true',
                                           help="with -r: register every (timepoint, region) on its own tiles instead of once")),
     (('--all-pairs-registration',), dict(action='store_true',
@@ -367,7 +373,9 @@ def main(argv=None):
                             channel_shifts=channel_shifts_of(args.channel_shift),
                             channel_affines=channel_affines_of(args.channel_affine),
                             dark_frames=dark_frames_of(args.dark_frame),
-                            dark_pedestal=args.dark_pedestal)
+                            dark_pedestal=args.dark_pedestal,
+                            ome_tiff_layout=args.ome_tiff_layout,
+                            ome_tiff_compression=args.ome_tiff_compression)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -24,7 +24,8 @@ class StitchingParameters:
     ``input_folder``            Squid acquisition: ``acquisition parameters.json`` plus one sub-folder per
                                 timepoint holding ``coordinates.csv`` and ``<region>_<fov>_<z>_<channel>`` tiles
     ``output_format``           ``.ome.zarr`` (zarr v2 + NGFF 0.4, written plane by plane, also by several
-                                ranks at once) or ``.ome.tiff`` (BigTIFF with OME-XML)
+                                ranks at once) or ``.ome.tiff`` (BigTIFF with OME-XML; ``Stitcher(ome_tiff_layout='pyramid')``:
+                                tiled, deflate-encoded on the device, pyramid levels in SubIFDs, streamed)
     ``apply_flatfield``         tiles are divided by their channel's gain image inside the fusion kernel
     ``use_registration``        the centre tile and its right / bottom neighbours are phase-correlated on the
                                 device and every tile is placed by the two measured shifts; otherwise tiles are

@@ -807,6 +807,31 @@ int sq_blosc_encode_planes(const void *planes_dev, int64_t plane_stride, int64_t
                            uint64_t *offsets_dev, void *out_dev, int64_t out_capacity, uint32_t *status_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * TIFF tile encoding on the device: the tiles of n_planes (t, c, z) planes (tile_h x tile_w elements, little endian, ZERO past
+ * the plane's edge: a TIFF tile is always full) as RFC 1950 zlib streams -- TIFF Compression 8 ("Adobe deflate") -- packed
+ * densely into out_dev exactly like the Blosc frames above: tile i = plane-major, then tile row, then tile column, lives at
+ * out_dev[offsets_dev[i] .. offsets_dev[i + 1]) (n_tiles + 1 offsets; an all-zero tile has size 0: the writer points it at one
+ * shared stream).  predictor 2 = TIFF's horizontal differencing (inside every tile row each element but the first is replaced
+ * by its difference to its left neighbour, modulo 2^bits) before the bytes are coded, 1 = none.
+ * Stream: 78 01, then one deflate block per 16 KiB segment of the (predicted) tile bytes, then their Adler-32 (big endian).
+ * The only matches are element runs (distance = element size, length 3..258); every segment is one dynamic-Huffman block
+ * with its own code (lengths limited to 15; trivial code-length code; one distance symbol sent with one bit) or, when that
+ * does not shrink it, a stored block; a non-final segment ends with an empty stored block (sync flush), the last carries
+ * BFINAL.  tests/deflate_ref.py restates the stream in numpy; any inflater reads it.
+ * *status_dev != 0 afterwards: out_capacity was too small (sq_deflate_out_bound(), every segment stored, never is) and nothing
+ * was written to out_dev.  Strides in elements; dtype SQ_U8 or SQ_U16 (SQ_ERR_UNSUPPORTED otherwise); a tile may hold at most
+ * 32 MiB.  The size queries return a negative sq_status for a geometry the encode call refuses; sq_deflate_chunk_count is not
+ * told the dtype.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_deflate_chunk_count(int32_t n_planes, int32_t h, int32_t w, int32_t tile_h, int32_t tile_w);
+int64_t sq_deflate_out_bound(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w);
+int64_t sq_deflate_scratch_bytes(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w);
+int sq_deflate_encode_planes(const void *planes_dev, int64_t plane_stride, int64_t pitch, int32_t n_planes, int32_t h, int32_t w,
+                             int32_t dtype, int32_t tile_h, int32_t tile_w, int32_t predictor, void *scratch_dev,
+                             int64_t scratch_bytes, uint64_t *offsets_dev, void *out_dev, int64_t out_capacity,
+                             uint32_t *status_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Chunk files.  The store of save_region_ome_zarr (stitcher.py:771-859; zarr v2, one file per chunk, chunks (1,1,1,512,512)) is
  * hundreds of thousands of half-MB files per region; written one by one from the interpreter they were the wall of a files ->
  * store run once the codec ran on the device.  sq_write_files writes n_files files from ONE host buffer with native threads:
