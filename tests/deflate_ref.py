@@ -253,6 +253,12 @@ def compress_tile(data: bytes, esz: int, seg: int = SEG) -> bytes:
     return bytes(out) + adler_combine(parts).to_bytes(4, 'big')
 
 
+def block_kinds(data: bytes, esz: int, seg: int = SEG) -> str:
+    """'S' (stored) or 'D' (dynamic) for every segment of a tile's bytes, by compress_tile's rule."""
+    return ''.join('D' if len(dynamic_block(data[at:at + seg], esz, at + seg >= len(data))) < len(data[at:at + seg]) + 5 else 'S'
+                   for at in range(0, len(data), seg))
+
+
 def encode_planes(planes: np.ndarray, th: int, tw: int, predictor: int):
     """[n, H, W] -> the streams in the encoder's order: plane-major, then tile row, then tile column."""
     n, h, w = planes.shape

@@ -102,6 +102,80 @@ def test_the_code_length_limit_acts_on_fibonacci_counts():
     assert zlib.decompress(R.compress_tile(seg, 1)) == seg
 
 
+@pytest.mark.parametrize('predictor', [1, 2])
+@pytest.mark.parametrize('dtype', [np.uint8, np.uint16])
+def test_mixed_segments_are_stored_next_to_dynamic(dtype, predictor):
+    planes = K.mixed_segments(dtype)
+    side, esz = planes.shape[1], planes.dtype.itemsize
+    tiles = [R.tile_bytes(planes[p], 0, 0, side, side, predictor) for p in range(2)]
+    assert tuple(R.block_kinds(t, esz) for t in tiles) == K.MIXED_KINDS[planes.dtype.name]
+    assert K.MIXED_KINDS == {'uint16': ('SD', 'DS'), 'uint8': ('SSDD', 'DDSS')}
+    for t in tiles:
+        assert zlib.decompress(R.compress_tile(t, esz)) == t
+
+
+def test_the_code_length_limit_acts_on_uint16_fibonacci_counts():
+    planes = K.fibonacci_segment_u16()
+    assert planes.shape == (1, 64, 128) and planes.dtype == np.uint16
+    seg = R.tile_bytes(planes[0], 0, 0, 64, 128, 1)
+    assert len(seg) == R.SEG and seg[0::2] == seg[1::2]      # low byte = high byte: an element sends one code twice
+    toks = R.tokens(seg, 2)
+    assert all(k == 'lit' for k, _ in toks) and len(toks) == R.SEG
+    counts = [0] * 286
+    counts[256] = 1
+    for b in seg:
+        counts[b] += 1
+    assert sum(1 for c in counts if c) == 22
+    assert max(R.huffman_lengths(counts, None)) == 16
+    limited = R.huffman_lengths(counts)
+    assert max(limited) == 15 and sum(2 ** (15 - l) for l in limited if l) == 1 << 15
+    assert limited[1] == 15      # the rarest value: its element is two 15-bit codes in one word
+    stream = R.compress_tile(seg, 2)
+    assert R.block_kinds(seg, 2) == 'D' and len(stream) == 5423
+    assert zlib.decompress(stream) == seg
+
+
+def test_off_grid_tiles_end_inside_a_round_of_64():
+    last = {(name, np.dtype(dt).name): K.last_segment_elements(th, tw, dt)
+            for name, _, _, (th, tw) in K.OFF_GRID for dt in (np.uint8, np.uint16)}
+    assert last['t1x1', 'uint16'] == last['t1x1', 'uint8'] == 1
+    assert last['t5x7', 'uint16'] == 35 and last['t3x64', 'uint16'] == 192 and last['t37x53', 'uint16'] == 1961
+    assert last['t100x100-runs', 'uint16'] == 1808 and 1808 % 64 == 16 and last['t100x100-runs', 'uint8'] == 10000
+    assert last['t129x127', 'uint16'] == 8191 and 8191 % 64 == 63 and last['t129x127', 'uint8'] == 16383
+    assert last['plane10x10-t16x32', 'uint16'] == 512
+    assert any(v % 2 for v in last.values()) and sum(1 for v in last.values() if v % 64) >= 8
+    assert ometiff.check_tile_shape((16, 32)) == (16, 32)
+    for name, _, _, tile in K.OFF_GRID[:-1]:      # none of the others is a TIFF tile
+        with pytest.raises(ValueError):
+            ometiff.check_tile_shape(tile)
+    planes, _, _ = K.off_grid('t1x1', np.uint16)
+    assert planes.shape == (2, 11, 15) and planes.size == 330
+
+
+@pytest.mark.parametrize('predictor', [1, 2])
+@pytest.mark.parametrize('dtype', [np.uint8, np.uint16])
+@pytest.mark.parametrize('name', [c[0] for c in K.OFF_GRID])
+def test_reference_streams_of_off_grid_tiles_inflate(name, dtype, predictor):
+    planes, th, tw = K.off_grid(name, dtype)
+    streams, want = R.encode_planes(planes, th, tw, predictor), R.expected_tiles(planes, th, tw, predictor)
+    n, h, w = planes.shape
+    assert len(streams) == len(want) == n * -(-h // th) * -(-w // tw)
+    assert any(want)
+    for s, t in zip(streams, want):
+        assert (zlib.decompress(s) if s else b'') == t
+
+
+def test_reference_stream_of_all_ones_inflates():
+    for dtype in (np.uint8, np.uint16):
+        planes = K.all_ones((1, 100, 100), dtype)
+        assert set(planes.tobytes()) == {0xFF}
+        for predictor in (1, 2):
+            t = R.tile_bytes(planes[0], 0, 0, 100, 100, predictor)
+            assert zlib.decompress(R.compress_tile(t, planes.dtype.itemsize)) == t
+    seg = bytes([0xFF]) * R.SEG      # the largest sums a segment contributes, and their combination over 2048 segments
+    assert R.adler_combine([(R.SEG,) + R.adler_sums(seg)] * 2048) == zlib.adler32(seg * 2048)
+
+
 def test_adler_sums_combine_to_zlibs():
     rng = np.random.default_rng(3)
     data = rng.integers(0, 256, 50000).astype(np.uint8).tobytes()

@@ -11,57 +11,10 @@ import pytest
 import deflate_cases as K
 import deflate_ref as R
 import stream_cases as SC
-import tile_layouts
+from deflate_device import _dev, check_exact, device_planes
 from image_stitcher_amd import native
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    import torch
-    assert torch.cuda.is_available()
-    return torch.device('cuda:0')
-
-
-def device_planes(planes_np, padded: bool):
-    """The stack on the device: dense, or with a padded pitch and plane stride behind a lead-in (tile_layouts.padded)."""
-    import torch
-    if not padded:
-        return torch.from_numpy(planes_np).to(_dev())
-    lay = tile_layouts.padded(planes_np, pad=5, base_offset=16, gap=11)
-    n, h, w = lay.shape
-    buf = torch.from_numpy(lay.buffer).to(_dev())
-    return torch.as_strided(buf, (n, h, w), (lay.tile_stride, lay.pitch, 1), lay.base_offset)
-
-
-def encode(planes_np, th, tw, predictor, padded=False):
-    """-> (the stream of every tile, b'' for an all-zero one; the buffers)."""
-    import torch
-    buf = native.deflate_encode_planes(device_planes(planes_np, padded), th, tw, predictor)
-    torch.cuda.synchronize()
-    assert int(buf.status.item()) == 0
-    offsets, out = buf.offsets.cpu().numpy(), buf.out.cpu().numpy()
-    assert offsets[0] == 0 and np.all(np.diff(offsets) >= 0) and offsets[-1] <= buf.bound == len(out)
-    assert len(offsets) == buf.n_chunks + 1
-    return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(len(offsets) - 1)], buf
-
-
-def check_exact(planes_np, th, tw, predictor, padded=False):
-    """Every stream inflates to its tile's predicted bytes; -> (total stream bytes, raw bytes of all tiles, streams)."""
-    streams, _ = encode(planes_np, th, tw, predictor, padded)
-    want = R.expected_tiles(planes_np, th, tw, predictor)
-    assert len(streams) == len(want)
-    for i, (s, w) in enumerate(zip(streams, want)):
-        if not w:
-            assert s == b'', f'tile {i} is all zero and has a stream of {len(s)} bytes'
-            continue
-        assert s[:2] == b'\x78\x01', f'tile {i}: zlib header {s[:2].hex()}'
-        d = zlib.decompressobj()
-        got = d.decompress(s)
-        assert d.eof and d.unused_data == b'', f'tile {i}: the stream does not end with its last block and checksum'
-        assert got == w, f'tile {i}: inflated bytes differ'
-    raw = len(want) * th * tw * planes_np.dtype.itemsize
-    return sum(len(s) for s in streams), raw, streams
 
 
 @pytest.mark.parametrize('predictor', [1, 2])
