@@ -194,6 +194,12 @@ EXPORTS = {
     'sq_deflate_encode_planes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                            C.c_void_p]),
+    'sq_jpeg_chunk_count': (C.c_int64, [C.c_int32] * 5),
+    'sq_jpeg_out_bound': (C.c_int64, [C.c_int32] * 6),
+    'sq_jpeg_scratch_bytes': (C.c_int64, [C.c_int32] * 6),
+    'sq_jpeg_encode_planes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p]),
     'sq_basic_workspace_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'sq_basic_fit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_BasicInfo), C.c_void_p]),
@@ -1949,6 +1955,60 @@ def deflate_encode_planes(planes, tile_h: int, tile_w: int, predictor: int = 2, 
                                           buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(),
                                           buffers.out.numel(), buffers.status.data_ptr(), _stream_ptr(stream)),
                'sq_deflate_encode_planes')
+    return buffers
+
+
+class JpegBuffers:
+    """Device buffers of one sq_jpeg_encode_planes geometry: scratch, tile offsets, packed JPEG streams, status.  ``bound`` is
+    the capacity of ``out`` -- what a caller page-locks to fetch the streams: the tiles' raw bytes plus a header per tile, not
+    sq_jpeg_out_bound()'s worst case (6.5 times raw, reached only by noise at the highest quality).  Tiles that do not fit set
+    the status word and nothing is written; ``capacity`` overrides the default (``worst_case`` is the bound that never fails)."""
+
+    def __init__(self, n_planes: int, h: int, w: int, tile_h: int, tile_w: int, device, capacity: Optional[int] = None):
+        import torch
+        from . import jpegtile
+        L = lib()
+        self.geometry = (int(n_planes), int(h), int(w), SQ_U8, int(tile_h), int(tile_w))
+        self.n_chunks = int(L.sq_jpeg_chunk_count(n_planes, h, w, tile_h, tile_w))
+        self.worst_case = int(L.sq_jpeg_out_bound(*self.geometry))
+        need = int(L.sq_jpeg_scratch_bytes(*self.geometry))
+        _size(min(self.n_chunks, self.worst_case, need), 'sq_jpeg geometry')
+        self.bound = int(capacity) if capacity is not None else \
+            min(self.worst_case, self.n_chunks * (int(tile_h) * int(tile_w) + jpegtile.HEADER_BYTES + 2))
+        if self.bound < 0:
+            raise ValueError(f"capacity must be >= 0, got {capacity}")
+        self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        self.offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=device)
+        self.out = torch.empty(max(self.bound, 1), dtype=torch.uint8, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def jpeg_overflow_message(quality: int) -> str:
+    """What a caller reports when ``JpegBuffers.status`` came back non-zero with the default capacity."""
+    return (f"sq_jpeg_encode_planes: the tiles of a batch did not shrink below their raw size at quality {quality} (noise, not an "
+            f"image?); lower --ome-tiff-quality or write this data with --ome-tiff-compression deflate")
+
+
+def jpeg_encode_planes(planes, tile_h: int, tile_w: int, quality: int = 90, buffers: Optional[JpegBuffers] = None,
+                       stream=None, capacity: Optional[int] = None) -> JpegBuffers:
+    """Enqueue the baseline JPEG encoding (TIFF Compression 7; include/squidstitch.h, stated in numpy by jpegtile.py) of the TIFF
+    tiles of ``planes`` [n, H, W] (uint8 device tensor, unit-stride rows, any pitch / plane stride; tiles are full, zero past
+    the plane's edge; sides multiples of 8).  Returns the buffers: after the stream has run, tile i (plane-major, tile row, tile
+    column) is ``buffers.out[offsets[i]:offsets[i + 1]]`` (size 0 = all-zero tile) unless ``buffers.status`` is non-zero: then
+    ``buffers.bound`` was too small and nothing was written.  Nothing is synchronised or copied here."""
+    L = lib()
+    n, h, w = _plane_stack(planes, 'planes', integer_only=False)
+    quality = _int_in(quality, 1, 100, 'quality')
+    _size(L.sq_jpeg_out_bound(n, h, w, sq_dtype_of(np_dtype_of_torch(planes.dtype)), int(tile_h), int(tile_w)),
+          'sq_jpeg_encode_planes')      # (the entry point's refusal of anything but uint8, before buffers are made for it)
+    with _on_stream(stream):
+        if buffers is None or buffers.geometry != (n, h, w, SQ_U8, int(tile_h), int(tile_w)) \
+                or (capacity is not None and buffers.bound != int(capacity)):
+            buffers = JpegBuffers(n, h, w, tile_h, tile_w, planes.device, capacity=capacity)
+        _check(L.sq_jpeg_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h,
+                                       w, SQ_U8, int(tile_h), int(tile_w), quality, buffers.scratch.data_ptr(),
+                                       buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(),
+                                       buffers.bound, buffers.status.data_ptr(), _stream_ptr(stream)), 'sq_jpeg_encode_planes')
     return buffers
 
 

@@ -6,9 +6,11 @@ dim_order TCZYX, channel names, RGB channel colours, physical pixel sizes).  aic
 the hot path and absent offline; this is the package-free equivalent ("next" row 8(f)1).
 
 ``--ome-tiff-layout pyramid`` writes the OME-TIFF 6 pyramid instead: tiled planes, Adobe-deflate tiles with the horizontal
-predictor encoded ON THE DEVICE (csrc/deflate.hip), reduced levels in SubIFDs.  ``PyramidTiff`` is the container (a BigTIFF that
-is appended to while planes stream in, its IFDs written at close), ``PyramidTiffWriter`` streams planes into it with
-``omezarr.PlaneStreamWriter``'s protocol, ``read_pyramid_tiff`` reads it back for the tests.
+predictor encoded ON THE DEVICE (csrc/deflate.hip) -- or, for uint8 planes and ``--ome-tiff-compression jpeg``, baseline JPEG
+tiles (TIFF Compression 7, csrc/jpeg.hip; the stream is stated in jpegtile.py) --, reduced levels in SubIFDs.  ``PyramidTiff``
+is the container (a BigTIFF that is appended to while planes stream in, its IFDs written at close), ``PyramidTiffWriter``
+streams planes into it with ``omezarr.PlaneStreamWriter``'s protocol, ``read_pyramid_tiff`` reads it back for the tests
+(JPEG tiles through Pillow), ``read_tile_streams`` returns the tiles' raw bytes.
 """
 from __future__ import annotations
 
@@ -126,21 +128,51 @@ def read_ome_tiff(path: str):
 
 # ---------------------------------------------------------------------------------------------- the pyramid layout
 TIFF_LAYOUTS = ('planes', 'pyramid')
-TIFF_COMPRESSIONS = ('deflate', 'none')
+TIFF_COMPRESSIONS = ('deflate', 'none', 'jpeg')
 PREDICTOR_HORIZONTAL = 2
+_TIFF_COMPRESSION_TAG = {'none': 1, 'deflate': 8, 'jpeg': 7}
+_COMPRESSION_NAMES = "'deflate' or 'none' (or 'jpeg', for uint8 planes)"
 
 
-def check_tiff_options(layout: str, compression: str, output_format: str, chunks=None) -> tuple:
-    """-> (layout, compression) validated; the pyramid needs .ome.tiff output and tile sides that are multiples of 16 (TIFF 6)."""
+def check_tiff_options(layout: str, compression: str, output_format: str, chunks=None, quality=None) -> tuple:
+    """-> (layout, compression) validated; the pyramid needs .ome.tiff output and tile sides that are multiples of 16 (TIFF 6);
+    'jpeg' is a codec of TIFF tiles only (and ``quality``, when given, lies in 1..100)."""
     if layout not in TIFF_LAYOUTS:
         raise ValueError(f"ome_tiff_layout must be 'planes' or 'pyramid', got {layout!r}")
     if compression not in TIFF_COMPRESSIONS:
-        raise ValueError(f"ome_tiff_compression must be 'deflate' or 'none', got {compression!r}")
+        raise ValueError(f"ome_tiff_compression must be {_COMPRESSION_NAMES}, got {compression!r}")
+    if quality is not None:
+        from . import jpegtile
+        jpegtile.check_quality(quality)
+    if compression == 'jpeg' and str(output_format).endswith('.zarr'):
+        raise ValueError("ome_tiff_compression='jpeg' is a codec of TIFF tiles: it needs .ome.tiff output, not an .ome.zarr store")
+    if compression == 'jpeg' and layout != 'pyramid':      # (the planes layout writes raw strips whatever the codec: say so for a lossy one)
+        raise ValueError("ome_tiff_compression='jpeg' needs ome_tiff_layout='pyramid' (the planes layout writes uncompressed strips)")
     if layout == 'pyramid':
         if str(output_format).endswith('.zarr'):
             raise ValueError("ome_tiff_layout='pyramid' needs .ome.tiff output (an .ome.zarr store has its own pyramid)")
         check_tile_shape((chunks or (1, 1, 1, 512, 512))[3:5])
     return layout, compression
+
+
+def check_jpeg_dtype(dtype) -> None:
+    if np.dtype(dtype) != np.dtype('uint8'):
+        raise ValueError(f"ome_tiff_compression='jpeg' holds uint8 planes (baseline JPEG is 8 bits), got {np.dtype(dtype)}; "
+                         f"write this data with 'deflate'")
+
+
+def jpeg_buffers_plane_bytes(h: int, w: int, num_levels: int, tile, slots: int = 2) -> int:
+    """Device bytes the JPEG encoder's packed-stream buffers (native.JpegBuffers.bound: raw tiles + a header each) add per
+    plane of a writer's batch, over its levels and slots -- what the stream writer's batch is sized with."""
+    from . import jpegtile
+    th, tw = (int(v) for v in tile)
+    total = 0
+    for _ in range(max(1, int(num_levels))):
+        total += -(-h // th) * -(-w // tw) * (th * tw + jpegtile.HEADER_BYTES + 2)
+        h, w = h // 2, w // 2
+        if h < 1 or w < 1:
+            break
+    return slots * total
 
 
 def check_tile_shape(tile) -> tuple:
@@ -158,13 +190,18 @@ class PyramidTiff:
     0 when appended) points at ONE zero-tile stream written when the file is opened -- so does every tile of a plane that is
     never appended."""
 
-    def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, tile=(512, 512), compression: str = 'deflate', xml: str = ''):
+    def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, tile=(512, 512), compression: str = 'deflate', xml: str = '',
+                 quality: int = 90):
+        from . import jpegtile
         self.path = path
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype('uint8'), np.dtype('uint16')):
             raise ValueError(f"the pyramid layout holds uint8 or uint16 planes, got {self.dtype}")
         if compression not in TIFF_COMPRESSIONS:
-            raise ValueError(f"compression must be 'deflate' or 'none', got {compression!r}")
+            raise ValueError(f"compression must be {_COMPRESSION_NAMES}, got {compression!r}")
+        self.quality = jpegtile.check_quality(quality)
+        if compression == 'jpeg':
+            check_jpeg_dtype(self.dtype)
         self.th, self.tw = check_tile_shape(tile)
         self.compression = compression
         self.shapes = [tuple(int(v) for v in s) for s in shapes]
@@ -173,7 +210,10 @@ class PyramidTiff:
         self.xml = xml
         self.grid = [(-(-s[3] // self.th), -(-s[4] // self.tw)) for s in self.shapes]
         zero = bytes(self.th * self.tw * self.dtype.itemsize)
-        self.zero_tile = zlib.compress(zero, 1) if compression == 'deflate' else zero
+        if compression == 'jpeg':       # (a tile of zeros is not the cheapest JPEG block -- grey 128 is -- but it is one stream)
+            self.zero_tile = jpegtile.encode_tile(np.zeros((self.th, self.tw), np.uint8), self.quality)
+        else:
+            self.zero_tile = zlib.compress(zero, 1) if compression == 'deflate' else zero
         self._fh = open(path, 'wb')
         self._fh.write(struct.pack('<2sHHHQ', b'II', 43, 8, 0, 0))
         self._zero_at = 16
@@ -213,8 +253,10 @@ class PyramidTiff:
         return total
 
     def append_planes(self, level: int, planes: Sequence[int], arrays: np.ndarray) -> int:
-        """Host planes [m, y, x] of ``level`` cut into full tiles here (compression 'none', or 'deflate' with host zlib -- the
-        streams the device encoder's stand in for in the CPU tests): zero tiles take no bytes."""
+        """Host planes [m, y, x] of ``level`` cut into full tiles here (compression 'none', 'deflate' with host zlib -- the
+        streams the device encoder's stand in for in the CPU tests -- or 'jpeg' through jpegtile.encode_tile, the very streams of
+        the device encoder): zero tiles take no bytes."""
+        from . import jpegtile
         gy, gx = self.grid[level]
         m, y, x = arrays.shape
         pad = np.zeros((m, gy * self.th, gx * self.tw), self.dtype.newbyteorder('<'))
@@ -228,6 +270,8 @@ class PyramidTiff:
                 pred = tile.copy()
                 pred[:, 1:] = tile[:, 1:] - tile[:, :-1]
                 raw = zlib.compress(pred.tobytes(), 1)
+            elif self.compression == 'jpeg':
+                raw = jpegtile.encode_tile(tile, self.quality)
             else:
                 raw = tile.tobytes()
             chunks.append(raw)
@@ -238,7 +282,7 @@ class PyramidTiff:
         s = self.shapes[level]
         n_tiles = self.offsets[level].shape[1]
         ents = [(254, 4, 1, 1 if level else 0), (256, 4, 1, s[4]), (257, 4, 1, s[3]), (258, 3, 1, self.dtype.itemsize * 8),
-                (259, 3, 1, 8 if self.compression == 'deflate' else 1), (262, 3, 1, 1), (277, 3, 1, 1),
+                (259, 3, 1, _TIFF_COMPRESSION_TAG[self.compression]), (262, 3, 1, 1), (277, 3, 1, 1),
                 (322, 4, 1, self.tw), (323, 4, 1, self.th), (339, 3, 1, 1)]
         if self.compression == 'deflate':
             ents.append((317, 3, 1, PREDICTOR_HORIZONTAL))
@@ -291,13 +335,15 @@ class PyramidTiff:
         raw = sum(self.n_planes * s[3] * s[4] * self.dtype.itemsize for s in self.shapes)
         self.bytes_written = base + len(tail)
         self.stats = {'levels': n_levels, 'tile': (self.th, self.tw), 'tiles': total_tiles,
-                      'zero_tiles': total_tiles - self.tiles_written, 'raw_bytes': raw, 'written_bytes': self.bytes_written}
+                      'zero_tiles': total_tiles - self.tiles_written, 'raw_bytes': raw, 'written_bytes': self.bytes_written,
+                      'compression': self.compression, 'quality': self.quality if self.compression == 'jpeg' else None}
         return self.stats
 
 
 def tiff_summary(path: str, stats: dict) -> str:
     return (f"[ome-tiff] {os.path.basename(path)}: {stats['levels']} levels, tiles {stats['tile'][0]} x {stats['tile'][1]}, "
-            f"{stats['tiles']} tiles ({stats['zero_tiles']} zero), {stats['raw_bytes']} -> {stats['written_bytes']} bytes")
+            f"{stats['tiles']} tiles ({stats['zero_tiles']} zero), {stats['raw_bytes']} -> {stats['written_bytes']} bytes"
+            + (f", jpeg quality {stats['quality']}" if stats.get('compression') == 'jpeg' else ''))
 
 
 def _parse_ifd(buf, off: int):
@@ -328,11 +374,17 @@ def _read_tiled_plane(buf, tags) -> np.ndarray:
     full = np.zeros((gy * th, gx * tw), dt)
     for k in range(gy * gx):
         raw = bytes(buf[int(offs[k]):int(offs[k]) + int(cnts[k])])
-        if comp == 8:
-            raw = zlib.decompress(raw)
-        elif comp != 1:
-            raise ValueError(f"compression {comp}")
-        tile = np.frombuffer(raw, dt).reshape(th, tw)
+        if comp == 7:
+            from . import jpegtile
+            tile = jpegtile.decode_tile(raw)      # (Pillow; RuntimeError where it is absent)
+            if tile.shape != (th, tw) or dt != np.dtype('uint8'):
+                raise ValueError(f"JPEG tile of {tile.shape}, the IFD says {th} x {tw} {dt}")
+        else:
+            if comp == 8:
+                raw = zlib.decompress(raw)
+            elif comp != 1:
+                raise ValueError(f"compression {comp}")
+            tile = np.frombuffer(raw, dt).reshape(th, tw)
         if pred == 2:
             tile = np.cumsum(tile, axis=1, dtype=dt)
         iy, ix = divmod(k, gx)
@@ -356,6 +408,17 @@ def read_pyramid_structure(path: str):
     return buf, ifds
 
 
+def read_tile_streams(path: str):
+    """The raw bytes of every tile of a file written through ``PyramidTiff`` (tests): ``streams[l][p]`` is the list of the tile
+    streams of plane p (IFD order) at level l, in tile order; a tile of zeros shows the shared zero-tile stream."""
+    buf, ifds = read_pyramid_structure(path)
+    levels = [[] for _ in range(1 + len(ifds[0]['sub']))]
+    for tags in ifds:
+        for lv, t in enumerate([tags] + tags['sub']):
+            levels[lv].append([bytes(buf[int(o):int(o) + int(c)]) for o, c in zip(t[324][2], t[325][2])])
+    return levels
+
+
 def read_pyramid_tiff(path: str):
     """A file written through ``PyramidTiff`` back into memory (tests): -> (levels, xml) with ``levels[l]`` the list of the planes
     of level l in IFD order.  Parses the structure, inflates with ``zlib.decompress``, undoes the predictor with numpy."""
@@ -374,23 +437,26 @@ def read_pyramid_tiff(path: str):
 class PyramidTiffWriter:
     """Streams fused planes from the device into a ``PyramidTiff``, with ``omezarr.PlaneStreamWriter``'s protocol (acquire / submit /
     retarget / matches / drain / close; ``histogram`` and ``composite`` hooks; two slots), so that ``Stitcher.stitch_planes``
-    drives it unchanged.  submit() enqueues the pyramid kernels and, with compression 'deflate', the tile encoder
-    (sq_deflate_encode_planes, predictor 2) behind the fusion; a writer thread fetches exactly the packed streams and appends
-    them with one write per level per batch, straight from the page-locked buffer.  'none': the planes are copied out and cut
-    into tiles on the host.  ``meta``: the keyword arguments of ``ome_xml`` but shape and dtype (pixel_size_um, dz_um,
-    channel_names, channel_colors, name)."""
+    drives it unchanged.  submit() enqueues the pyramid kernels and, with compression 'deflate' or 'jpeg', the tile encoder
+    (sq_deflate_encode_planes, predictor 2; sq_jpeg_encode_planes at ``quality``, uint8 planes only) behind the fusion; a
+    writer thread fetches exactly the packed streams and appends them with one write per level per batch, straight from the
+    page-locked buffer.  'none': the planes are copied out and cut into tiles on the host.  ``meta``: the keyword arguments of
+    ``ome_xml`` but shape and dtype (pixel_size_um, dz_um, channel_names, channel_colors, name)."""
 
     def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, meta: dict, chunks=(1, 1, 1, 512, 512), batch: int = 1,
                  compression: str = 'deflate', device='cuda:0', slots: int = 2, buffers=None, canvas_arena=None,
-                 pyramid_method: str = 'nearest', verbose: bool = True):
+                 pyramid_method: str = 'nearest', verbose: bool = True, quality: int = 90):
         import queue
         import threading
         import torch
-        from . import native, omezarr
+        from . import jpegtile, native, omezarr
         self.chunks = tuple(chunks)
         self.tile = check_tile_shape(self.chunks[3:5])
         if compression not in TIFF_COMPRESSIONS:
-            raise ValueError(f"compression must be 'deflate' or 'none', got {compression!r}")
+            raise ValueError(f"compression must be {_COMPRESSION_NAMES}, got {compression!r}")
+        self.quality = jpegtile.check_quality(quality)
+        if compression == 'jpeg':
+            check_jpeg_dtype(dtype)
         self.compression, self.batch = compression, int(batch)
         self.pyramid_method = omezarr.check_pyramid_method(pyramid_method)
         self.shapes = [tuple(int(v) for v in s) for s in shapes]
@@ -402,13 +468,15 @@ class PyramidTiffWriter:
         self.verbose = verbose
         tdtype = native.torch_dtype_of(self.dtype.type)
         yx = [tuple(s[3:]) for s in self.shapes]
-        self._deflate = compression == 'deflate'
+        self._encoded = compression in ('deflate', 'jpeg')      # tiles are encoded on the device
+        self._jpeg = compression == 'jpeg'
         if buffers is None:
             dev = [[native.empty_canvas(self.batch, s[0], s[1], tdtype, device, arena=canvas_arena) if lv == 0 else
                     torch.empty((self.batch,) + s, dtype=tdtype, device=device) for lv, s in enumerate(yx)] for _ in range(slots)]
-            if self._deflate:
-                enc = [[native.DeflateBuffers(self.batch, s[0], s[1], self.dtype, self.tile[0], self.tile[1], device) for s in yx]
-                       for _ in range(slots)]
+            if self._encoded:
+                make = (lambda s: native.JpegBuffers(self.batch, s[0], s[1], self.tile[0], self.tile[1], device)) if self._jpeg else \
+                    (lambda s: native.DeflateBuffers(self.batch, s[0], s[1], self.dtype, self.tile[0], self.tile[1], device))
+                enc = [[make(s) for s in yx] for _ in range(slots)]
                 host = [[(torch.empty(e.bound, dtype=torch.uint8, pin_memory=True),
                           torch.empty(e.n_chunks + 1, dtype=torch.int64, pin_memory=True),
                           torch.empty(1, dtype=torch.int32, pin_memory=True)) for e in slot_enc] for slot_enc in enc]
@@ -416,10 +484,10 @@ class PyramidTiffWriter:
             else:
                 buffers = (dev, [[torch.empty((self.batch,) + s, dtype=tdtype, pin_memory=True) for s in yx] for _ in range(slots)])
         self.buffers = buffers
-        if self._deflate != (len(buffers) == 3):
+        if self._encoded != (len(buffers) == 3):
             raise ValueError("buffers do not match this writer's compression")
         self._dev, self._host = buffers[0], buffers[1]
-        self._enc = buffers[2] if self._deflate else None
+        self._enc = buffers[2] if self._encoded else None
         if len(self._dev) != slots or [tuple(t.shape) for t in self._dev[0]] != [(self.batch,) + s for s in yx] \
                 or self._dev[0][0].dtype != tdtype:
             raise ValueError("buffers do not match this writer's geometry")
@@ -442,7 +510,8 @@ class PyramidTiffWriter:
     def _open(self, path: str, meta: dict) -> None:
         xml = ome_xml(self.shapes[0], self.dtype, meta.get('channel_names', ()), meta.get('channel_colors', ()),
                       meta['pixel_size_um'], meta.get('dz_um', 1.0), meta.get('name', 'stitched'))
-        self._file = PyramidTiff(path, self.shapes, self.dtype, tile=self.tile, compression=self.compression, xml=xml)
+        self._file = PyramidTiff(path, self.shapes, self.dtype, tile=self.tile, compression=self.compression, xml=xml,
+                                 quality=self.quality)
 
     def _finish(self, file: PyramidTiff) -> None:
         if file.closed:
@@ -464,7 +533,7 @@ class PyramidTiffWriter:
                     continue
                 event.synchronize()
                 planes = [file.plane_index(*c) for c in coords]
-                if self._deflate:
+                if self._encoded:
                     self._write_streams(slot, planes, file)
                 else:
                     for lv, h in enumerate(self._host[slot]):
@@ -485,7 +554,9 @@ class PyramidTiffWriter:
         with torch.cuda.stream(self._frame_stream):     # the encoder has finished: _dispatch waited for the slot's event
             for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
                 if int(status[0]):
-                    raise RuntimeError("sq_deflate_encode_planes: output buffer too small")
+                    from . import native
+                    raise RuntimeError(native.jpeg_overflow_message(self.quality) if self._jpeg else
+                                       "sq_deflate_encode_planes: output buffer too small")
                 total = int(offsets[m * (enc.n_chunks // self.batch)])
                 totals.append(total)
                 if total:
@@ -524,17 +595,20 @@ class PyramidTiffWriter:
         if self.composite is not None:
             self.composite.add(dev[0][:m], coords, self.row_offset)
         omezarr.device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
-        if self._deflate:      # encode every level's tiles behind the pyramid, on the caller's stream
+        if self._encoded:      # encode every level's tiles behind the pyramid, on the caller's stream
             for lv, enc in enumerate(self._enc[slot]):
                 full = dev[lv]     # the buffers are sized for a full batch: what lies past m is zeroed and costs no bytes
-                native.deflate_encode_planes(full if m == self.batch else omezarr._pad_planes(full, m), self.tile[0], self.tile[1],
-                                             PREDICTOR_HORIZONTAL, enc)
+                planes = full if m == self.batch else omezarr._pad_planes(full, m)
+                if self._jpeg:
+                    native.jpeg_encode_planes(planes, self.tile[0], self.tile[1], self.quality, enc)
+                else:
+                    native.deflate_encode_planes(planes, self.tile[0], self.tile[1], PREDICTOR_HORIZONTAL, enc)
         fused = torch.cuda.Event()
         fused.record()
         event = torch.cuda.Event()
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(fused)
-            if self._deflate:
+            if self._encoded:
                 for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
                     offsets.copy_(enc.offsets, non_blocking=True)
                     status.copy_(enc.status, non_blocking=True)
@@ -559,9 +633,11 @@ class PyramidTiffWriter:
         self._queue.put((None, None, None, self._file))
         self._open(path, meta)
 
-    def matches(self, shapes: Sequence[tuple], dtype, batch: int, compression: str, chunks, pyramid_method: str = 'nearest') -> bool:
+    def matches(self, shapes: Sequence[tuple], dtype, batch: int, compression: str, chunks, pyramid_method: str = 'nearest', *,
+                quality: int = 90) -> bool:
         """Can this writer take planes of these level shapes (its buffers are sized for one geometry)?"""
         return (self._thread.is_alive() and self.batch == int(batch) and self.compression == compression
+                and (compression != 'jpeg' or self.quality == int(quality))
                 and self.chunks == tuple(chunks) and self.pyramid_method == pyramid_method
                 and self.shapes == [tuple(int(v) for v in s) for s in shapes] and self.dtype == np.dtype(dtype))
 
@@ -592,7 +668,7 @@ class PyramidTiffWriter:
 
 
 def write_pyramid_tiff(path: str, image, *, meta: dict, num_levels: int = 1, chunks=(1, 1, 1, 512, 512), compression: str = 'deflate',
-                       device=None, pyramid_method: str = 'nearest', composite=None, verbose: bool = True) -> str:
+                       device=None, pyramid_method: str = 'nearest', composite=None, verbose: bool = True, quality: int = 90) -> str:
     """Write a (T, C, Z, Y, X) uint8 / uint16 array (numpy, or a device tensor) as a pyramid OME-TIFF through
     ``PyramidTiffWriter``, a batch of planes at a time (what ``omezarr.write_ome_zarr`` is to a store)."""
     import torch
@@ -608,7 +684,7 @@ def write_pyramid_tiff(path: str, image, *, meta: dict, num_levels: int = 1, chu
     batch = max(1, min(len(coords), (1 << 30) // max(1, shape[3] * shape[4] * dtype.itemsize)))
     with PyramidTiffWriter(path, shapes, dtype, meta=meta, chunks=chunks, batch=batch, compression=compression,
                            device=planes.device if on_device else (device if device is not None else 'cuda:0'),
-                           pyramid_method=pyramid_method, verbose=verbose) as writer:
+                           pyramid_method=pyramid_method, verbose=verbose, quality=quality) as writer:
         writer.composite = composite
         for b0 in range(0, len(coords), batch):
             part = planes[b0:b0 + batch]

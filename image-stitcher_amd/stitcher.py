@@ -86,7 +86,7 @@ class Stitcher:
                  seam_qc: bool = False, seam_qc_radius: int = 2, seam_qc_min_pixels: int = 256, seam_qc_min_ncc: float = 0.5,
                  tile_binning: int = 1, tile_binning_method: str = 'mean', distortion_correction: int = 0,
                  channel_shifts=None, channel_affines=None, dark_frames=None, dark_pedestal=0,
-                 ome_tiff_layout: str = 'planes', ome_tiff_compression: str = 'deflate'):
+                 ome_tiff_layout: str = 'planes', ome_tiff_compression: str = 'deflate', ome_tiff_quality: int = 90):
         self.update_progress = Signal(int, int)
         self.getting_flatfields = Signal()
         self.starting_stitching = Signal()
@@ -327,9 +327,12 @@ class Stitcher:
         # file of write_ome_tiff, from the fused region in host memory); 'pyramid' = the OME-TIFF 6 pyramid -- tiled planes
         # (chunks[3:5], sides multiples of 16), num_pyramid_levels levels in SubIFDs, streamed batch by batch like a store;
         # ome_tiff_compression 'deflate' = Adobe deflate with the horizontal predictor, encoded on the device
-        # (sq_deflate_encode_planes), 'none' = raw tiles.
+        # (sq_deflate_encode_planes), 'none' = raw tiles, 'jpeg' = baseline JPEG tiles (TIFF Compression 7) at ome_tiff_quality
+        # (1..100; 90 is a choice, not a measurement), encoded on the device (sq_jpeg_encode_planes): uint8 acquisitions only,
+        # refused once the metadata has told the dtype.  Lossy: the depth-map file of --focus-depth-map stays deflate.
         self.ome_tiff_layout, self.ome_tiff_compression = ometiff.check_tiff_options(ome_tiff_layout, ome_tiff_compression,
-                                                                                     self.output_format)
+                                                                                     self.output_format, quality=ome_tiff_quality)
+        self.ome_tiff_quality = int(ome_tiff_quality)
         if flatfield_estimator not in ('auto', 'basic', 'basicpy', 'mean'):
             raise ValueError("flatfield_estimator must be 'auto', 'basic', 'basicpy' or 'mean'")
         self.flatfield_estimator = flatfield_estimator
@@ -509,6 +512,8 @@ class Stitcher:
         first_image = read_image(first['filepath'])
         self.dtype = first_image.dtype.type
         self._check_despeckle_dtype()
+        if self.ome_tiff_compression == 'jpeg' and self._tiff_pyramid():
+            ometiff.check_jpeg_dtype(self.dtype)
         if first_image.ndim in (2, 3):
             self.file_height, self.file_width = first_image.shape[:2]
             self.input_height, self.input_width = self.file_height, self.file_width
@@ -1452,6 +1457,9 @@ class Stitcher:
                     flats_dev[ci] = torch.from_numpy(np.ascontiguousarray(ff)).to(self.device)
             if stream_to is not None and groups:
                 widest = chain.writer_plane_bytes(max(len(rect_of[sig]) for sig in groups))      # of the longest list
+                if self._tiff_pyramid() and self.ome_tiff_compression == 'jpeg':      # the encoder's packed streams, per slot
+                    widest += ometiff.jpeg_buffers_plane_bytes(hc, wc, self.num_pyramid_levels,
+                                                               (self.chunks or (1, 1, 1, 512, 512))[3:5])
                 writer = stream_to(max(1, min(max(len(pl) for pl in groups.values()), budget // max(1, widest))))
             def parts_of(t):      # the tensors of a target that this call writes
                 return t if isinstance(t, tuple) else ((t.out,) if isinstance(t, FocusFollower) else (t,))
@@ -2176,9 +2184,9 @@ class Stitcher:
                                              num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
                                              name=f"{region}_t{timepoint}_depth", compression=self.zarr_compression,
                                              device=depth.device if hasattr(depth, 'data_ptr') else self._device)
-        if self._tiff_pyramid():      # (levels by nearest: a mean of depths is no depth)
+        if self._tiff_pyramid():      # (levels by nearest: a mean of depths is no depth; never JPEG: a lossy depth index is wrong)
             return self._write_pyramid_tiff(output_path, depth, labels, [0xFFFFFF] * len(labels), f"{region}_t{timepoint}_depth",
-                                            'nearest', None)
+                                            'nearest', None, lossless=True)
         if hasattr(depth, 'cpu'):
             depth = depth.cpu().numpy()
         print(f"Writing OME-TIFF to: {output_path}")
@@ -2310,13 +2318,15 @@ class Stitcher:
         return {'pixel_size_um': self.pixel_size_um, 'dz_um': self._dz_um(), 'channel_names': channel_names,
                 'channel_colors': channel_colors, 'name': name}
 
-    def _write_pyramid_tiff(self, output_path, image, channel_names, channel_colors, name, pyramid_method, composite) -> str:
+    def _write_pyramid_tiff(self, output_path, image, channel_names, channel_colors, name, pyramid_method, composite,
+                            lossless: bool = False) -> str:
         """A (T, C, Z, Y, X) image that exists in one piece (a projection, a depth map, a region fused by stitch_region) as a
-        pyramid OME-TIFF, through the streaming writer."""
+        pyramid OME-TIFF, through the streaming writer.  ``lossless``: deflate where the run's codec is JPEG."""
+        compression = 'deflate' if lossless and self.ome_tiff_compression == 'jpeg' else self.ome_tiff_compression
         return ometiff.write_pyramid_tiff(output_path, image, meta=self._tiff_meta(channel_names, channel_colors, name),
                                           num_levels=self.num_pyramid_levels, chunks=self.chunks or (1, 1, 1, 512, 512),
-                                          compression=self.ome_tiff_compression, device=self.device,
-                                          pyramid_method=pyramid_method, composite=composite)
+                                          compression=compression, device=self.device,
+                                          pyramid_method=pyramid_method, composite=composite, quality=self.ome_tiff_quality)
 
     def stream_region_to_tiff(self, timepoint, region, progress_callback=None, project_to=None):
         """stream_region_to_zarr's counterpart for ``ome_tiff_layout='pyramid'``: the region streams to
@@ -2336,15 +2346,17 @@ class Stitcher:
         def make_writer(batch):
             w = self._stream_writer
             if isinstance(w, ometiff.PyramidTiffWriter) and \
-                    w.matches(shapes, self.dtype, batch, self.ome_tiff_compression, chunks, self.pyramid_method):
+                    w.matches(shapes, self.dtype, batch, self.ome_tiff_compression, chunks, self.pyramid_method,
+                              quality=self.ome_tiff_quality):
                 w.retarget(output_path, meta=meta)      # the same geometry: the next file through the same writer
             else:
                 self._close_stream_writer()
                 key = ('tiff-writer', tuple(tuple(s[3:]) for s in shapes), batch, np.dtype(self.dtype).str, self.ome_tiff_compression,
-                       tuple(chunks))
+                       tuple(chunks)) + ((self.ome_tiff_quality,) if self.ome_tiff_compression == 'jpeg' else ())
                 w = ometiff.PyramidTiffWriter(output_path, shapes, self.dtype, meta=meta, chunks=chunks, batch=batch,
                                               compression=self.ome_tiff_compression, device=self.device,
-                                              buffers=self._buffer_cache.get(key), pyramid_method=self.pyramid_method)
+                                              buffers=self._buffer_cache.get(key), pyramid_method=self.pyramid_method,
+                                              quality=self.ome_tiff_quality)
                 self._keep_buffers(key, w.buffers)
                 self._stream_writer = w
             w.composite = composite
@@ -2357,7 +2369,7 @@ class Stitcher:
         if not made:      # no plane of the region has a tile: a file of zero tiles all the same
             self._close_stream_writer()
             ometiff.PyramidTiff(output_path, shapes, self.dtype, tile=chunks[3:5], compression=self.ome_tiff_compression,
-                                xml=ometiff.ome_xml(shapes[0], self.dtype, **{k: meta[k] for k in
+                                quality=self.ome_tiff_quality, xml=ometiff.ome_xml(shapes[0], self.dtype, **{k: meta[k] for k in
                                                     ('channel_names', 'channel_colors', 'pixel_size_um', 'dz_um', 'name')})).close()
         if not self._defer_drain:      # (run() keeps the writer for the next region and closes it at its end)
             self._close_stream_writer()

@@ -64,9 +64,12 @@ FLAGS = (
     (('--ome-tiff-layout',), dict(choices=['planes', 'pyramid'], default='planes',
                                   help="with -f .ome.tiff: planes = one uncompressed strip per plane, level 0 only; pyramid = tiled "
                                        "planes with the pyramid levels in SubIFDs (OME-TIFF 6), streamed batch by batch")),
-    (('--ome-tiff-compression',), dict(choices=['deflate', 'none'], default='deflate',
+    (('--ome-tiff-compression',), dict(choices=['deflate', 'none', 'jpeg'], default='deflate',
                                        help="with --ome-tiff-layout pyramid: deflate = Adobe deflate tiles with the horizontal "
-                                            "predictor, encoded on the device; none = raw tiles")),
+                                            "predictor, encoded on the device; none = raw tiles; jpeg = baseline JPEG tiles (TIFF "
+                                            "Compression 7, lossy, uint8 acquisitions only), encoded on the device")),
+    (('--ome-tiff-quality',), dict(type=int, default=90, metavar='Q',
+                                   help="with --ome-tiff-compression jpeg: libjpeg's quality scale, 1..100 (default 90)")),
     (('--per-region-registration',), dict(action='store_true',
                                           help="with -r: register every (timepoint, region) on its own tiles instead of once")),
     (('--all-pairs-registration',), dict(action='store_true',
@@ -375,7 +378,8 @@ def main(argv=None):
                             dark_frames=dark_frames_of(args.dark_frame),
                             dark_pedestal=args.dark_pedestal,
                             ome_tiff_layout=args.ome_tiff_layout,
-                            ome_tiff_compression=args.ome_tiff_compression)
+                            ome_tiff_compression=args.ome_tiff_compression,
+                            ome_tiff_quality=args.ome_tiff_quality)
         print("Starting stitching with parameters:")
         for k, v in params.to_dict().items():
             print(f"{k}: {v}")

@@ -25,7 +25,8 @@ class StitchingParameters:
                                 timepoint holding ``coordinates.csv`` and ``<region>_<fov>_<z>_<channel>`` tiles
     ``output_format``           ``.ome.zarr`` (zarr v2 + NGFF 0.4, written plane by plane, also by several
                                 ranks at once) or ``.ome.tiff`` (BigTIFF with OME-XML; ``Stitcher(ome_tiff_layout='pyramid')``:
-                                tiled, deflate-encoded on the device, pyramid levels in SubIFDs, streamed)
+                                tiled, deflate-encoded on the device, pyramid levels in SubIFDs, streamed;
+                                ``ome_tiff_compression='jpeg'``: baseline JPEG tiles for uint8 acquisitions)
     ``apply_flatfield``         tiles are divided by their channel's gain image inside the fusion kernel
     ``use_registration``        the centre tile and its right / bottom neighbours are phase-correlated on the
                                 device and every tile is placed by the two measured shifts; otherwise tiles are

@@ -832,7 +832,36 @@ int sq_deflate_encode_planes(const void *planes_dev, int64_t plane_stride, int64
                              uint32_t *status_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Chunk files.  The store of save_region_ome_zarr (stitcher.py:771-859; zarr v2, one file per chunk, chunks (1,1,1,512,512)) is
+ * Lossy TIFF tile encoding on the device: the same tiles, packed the same way (offsets, size 0 for an all-zero tile, status),
+ * as baseline JPEG streams -- TIFF Compression 7, one self-contained ITU-T T.81 stream per tile, no JPEGTables tag, no APPn:
+ *   SOI | DQT (table 0) | SOF0 (P = 8, Y = tile_h, X = tile_w, one component, H = V = 1, Tq = 0) | DHT (DC 0, AC 0) |
+ *   DRI (Ri = tile_w / 8) | SOS (Ss = 0, Se = 63, Ah = Al = 0) | entropy-coded data | EOI
+ * Quantisation: the Annex K.1 luminance table scaled by libjpeg's rule for `quality` q in 1..100: s = 5000 / q (integer) for
+ * q < 50, else 200 - 2 q; Q = clamp((base s + 50) / 100, 1, 255).  Huffman tables: Annex K.3.3 luminance DC and AC, fixed.
+ * One restart interval = one row of blocks: padded with 1-bits to a byte, RSTm (m counting mod 8) between intervals, none after
+ * the last, DC prediction 0 at the start of each.  FF 00 for every FF of the data.  Zigzag order, ZRL for runs of 16 zeros,
+ * EOB unless coefficient 63 is non-zero; categories up to 11 (DC difference) and 10 (AC).
+ * Forward transform, exact in integers: x = pixel - 128; C[u][j] = round(2^10 a(u) cos((2 j + 1) u pi / 16)) (a(0) = sqrt(1/8),
+ * else 1/2) as 64 literal integers; N = C x C^T without intermediate rounding; coefficient = sign(N) ((|N| + D / 2) / D) with
+ * D = Q 2^20 (integer division).  Bound: the absolute values of a row of C sum to at most 2896, so |N| <= 128 * 2896^2 < 2^30
+ * and |N| + D / 2 < 2^31.  image-stitcher_amd/jpegtile.py states all of this in numpy; the device's bytes equal its bytes.
+ * dtype SQ_U8 only (SQ_ERR_UNSUPPORTED otherwise); tile sides that are no multiples of 8 and a quality outside 1..100 are
+ * SQ_ERR_INVALID; a tile holds at most 32 Mi elements and its sides stay below 65536.
+ * *status_dev != 0 afterwards: out_capacity was too small, and NO byte was written to out_dev (the exact sizes are known before
+ * the first byte is written).  sq_jpeg_out_bound() is the true worst case -- every block at the longest codes (20 + 63 * 26
+ * bits) and every byte stuffed, about 6.5 times the raw tiles -- and never too small; callers that allocate less (the raw size
+ * is plenty for images) must check the status.  Strides in elements.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_jpeg_chunk_count(int32_t n_planes, int32_t h, int32_t w, int32_t tile_h, int32_t tile_w);
+int64_t sq_jpeg_out_bound(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w);
+int64_t sq_jpeg_scratch_bytes(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w);
+int sq_jpeg_encode_planes(const void *planes_dev, int64_t plane_stride, int64_t pitch, int32_t n_planes, int32_t h, int32_t w,
+                          int32_t dtype, int32_t tile_h, int32_t tile_w, int32_t quality, void *scratch_dev,
+                          int64_t scratch_bytes, uint64_t *offsets_dev, void *out_dev, int64_t out_capacity,
+                          uint32_t *status_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Chunk files. The store of save_region_ome_zarr (stitcher.py:771-859; zarr v2, one file per chunk, chunks (1,1,1,512,512)) is
  * hundreds of thousands of half-MB files per region; written one by one from the interpreter they were the wall of a files ->
  * store run once the codec ran on the device.  sq_write_files writes n_files files from ONE host buffer with native threads:
  * file i is the NUL-terminated string at paths + path_offsets[i] and holds data[data_offsets[i] .. data_offsets[i + 1]) (created
