@@ -41,6 +41,7 @@ using namespace sq;
 namespace {
 
 constexpr int HEADER = 312;                     // SOI .. SOS
+constexpr int MAX_SIDE = 65496;                 // the largest multiple of 8 below libjpeg's JPEG_MAX_DIMENSION (65500)
 constexpr int BLOCK_BITS = 20 + 63 * 26;        // longest DC code 9 + 11 bits, 63 times the longest AC code 16 + 10 bits
 constexpr int STAGE = (31 + 64 * BLOCK_BITS + 31) / 32 + 3;      // words of the bit window: a carried partial word + 64 blocks
 
@@ -392,8 +393,9 @@ int geometry(JpegParams &P, int32_t h, int32_t w, int32_t n_planes, int32_t dtyp
         return fail(SQ_ERR_INVALID, "sq_jpeg: bad sizes (%dx%d planes %d tiles %dx%d: tile sides are multiples of 8)", h, w, n_planes,
                     th, tw);
     if (dtype != SQ_U8) return fail(SQ_ERR_UNSUPPORTED, "sq_jpeg: dtype %d (uint8 planes only: baseline JPEG holds 8 bits)", dtype);
-    if (th > 65528 || tw > 65528 || (int64_t)th * tw > (int64_t)32 << 20)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_jpeg: tiles of %d x %d (sides below 65536, at most 32 Mi elements)", th, tw);
+    // T.81 holds sides below 65536, but libjpeg -- the decoder behind nearly every TIFF reader -- refuses more than 65500
+    if (th > MAX_SIDE || tw > MAX_SIDE || (int64_t)th * tw > (int64_t)32 << 20)
+        return fail(SQ_ERR_UNSUPPORTED, "sq_jpeg: tiles of %d x %d (sides up to %d, at most 32 Mi elements)", th, tw, MAX_SIDE);
     P.h = h;
     P.w = w;
     P.n_planes = n_planes;

@@ -73,6 +73,8 @@ AC_VALS = (
 
 HEADER_BYTES = 2 + (2 + 67) + (2 + 11) + (2 + 2 + 29 + 179) + (2 + 4) + (2 + 8)      # SOI .. SOS: 312
 DEFAULT_QUALITY = 90
+# T.81 holds sides below 65536; libjpeg (JPEG_MAX_DIMENSION 65500), the decoder behind nearly every TIFF reader, refuses larger ones
+MAX_SIDE = 65496
 EOB, ZRL = 0x00, 0xF0
 
 
@@ -111,8 +113,8 @@ AC_CODE, AC_LEN = _canonical(AC_BITS, AC_VALS)
 def header(tile_h: int, tile_w: int, quality: int) -> bytes:
     """SOI .. SOS of a tile: HEADER_BYTES bytes."""
     th, tw = int(tile_h), int(tile_w)
-    if th < 8 or tw < 8 or th % 8 or tw % 8 or th > 65528 or tw > 65528:
-        raise ValueError(f"JPEG tile sides must be multiples of 8 in 8..65528, got {th} x {tw}")
+    if th < 8 or tw < 8 or th % 8 or tw % 8 or th > MAX_SIDE or tw > MAX_SIDE:
+        raise ValueError(f"JPEG tile sides must be multiples of 8 in 8..{MAX_SIDE}, got {th} x {tw}")
     q = quant_table(quality)
     be16 = lambda v: bytes((v >> 8, v & 255))
     out = b'\xFF\xD8'

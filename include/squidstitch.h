@@ -846,7 +846,8 @@ int sq_deflate_encode_planes(const void *planes_dev, int64_t plane_stride, int64
  * D = Q 2^20 (integer division).  Bound: the absolute values of a row of C sum to at most 2896, so |N| <= 128 * 2896^2 < 2^30
  * and |N| + D / 2 < 2^31.  image-stitcher_amd/jpegtile.py states all of this in numpy; the device's bytes equal its bytes.
  * dtype SQ_U8 only (SQ_ERR_UNSUPPORTED otherwise); tile sides that are no multiples of 8 and a quality outside 1..100 are
- * SQ_ERR_INVALID; a tile holds at most 32 Mi elements and its sides stay below 65536.
+ * SQ_ERR_INVALID; a tile holds at most 32 Mi elements and its sides are at most 65496
+ * (libjpeg reads no image above 65500; SQ_ERR_UNSUPPORTED beyond).
  * *status_dev != 0 afterwards: out_capacity was too small, and NO byte was written to out_dev (the exact sizes are known before
  * the first byte is written).  sq_jpeg_out_bound() is the true worst case -- every block at the longest codes (20 + 63 * 26
  * bits) and every byte stuffed, about 6.5 times the raw tiles -- and never too small; callers that allocate less (the raw size

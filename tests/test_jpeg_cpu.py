@@ -1,7 +1,8 @@
 """The JPEG tile stream as the host states it (image-stitcher_amd/jpegtile.py, what csrc/jpeg.hip is held to byte for byte in
 tests/test_jpeg_gpu.py) against libjpeg through Pillow: tables, decodability, fidelity, structure; the contents of
 tests/jpeg_cases.py held to what they are there for; the pyramid TIFF container with Compression 7 through the host path; the
-files of 'deflate' and 'none' untouched; the refusals.  No device."""
+files of 'deflate' and 'none' untouched; the refusals; the definition held to the independent reference of tests/jpeg_ref.py (a
+baseline decoder and a float64 DCT) on the edge cases of tests/test_jpeg_edges_gpu.py, and those cases to their purpose.  No device."""
 import io
 import os
 import re
@@ -13,6 +14,7 @@ import numpy as np
 import pytest
 
 import jpeg_cases as K
+import jpeg_ref as R
 from image_stitcher_amd import jpegtile as J
 from image_stitcher_amd import native, ometiff, omezarr, stitcher_cli
 from image_stitcher_amd.stitcher import Stitcher
@@ -380,3 +382,269 @@ def test_abi_and_sizes():
         planes = K.content(name, (1, 16, 1040), seed=9)
         assert len(J.encode_tile(planes[0], 100)) <= L.sq_jpeg_out_bound(1, 16, 1040, native.SQ_U8, 16, 1040)
     assert ometiff.jpeg_buffers_plane_bytes(100, 150, 2, (32, 32)) == 2 * ((4 * 5 + 2 * 3) * (32 * 32 + 314))
+
+
+# ---------------------------------------------------------------------------------------------------- the independent reference
+# tests/jpeg_ref.py restates the two halves of the operation -- T.81's baseline decoding down to the quantised coefficients, and a
+# float64 DCT -- and the cases below are the ones tests/test_jpeg_edges_gpu.py encodes on the device: here the host definition is
+# held to the reference, and every case to what it is there for.
+E_BOUND = R.transform_bound(J.DCT_MATRIX, J.DCT_SCALE_BITS)
+WORST_EXCESS = {}      # test -> the largest (|c Q - n| - Q / 2) / E it met; printed, and below 1 by rounding_excess's assertion
+
+
+def _excess(key, coefficients, divisors, tile):
+    r = R.rounding_excess(coefficients, divisors, tile, E_BOUND)
+    WORST_EXCESS[key] = max(WORST_EXCESS.get(key, -np.inf), r)
+    return r
+
+
+def test_the_reference_is_independent_and_its_bound_is_what_it_says():
+    with open(R.__file__) as fh:
+        assert 'jpegtile' not in fh.read().split('"""', 2)[2]      # (its docstring names what it is a reference of)
+    assert np.array_equal(R.ZIGZAG, J.ZIGZAG)
+    a = R.dct_matrix()
+    assert np.allclose(a @ a.T, np.eye(8), atol=1e-15)
+    assert 0.17 < E_BOUND.min() and E_BOUND.max() < 0.92 and abs(E_BOUND[0] - 0.21875) < 1e-9
+    # the bound is reached: the block of +-128 whose signs are those of the terms of position (u, v)
+    for u, v in ((0, 0), (1, 1), (7, 7), (3, 6)):
+        diff = np.outer(J.DCT_MATRIX[u], J.DCT_MATRIX[v]) / 2.0 ** 20 - np.outer(a[u], a[v])
+        x = 128 * np.where(diff >= 0, 1, -1)
+        n_int = (J.DCT_MATRIX @ x @ J.DCT_MATRIX.T)[u, v] / 2.0 ** 20
+        assert abs(abs(n_int - (a @ x @ a.T)[u, v]) - E_BOUND[8 * u + v]) < 1e-9
+
+
+def test_the_reference_decoder_refuses_what_a_reader_must_not_meet():
+    tile = K.content('uniform', (1, 24, 16), seed=5)[0]
+    good = J.encode_tile(tile, 90)
+    d = R.decode(good)
+    assert (d.height, d.width, d.restart_interval, len(d.pads)) == (24, 16, 2, 3)
+    assert np.array_equal(d.coefficients, J.quantised_blocks(tile, 90))
+    assert np.array_equal(d.divisors, J.quant_table(90)[J.ZIGZAG])
+    rst = [i for i in range(J.HEADER_BYTES, len(good) - 2) if good[i] == 0xFF and good[i + 1] != 0]
+    assert [good[i + 1] for i in rst] == [0xD0, 0xD1]
+    edit = lambda at, b: good[:at] + bytes([b]) + good[at + 1:]
+    cases = {
+        'RST1 where RST0 belongs': edit(rst[0] + 1, 0xD1),
+        'EOI where RST1 belongs': edit(rst[1] + 1, 0xD9),
+        'RST2 where EOI belongs': edit(len(good) - 1, 0xD2),
+        'a byte behind EOI': good + b'\x00',
+        'no EOI': good[:-2],
+        'an interval removed': good[:rst[0]] + good[rst[1]:],
+        'FF that is not stuffed': good[:J.HEADER_BYTES + 3] + b'\xFF\x41' + good[J.HEADER_BYTES + 5:],
+        'a byte more in an interval': good[:rst[0]] + b'\x7F' + good[rst[0]:],
+        'a byte less in an interval': good[:rst[0] - 1] + good[rst[0]:],
+        'progressive': good.replace(b'\xFF\xC0\x00\x0B', b'\xFF\xC2\x00\x0B'),
+    }
+    pads = R.decode(good).pads
+    k = next(i for i, p in enumerate(pads) if p)      # padding with a 0 bit in it
+    end = rst[k] if k < 2 else len(good) - 2
+    cases['a 0 among the padding bits'] = edit(end - 1, good[end - 1] & 0xFE)
+    for what, bad in cases.items():
+        with pytest.raises(R.StreamError, match=r'^byte \d+: '):
+            R.decode(bad)
+            pytest.fail(f'{what}: accepted')
+
+
+@pytest.mark.parametrize('shape_name', ['edges', 'rounds'])
+def test_the_definition_rounds_to_nearest_under_its_transform(shape_name):
+    """Every existing content at qualities 1, 4, .., 100: every coefficient of the host definition is the nearest multiple of its
+    divisor to the float64 DCT, up to the distance E between the two transforms."""
+    _, shape, (th, tw), _ = next(s for s in K.SHAPES if s[0] == shape_name)
+    for name in K.CONTENTS:
+        for tile in K.tiles_of(K.content(name, shape, seed=len(name)), th, tw):
+            for quality in range(1, 101, 3):
+                _excess(shape_name, J.quantised_blocks(tile, quality), J.quant_table(quality)[J.ZIGZAG], tile)
+    print(f'{shape_name}: largest (|cQ - n| - Q/2) / E = {WORST_EXCESS[shape_name]:.4f}')
+    assert WORST_EXCESS[shape_name] < 1
+
+
+def _held_to_the_reference(planes, th, tw, quality, key):
+    """Every stream of the planes: Pillow decodes it without a warning at the tile's size, the independent decoder finds exactly
+    the definition's coefficients in it, and those are nearest under the float64 transform.  -> the decoded streams."""
+    out = []
+    for tile, stream in zip(K.tiles_of(planes, th, tw), K.expected_streams(planes, th, tw, quality)):
+        if not tile.any():
+            assert stream == b''
+            out.append(None)
+            continue
+        assert decode(stream).shape == (th, tw)
+        d = R.decode(stream)
+        assert (d.height, d.width, d.restart_interval) == (th, tw, tw // 8)
+        assert np.array_equal(d.coefficients, J.quantised_blocks(tile, quality)), key
+        assert np.array_equal(d.divisors, J.quant_table(quality)[J.ZIGZAG])
+        _excess(key, d.coefficients, d.divisors, tile)
+        out.append(d)
+    return out
+
+
+def _distinct_edge_shapes():
+    """The phase layouts hold the planes of 'mixed': the same tiles, the same streams.  On the host one of them is enough."""
+    return [s[0] for s in K.EDGE_SHAPES if not s[0].startswith('phase')]
+
+
+@pytest.mark.parametrize('shape_name', _distinct_edge_shapes())
+def test_every_edge_case_on_the_host(shape_name):
+    _, shape, (th, tw), _ = K.edge_shape(shape_name)
+    contents = dict(K.EDGE_CONTENTS)
+    if shape_name in K.FULL_CONTENT_SHAPES:
+        contents.update({name: K.QUALITIES for name in K.CONTENTS if name not in contents})
+    streams = 0
+    for name, qualities in contents.items():
+        for quality in qualities:
+            got = _held_to_the_reference(K.edge_content(name, shape_name, quality), th, tw, quality, shape_name)
+            streams += sum(d is not None for d in got)
+            assert (streams > 0) or name == 'zero' or shape_name.startswith('tiny')
+    print(f'{shape_name}: {streams} streams, largest (|cQ - n| - Q/2) / E = {WORST_EXCESS.get(shape_name, float("nan")):.4f}')
+
+
+def test_the_edge_shapes_reach_what_they_are_there_for():
+    geo = {name: (shape, tile, layout) for name, shape, tile, layout in K.EDGE_SHAPES}
+    tiles = lambda name: geo[name][0][0] * -(-geo[name][0][1] // geo[name][1][0]) * -(-geo[name][0][2] // geo[name][1][1])
+    # the 64-bit load: base, pitch and plane stride all multiples of 8 -- and then only blocks that lie inside the width
+    aligned = lambda name: (geo[name][2][0] | geo[name][2][1] | geo[name][2][2]) % 8 == 0
+    assert aligned('mixed') and geo['mixed'][0][2] % 8 == 6 and geo['mixed'][2][0] > geo['mixed'][0][2]
+    assert [geo[f'phase{k}'][2] for k in range(1, 8)] == [(72, 24 * 72, k) for k in range(1, 8)]
+    assert not any(aligned(f'phase{k}') for k in range(1, 8))
+    assert not aligned('stride') and geo['stride'][2][0] % 8 == 0 and geo['stride'][2][2] == 0 and geo['stride'][2][1] % 8 == 4
+    for name in ['mixed', 'stride'] + [f'phase{k}' for k in range(1, 8)]:
+        for content in K.EDGE_CONTENTS:
+            planes = K.edge_content(content, name, K.EDGE_CONTENTS[content][0])
+            assert K.longest_guard_run(planes) < 3
+            buf, at = K.guarded(planes, geo[name][2])
+            n, h, w = planes.shape
+            pitch, stride, base = geo[name][2]
+            assert at == 256 + base
+            inside = np.zeros(len(buf), bool)
+            for p in range(n):
+                for y in range(h):
+                    row = at + p * stride + y * pitch
+                    assert np.array_equal(buf[row:row + w], planes[p, y])
+                    inside[row:row + w] = True
+            assert (buf[~inside] == K.GUARD).all() and not inside[:256].any() and not inside[-64:].any()
+            if pitch > w:      # guard bytes behind every row; 'stride' has them behind every plane
+                assert all(not inside[at + p * stride + y * pitch + w] for p in range(n) for y in range(h))
+            assert all(not inside[at + p * stride + (h - 1) * pitch + w] for p in range(n))
+    # rounds of 64 blocks, rounds of 64 intervals
+    assert (geo['round64'][1][1] // 8, geo['round65'][1][1] // 8) == (64, 65)
+    assert (geo['tall65'][1][0] // 8, geo['tall129'][1][0] // 8) == (65, 129)
+    # the scan's elements per thread: per = ceil(tiles / 1024); with 1025 tiles the threads from 513 on have lo == hi == n
+    assert [tiles(n) for n in ('tiles1024', 'tiles1025', 'tiles2625')] == [1024, 1025, 2625]
+    assert [-(-tiles(n) // 1024) for n in ('tiles1024', 'tiles1025', 'tiles2625')] == [1, 2, 3]
+    assert min(1025, 513 * 2) == 1025 and min(1025, 512 * 2) < 1025
+    planes = K.edge_content('uniform', 'tiles2625', 100)
+    sizes = np.array([len(s) for s in K.expected_streams(planes, 8, 8, 100)])
+    assert not sizes[875:1750].any() and sizes[1750:].all()                      # plane 1: no tile has a stream
+    assert not sizes[5 * 35:10 * 35].any() and sizes[:5 * 35].all() and sizes[10 * 35:875].all()
+    # the format's limits
+    assert geo['widest'][1] == (8, 65496) and tiles('widest') == 2 and geo['tallest'][1] == (65496, 8) and tiles('tallest') == 1
+    assert -(-8187 // 64) == 128
+    head = J.header(65496, 8, 50)
+    assert head[2 + 69 + 5:2 + 69 + 9] == b'\xFF\xD8\x00\x08'
+    assert R.decode(J.encode_tile(np.full((8, 65496), 9, np.uint8), 50)).restart_interval == 8187
+    # planes smaller than a block, than a tile
+    assert geo['tiny1'][0] == (1, 1, 1) and geo['tiny79'][0] == (1, 7, 9) and tiles('tiny1') == tiles('tiny79') == 1
+
+
+def _data_bits(d):
+    return sum(b[-1] for b in d.block_bits)
+
+
+def test_binary_is_denser_than_noise():
+    shape = (1, 16, 1040)
+    bits = {}
+    for name in ('uniform', 'binary'):
+        tile = K.content(name, shape, seed=8)[0]
+        d = R.decode(J.encode_tile(tile, 100))
+        bits[name] = _data_bits(d) / (2 * 130)
+        if name == 'binary':
+            assert np.abs(d.coefficients[:, :, 1:]).max() > 500
+    print(f'bits per block at quality 100: uniform {bits["uniform"]:.0f}, binary {bits["binary"]:.0f}')
+    assert bits['binary'] > bits['uniform'] + 100
+
+
+@pytest.mark.parametrize('case', [c[0] for c in K.FFRUNS_SHAPES])
+def test_ffruns_puts_ff_where_stuffing_is_hard(case):
+    """Among the un-stuffed data: two FF in a row; an FF in the last byte of word 63 of a 64-word group of stuff_out (the next
+    lane's output starts behind its stuffed zero in another group); an FF in each of the four bytes of a word."""
+    _, shape, (th, tw) = next(c for c in K.FFRUNS_SHAPES if c[0] == case)
+    planes = K.content('ffruns', shape)
+    (d,) = _held_to_the_reference(planes, th, tw, 100, 'ffruns ' + case)
+    places = [p for data, bits in zip(d.intervals, d.block_bits) for p in K.ff_places(data, bits)]
+    assert max(K.longest_ff_run(data) for data in d.intervals) >= 2
+    assert any(word % 64 == 63 and byte == 3 for word, byte in places)
+    assert {byte for _, byte in places} == {0, 1, 2, 3}
+    assert max(word for word, _ in places) >= 128      # a round of more than two groups
+    print(f'ffruns {case}: {len(places)} FF, {sum(1 for w, b in places if w % 64 == 63 and b == 3)} of them end a group')
+
+
+def test_dcsweep_crosses_every_rounding_boundary_of_the_dc():
+    _, shape, (th, tw), _ = K.edge_shape('widest')
+    planes = K.content('dcsweep', shape)
+    sums = planes[0].reshape(8, -1, 8).transpose(1, 0, 2).reshape(-1, 64).astype(np.int64).sum(axis=1)
+    assert np.array_equal(sums, np.minimum(np.arange(2 * 8187), 16320))
+    tiles = K.tiles_of(planes, th, tw)
+    for quality, crossed in zip(K.DCSWEEP_QUALITIES, (127, 255, 680, 2040)):
+        got = _held_to_the_reference(planes, th, tw, quality, 'dcsweep')
+        dc = np.concatenate([d.coefficients[0, :, 0] for d in got])
+        # the rule in plain integers: numerator 362^2 (S - 8192), divisor Q 2^20, rounded half away from zero; monotonic in S
+        q = int(got[0].divisors[0])
+        rule = [(1 if s > 8192 else -1) * ((362 * 362 * abs(s - 8192) + q * 2 ** 19) // (q * 2 ** 20)) for s in (0, 16320)]
+        assert np.all(np.diff(dc) >= 0) and [dc[0], dc[-1]] == rule
+        assert int((np.diff(dc) != 0).sum()) == rule[1] - rule[0] == crossed
+        if quality == 100:
+            assert np.array_equal(np.unique(dc), np.arange(-1024, 1017))
+
+
+def test_noise_on_the_tallest_tile_ends_its_intervals_every_way():
+    _, shape, (th, tw), _ = K.edge_shape('tallest')
+    (stream,) = K.expected_streams(K.edge_content('uniform', 'tallest', 100), th, tw, 100)
+    d = R.decode(stream)
+    assert len(d.pads) == 8187 and set(d.pads) == set(range(8))
+    last_ff = sum(data[-1] == 0xFF for data in d.intervals)
+    assert last_ff > 0
+    print(f'tallest uniform q100: {last_ff} of 8187 intervals end with FF; pads {np.bincount(d.pads).tolist()}')
+
+
+def test_the_quality_sweep_meets_every_divisor():
+    rule = set()
+    for quality in range(1, 101):
+        s = 5000 // quality if quality < 50 else 200 - 2 * quality
+        rule |= {min(255, max(1, (int(b) * s + 50) // 100)) for b in J.BASE_TABLE}
+    assert len(rule) == 251
+    planes = K.sweep_tile()
+    assert not planes[0, :8, 8:16].any() and (planes[0, 8:, 40:48] == 255).all()
+    met = set()
+    for quality in range(1, 101):
+        (d,) = _held_to_the_reference(planes, 16, 64, quality, 'sweep')
+        met |= set(d.divisors.tolist())
+    assert met == rule
+    print(f'quality sweep: largest (|cQ - n| - Q/2) / E = {WORST_EXCESS["sweep"]:.4f}')
+
+
+def test_no_tile_is_larger_than_libjpeg_reads():
+    """T.81 holds sides up to 65535, libjpeg (JPEG_MAX_DIMENSION) decodes nothing above 65500: the largest side the definition and
+    the library take is the largest multiple of 8 below that, and Pillow decodes it; the next one is refused by both, as Pillow
+    refuses its stream."""
+    Image = pil()
+    assert J.MAX_SIDE == 65496
+    L = native.lib()
+    for th, tw in ((8, J.MAX_SIDE), (J.MAX_SIDE, 8)):
+        tile = K.content('ramp', (1, th, tw))[0]
+        got = decode(J.encode_tile(tile, 100))
+        assert got.shape == (th, tw) and np.abs(got.astype(int) - tile).max() <= 2
+        assert L.sq_jpeg_chunk_count(1, th, tw, th, tw) == 1
+        assert L.sq_jpeg_out_bound(1, th, tw, native.SQ_U8, th, tw) > 0 and L.sq_jpeg_scratch_bytes(1, th, tw, native.SQ_U8, th, tw) > 0
+    for side in (65504, 65528, 65536):
+        for th, tw in ((8, side), (side, 8)):
+            with pytest.raises(ValueError, match='8..65496'):
+                J.header(th, tw, 90)
+            assert L.sq_jpeg_chunk_count(1, th, tw, th, tw) == native.SQ_ERR_UNSUPPORTED
+            assert L.sq_jpeg_out_bound(1, th, tw, native.SQ_U8, th, tw) == native.SQ_ERR_UNSUPPORTED
+    # what the limit is there for: the same header with the next side in it is a stream libjpeg does not open
+    s = bytearray(J.encode_tile(np.full((8, J.MAX_SIDE), 9, np.uint8), 50))
+    at = 2 + 69 + 7
+    assert s[at:at + 2] == bytes((J.MAX_SIDE >> 8, J.MAX_SIDE & 255))
+    s[at:at + 2] = bytes((65504 >> 8, 65504 & 255))
+    with pytest.raises(OSError):
+        with Image.open(io.BytesIO(bytes(s))) as im:
+            im.load()

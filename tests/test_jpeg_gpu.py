@@ -10,35 +10,9 @@ import stream_cases as SC
 from deflate_device import _dev, device_planes
 from image_stitcher_amd import jpegtile as J
 from image_stitcher_amd import native
+from jpeg_device import check_equal, device_streams
 
 pytestmark = pytest.mark.gpu
-
-
-def device_streams(buf):
-    offsets, out = buf.offsets.cpu().numpy(), buf.out.cpu().numpy()
-    assert offsets[0] == 0 and np.all(np.diff(offsets) >= 0) and offsets[-1] <= buf.bound
-    assert len(offsets) == buf.n_chunks + 1
-    return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(len(offsets) - 1)]
-
-
-def first_difference(got: bytes, want: bytes) -> str:
-    n = min(len(got), len(want))
-    at = next((i for i in range(n) if got[i] != want[i]), n)
-    return f'{len(got)} device / {len(want)} host bytes, first difference at {at}: {got[at:at + 8].hex()} / {want[at:at + 8].hex()}'
-
-
-def check_equal(planes, th, tw, quality, padded, label):
-    import torch
-    n, h, w = planes.shape
-    worst = int(native.lib().sq_jpeg_out_bound(n, h, w, native.SQ_U8, th, tw))
-    buf = native.jpeg_encode_planes(device_planes(planes, padded), th, tw, quality, capacity=worst)
-    torch.cuda.synchronize()
-    assert int(buf.status.item()) == 0, label
-    got, want = device_streams(buf), K.expected_streams(planes, th, tw, quality)
-    assert len(got) == len(want)
-    for i, (g, w_) in enumerate(zip(got, want)):
-        assert g == w_, f'{label}, tile {i}: {first_difference(g, w_)}'
-    return got
 
 
 @pytest.mark.parametrize('quality', K.QUALITIES)
