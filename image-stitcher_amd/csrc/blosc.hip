@@ -15,15 +15,14 @@
 //                       LDS, then a wave-parallel LZ4: every round the 64 lanes hash the 4 bytes at 64 consecutive
 //                       positions against a 2048-entry LDS table, ballot the verified matches, extend them 64 bytes at a
 //                       time and emit the sequences (literal runs copied 64 bytes per instruction).
-//   chunk_size_kernel / scan_kernel / assemble_kernel
-//                       chunk sizes -> exclusive scan -> headers, bstarts and blocks packed densely, so that only the
-//                       COMPRESSED bytes cross PCIe.
+//   chunk_size_kernel / assemble_kernel
+//                       chunk sizes -> exclusive scan (packed_stream.h) -> headers, bstarts and blocks packed densely, so that
+//                       only the COMPRESSED bytes cross PCIe.
+// Grid, argument checks, scratch carving and the scan are packed_stream.h's: a chunk is its tile, a block its part.
 // HBM-bound integer/byte work; nothing here is GEMM-shaped.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
-#include "common.h"
+#include "packed_stream.h"
 
 using namespace sq;
 
@@ -33,20 +32,16 @@ constexpr int BLK = 16384;                       // Blosc block size (bytes)
 constexpr int HBITS = 11, HSIZE = 1 << HBITS;
 constexpr int SLOT = BLK + BLK / 255 + 96;       // worst-case LZ4 output of one block + slack for the cooperative writers
 
-struct BloscParams {
+struct BloscParams {                  // tiles are the chunks, parts their 16 KiB blocks
     const void *planes;
     int64_t plane_stride, pitch;      // elements
     int32_t n_planes, h, w, esz;      // element size 1 or 2
-    int32_t cy, cx, ncy, ncx;         // chunk shape, chunks per plane
-    int32_t chunk_bytes, nb;          // uncompressed chunk size, blocks per chunk
-    int64_t n_chunks, n_blocks;
-    uint8_t *slots;                   // [n_blocks][SLOT]
-    uint32_t *blk_size;               // [n_blocks]
-    uint32_t *chunk_any;              // [n_chunks]
-    uint64_t *offsets;                // [n_chunks + 1]: chunk c lives at out[offsets[c] .. offsets[c + 1])
-    uint8_t *out;
-    int64_t out_capacity;
-    uint32_t *status;                 // [0] != 0: out too small
+    TileGrid g;
+    int32_t tile_bytes, parts;        // uncompressed chunk size, blocks per chunk
+    int64_t n_tiles, n_units;
+    uint8_t *slots;                   // [n_units][SLOT]
+    uint32_t *blk_size;               // [n_units]
+    PackedOut o;
 };
 
 __device__ __forceinline__ uint32_t load4(const uint32_t *w, int p) {   // 4 bytes at any byte offset of an LDS word array
@@ -68,24 +63,24 @@ __global__ __launch_bounds__(256) void lz4_blocks_kernel(const BloscParams P) {
     __shared__ uint16_t ht_all[4][HSIZE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t gb = (int64_t)blockIdx.x * 4 + wave;
-    if (gb >= P.n_blocks) return;     // whole wave
+    if (gb >= P.n_units) return;     // whole wave
     uint32_t *src = src_all[wave];
     uint16_t *ht = ht_all[wave];
     uint8_t *srcb = reinterpret_cast<uint8_t *>(src);
-    const int64_t chunk = gb / P.nb;
-    const int b = (int)(gb - chunk * P.nb);
-    const int per_plane = P.ncy * P.ncx;
+    const int64_t chunk = gb / P.parts;
+    const int b = (int)(gb - chunk * P.parts);
+    const int per_plane = P.g.nty * P.g.ntx;
     const int plane = (int)(chunk / per_plane);
-    const int ci = (int)(chunk - (int64_t)plane * per_plane);
-    const int cyi = ci / P.ncx, cxi = ci - cyi * P.ncx;
-    const int n = min(BLK, P.chunk_bytes - b * BLK);      // bytes of this block
+    const int ti = (int)(chunk - (int64_t)plane * per_plane);
+    const int cyi = ti / P.g.ntx, cxi = ti - cyi * P.g.ntx;
+    const int n = min(BLK, P.tile_bytes - b * BLK);      // bytes of this block
     const int nel = n / P.esz;
     const int e0 = b * (BLK / P.esz);                     // first chunk element of the block
     // ---- gather + byte shuffle into LDS --------------------------------------------------------------------------
     uint32_t any = 0;
     for (int e = lane; e < nel; e += 64) {
-        const int ce = e0 + e, row = ce / P.cx, col = ce - row * P.cx;
-        const int y = cyi * P.cy + row, x = cxi * P.cx + col;
+        const int ce = e0 + e, row = ce / P.g.tw, col = ce - row * P.g.tw;
+        const int y = cyi * P.g.th + row, x = cxi * P.g.tw + col;
         uint32_t v = 0;
         if (y < P.h && x < P.w) {
             const int64_t at = (int64_t)plane * P.plane_stride + (int64_t)y * P.pitch + x;
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(256) void lz4_blocks_kernel(const BloscParams P) {
     }
     if (lane < 32) src[(n + 3) / 4 + (lane & 7)] = 0;    // defined bytes past the end for load4
     for (int i = lane; i < HSIZE; i += 64) ht[i] = 0xFFFF;
-    if (__builtin_amdgcn_ballot_w64(any != 0) && lane == 0) atomicOr(&P.chunk_any[chunk], 1u);
+    if (__builtin_amdgcn_ballot_w64(any != 0) && lane == 0) atomicOr(&P.o.tile_any[chunk], 1u);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     // the tail write above must not clobber data: (n + 3) / 4 is the first word wholly past the block
@@ -177,94 +172,61 @@ __global__ __launch_bounds__(256) void lz4_blocks_kernel(const BloscParams P) {
 __global__ __launch_bounds__(64) void chunk_size_kernel(const BloscParams P, uint64_t *sizes) {
     const int64_t chunk = blockIdx.x;
     uint64_t s = 0;
-    for (int b = threadIdx.x; b < P.nb; b += 64) s += 4u + P.blk_size[chunk * P.nb + b];
+    for (int b = threadIdx.x; b < P.parts; b += 64) s += 4u + P.blk_size[chunk * P.parts + b];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (threadIdx.x == 0) sizes[chunk] = P.chunk_any[chunk] ? 16u + 4u * (uint64_t)P.nb + s : 0u;
-}
-
-// exclusive scan of n sizes in place -> offsets[0..n], one workgroup (n is a few hundred thousand at most)
-__global__ __launch_bounds__(1024) void scan_kernel(uint64_t *v, int64_t n, int64_t capacity, uint32_t *status) {
-    __shared__ uint64_t part[1024];
-    const int tid = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    uint64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += v[i];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t run = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const uint64_t t = part[i];
-            part[i] = run;
-            run += t;
-        }
-        v[n] = run;
-        if ((int64_t)run > capacity) *status = 1u;
-    }
-    __syncthreads();
-    uint64_t run = part[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-        const uint64_t t = v[i];
-        v[i] = run;
-        run += t;
-    }
+    if (threadIdx.x == 0) sizes[chunk] = P.o.tile_any[chunk] ? 16u + 4u * (uint64_t)P.parts + s : 0u;
 }
 
 __global__ __launch_bounds__(256) void assemble_kernel(const BloscParams P) {
-    if (*P.status) return;
+    if (*P.o.status) return;
     const int64_t chunk = blockIdx.x;
-    const uint64_t at = P.offsets[chunk], size = P.offsets[chunk + 1] - at;
+    const uint64_t at = P.o.offsets[chunk], size = P.o.offsets[chunk + 1] - at;
     if (size == 0) return;
-    uint8_t *dst = P.out + at;
+    uint8_t *dst = P.o.out + at;
     __shared__ uint32_t bstart[2048];     // chunk_bytes <= 2048 * BLK = 32 MiB
     const int tid = threadIdx.x;
     if (tid == 0) {
-        uint32_t run = 16u + 4u * (uint32_t)P.nb;
-        for (int b = 0; b < P.nb; ++b) {
+        uint32_t run = 16u + 4u * (uint32_t)P.parts;
+        for (int b = 0; b < P.parts; ++b) {
             bstart[b] = run;
-            run += 4u + P.blk_size[chunk * P.nb + b];
+            run += 4u + P.blk_size[chunk * P.parts + b];
         }
-        const uint32_t blocksize = (uint32_t)min(BLK, P.chunk_bytes);
+        const uint32_t blocksize = (uint32_t)min(BLK, P.tile_bytes);
         dst[0] = 2;                                                   // BLOSC_VERSION_FORMAT
         dst[1] = 1;                                                   // LZ4 format version
         dst[2] = (uint8_t)((P.esz > 1 ? 0x01 : 0x00) | 0x10 | (1 << 5));   // shuffle | don't split | LZ4
         dst[3] = (uint8_t)P.esz;
-        const uint32_t words[3] = {(uint32_t)P.chunk_bytes, blocksize, (uint32_t)size};
+        const uint32_t words[3] = {(uint32_t)P.tile_bytes, blocksize, (uint32_t)size};
         for (int k = 0; k < 3; ++k)
             for (int j = 0; j < 4; ++j) dst[4 + 4 * k + j] = (uint8_t)(words[k] >> (8 * j));
     }
     __syncthreads();
-    for (int b = tid; b < P.nb; b += 256)
+    for (int b = tid; b < P.parts; b += 256)
         for (int j = 0; j < 4; ++j) dst[16 + 4 * b + j] = (uint8_t)(bstart[b] >> (8 * j));
-    for (int b = 0; b < P.nb; ++b) {
-        const uint32_t cb = P.blk_size[chunk * P.nb + b];
+    for (int b = 0; b < P.parts; ++b) {
+        const uint32_t cb = P.blk_size[chunk * P.parts + b];
         uint8_t *o = dst + bstart[b];
         if (tid < 4) o[tid] = (uint8_t)(cb >> (8 * tid));
-        const uint8_t *s = P.slots + (chunk * P.nb + b) * SLOT;
+        const uint8_t *s = P.slots + (chunk * P.parts + b) * SLOT;
         for (uint32_t k = tid; k < cb; k += 256) o[4 + k] = s[k];
     }
 }
 
+constexpr const char *FN = "sq_blosc_encode_planes";
+
 int geometry(BloscParams &P, int32_t h, int32_t w, int32_t n_planes, int32_t dtype, int32_t cy, int32_t cx) {
-    if (h < 1 || w < 1 || n_planes < 0 || cy < 1 || cx < 1) return fail(SQ_ERR_INVALID, "sq_blosc: bad sizes (%dx%d planes %d chunks %dx%d)", h, w, n_planes, cy, cx);
-    if (dtype != SQ_U8 && dtype != SQ_U16) return fail(SQ_ERR_UNSUPPORTED, "sq_blosc: dtype %d (uint8 / uint16 planes)", dtype);
-    P.esz = dtype == SQ_U16 ? 2 : 1;
-    P.h = h;
-    P.w = w;
-    P.n_planes = n_planes;
-    P.cy = cy;                   // as given: the caller clamps a chunk dimension to the ARRAY's (zarr's rule) -- a row band
-    P.cx = cx;                   // of a plane is shorter than the array and still has full-height, zero-padded chunks
-    P.ncy = (h + P.cy - 1) / P.cy;
-    P.ncx = (w + P.cx - 1) / P.cx;
-    const int64_t cb = (int64_t)P.cy * P.cx * P.esz;
-    if (cb > (int64_t)2048 * BLK) return fail(SQ_ERR_UNSUPPORTED, "sq_blosc: chunks of %lld bytes (at most 32 MiB)", (long long)cb);
-    P.chunk_bytes = (int32_t)cb;
-    P.nb = (int32_t)((cb + BLK - 1) / BLK);
-    P.n_chunks = (int64_t)n_planes * P.ncy * P.ncx;
-    P.n_blocks = P.n_chunks * P.nb;
-    return SQ_OK;
+    int rc = stream_grid(P.g, P.n_tiles, "sq_blosc", "chunks", false, h, w, n_planes, cy, cx);
+    if (rc == SQ_OK) rc = stream_byte_parts(P.g, "sq_blosc", "chunks", dtype, P.esz, P.tile_bytes, P.parts);
+    P.n_planes = n_planes, P.h = h, P.w = w;
+    P.n_units = P.n_tiles * P.parts;
+    return rc;
 }
-int64_t up256(int64_t v) { return (v + 255) & ~int64_t(255); }
+
+void carve(BloscParams &P, Scratch &sc) {
+    P.slots = sc.take<uint8_t>(P.n_units * SLOT);
+    P.blk_size = sc.take<uint32_t>(P.n_units);
+    P.o.tile_any = sc.take<uint32_t>(P.n_tiles);
+}
 
 }  // namespace
 
@@ -272,62 +234,46 @@ extern "C" int64_t sq_blosc_chunk_count(int32_t n_planes, int32_t h, int32_t w, 
     BloscParams P{};   // the count does not depend on the element size: refuse only what no dtype could encode
     const int rc = geometry(P, h, w, n_planes, SQ_U8, cy, cx);
     if (rc != SQ_OK) return rc;
-    return P.n_chunks;
+    return P.n_tiles;
 }
 
 extern "C" int64_t sq_blosc_out_bound(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t cy, int32_t cx) {
     BloscParams P{};
     const int rc = geometry(P, h, w, n_planes, dtype, cy, cx);
     if (rc != SQ_OK) return rc;
-    return P.n_chunks * (16 + 8 * (int64_t)P.nb + P.chunk_bytes);
+    return P.n_tiles * (16 + 8 * (int64_t)P.parts + P.tile_bytes);
 }
 
 extern "C" int64_t sq_blosc_scratch_bytes(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t cy, int32_t cx) {
     BloscParams P{};
     const int rc = geometry(P, h, w, n_planes, dtype, cy, cx);
     if (rc != SQ_OK) return rc;
-    return up256(P.n_blocks * SLOT) + up256(P.n_blocks * 4) + up256(P.n_chunks * 4) + 256;
+    Scratch sc{0};
+    carve(P, sc);
+    return sc.bytes();
 }
 
 extern "C" int sq_blosc_encode_planes(const void *planes_dev, int64_t plane_stride, int64_t pitch, int32_t n_planes, int32_t h,
                                       int32_t w, int32_t dtype, int32_t chunk_h, int32_t chunk_w, void *scratch_dev,
                                       int64_t scratch_bytes, uint64_t *offsets_dev, void *out_dev, int64_t out_capacity,
                                       uint32_t *status_dev, void *stream_) {
-    if (!planes_dev || !scratch_dev || !offsets_dev || !out_dev || !status_dev) return fail(SQ_ERR_INVALID, "sq_blosc_encode_planes: NULL argument");
-    BloscParams P{};
-    int rc = geometry(P, h, w, n_planes, dtype, chunk_h, chunk_w);
+    int rc = stream_null(FN, planes_dev, scratch_dev, offsets_dev, out_dev, status_dev);
     if (rc != SQ_OK) return rc;
-    if (pitch < w || (n_planes > 1 && plane_stride < (int64_t)(h - 1) * pitch + w))
-        return fail(SQ_ERR_INVALID, "sq_blosc_encode_planes: pitch / plane stride smaller than the plane");
-    if (scratch_bytes < sq_blosc_scratch_bytes(n_planes, h, w, dtype, chunk_h, chunk_w))
-        return fail(SQ_ERR_WORKSPACE, "sq_blosc_encode_planes: scratch %lld < %lld bytes", (long long)scratch_bytes,
-                    (long long)sq_blosc_scratch_bytes(n_planes, h, w, dtype, chunk_h, chunk_w));
-    if (reinterpret_cast<uintptr_t>(scratch_dev) % 256 || reinterpret_cast<uintptr_t>(offsets_dev) % 8)
-        return fail(SQ_ERR_INVALID, "sq_blosc_encode_planes: scratch must be 256-byte, offsets 8-byte aligned");
-    if (P.n_blocks > (int64_t)4 * 2147483647 || P.n_chunks > 2147483647) return fail(SQ_ERR_UNSUPPORTED, "sq_blosc_encode_planes: too many chunks");
+    BloscParams P{};
+    rc = geometry(P, h, w, n_planes, dtype, chunk_h, chunk_w);
+    if (rc != SQ_OK) return rc;
+    Scratch sc{reinterpret_cast<uintptr_t>(scratch_dev)};
+    carve(P, sc);
+    rc = stream_args(FN, P.o, n_planes, h, w, plane_stride, pitch, scratch_dev, scratch_bytes, sc.bytes(), offsets_dev, out_dev, out_capacity, status_dev);
+    if (rc != SQ_OK) return rc;
+    if (P.n_units > (int64_t)4 * 2147483647 || P.n_tiles > 2147483647) return fail(SQ_ERR_UNSUPPORTED, "%s: too many chunks", FN);
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    if (P.n_chunks == 0) {
-        if (hipMemsetAsync(offsets_dev, 0, 8, s) != hipSuccess) return fail(SQ_ERR_HIP, "sq_blosc_encode_planes: memset");
-        return SQ_OK;
-    }
-    char *sc = static_cast<char *>(scratch_dev);
-    P.planes = planes_dev;
-    P.plane_stride = plane_stride;
-    P.pitch = pitch;
-    P.slots = reinterpret_cast<uint8_t *>(sc);
-    P.blk_size = reinterpret_cast<uint32_t *>(sc + up256(P.n_blocks * SLOT));
-    P.chunk_any = reinterpret_cast<uint32_t *>(sc + up256(P.n_blocks * SLOT) + up256(P.n_blocks * 4));
-    P.offsets = offsets_dev;
-    P.out = static_cast<uint8_t *>(out_dev);
-    P.out_capacity = out_capacity;
-    P.status = status_dev;
-    if (hipMemsetAsync(P.chunk_any, 0, (size_t)P.n_chunks * 4, s) != hipSuccess || hipMemsetAsync(status_dev, 0, 4, s) != hipSuccess)
-        return fail(SQ_ERR_HIP, "sq_blosc_encode_planes: memset");
-    hipLaunchKernelGGL(lz4_blocks_kernel, dim3((unsigned)((P.n_blocks + 3) / 4)), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(chunk_size_kernel, dim3((unsigned)P.n_chunks), dim3(64), 0, s, P, offsets_dev);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, offsets_dev, P.n_chunks, out_capacity, status_dev);
-    hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)P.n_chunks), dim3(256), 0, s, P);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_blosc_encode_planes: launch failed: %s", hipGetErrorString(e));
-    return SQ_OK;
+    rc = stream_begin(FN, P.o, P.n_tiles, s);
+    if (rc != SQ_OK || P.n_tiles == 0) return rc;
+    P.planes = planes_dev, P.plane_stride = plane_stride, P.pitch = pitch;
+    hipLaunchKernelGGL(lz4_blocks_kernel, dim3((unsigned)((P.n_units + 3) / 4)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(chunk_size_kernel, dim3((unsigned)P.n_tiles), dim3(64), 0, s, P, offsets_dev);
+    stream_scan(P.o, P.n_tiles, s);
+    hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)P.n_tiles), dim3(256), 0, s, P);
+    return stream_end(FN);
 }

@@ -25,16 +25,16 @@
 //                            every lane its bit position, the bits are OR-ed into a window of LDS words that is flushed to
 //                            the segment's slot as whole words.  The exact size is known before pass 2, so a segment that
 //                            would not shrink is stored instead and no write can pass the slot.
-//   tile_size_kernel / scan_kernel / assemble_kernel
-//                            tile sizes -> exclusive scan -> header, segments and the combined Adler-32 packed densely, so
-//                            that only the COMPRESSED bytes cross PCIe (as in blosc.hip).
+//   tile_size_kernel / deflate_assemble_kernel
+//                            tile sizes -> exclusive scan (packed_stream.h) -> header, segments and the combined Adler-32 packed
+//                            densely, so that only the COMPRESSED bytes cross PCIe.
+// Grid, argument checks, scratch carving, wave helpers and the scan are packed_stream.h's: a segment is a part of its tile.
 // Integer / bit work out of LDS; nothing here is GEMM-shaped.  22 KiB of LDS per wave: 7 waves per CU.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "packed_stream.h"
 
 using namespace sq;
 
@@ -47,22 +47,18 @@ constexpr int NLITLEN = 286;
 constexpr int STAGE = 160;              // LDS words of the bit window (at most 64 kept + 64 new + the partial one)
 constexpr uint32_t ADLER = 65521u;
 
-struct DeflateParams {
+struct DeflateParams {                // parts are the tile's 16 KiB segments
     const void *planes;
     int64_t plane_stride, pitch;      // elements
     int32_t n_planes, h, w, esz;      // element size 1 or 2
-    int32_t th, tw, nty, ntx;         // tile shape, tiles per plane
-    int32_t tile_bytes, nseg;         // uncompressed tile size, segments per tile
+    TileGrid g;
+    int32_t tile_bytes, parts;        // uncompressed tile size, segments per tile
     int32_t predictor;                // 1: none, 2: horizontal differencing
-    int64_t n_tiles, n_segs;
-    uint8_t *slots;                   // [n_segs][SLOT]
-    uint32_t *seg_size;               // [n_segs]
-    uint32_t *seg_adler;              // [n_segs]: sum of bytes | weighted sum << 16, both mod 65521
-    uint32_t *tile_any;               // [n_tiles]
-    uint64_t *offsets;                // [n_tiles + 1]
-    uint8_t *out;
-    int64_t out_capacity;
-    uint32_t *status;                 // [0] != 0: out too small
+    int64_t n_tiles, n_units;
+    uint8_t *slots;                   // [n_units][SLOT]
+    uint32_t *seg_size;               // [n_units]
+    uint32_t *seg_adler;              // [n_units]: sum of bytes | weighted sum << 16, both mod 65521
+    PackedOut o;
 };
 
 struct WaveLds {
@@ -75,16 +71,6 @@ struct WaveLds {
     uint32_t bl[16], next[16];
     uint32_t info[4];                 // data bits, literal / length codes sent
 };
-
-__device__ __forceinline__ void wave_sync() {   // LDS (and slot) writes of this wave are visible to its other lanes
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // first index j in [cs, lim) whose bit is clear, else lim (lim <= number of elements: no word past the last is read)
 __device__ __forceinline__ int run_end(const uint64_t *eqw, int cs, int lim) {
@@ -150,11 +136,7 @@ __device__ __forceinline__ void flush(Emitter &E, int full, int lane) {      // 
 
 // every lane appends nb (0..32) bits of val, in lane order; called by the whole wave
 __device__ __forceinline__ void emit(Emitter &E, uint32_t val, int nb, int lane) {
-    int incl = nb;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
+    const int incl = wave_scan(nb, lane);
     const int total = __shfl(incl, 63);
     if (nb) {
         const int pos = E.bitpos + incl - nb;
@@ -256,23 +238,23 @@ __global__ __launch_bounds__(64) void deflate_segments_kernel(const DeflateParam
     __shared__ WaveLds L;
     const int lane = threadIdx.x;
     const int64_t gs = blockIdx.x;
-    const int64_t tile = gs / P.nseg;
-    const int b = (int)(gs - tile * P.nseg);
-    const int per_plane = P.nty * P.ntx;
+    const int64_t tile = gs / P.parts;
+    const int b = (int)(gs - tile * P.parts);
+    const int per_plane = P.g.nty * P.g.ntx;
     const int plane = (int)(tile / per_plane);
     const int ti = (int)(tile - (int64_t)plane * per_plane);
-    const int tyi = ti / P.ntx, txi = ti - tyi * P.ntx;
+    const int tyi = ti / P.g.ntx, txi = ti - tyi * P.g.ntx;
     const int n = min(SEG, P.tile_bytes - b * SEG);      // bytes of this segment (a multiple of ESZ)
     const int nel = n / ESZ;
     const int e0 = b * (SEG / ESZ);
-    const bool last = b == P.nseg - 1;
+    const bool last = b == P.parts - 1;
     T *el = reinterpret_cast<T *>(L.src);
     const T *in = static_cast<const T *>(P.planes);
     // ---- gather + predictor into LDS, Adler sums ------------------------------------------------------------------
     uint32_t any = 0, a1 = 0, a2 = 0;
     for (int e = lane; e < nel; e += 64) {
-        const int ce = e0 + e, row = ce / P.tw, col = ce - row * P.tw;
-        const int y = tyi * P.th + row, x = txi * P.tw + col;
+        const int ce = e0 + e, row = ce / P.g.tw, col = ce - row * P.g.tw;
+        const int y = tyi * P.g.th + row, x = txi * P.g.tw + col;
         uint32_t v = 0, left = 0;
         if (y < P.h) {
             const int64_t at = (int64_t)plane * P.plane_stride + (int64_t)y * P.pitch + x;
@@ -293,7 +275,7 @@ __global__ __launch_bounds__(64) void deflate_segments_kernel(const DeflateParam
     }
     for (int i = lane; i < NSYM; i += 64) L.tab[i] = 0;
     for (int i = lane; i < STAGE; i += 64) L.stage[i] = 0;
-    if (__builtin_amdgcn_ballot_w64(any != 0) && lane == 0) atomicOr(&P.tile_any[tile], 1u);
+    if (__builtin_amdgcn_ballot_w64(any != 0) && lane == 0) atomicOr(&P.o.tile_any[tile], 1u);
     {
         const uint32_t s1 = (uint32_t)wave_sum((int)(a1 % ADLER)) % ADLER, s2 = (uint32_t)wave_sum((int)(a2 % ADLER)) % ADLER;
         if (lane == 0) P.seg_adler[gs] = s1 | (s2 << 16);
@@ -442,53 +424,25 @@ __global__ __launch_bounds__(64) void deflate_segments_kernel(const DeflateParam
 __global__ __launch_bounds__(64) void tile_size_kernel(const DeflateParams P, uint64_t *sizes) {
     const int64_t tile = blockIdx.x;
     uint64_t s = 0;
-    for (int b = threadIdx.x; b < P.nseg; b += 64) s += P.seg_size[tile * P.nseg + b];
+    for (int b = threadIdx.x; b < P.parts; b += 64) s += P.seg_size[tile * P.parts + b];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (threadIdx.x == 0) sizes[tile] = P.tile_any[tile] ? 2u + s + 4u : 0u;
-}
-
-// exclusive scan of n sizes in place -> offsets[0..n], one workgroup (blosc.hip's, for this file's launch)
-__global__ __launch_bounds__(1024) void deflate_scan_kernel(uint64_t *v, int64_t n, int64_t capacity, uint32_t *status) {
-    __shared__ uint64_t part[1024];
-    const int tid = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    uint64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += v[i];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t run = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const uint64_t t = part[i];
-            part[i] = run;
-            run += t;
-        }
-        v[n] = run;
-        if ((int64_t)run > capacity) *status = 1u;
-    }
-    __syncthreads();
-    uint64_t run = part[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-        const uint64_t t = v[i];
-        v[i] = run;
-        run += t;
-    }
+    if (threadIdx.x == 0) sizes[tile] = P.o.tile_any[tile] ? 2u + s + 4u : 0u;
 }
 
 __global__ __launch_bounds__(256) void deflate_assemble_kernel(const DeflateParams P) {
-    if (*P.status) return;
+    if (*P.o.status) return;
     const int64_t tile = blockIdx.x;
-    const uint64_t at = P.offsets[tile], size = P.offsets[tile + 1] - at;
+    const uint64_t at = P.o.offsets[tile], size = P.o.offsets[tile + 1] - at;
     if (size == 0) return;
-    uint8_t *dst = P.out + at;
+    uint8_t *dst = P.o.out + at;
     __shared__ uint32_t start[2048];      // tile_bytes <= 2048 * SEG = 32 MiB
     const int tid = threadIdx.x;
     if (tid == 0) {
         uint32_t run = 2, a = 1, b = 0;   // Adler-32 of the concatenation, from the segments' sums
-        for (int s = 0; s < P.nseg; ++s) {
+        for (int s = 0; s < P.parts; ++s) {
             start[s] = run;
-            run += P.seg_size[tile * P.nseg + s];
-            const uint32_t ad = P.seg_adler[tile * P.nseg + s];
+            run += P.seg_size[tile * P.parts + s];
+            const uint32_t ad = P.seg_adler[tile * P.parts + s];
             const uint32_t len = (uint32_t)min(SEG, P.tile_bytes - s * SEG);
             b = (uint32_t)((b + (uint64_t)len * a + (ad >> 16)) % ADLER);
             a = (a + (ad & 0xFFFFu)) % ADLER;
@@ -499,35 +453,30 @@ __global__ __launch_bounds__(256) void deflate_assemble_kernel(const DeflatePara
         for (int j = 0; j < 4; ++j) dst[run + j] = (uint8_t)(adler >> (24 - 8 * j));
     }
     __syncthreads();
-    for (int s = 0; s < P.nseg; ++s) {
-        const uint32_t cb = P.seg_size[tile * P.nseg + s];
+    for (int s = 0; s < P.parts; ++s) {
+        const uint32_t cb = P.seg_size[tile * P.parts + s];
         uint8_t *o = dst + start[s];
-        const uint8_t *src = P.slots + (tile * P.nseg + s) * SLOT;
+        const uint8_t *src = P.slots + (tile * P.parts + s) * SLOT;
         for (uint32_t k = tid; k < cb; k += 256) o[k] = src[k];
     }
 }
 
+constexpr const char *FN = "sq_deflate_encode_planes";
+
 int geometry(DeflateParams &P, int32_t h, int32_t w, int32_t n_planes, int32_t dtype, int32_t th, int32_t tw) {
-    if (h < 1 || w < 1 || n_planes < 0 || th < 1 || tw < 1)
-        return fail(SQ_ERR_INVALID, "sq_deflate: bad sizes (%dx%d planes %d tiles %dx%d)", h, w, n_planes, th, tw);
-    if (dtype != SQ_U8 && dtype != SQ_U16) return fail(SQ_ERR_UNSUPPORTED, "sq_deflate: dtype %d (uint8 / uint16 planes)", dtype);
-    P.esz = dtype == SQ_U16 ? 2 : 1;
-    P.h = h;
-    P.w = w;
-    P.n_planes = n_planes;
-    P.th = th;                   // as given: a TIFF tile is always full, zero-padded past the plane's edge
-    P.tw = tw;
-    P.nty = (h + th - 1) / th;
-    P.ntx = (w + tw - 1) / tw;
-    const int64_t tb = (int64_t)th * tw * P.esz;
-    if (tb > (int64_t)2048 * SEG) return fail(SQ_ERR_UNSUPPORTED, "sq_deflate: tiles of %lld bytes (at most 32 MiB)", (long long)tb);
-    P.tile_bytes = (int32_t)tb;
-    P.nseg = (int32_t)((tb + SEG - 1) / SEG);
-    P.n_tiles = (int64_t)n_planes * P.nty * P.ntx;
-    P.n_segs = P.n_tiles * P.nseg;
-    return SQ_OK;
+    int rc = stream_grid(P.g, P.n_tiles, "sq_deflate", "tiles", false, h, w, n_planes, th, tw);
+    if (rc == SQ_OK) rc = stream_byte_parts(P.g, "sq_deflate", "tiles", dtype, P.esz, P.tile_bytes, P.parts);
+    P.n_planes = n_planes, P.h = h, P.w = w;
+    P.n_units = P.n_tiles * P.parts;
+    return rc;
 }
-int64_t up256(int64_t v) { return (v + 255) & ~int64_t(255); }
+
+void carve(DeflateParams &P, Scratch &sc) {
+    P.slots = sc.take<uint8_t>(P.n_units * SLOT);
+    P.seg_size = sc.take<uint32_t>(P.n_units);
+    P.seg_adler = sc.take<uint32_t>(P.n_units);
+    P.o.tile_any = sc.take<uint32_t>(P.n_tiles);
+}
 
 }  // namespace
 
@@ -542,67 +491,45 @@ extern "C" int64_t sq_deflate_out_bound(int32_t n_planes, int32_t h, int32_t w, 
     DeflateParams P{};
     const int rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
     if (rc != SQ_OK) return rc;
-    return P.n_tiles * (2 + 4 + 5 * (int64_t)P.nseg + P.tile_bytes);      // every segment stored
+    return P.n_tiles * (2 + 4 + 5 * (int64_t)P.parts + P.tile_bytes);      // every segment stored
 }
 
 extern "C" int64_t sq_deflate_scratch_bytes(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w) {
     DeflateParams P{};
     const int rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
     if (rc != SQ_OK) return rc;
-    return up256(P.n_segs * SLOT) + 2 * up256(P.n_segs * 4) + up256(P.n_tiles * 4) + 256;
+    Scratch sc{0};
+    carve(P, sc);
+    return sc.bytes();
 }
 
 extern "C" int sq_deflate_encode_planes(const void *planes_dev, int64_t plane_stride, int64_t pitch, int32_t n_planes, int32_t h,
                                         int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w, int32_t predictor,
                                         void *scratch_dev, int64_t scratch_bytes, uint64_t *offsets_dev, void *out_dev,
                                         int64_t out_capacity, uint32_t *status_dev, void *stream_) {
-    if (!planes_dev || !scratch_dev || !offsets_dev || !out_dev || !status_dev) return fail(SQ_ERR_INVALID, "sq_deflate_encode_planes: NULL argument");
-    DeflateParams P{};
-    int rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
+    int rc = stream_null(FN, planes_dev, scratch_dev, offsets_dev, out_dev, status_dev);
     if (rc != SQ_OK) return rc;
-    if (predictor != 1 && predictor != 2) return fail(SQ_ERR_INVALID, "sq_deflate_encode_planes: predictor %d (1: none, 2: horizontal)", predictor);
-    if (out_capacity < 0) return fail(SQ_ERR_INVALID, "sq_deflate_encode_planes: negative out_capacity");
-    if (pitch < w || (n_planes > 1 && plane_stride < (int64_t)(h - 1) * pitch + w))
-        return fail(SQ_ERR_INVALID, "sq_deflate_encode_planes: pitch / plane stride smaller than the plane");
-    if (scratch_bytes < sq_deflate_scratch_bytes(n_planes, h, w, dtype, tile_h, tile_w))
-        return fail(SQ_ERR_WORKSPACE, "sq_deflate_encode_planes: scratch %lld < %lld bytes", (long long)scratch_bytes,
-                    (long long)sq_deflate_scratch_bytes(n_planes, h, w, dtype, tile_h, tile_w));
-    if (reinterpret_cast<uintptr_t>(scratch_dev) % 256 || reinterpret_cast<uintptr_t>(offsets_dev) % 8)
-        return fail(SQ_ERR_INVALID, "sq_deflate_encode_planes: scratch must be 256-byte, offsets 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(planes_dev) % P.esz) return fail(SQ_ERR_INVALID, "sq_deflate_encode_planes: planes not aligned to their element");
-    if (P.n_segs > 2147483647) return fail(SQ_ERR_UNSUPPORTED, "sq_deflate_encode_planes: too many tiles");
+    DeflateParams P{};
+    rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
+    if (rc != SQ_OK) return rc;
+    if (predictor != 1 && predictor != 2) return fail(SQ_ERR_INVALID, "%s: predictor %d (1: none, 2: horizontal)", FN, predictor);
+    Scratch sc{reinterpret_cast<uintptr_t>(scratch_dev)};
+    carve(P, sc);
+    rc = stream_args(FN, P.o, n_planes, h, w, plane_stride, pitch, scratch_dev, scratch_bytes, sc.bytes(), offsets_dev, out_dev, out_capacity, status_dev);
+    if (rc != SQ_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(planes_dev) % P.esz) return fail(SQ_ERR_INVALID, "%s: planes not aligned to their element", FN);
+    if (P.n_units > 2147483647) return fail(SQ_ERR_UNSUPPORTED, "%s: too many tiles", FN);
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    if (P.n_tiles == 0) {
-        if (hipMemsetAsync(offsets_dev, 0, 8, s) != hipSuccess || hipMemsetAsync(status_dev, 0, 4, s) != hipSuccess)
-            return fail(SQ_ERR_HIP, "sq_deflate_encode_planes: memset");
-        return SQ_OK;
-    }
-    char *sc = static_cast<char *>(scratch_dev);
-    P.planes = planes_dev;
-    P.plane_stride = plane_stride;
-    P.pitch = pitch;
+    rc = stream_begin(FN, P.o, P.n_tiles, s);
+    if (rc != SQ_OK || P.n_tiles == 0) return rc;
+    P.planes = planes_dev, P.plane_stride = plane_stride, P.pitch = pitch;
     P.predictor = predictor;
-    P.slots = reinterpret_cast<uint8_t *>(sc);
-    sc += up256(P.n_segs * SLOT);
-    P.seg_size = reinterpret_cast<uint32_t *>(sc);
-    sc += up256(P.n_segs * 4);
-    P.seg_adler = reinterpret_cast<uint32_t *>(sc);
-    sc += up256(P.n_segs * 4);
-    P.tile_any = reinterpret_cast<uint32_t *>(sc);
-    P.offsets = offsets_dev;
-    P.out = static_cast<uint8_t *>(out_dev);
-    P.out_capacity = out_capacity;
-    P.status = status_dev;
-    if (hipMemsetAsync(P.tile_any, 0, (size_t)P.n_tiles * 4, s) != hipSuccess || hipMemsetAsync(status_dev, 0, 4, s) != hipSuccess)
-        return fail(SQ_ERR_HIP, "sq_deflate_encode_planes: memset");
     if (P.esz == 2)
-        hipLaunchKernelGGL(deflate_segments_kernel<2>, dim3((unsigned)P.n_segs), dim3(64), 0, s, P);
+        hipLaunchKernelGGL(deflate_segments_kernel<2>, dim3((unsigned)P.n_units), dim3(64), 0, s, P);
     else
-        hipLaunchKernelGGL(deflate_segments_kernel<1>, dim3((unsigned)P.n_segs), dim3(64), 0, s, P);
+        hipLaunchKernelGGL(deflate_segments_kernel<1>, dim3((unsigned)P.n_units), dim3(64), 0, s, P);
     hipLaunchKernelGGL(tile_size_kernel, dim3((unsigned)P.n_tiles), dim3(64), 0, s, P, offsets_dev);
-    hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(1024), 0, s, offsets_dev, P.n_tiles, out_capacity, status_dev);
+    stream_scan(P.o, P.n_tiles, s);
     hipLaunchKernelGGL(deflate_assemble_kernel, dim3((unsigned)P.n_tiles), dim3(256), 0, s, P);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_deflate_encode_planes: launch failed: %s", hipGetErrorString(e));
-    return SQ_OK;
+    return stream_end(FN);
 }

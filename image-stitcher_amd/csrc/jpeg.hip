@@ -26,15 +26,16 @@
 //                            EMIT = false only counts the stuffed bytes (and notes whether the tile holds a non-zero pixel);
 //                            EMIT = true repeats the work and writes to the interval's final place -- the exact sizes are known
 //                            before any byte is written, so nothing can pass out_capacity and no slot memory is needed.
-//   jpeg_tile_kernel / jpeg_scan_kernel
-//                            interval sizes -> interval starts inside the tile and the tile's size -> exclusive scan.
+//   jpeg_tile_kernel         interval sizes -> interval starts inside the tile and the tile's size -> exclusive scan
+//                            (packed_stream.h).
+// Grid, argument checks, scratch carving, wave helpers and the scan are packed_stream.h's: an interval is a part of its tile.
 // Integer / bit work out of LDS; nothing here is GEMM-shaped.  A wave holds 22 KiB of LDS (8 KiB coefficients, 13 KiB bit window
 // -- the worst case of 64 blocks, 20 + 63 * 26 bits each --, 1 KiB code tables): 7 waves per CU.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "common.h"
+#include "packed_stream.h"
 
 using namespace sq;
 
@@ -94,20 +95,16 @@ constexpr Tables make_tables() {
 constexpr Tables TABLES = make_tables();
 __constant__ Tables d_tables = make_tables();
 
-struct JpegParams {
+struct JpegParams {                   // parts are the tile's restart intervals (rows of blocks)
     const uint8_t *planes;
     int64_t plane_stride, pitch;      // elements
     int32_t n_planes, h, w;
-    int32_t th, tw, nty, ntx;         // tile shape, tiles per plane
-    int32_t nint, nblk;               // intervals (block rows) per tile, blocks per interval
+    int32_t th, tw, nty, ntx;         // TileGrid's fields, flat: the struct embedded here changed the counting pass's code
+    int32_t parts, nblk;              // intervals per tile, blocks per interval
     int32_t aligned;                  // every block row starts on an 8-byte boundary
-    int64_t n_tiles, n_ints;
-    uint32_t *int_size;               // [n_ints]: stuffed bytes of the interval, then its start behind the tile's header
-    uint32_t *tile_any;               // [n_tiles]
-    uint64_t *offsets;                // [n_tiles + 1]
-    uint8_t *out;
-    int64_t out_capacity;
-    uint32_t *status;                 // [0] != 0: out too small
+    int64_t n_tiles, n_units;
+    uint32_t *int_size;               // [n_units]: stuffed bytes of the interval, then its start behind the tile's header
+    PackedOut o;
     uint32_t recip[64];               // floor(2^16 / Q), natural order
     uint8_t q[64];                    // the divisors Q, natural order
     uint8_t header[HEADER];
@@ -119,19 +116,6 @@ struct WaveLds {
     uint32_t ac[256];
     uint32_t dc[12];
 };
-
-__device__ __forceinline__ void wave_sync() {   // LDS writes of this wave are visible to its other lanes
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int wave_scan(int v, int lane) {      // inclusive
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
 
 // one 8-point pass over a[0], a[S], .., a[7 S]: out[u] = sum_j CM[u][j] a[j], through the symmetry CM[u][7 - j] = (-1)^u CM[u][j]
 template <int S>
@@ -238,18 +222,18 @@ __global__ __launch_bounds__(64) void jpeg_intervals_kernel(const JpegParams P) 
     __shared__ WaveLds L;
     const int lane = threadIdx.x;
     const int64_t gi = blockIdx.x;
-    const int64_t tile = gi / P.nint;
-    const int b = (int)(gi - tile * P.nint);
+    const int64_t tile = gi / P.parts;
+    const int b = (int)(gi - tile * P.parts);
     const int per_plane = P.nty * P.ntx;
     const int plane = (int)(tile / per_plane);
     const int ti = (int)(tile - (int64_t)plane * per_plane);
     const int tyi = ti / P.ntx, txi = ti - tyi * P.ntx;
     uint8_t *dst = nullptr;
     if (EMIT) {
-        if (*P.status) return;
-        const uint64_t at = P.offsets[tile];
-        if (P.offsets[tile + 1] == at) return;      // a tile of zeros
-        uint8_t *base = P.out + at;
+        if (*P.o.status) return;
+        const uint64_t at = P.o.offsets[tile];
+        if (P.o.offsets[tile + 1] == at) return;      // a tile of zeros
+        uint8_t *base = P.o.out + at;
         if (b == 0)
             for (int k = lane; k < HEADER; k += 64) base[k] = P.header[k];
         dst = base + HEADER + P.int_size[gi];
@@ -336,11 +320,11 @@ __global__ __launch_bounds__(64) void jpeg_intervals_kernel(const JpegParams P) 
     if (EMIT) {
         if (lane == 0) {                        // RSTm between intervals, EOI behind the last
             dst[done] = 0xFF;
-            dst[done + 1] = b == P.nint - 1 ? 0xD9 : (uint8_t)(0xD0 + (b & 7));
+            dst[done + 1] = b == P.parts - 1 ? 0xD9 : (uint8_t)(0xD0 + (b & 7));
         }
     } else {
         if (lane == 0) P.int_size[gi] = (uint32_t)done;
-        if (__builtin_amdgcn_ballot_w64(any != 0) && lane == 0) atomicOr(&P.tile_any[tile], 1u);
+        if (__builtin_amdgcn_ballot_w64(any != 0) && lane == 0) atomicOr(&P.o.tile_any[tile], 1u);
     }
 }
 
@@ -348,68 +332,40 @@ __global__ __launch_bounds__(64) void jpeg_intervals_kernel(const JpegParams P) 
 __global__ __launch_bounds__(64) void jpeg_tile_kernel(const JpegParams P, uint64_t *sizes) {
     const int64_t tile = blockIdx.x;
     const int lane = threadIdx.x;
-    uint32_t *v = P.int_size + tile * P.nint;
+    uint32_t *v = P.int_size + tile * P.parts;
     uint32_t run = 0;
-    for (int i0 = 0; i0 < P.nint; i0 += 64) {
+    for (int i0 = 0; i0 < P.parts; i0 += 64) {
         const int i = i0 + lane;
-        const int n = i < P.nint ? (int)v[i] + 2 : 0;
+        const int n = i < P.parts ? (int)v[i] + 2 : 0;
         const int incl = wave_scan(n, lane);
-        if (i < P.nint) v[i] = run + (uint32_t)(incl - n);
+        if (i < P.parts) v[i] = run + (uint32_t)(incl - n);
         run += (uint32_t)__shfl(incl, 63);
     }
-    if (lane == 0) sizes[tile] = P.tile_any[tile] ? (uint64_t)HEADER + run : 0u;
+    if (lane == 0) sizes[tile] = P.o.tile_any[tile] ? (uint64_t)HEADER + run : 0u;
 }
 
-// exclusive scan of n sizes in place -> offsets[0..n], one workgroup (deflate.hip's, for this file's launch)
-__global__ __launch_bounds__(1024) void jpeg_scan_kernel(uint64_t *v, int64_t n, int64_t capacity, uint32_t *status) {
-    __shared__ uint64_t part[1024];
-    const int tid = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    uint64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += v[i];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t run = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const uint64_t t = part[i];
-            part[i] = run;
-            run += t;
-        }
-        v[n] = run;
-        if ((int64_t)run > capacity) *status = 1u;
-    }
-    __syncthreads();
-    uint64_t run = part[tid];
-    for (int64_t i = lo; i < hi; ++i) {
-        const uint64_t t = v[i];
-        v[i] = run;
-        run += t;
-    }
-}
+constexpr const char *FN = "sq_jpeg_encode_planes";
 
 int geometry(JpegParams &P, int32_t h, int32_t w, int32_t n_planes, int32_t dtype, int32_t th, int32_t tw) {
-    if (h < 1 || w < 1 || n_planes < 0 || th < 8 || tw < 8 || th % 8 || tw % 8)
-        return fail(SQ_ERR_INVALID, "sq_jpeg: bad sizes (%dx%d planes %d tiles %dx%d: tile sides are multiples of 8)", h, w, n_planes,
-                    th, tw);
+    TileGrid g{};
+    const int rc = stream_grid(g, P.n_tiles, "sq_jpeg", "tiles", true, h, w, n_planes, th, tw);
+    if (rc != SQ_OK) return rc;
+    P.th = g.th, P.tw = g.tw, P.nty = g.nty, P.ntx = g.ntx;
     if (dtype != SQ_U8) return fail(SQ_ERR_UNSUPPORTED, "sq_jpeg: dtype %d (uint8 planes only: baseline JPEG holds 8 bits)", dtype);
     // T.81 holds sides below 65536, but libjpeg -- the decoder behind nearly every TIFF reader -- refuses more than 65500
     if (th > MAX_SIDE || tw > MAX_SIDE || (int64_t)th * tw > (int64_t)32 << 20)
         return fail(SQ_ERR_UNSUPPORTED, "sq_jpeg: tiles of %d x %d (sides up to %d, at most 32 Mi elements)", th, tw, MAX_SIDE);
-    P.h = h;
-    P.w = w;
-    P.n_planes = n_planes;
-    P.th = th;                   // as given: a TIFF tile is always full, zero-padded past the plane's edge
-    P.tw = tw;
-    P.nty = (h + th - 1) / th;
-    P.ntx = (w + tw - 1) / tw;
-    P.nint = th / 8;
+    P.n_planes = n_planes, P.h = h, P.w = w;
+    P.parts = th / 8;
     P.nblk = tw / 8;
-    P.n_tiles = (int64_t)n_planes * P.nty * P.ntx;
-    P.n_ints = P.n_tiles * P.nint;
+    P.n_units = P.n_tiles * P.parts;
     return SQ_OK;
 }
-int64_t up256(int64_t v) { return (v + 255) & ~int64_t(255); }
+
+void carve(JpegParams &P, Scratch &sc) {
+    P.int_size = sc.take<uint32_t>(P.n_units);
+    P.o.tile_any = sc.take<uint32_t>(P.n_tiles);
+}
 
 void put16(uint8_t *&o, int v) {
     *o++ = (uint8_t)(v >> 8);
@@ -475,60 +431,42 @@ extern "C" int64_t sq_jpeg_out_bound(int32_t n_planes, int32_t h, int32_t w, int
     if (rc != SQ_OK) return rc;
     // every block at its longest codes and every byte of the data an FF; a marker behind every interval
     const int64_t interval = 2 * (((int64_t)P.nblk * BLOCK_BITS + 7) / 8) + 2;
-    return P.n_tiles * (HEADER + P.nint * interval);
+    return P.n_tiles * (HEADER + P.parts * interval);
 }
 
 extern "C" int64_t sq_jpeg_scratch_bytes(int32_t n_planes, int32_t h, int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w) {
     JpegParams P{};
     const int rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
     if (rc != SQ_OK) return rc;
-    return up256(P.n_ints * 4) + up256(P.n_tiles * 4) + 256;
+    Scratch sc{0};
+    carve(P, sc);
+    return sc.bytes();
 }
 
 extern "C" int sq_jpeg_encode_planes(const void *planes_dev, int64_t plane_stride, int64_t pitch, int32_t n_planes, int32_t h,
                                      int32_t w, int32_t dtype, int32_t tile_h, int32_t tile_w, int32_t quality, void *scratch_dev,
                                      int64_t scratch_bytes, uint64_t *offsets_dev, void *out_dev, int64_t out_capacity,
                                      uint32_t *status_dev, void *stream_) {
-    if (!planes_dev || !scratch_dev || !offsets_dev || !out_dev || !status_dev) return fail(SQ_ERR_INVALID, "sq_jpeg_encode_planes: NULL argument");
-    JpegParams P{};
-    int rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
+    int rc = stream_null(FN, planes_dev, scratch_dev, offsets_dev, out_dev, status_dev);
     if (rc != SQ_OK) return rc;
-    if (quality < 1 || quality > 100) return fail(SQ_ERR_INVALID, "sq_jpeg_encode_planes: quality %d (1..100)", quality);
-    if (out_capacity < 0) return fail(SQ_ERR_INVALID, "sq_jpeg_encode_planes: negative out_capacity");
-    if (pitch < w || (n_planes > 1 && plane_stride < (int64_t)(h - 1) * pitch + w))
-        return fail(SQ_ERR_INVALID, "sq_jpeg_encode_planes: pitch / plane stride smaller than the plane");
-    if (scratch_bytes < sq_jpeg_scratch_bytes(n_planes, h, w, dtype, tile_h, tile_w))
-        return fail(SQ_ERR_WORKSPACE, "sq_jpeg_encode_planes: scratch %lld < %lld bytes", (long long)scratch_bytes,
-                    (long long)sq_jpeg_scratch_bytes(n_planes, h, w, dtype, tile_h, tile_w));
-    if (reinterpret_cast<uintptr_t>(scratch_dev) % 256 || reinterpret_cast<uintptr_t>(offsets_dev) % 8)
-        return fail(SQ_ERR_INVALID, "sq_jpeg_encode_planes: scratch must be 256-byte, offsets 8-byte aligned");
-    if (P.n_ints > 2147483647) return fail(SQ_ERR_UNSUPPORTED, "sq_jpeg_encode_planes: too many tiles");
+    JpegParams P{};
+    rc = geometry(P, h, w, n_planes, dtype, tile_h, tile_w);
+    if (rc != SQ_OK) return rc;
+    if (quality < 1 || quality > 100) return fail(SQ_ERR_INVALID, "%s: quality %d (1..100)", FN, quality);
+    Scratch sc{reinterpret_cast<uintptr_t>(scratch_dev)};
+    carve(P, sc);
+    rc = stream_args(FN, P.o, n_planes, h, w, plane_stride, pitch, scratch_dev, scratch_bytes, sc.bytes(), offsets_dev, out_dev, out_capacity, status_dev);
+    if (rc != SQ_OK) return rc;
+    if (P.n_units > 2147483647) return fail(SQ_ERR_UNSUPPORTED, "%s: too many tiles", FN);
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    if (P.n_tiles == 0) {
-        if (hipMemsetAsync(offsets_dev, 0, 8, s) != hipSuccess || hipMemsetAsync(status_dev, 0, 4, s) != hipSuccess)
-            return fail(SQ_ERR_HIP, "sq_jpeg_encode_planes: memset");
-        return SQ_OK;
-    }
-    char *sc = static_cast<char *>(scratch_dev);
-    P.planes = static_cast<const uint8_t *>(planes_dev);
-    P.plane_stride = plane_stride;
-    P.pitch = pitch;
+    rc = stream_begin(FN, P.o, P.n_tiles, s);
+    if (rc != SQ_OK || P.n_tiles == 0) return rc;
+    P.planes = static_cast<const uint8_t *>(planes_dev), P.plane_stride = plane_stride, P.pitch = pitch;
     P.aligned = ((reinterpret_cast<uintptr_t>(planes_dev) | (uintptr_t)plane_stride | (uintptr_t)pitch) & 7) == 0;
-    P.int_size = reinterpret_cast<uint32_t *>(sc);
-    sc += up256(P.n_ints * 4);
-    P.tile_any = reinterpret_cast<uint32_t *>(sc);
-    P.offsets = offsets_dev;
-    P.out = static_cast<uint8_t *>(out_dev);
-    P.out_capacity = out_capacity;
-    P.status = status_dev;
     tables_and_header(P, quality);
-    if (hipMemsetAsync(P.tile_any, 0, (size_t)P.n_tiles * 4, s) != hipSuccess || hipMemsetAsync(status_dev, 0, 4, s) != hipSuccess)
-        return fail(SQ_ERR_HIP, "sq_jpeg_encode_planes: memset");
-    hipLaunchKernelGGL(jpeg_intervals_kernel<false>, dim3((unsigned)P.n_ints), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(jpeg_intervals_kernel<false>, dim3((unsigned)P.n_units), dim3(64), 0, s, P);
     hipLaunchKernelGGL(jpeg_tile_kernel, dim3((unsigned)P.n_tiles), dim3(64), 0, s, P, offsets_dev);
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(1024), 0, s, offsets_dev, P.n_tiles, out_capacity, status_dev);
-    hipLaunchKernelGGL(jpeg_intervals_kernel<true>, dim3((unsigned)P.n_ints), dim3(64), 0, s, P);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_jpeg_encode_planes: launch failed: %s", hipGetErrorString(e));
-    return SQ_OK;
+    stream_scan(P.o, P.n_tiles, s);
+    hipLaunchKernelGGL(jpeg_intervals_kernel<true>, dim3((unsigned)P.n_units), dim3(64), 0, s, P);
+    return stream_end(FN);
 }

@@ -1882,22 +1882,85 @@ def write_files(paths: Sequence[str], data: np.ndarray, data_offsets: np.ndarray
     return int(done.value)
 
 
-class BloscBuffers:
-    """Device buffers of one sq_blosc_encode_planes geometry: scratch, chunk offsets, packed frames, status."""
+class _StreamBuffers:
+    """Device buffers of one geometry of a packed-stream encoder (``sq_<codec>_encode_planes``): scratch, tile offsets, packed
+    streams, status.  ``bound`` is the capacity of ``out``."""
+    codec = ''
 
-    def __init__(self, n_planes: int, h: int, w: int, np_dtype, chunk_h: int, chunk_w: int, device):
+    def __init__(self, n_planes: int, h: int, w: int, dt: int, tile_h: int, tile_w: int, device, capacity: Optional[int] = None):
         import torch
         L = lib()
-        dt = sq_dtype_of(np_dtype)
-        self.geometry = (int(n_planes), int(h), int(w), dt, int(chunk_h), int(chunk_w))
-        self.n_chunks = int(L.sq_blosc_chunk_count(n_planes, h, w, chunk_h, chunk_w))
-        self.bound = int(L.sq_blosc_out_bound(*self.geometry))
-        need = int(L.sq_blosc_scratch_bytes(*self.geometry))
-        _size(min(self.n_chunks, self.bound, need), 'sq_blosc geometry')
+        self.geometry = (int(n_planes), int(h), int(w), dt, int(tile_h), int(tile_w))
+        self.n_chunks = int(getattr(L, f'sq_{self.codec}_chunk_count')(n_planes, h, w, tile_h, tile_w))
+        worst = int(getattr(L, f'sq_{self.codec}_out_bound')(*self.geometry))
+        need = int(getattr(L, f'sq_{self.codec}_scratch_bytes')(*self.geometry))
+        _size(min(self.n_chunks, worst, need), f'sq_{self.codec} geometry')
+        self.bound = self._capacity(worst, capacity)
         self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
         self.offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=device)
         self.out = torch.empty(max(self.bound, 1), dtype=torch.uint8, device=device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _capacity(self, worst: int, capacity: Optional[int]) -> int:
+        return worst
+
+    def _out_capacity(self) -> int:      # what the entry point is told
+        return self.out.numel()
+
+
+class BloscBuffers(_StreamBuffers):
+    """Device buffers of one sq_blosc_encode_planes geometry: scratch, chunk offsets, packed frames, status."""
+    codec = 'blosc'
+
+    def __init__(self, n_planes: int, h: int, w: int, np_dtype, chunk_h: int, chunk_w: int, device):
+        super().__init__(n_planes, h, w, sq_dtype_of(np_dtype), chunk_h, chunk_w, device)
+
+
+class DeflateBuffers(_StreamBuffers):
+    """Device buffers of one sq_deflate_encode_planes geometry: scratch, tile offsets, packed zlib streams, status."""
+    codec = 'deflate'
+
+    def __init__(self, n_planes: int, h: int, w: int, np_dtype, tile_h: int, tile_w: int, device):
+        super().__init__(n_planes, h, w, sq_dtype_of(np_dtype), tile_h, tile_w, device)
+
+
+class JpegBuffers(_StreamBuffers):
+    """Device buffers of one sq_jpeg_encode_planes geometry: scratch, tile offsets, packed JPEG streams, status.  ``bound`` is
+    the capacity of ``out`` -- what a caller page-locks to fetch the streams: the tiles' raw bytes plus a header per tile, not
+    sq_jpeg_out_bound()'s worst case (6.5 times raw, reached only by noise at the highest quality).  Tiles that do not fit set
+    the status word and nothing is written; ``capacity`` overrides the default (``worst_case`` is the bound that never fails)."""
+    codec = 'jpeg'
+
+    def __init__(self, n_planes: int, h: int, w: int, tile_h: int, tile_w: int, device, capacity: Optional[int] = None):
+        super().__init__(n_planes, h, w, SQ_U8, tile_h, tile_w, device, capacity)
+
+    def _capacity(self, worst: int, capacity: Optional[int]) -> int:
+        from . import jpegtile
+        self.worst_case = worst
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError(f"capacity must be >= 0, got {capacity}")
+        th, tw = self.geometry[4:]
+        return int(capacity) if capacity is not None else min(worst, self.n_chunks * (th * tw + jpegtile.HEADER_BYTES + 2))
+
+    def _out_capacity(self) -> int:      # exactly ``bound``, also when it is 0
+        return self.bound
+
+
+def _encode_planes(codec: str, planes, nhw: tuple, dt: int, tile_h: int, tile_w: int, extra: tuple, buffers, make, stream,
+                   capacity: Optional[int] = None):
+    """The common part of the three ``*_encode_planes``, behind their own checks: the buffers of the geometry (``buffers`` when they
+    are of it, else ``make()``), the strides and the call; ``extra`` are the codec's arguments behind the tile shape."""
+    n, h, w = nhw
+    with _on_stream(stream):
+        if buffers is None or buffers.codec != codec or buffers.geometry != (n, h, w, dt, int(tile_h), int(tile_w)) \
+                or (capacity is not None and buffers.bound != int(capacity)):
+            buffers = make()
+        fn = f'sq_{codec}_encode_planes'
+        _check(getattr(lib(), fn)(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h, w, dt,
+                                  int(tile_h), int(tile_w), *extra, buffers.scratch.data_ptr(), buffers.scratch.numel(),
+                                  buffers.offsets.data_ptr(), buffers.out.data_ptr(), buffers._out_capacity(),
+                                  buffers.status.data_ptr(), _stream_ptr(stream)), fn)
+    return buffers
 
 
 def blosc_encode_planes(planes, chunk_h: int, chunk_w: int, buffers: Optional[BloscBuffers] = None, stream=None) -> BloscBuffers:
@@ -1905,35 +1968,10 @@ def blosc_encode_planes(planes, chunk_h: int, chunk_w: int, buffers: Optional[Bl
     unit-stride rows, any pitch / plane stride).  Returns the buffers: after the stream has run, chunk i (plane-major,
     chunk row, chunk column) is ``buffers.out[offsets[i]:offsets[i + 1]]`` with ``offsets = buffers.offsets``
     (size 0 = all-zero chunk).  Nothing is synchronised or copied here."""
-    L = lib()
     n, h, w = _plane_stack(planes, 'planes', integer_only=False)
     npdt = np_dtype_of_torch(planes.dtype)
-    with _on_stream(stream):
-        if buffers is None or buffers.geometry != (n, h, w, sq_dtype_of(npdt), int(chunk_h), int(chunk_w)):
-            buffers = BloscBuffers(n, h, w, npdt, chunk_h, chunk_w, planes.device)
-        _check(L.sq_blosc_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h, w,
-                                        sq_dtype_of(npdt), int(chunk_h), int(chunk_w), buffers.scratch.data_ptr(),
-                                        buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(), buffers.out.numel(),
-                                        buffers.status.data_ptr(), _stream_ptr(stream)), 'sq_blosc_encode_planes')
-    return buffers
-
-
-class DeflateBuffers:
-    """Device buffers of one sq_deflate_encode_planes geometry: scratch, tile offsets, packed zlib streams, status."""
-
-    def __init__(self, n_planes: int, h: int, w: int, np_dtype, tile_h: int, tile_w: int, device):
-        import torch
-        L = lib()
-        dt = sq_dtype_of(np_dtype)
-        self.geometry = (int(n_planes), int(h), int(w), dt, int(tile_h), int(tile_w))
-        self.n_chunks = int(L.sq_deflate_chunk_count(n_planes, h, w, tile_h, tile_w))
-        self.bound = int(L.sq_deflate_out_bound(*self.geometry))
-        need = int(L.sq_deflate_scratch_bytes(*self.geometry))
-        _size(min(self.n_chunks, self.bound, need), 'sq_deflate geometry')
-        self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        self.offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=device)
-        self.out = torch.empty(max(self.bound, 1), dtype=torch.uint8, device=device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+    return _encode_planes('blosc', planes, (n, h, w), sq_dtype_of(npdt), chunk_h, chunk_w, (), buffers,
+                          lambda: BloscBuffers(n, h, w, npdt, chunk_h, chunk_w, planes.device), stream)
 
 
 def deflate_encode_planes(planes, tile_h: int, tile_w: int, predictor: int = 2, buffers: Optional[DeflateBuffers] = None,
@@ -1943,44 +1981,11 @@ def deflate_encode_planes(planes, tile_h: int, tile_w: int, predictor: int = 2, 
     none).  Returns the buffers: after the stream has run, tile i (plane-major, tile row, tile column) is
     ``buffers.out[offsets[i]:offsets[i + 1]]`` with ``offsets = buffers.offsets`` (size 0 = all-zero tile).  Nothing is
     synchronised or copied here."""
-    L = lib()
     n, h, w = _plane_stack(planes, 'planes', integer_only=False)
     npdt = np_dtype_of_torch(planes.dtype)
     predictor = _int_in(predictor, 1, 2, 'predictor')
-    with _on_stream(stream):
-        if buffers is None or buffers.geometry != (n, h, w, sq_dtype_of(npdt), int(tile_h), int(tile_w)):
-            buffers = DeflateBuffers(n, h, w, npdt, tile_h, tile_w, planes.device)
-        _check(L.sq_deflate_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h,
-                                          w, sq_dtype_of(npdt), int(tile_h), int(tile_w), predictor, buffers.scratch.data_ptr(),
-                                          buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(),
-                                          buffers.out.numel(), buffers.status.data_ptr(), _stream_ptr(stream)),
-               'sq_deflate_encode_planes')
-    return buffers
-
-
-class JpegBuffers:
-    """Device buffers of one sq_jpeg_encode_planes geometry: scratch, tile offsets, packed JPEG streams, status.  ``bound`` is
-    the capacity of ``out`` -- what a caller page-locks to fetch the streams: the tiles' raw bytes plus a header per tile, not
-    sq_jpeg_out_bound()'s worst case (6.5 times raw, reached only by noise at the highest quality).  Tiles that do not fit set
-    the status word and nothing is written; ``capacity`` overrides the default (``worst_case`` is the bound that never fails)."""
-
-    def __init__(self, n_planes: int, h: int, w: int, tile_h: int, tile_w: int, device, capacity: Optional[int] = None):
-        import torch
-        from . import jpegtile
-        L = lib()
-        self.geometry = (int(n_planes), int(h), int(w), SQ_U8, int(tile_h), int(tile_w))
-        self.n_chunks = int(L.sq_jpeg_chunk_count(n_planes, h, w, tile_h, tile_w))
-        self.worst_case = int(L.sq_jpeg_out_bound(*self.geometry))
-        need = int(L.sq_jpeg_scratch_bytes(*self.geometry))
-        _size(min(self.n_chunks, self.worst_case, need), 'sq_jpeg geometry')
-        self.bound = int(capacity) if capacity is not None else \
-            min(self.worst_case, self.n_chunks * (int(tile_h) * int(tile_w) + jpegtile.HEADER_BYTES + 2))
-        if self.bound < 0:
-            raise ValueError(f"capacity must be >= 0, got {capacity}")
-        self.scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-        self.offsets = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=device)
-        self.out = torch.empty(max(self.bound, 1), dtype=torch.uint8, device=device)
-        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+    return _encode_planes('deflate', planes, (n, h, w), sq_dtype_of(npdt), tile_h, tile_w, (predictor,), buffers,
+                          lambda: DeflateBuffers(n, h, w, npdt, tile_h, tile_w, planes.device), stream)
 
 
 def jpeg_overflow_message(quality: int) -> str:
@@ -1996,20 +2001,12 @@ def jpeg_encode_planes(planes, tile_h: int, tile_w: int, quality: int = 90, buff
     the plane's edge; sides multiples of 8).  Returns the buffers: after the stream has run, tile i (plane-major, tile row, tile
     column) is ``buffers.out[offsets[i]:offsets[i + 1]]`` (size 0 = all-zero tile) unless ``buffers.status`` is non-zero: then
     ``buffers.bound`` was too small and nothing was written.  Nothing is synchronised or copied here."""
-    L = lib()
     n, h, w = _plane_stack(planes, 'planes', integer_only=False)
     quality = _int_in(quality, 1, 100, 'quality')
-    _size(L.sq_jpeg_out_bound(n, h, w, sq_dtype_of(np_dtype_of_torch(planes.dtype)), int(tile_h), int(tile_w)),
+    _size(lib().sq_jpeg_out_bound(n, h, w, sq_dtype_of(np_dtype_of_torch(planes.dtype)), int(tile_h), int(tile_w)),
           'sq_jpeg_encode_planes')      # (the entry point's refusal of anything but uint8, before buffers are made for it)
-    with _on_stream(stream):
-        if buffers is None or buffers.geometry != (n, h, w, SQ_U8, int(tile_h), int(tile_w)) \
-                or (capacity is not None and buffers.bound != int(capacity)):
-            buffers = JpegBuffers(n, h, w, tile_h, tile_w, planes.device, capacity=capacity)
-        _check(L.sq_jpeg_encode_planes(planes.data_ptr(), planes.stride(0) if n > 1 else h * planes.stride(1), planes.stride(1), n, h,
-                                       w, SQ_U8, int(tile_h), int(tile_w), quality, buffers.scratch.data_ptr(),
-                                       buffers.scratch.numel(), buffers.offsets.data_ptr(), buffers.out.data_ptr(),
-                                       buffers.bound, buffers.status.data_ptr(), _stream_ptr(stream)), 'sq_jpeg_encode_planes')
-    return buffers
+    return _encode_planes('jpeg', planes, (n, h, w), SQ_U8, tile_h, tile_w, (quality,), buffers,
+                          lambda: JpegBuffers(n, h, w, tile_h, tile_w, planes.device, capacity=capacity), stream, capacity)
 
 
 def basic_fit(tiles, smoothness_flatfield: float = 1.0, stream=None):

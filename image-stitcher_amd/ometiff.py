@@ -22,6 +22,8 @@ from xml.sax.saxutils import escape
 
 import numpy as np
 
+from .planewriter import SlotRingWriter
+
 _OME_TYPES = {np.dtype('uint8'): 'uint8', np.dtype('uint16'): 'uint16', np.dtype('float32'): 'float'}
 
 
@@ -434,22 +436,20 @@ def read_pyramid_tiff(path: str):
     return levels, xml
 
 
-class PyramidTiffWriter:
-    """Streams fused planes from the device into a ``PyramidTiff``, with ``omezarr.PlaneStreamWriter``'s protocol (acquire / submit /
-    retarget / matches / drain / close; ``histogram`` and ``composite`` hooks; two slots), so that ``Stitcher.stitch_planes``
-    drives it unchanged.  submit() enqueues the pyramid kernels and, with compression 'deflate' or 'jpeg', the tile encoder
-    (sq_deflate_encode_planes, predictor 2; sq_jpeg_encode_planes at ``quality``, uint8 planes only) behind the fusion; a
-    writer thread fetches exactly the packed streams and appends them with one write per level per batch, straight from the
+class PyramidTiffWriter(SlotRingWriter):
+    """Streams fused planes from the device into a ``PyramidTiff`` through ``planewriter.SlotRingWriter``'s slot ring and protocol
+    (acquire / submit / retarget / matches / drain / close; ``histogram`` and ``composite`` hooks), so that
+    ``Stitcher.stitch_planes`` drives it like ``omezarr.PlaneStreamWriter``.  With compression 'deflate' or 'jpeg' submit() runs
+    the tile encoder (sq_deflate_encode_planes, predictor 2; sq_jpeg_encode_planes at ``quality``, uint8 planes only) behind the
+    fusion, and the writer thread appends the packed streams with one write per level per batch, straight from the
     page-locked buffer.  'none': the planes are copied out and cut into tiles on the host.  ``meta``: the keyword arguments of
     ``ome_xml`` but shape and dtype (pixel_size_um, dz_um, channel_names, channel_colors, name)."""
+    thread_name = 'tiff-writer'
 
     def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, meta: dict, chunks=(1, 1, 1, 512, 512), batch: int = 1,
                  compression: str = 'deflate', device='cuda:0', slots: int = 2, buffers=None, canvas_arena=None,
                  pyramid_method: str = 'nearest', verbose: bool = True, quality: int = 90):
-        import queue
-        import threading
-        import torch
-        from . import jpegtile, native, omezarr
+        from . import jpegtile
         self.chunks = tuple(chunks)
         self.tile = check_tile_shape(self.chunks[3:5])
         if compression not in TIFF_COMPRESSIONS:
@@ -457,51 +457,37 @@ class PyramidTiffWriter:
         self.quality = jpegtile.check_quality(quality)
         if compression == 'jpeg':
             check_jpeg_dtype(dtype)
-        self.compression, self.batch = compression, int(batch)
-        self.pyramid_method = omezarr.check_pyramid_method(pyramid_method)
+        self.compression = compression
         self.shapes = [tuple(int(v) for v in s) for s in shapes]
         self.dtype = np.dtype(dtype)
         self.row_offset = 0
-        self.bytes_written = 0
-        self.histogram = None       # as PlaneStreamWriter's: optional device int64 [C, bins] target of level 0's value counts
-        self.composite = None       # as PlaneStreamWriter's: optional composite.CompositeTarget handed every plane
         self.verbose = verbose
-        tdtype = native.torch_dtype_of(self.dtype.type)
-        yx = [tuple(s[3:]) for s in self.shapes]
-        self._encoded = compression in ('deflate', 'jpeg')      # tiles are encoded on the device
-        self._jpeg = compression == 'jpeg'
-        if buffers is None:
-            dev = [[native.empty_canvas(self.batch, s[0], s[1], tdtype, device, arena=canvas_arena) if lv == 0 else
-                    torch.empty((self.batch,) + s, dtype=tdtype, device=device) for lv, s in enumerate(yx)] for _ in range(slots)]
-            if self._encoded:
-                make = (lambda s: native.JpegBuffers(self.batch, s[0], s[1], self.tile[0], self.tile[1], device)) if self._jpeg else \
-                    (lambda s: native.DeflateBuffers(self.batch, s[0], s[1], self.dtype, self.tile[0], self.tile[1], device))
-                enc = [[make(s) for s in yx] for _ in range(slots)]
-                host = [[(torch.empty(e.bound, dtype=torch.uint8, pin_memory=True),
-                          torch.empty(e.n_chunks + 1, dtype=torch.int64, pin_memory=True),
-                          torch.empty(1, dtype=torch.int32, pin_memory=True)) for e in slot_enc] for slot_enc in enc]
-                buffers = (dev, host, enc)
-            else:
-                buffers = (dev, [[torch.empty((self.batch,) + s, dtype=tdtype, pin_memory=True) for s in yx] for _ in range(slots)])
-        self.buffers = buffers
-        if self._encoded != (len(buffers) == 3):
-            raise ValueError("buffers do not match this writer's compression")
-        self._dev, self._host = buffers[0], buffers[1]
-        self._enc = buffers[2] if self._encoded else None
-        if len(self._dev) != slots or [tuple(t.shape) for t in self._dev[0]] != [(self.batch,) + s for s in yx] \
-                or self._dev[0][0].dtype != tdtype:
-            raise ValueError("buffers do not match this writer's geometry")
-        self._copy_stream = torch.cuda.Stream(device=device)
-        self._frame_stream = torch.cuda.Stream(device=device)
-        self._free = [threading.Event() for _ in range(slots)]
-        for e in self._free:
-            e.set()
-        self._slot, self._m, self._error = -1, 0, None
+        self._init_ring(self.shapes, self.dtype, batch=batch, device=device, slots=slots, buffers=buffers, canvas_arena=canvas_arena,
+                        pyramid_method=pyramid_method, encoded=compression in ('deflate', 'jpeg'))
         self._file = None
         self._open(path, meta)
-        self._queue: "queue.Queue" = queue.Queue()
-        self._thread = threading.Thread(target=self._dispatch, name='tiff-writer', daemon=True)
         self._thread.start()
+
+    def _make_encoder(self, lv: int, yx, device):
+        from . import native
+        if self.compression == 'jpeg':
+            return native.JpegBuffers(self.batch, yx[0], yx[1], self.tile[0], self.tile[1], device)
+        return native.DeflateBuffers(self.batch, yx[0], yx[1], self.dtype, self.tile[0], self.tile[1], device)
+
+    def _encode(self, planes, enc) -> None:
+        from . import native
+        if self.compression == 'jpeg':
+            native.jpeg_encode_planes(planes, self.tile[0], self.tile[1], self.quality, enc)
+        else:
+            native.deflate_encode_planes(planes, self.tile[0], self.tile[1], PREDICTOR_HORIZONTAL, enc)
+
+    def _overflow_message(self) -> str:
+        from . import native
+        return native.jpeg_overflow_message(self.quality) if self.compression == 'jpeg' else \
+            "sq_deflate_encode_planes: output buffer too small"
+
+    def _target(self) -> PyramidTiff:
+        return self._file
 
     @property
     def path(self) -> str:
@@ -521,107 +507,24 @@ class PyramidTiffWriter:
         if self.verbose:
             print(tiff_summary(file.path, stats))
 
-    def _dispatch(self):
-        while True:
-            item = self._queue.get()
-            if item is None:
-                return
-            slot, coords, event, file = item
-            try:
-                if slot is None:          # the file is complete behind everything submitted to it
-                    self._finish(file)
-                    continue
-                event.synchronize()
-                planes = [file.plane_index(*c) for c in coords]
-                if self._encoded:
-                    self._write_streams(slot, planes, file)
-                else:
-                    for lv, h in enumerate(self._host[slot]):
-                        file.append_planes(lv, planes, h.numpy()[:len(planes)])
-            except BaseException as exc:   # surfaced by the next acquire() / drain() / close()
-                self._error = exc
-            finally:
-                if slot is not None:
-                    self._free[slot].set()
-
-    def _write_streams(self, slot: int, planes: Sequence[int], file: PyramidTiff) -> None:
-        """The tile offsets of this slot are on the host; fetch exactly the packed streams (only compressed bytes cross PCIe) and
-        append them, one write per level."""
-        import torch
-        m = len(planes)
-        done = torch.cuda.Event()
-        totals = []
-        with torch.cuda.stream(self._frame_stream):     # the encoder has finished: _dispatch waited for the slot's event
-            for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
-                if int(status[0]):
-                    from . import native
-                    raise RuntimeError(native.jpeg_overflow_message(self.quality) if self._jpeg else
-                                       "sq_deflate_encode_planes: output buffer too small")
-                total = int(offsets[m * (enc.n_chunks // self.batch)])
-                totals.append(total)
-                if total:
-                    frames[:total].copy_(enc.out[:total], non_blocking=True)
-            done.record()
-        done.synchronize()
+    def _write_streams(self, slot: int, coords: Sequence[tuple], file: PyramidTiff, totals) -> None:
+        """The slot's packed streams are on the host: append them, one write per level."""
+        planes = [file.plane_index(*c) for c in coords]
         for lv, (enc, (frames, offsets, _)) in enumerate(zip(self._enc[slot], self._host[slot])):
             per_plane = enc.n_chunks // self.batch
-            file.append(lv, planes, frames.numpy()[:totals[lv]], np.diff(offsets.numpy()[:m * per_plane + 1]))
+            file.append(lv, planes, frames.numpy()[:totals[lv]], np.diff(offsets.numpy()[:len(planes) * per_plane + 1]))
 
-    def _check(self):
-        if self._error is not None:
-            err, self._error = self._error, None
-            raise err
+    def _write_planes(self, slot: int, coords: Sequence[tuple], file: PyramidTiff) -> None:
+        planes = [file.plane_index(*c) for c in coords]
+        for lv, h in enumerate(self._host[slot]):
+            file.append_planes(lv, planes, h.numpy()[:len(planes)])
 
-    def acquire(self, m: int):
-        """Device canvas [m, Hc, Wc] of the next slot (contents undefined)."""
-        if not 0 < m <= self.batch:
-            raise ValueError(f"a slot holds 1..{self.batch} planes, asked for {m}")
-        self._slot = (self._slot + 1) % len(self._dev)
-        self._free[self._slot].wait()
-        self._check()
-        self._m = m
-        return self._dev[self._slot][0][:m]
+    def _last_item(self) -> tuple:
+        return None, None, None, self._file
 
-    def submit(self, coords: Sequence[tuple]) -> None:
-        """The canvas handed out by the last ``acquire`` is (being) filled on the current stream."""
-        import torch
-        from . import native, omezarr
-        slot, m = self._slot, self._m
-        if len(coords) != m:
-            raise ValueError(f"{m} planes acquired, {len(coords)} coordinates given")
-        dev = self._dev[slot]
-        if self.histogram is not None:
-            native.histogram_planes(dev[0][:m], [c for _, c, _ in coords], hist=self.histogram)
-        if self.composite is not None:
-            self.composite.add(dev[0][:m], coords, self.row_offset)
-        omezarr.device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
-        if self._encoded:      # encode every level's tiles behind the pyramid, on the caller's stream
-            for lv, enc in enumerate(self._enc[slot]):
-                full = dev[lv]     # the buffers are sized for a full batch: what lies past m is zeroed and costs no bytes
-                planes = full if m == self.batch else omezarr._pad_planes(full, m)
-                if self._jpeg:
-                    native.jpeg_encode_planes(planes, self.tile[0], self.tile[1], self.quality, enc)
-                else:
-                    native.deflate_encode_planes(planes, self.tile[0], self.tile[1], PREDICTOR_HORIZONTAL, enc)
-        fused = torch.cuda.Event()
-        fused.record()
-        event = torch.cuda.Event()
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(fused)
-            if self._encoded:
-                for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
-                    offsets.copy_(enc.offsets, non_blocking=True)
-                    status.copy_(enc.status, non_blocking=True)
-            else:
-                for d, h in zip(dev, self._host[slot]):
-                    if d.is_contiguous():
-                        h[:m].copy_(d[:m], non_blocking=True)
-                    else:                       # padded plane stride: every plane is contiguous, the stack is not
-                        for p in range(m):
-                            h[p].copy_(d[p], non_blocking=True)
-            event.record()
-        self._free[slot].clear()
-        self._queue.put((slot, list(coords), event, self._file))
+    def _shutdown(self, joined: bool) -> None:
+        if not joined and self._file is not None and not self._file.closed:      # the writer thread had died
+            self._finish(self._file)
 
     def retarget(self, path: str, row_offset: int = 0, level_heights=None, meta: Optional[dict] = None) -> None:
         """The planes submitted FROM NOW ON belong to another file of the same geometry: the current one is finished behind what
@@ -630,7 +533,7 @@ class PyramidTiffWriter:
             raise ValueError("a pyramid TIFF is written whole: no row bands")
         if meta is None:
             raise ValueError("retarget needs the next file's metadata")
-        self._queue.put((None, None, None, self._file))
+        self._queue.put(self._last_item())
         self._open(path, meta)
 
     def matches(self, shapes: Sequence[tuple], dtype, batch: int, compression: str, chunks, pyramid_method: str = 'nearest', *,
@@ -640,31 +543,6 @@ class PyramidTiffWriter:
                 and (compression != 'jpeg' or self.quality == int(quality))
                 and self.chunks == tuple(chunks) and self.pyramid_method == pyramid_method
                 and self.shapes == [tuple(int(v) for v in s) for s in shapes] and self.dtype == np.dtype(dtype))
-
-    def drain(self) -> None:
-        """Wait until everything submitted so far is in the file (the writer stays usable; the file is finished by close or
-        retarget)."""
-        for e in self._free:
-            e.wait()
-        self._check()
-
-    def close(self):
-        for e in self._free:
-            e.wait()
-        if self._thread.is_alive():
-            self._queue.put((None, None, None, self._file))
-            self._queue.put(None)
-            self._thread.join()
-        elif self._file is not None and not self._file.closed:
-            self._finish(self._file)
-        self._check()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def write_pyramid_tiff(path: str, image, *, meta: dict, num_levels: int = 1, chunks=(1, 1, 1, 512, 512), compression: str = 'deflate',

@@ -26,6 +26,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from .planewriter import SlotRingWriter
+
 
 def _write_json(path: str, obj) -> None:
     with open(path, 'w') as fh:
@@ -488,108 +490,48 @@ def write_depth_store(path: str, depth, *, num_z: int, labels: Sequence[str], pi
     return path
 
 
-class PlaneStreamWriter:
-    """Streams fused planes from the device into a store made by ``create_store``.
-
-    Two slots, each = a device canvas of ``batch`` planes, device buffers for its pyramid levels and
-    pinned host mirrors of all of them.  ``acquire(m)`` hands out the slot's canvas (waiting until the
-    slot's previous contents are on disk); the caller fuses into it on the current stream and calls
-    ``submit(coords)``, which enqueues the pyramid kernels behind the fusion and the D2H copies on a
-    separate copy stream behind those, and returns at once; a dispatcher thread waits for the copies
-    and fans the chunks out to the compression threads.  So batch k is copied out, compressed and
-    written while batch k+1 is read, copied in and fused.
-    """
+class PlaneStreamWriter(SlotRingWriter):
+    """Streams fused planes from the device into a store made by ``create_store`` (the slot ring and its protocol:
+    ``planewriter.SlotRingWriter``).  With compression 'blosc' the chunks are encoded on the device (csrc/blosc.hip) and the
+    writer thread writes one file per non-empty chunk; otherwise it fans the planes' chunks out to the compression threads."""
+    thread_name = 'zarr-writer'
 
     def __init__(self, path: str, shapes: Sequence[tuple], dtype, *, chunks=(1, 1, 1, 512, 512), batch: int = 1,
                  compression: str = 'zlib', level: int = 1, device='cuda:0', workers: Optional[int] = None, slots: int = 2,
                  buffers=None, row_offset: int = 0, level_heights: Optional[Sequence[int]] = None, canvas_arena=None,
                  pyramid_method: str = 'nearest'):
-        import queue
-        import threading
         from concurrent.futures import ThreadPoolExecutor
-        import torch
-        from . import native
         self.path, self.chunks, self.compression, self.level = path, tuple(chunks), compression, level
-        self.batch = int(batch)
-        # 'mean': all levels of a slot from one read of its canvas (sq_pyramid_mean) instead of one launch per level
-        self.pyramid_method = check_pyramid_method(pyramid_method)
+        self.dtype = np.dtype(dtype)
         # a writer of one row band: ``shapes`` are the band's level shapes, chunks land ``row_offset`` level-0 rows down
         self.row_offset, self.level_heights = int(row_offset), (None if level_heights is None else list(level_heights))
-        self.bytes_written = 0
-        # optional target of the value counts of level 0: a device int64 [C, bins] tensor; submit() adds the planes it is handed
-        # to row c of it (sq_histogram_planes).  None: nothing is launched.  Callers set it per store (``retarget`` keeps it).
-        self.histogram = None
-        # optional composite.CompositeTarget: submit() hands it the planes (and this writer's row offset) before the slot is
-        # released, so that it can reduce its source planes where they are final.  None: nothing is launched.
-        self.composite = None
-        tdtype = native.torch_dtype_of(np.dtype(dtype).type)
-        yx = [tuple(s[3:]) for s in shapes]
-        # ``buffers``: the (device, pinned host) slot buffers of an earlier writer of the same geometry --
-        # page-locking host memory costs more than a small region's whole fusion, so callers that write
-        # many regions (one per well and timepoint) hand them on
-        self._blosc = compression == 'blosc'
-        if buffers is None:
-            # level 0 = the fusion canvas: dense rows, planes on 128-byte lines (native.empty_canvas)
-            # (canvas_arena: a native.DeviceArena to carve the level-0 canvases from -- memory mapped over all memory classes of
-            #  the card, where the fusion kernel writes fastest; the slot tensors keep it alive)
-            dev = [[native.empty_canvas(self.batch, s[0], s[1], tdtype, device, arena=canvas_arena) if lv == 0 else
-                    torch.empty((self.batch,) + s, dtype=tdtype, device=device) for lv, s in enumerate(yx)] for _ in range(slots)]
-            if self._blosc:
-                # chunks are encoded on the device (csrc/blosc.hip): the host mirrors hold packed FRAMES, not planes
-                enc = [[native.BloscBuffers(self.batch, s[0], s[1], np.dtype(dtype), *self._chunk_yx(lv, s), device)
-                        for lv, s in enumerate(yx)] for _ in range(slots)]
-                host = [[(torch.empty(e.bound, dtype=torch.uint8, pin_memory=True),
-                          torch.empty(e.n_chunks + 1, dtype=torch.int64, pin_memory=True),
-                          torch.empty(1, dtype=torch.int32, pin_memory=True)) for e in slot_enc] for slot_enc in enc]
-                buffers = (dev, host, enc)
-            else:
-                buffers = (dev, [[torch.empty((self.batch,) + s, dtype=tdtype, pin_memory=True) for s in yx] for _ in range(slots)])
-        self.buffers = buffers
-        if self._blosc != (len(buffers) == 3):
-            raise ValueError("buffers do not match this writer's compression")
-        self._dev, self._host = buffers[0], buffers[1]
-        self._enc = buffers[2] if self._blosc else None
-        if len(self._dev) != slots or [tuple(t.shape) for t in self._dev[0]] != [(self.batch,) + s for s in yx] \
-                or self._dev[0][0].dtype != tdtype:
-            raise ValueError("buffers do not match this writer's geometry")
-        # D2H copies run on their own stream: the link is full duplex, so batch k leaves the device while
-        # batch k+1's tiles arrive and are fused on the caller's stream
-        self._copy_stream = torch.cuda.Stream(device=device)
-        # ... and the writer thread fetches a slot's packed frames on a stream of ITS own: on _copy_stream they would
-        # queue behind the wait for the NEXT slot's fusion (submit() parks that wait there) and the disk write-out the
-        # two slots are meant to overlap would serialise
-        self._frame_stream = torch.cuda.Stream(device=device)
-        self._free = [threading.Event() for _ in range(slots)]
-        for e in self._free:
-            e.set()
-        self._slot = -1
-        self._m = 0
-        self._error = None
+        self._init_ring(shapes, dtype, batch=batch, device=device, slots=slots, buffers=buffers, canvas_arena=canvas_arena,
+                        pyramid_method=pyramid_method, encoded=compression == 'blosc')
         self._pool = ThreadPoolExecutor(max_workers=workers if workers is not None else min(32, os.cpu_count() or 4))
-        self._queue: "queue.Queue" = queue.Queue()
-        self._thread = threading.Thread(target=self._dispatch, name='zarr-writer', daemon=True)
         self._thread.start()
 
-    def _dispatch(self):
-        while True:
-            item = self._queue.get()
-            if item is None:
-                return
-            slot, coords, event, target = item
-            path, row_offset, level_heights = target
-            try:
-                event.synchronize()
-                if self._blosc:
-                    self.bytes_written += self._write_frames(slot, coords, path, row_offset)
-                    continue
-                levels = [h.numpy() for h in self._host[slot]]
-                self.bytes_written += write_plane_levels(path, levels, coords, self.chunks, self.compression,
-                                                         self.level, pool=self._pool, row_offset=row_offset,
-                                                         level_heights=level_heights)
-            except BaseException as exc:   # surfaced by the next acquire() / close()
-                self._error = exc
-            finally:
-                self._free[slot].set()
+    def _make_encoder(self, lv: int, yx, device):
+        from . import native
+        return native.BloscBuffers(self.batch, yx[0], yx[1], self.dtype, *self._chunk_yx(lv, yx), device)
+
+    def _encode(self, planes, enc) -> None:
+        from . import native
+        native.blosc_encode_planes(planes, enc.geometry[4], enc.geometry[5], enc)
+
+    def _overflow_message(self) -> str:
+        return "sq_blosc_encode_planes: output buffer too small"
+
+    def _target(self) -> tuple:
+        return self.path, self.row_offset, self.level_heights
+
+    def _write_planes(self, slot: int, coords: Sequence[tuple], target) -> None:
+        path, row_offset, level_heights = target
+        levels = [h.numpy() for h in self._host[slot]]
+        self.bytes_written += write_plane_levels(path, levels, coords, self.chunks, self.compression, self.level, pool=self._pool,
+                                                 row_offset=row_offset, level_heights=level_heights)
+
+    def _shutdown(self, joined: bool) -> None:
+        self._pool.shutdown(wait=True)
 
     def _chunk_yx(self, lv: int, level_yx) -> tuple:
         """Chunk shape of pyramid level ``lv`` in the STORE: zarr clamps a chunk dimension to the array's -- the full
@@ -597,24 +539,9 @@ class PlaneStreamWriter:
         full_h = level_yx[0] if self.level_heights is None else int(self.level_heights[lv])
         return min(self.chunks[3], full_h), min(self.chunks[4], level_yx[1])
 
-    def _write_frames(self, slot: int, coords: Sequence[tuple], path: str, row_offset: int) -> int:
-        """Blosc mode: the chunk offsets of this slot are on the host; fetch exactly the packed frames (compressed bytes
-        only cross PCIe) and write one file per non-empty chunk."""
-        import torch
-        m = len(coords)
-        done = torch.cuda.Event()
-        totals = []
-        with torch.cuda.stream(self._frame_stream):     # the encoder has finished: _dispatch waited for the slot's event
-            for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
-                if int(status[0]):
-                    raise RuntimeError("sq_blosc_encode_planes: output buffer too small")
-                per_plane = enc.n_chunks // self.batch
-                total = int(offsets[m * per_plane])
-                totals.append(total)
-                if total:
-                    frames[:total].copy_(enc.out[:total], non_blocking=True)
-            done.record()
-        done.synchronize()
+    def _write_streams(self, slot: int, coords: Sequence[tuple], target, totals) -> None:
+        """Blosc mode: the slot's packed frames are on the host; write one file per non-empty chunk."""
+        path, row_offset, _ = target
         # one native call per pyramid level (native.write_files: open / write / close on native threads, straight from the
         # page-locked frame buffer): the paths and the directories are worked out here, a few hundred directories per batch
         from . import native
@@ -651,59 +578,7 @@ class PlaneStreamWriter:
                 raise RuntimeError("blosc frames are not packed densely")
             data_offsets = np.concatenate([starts, ends[-1:]]).astype(np.int64)
             written += native.write_files(paths, frames.numpy(), data_offsets, n_threads=self._pool._max_workers)
-        return written
-
-    def _check(self):
-        if self._error is not None:
-            err, self._error = self._error, None
-            raise err
-
-    def acquire(self, m: int):
-        """Device canvas [m, Hc, Wc] of the next slot (contents undefined)."""
-        if not 0 < m <= self.batch:
-            raise ValueError(f"a slot holds 1..{self.batch} planes, asked for {m}")
-        self._slot = (self._slot + 1) % len(self._dev)
-        self._free[self._slot].wait()
-        self._check()
-        self._m = m
-        return self._dev[self._slot][0][:m]
-
-    def submit(self, coords: Sequence[tuple]) -> None:
-        """The canvas handed out by the last ``acquire`` is (being) filled on the current stream."""
-        import torch
-        slot, m = self._slot, self._m
-        if len(coords) != m:
-            raise ValueError(f"{m} planes acquired, {len(coords)} coordinates given")
-        dev = self._dev[slot]
-        if self.histogram is not None:      # the m planes handed in, not the padding of a partly filled slot
-            from . import native
-            native.histogram_planes(dev[0][:m], [c for _, c, _ in coords], hist=self.histogram)
-        if self.composite is not None:
-            self.composite.add(dev[0][:m], coords, self.row_offset)
-        levels = device_levels(dev[0][:m], len(dev), out=dev[1:], method=self.pyramid_method)
-        if self._blosc:        # encode every level's chunks behind the pyramid, on the caller's stream
-            from . import native
-            for lv, enc in enumerate(self._enc[slot]):
-                full = dev[lv]     # the buffers are sized for a full batch: encode all of it when the batch is full
-                native.blosc_encode_planes(full if m == self.batch else _pad_planes(full, m), enc.geometry[4], enc.geometry[5], enc)
-        fused = torch.cuda.Event()
-        fused.record()                                  # fusion + pyramid (+ encoding) of this slot, on the caller's stream
-        event = torch.cuda.Event()
-        with torch.cuda.stream(self._copy_stream):
-            self._copy_stream.wait_event(fused)
-            if self._blosc:
-                for enc, (frames, offsets, status) in zip(self._enc[slot], self._host[slot]):
-                    offsets.copy_(enc.offsets, non_blocking=True)
-                    status.copy_(enc.status, non_blocking=True)
-            for d, h in (() if self._blosc else zip(dev, self._host[slot])):
-                if d.is_contiguous():
-                    h[:m].copy_(d[:m], non_blocking=True)
-                else:                       # padded plane stride: every plane is contiguous, the stack is not
-                    for p in range(m):
-                        h[p].copy_(d[p], non_blocking=True)
-            event.record()
-        self._free[slot].clear()
-        self._queue.put((slot, list(coords), event, (self.path, self.row_offset, self.level_heights)))
+        self.bytes_written += written
 
     def retarget(self, path: str, row_offset: int = 0, level_heights: Optional[Sequence[int]] = None) -> None:
         """The planes submitted FROM NOW ON belong to another store of the same geometry (the next well, the next timepoint): what
@@ -720,25 +595,3 @@ class PlaneStreamWriter:
                 and self.pyramid_method == pyramid_method
                 and [tuple(t.shape[1:]) for t in self._dev[0]] == yx
                 and self._dev[0][0].dtype == native.torch_dtype_of(np.dtype(dtype).type))
-
-    def drain(self) -> None:
-        """Wait until everything submitted so far is on disk (the writer stays usable)."""
-        for e in self._free:
-            e.wait()
-        self._check()
-
-    def close(self):
-        for e in self._free:
-            e.wait()
-        if self._thread.is_alive():
-            self._queue.put(None)
-            self._thread.join()
-        self._pool.shutdown(wait=True)
-        self._check()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False

@@ -795,6 +795,8 @@ int sq_seam_stats(const void *tiles_dev, int32_t n_planes, int32_t n_tiles, int3
  * densely into out_dev: chunk i = plane-major, then chunk row, then chunk column, lives at
  * out_dev[offsets_dev[i] .. offsets_dev[i + 1]) (n_chunks + 1 offsets; an all-zero chunk has size 0: the store's
  * fill_value stands for it).  *status_dev != 0 afterwards: out_capacity was too small (sq_blosc_out_bound() never is).
+ * Every accepted call clears *status_dev first, also one with no chunk at all (n_planes == 0: offsets_dev[0] = 0 and
+ * nothing else); a negative out_capacity is SQ_ERR_INVALID, as for the two tile encoders below.
  * Strides in elements; dtype SQ_U8 or SQ_U16.  Asynchronous on `stream` like the other entry points.
  * The three size queries return a negative sq_status for a geometry the encode call refuses (a chunk may hold at most
  * 32 MiB); sq_blosc_chunk_count is not told the dtype and refuses only what no dtype could encode.
