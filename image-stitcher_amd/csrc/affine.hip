@@ -46,19 +46,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// 16 bytes, and two neighbouring elements, in one load at the alignment of an element: the compiler is told so
-typedef u32x4 span_of_u16 __attribute__((aligned(2)));
-typedef u32x4 span_of_u8 __attribute__((aligned(1)));
-typedef uint32_t pair_of_u16 __attribute__((aligned(2)));
-typedef uint16_t pair_of_u8 __attribute__((aligned(1)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int TX_MAX = 128;                               // vectors across a workgroup, at most
@@ -349,49 +342,30 @@ extern "C" int sq_affine_tiles(const void *src_dev, void *dst_dev, int32_t n_ima
                             SQ_AFFINE_MAX_PPM, SQ_AFFINE_MAX_PPM);
     }
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    if (reinterpret_cast<uintptr_t>(src_dev) % esize || reinterpret_cast<uintptr_t>(dst_dev) % esize)
-        return fail(SQ_ERR_INVALID, "sq_affine_tiles: planes must be aligned to their element");
-    const int64_t src_plane = (int64_t)(h - 1) * src_pitch + w, dst_plane = (int64_t)(h - 1) * dst_pitch + w;
-    if (n_images > 1 && (src_plane_stride < src_plane || dst_plane_stride < dst_plane))
-        return fail(SQ_ERR_INVALID, "sq_affine_tiles: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (src_plane_stride > plane_limit || dst_plane_stride > plane_limit || src_plane > plane_limit || dst_plane > plane_limit)
-        return fail(SQ_ERR_INVALID, "sq_affine_tiles: extents beyond the address space");
-    {   // the extents (first to last element of all planes) must not overlap: a tap is read after its neighbour's result is written
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), d0 = reinterpret_cast<uintptr_t>(dst_dev);
-        const uintptr_t s1 = s0 + (uintptr_t)(((int64_t)(n_images - 1) * src_plane_stride + src_plane) * esize);
-        const uintptr_t d1 = d0 + (uintptr_t)(((int64_t)(n_images - 1) * dst_plane_stride + dst_plane) * esize);
-        if (s0 < d1 && d0 < s1) return fail(SQ_ERR_INVALID, "sq_affine_tiles: src and dst overlap (the map is out of place)");
-    }
+    const PlaneBatch src{src_dev, n_images, h, w, src_plane_stride, src_pitch, esize};
+    const PlaneBatch dst{dst_dev, n_images, h, w, dst_plane_stride, dst_pitch, esize};
+    if (const int rc = check_batches("sq_affine_tiles", "plane", {src, dst})) return rc;
+    // a tap is read after its neighbour's result is written
+    if (overlap(src, dst)) return fail(SQ_ERR_INVALID, "sq_affine_tiles: src and dst overlap (the map is out of place)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int vec = 16 / esize;
     AffineArgs a{};
     a.h = h;
     a.w = w;
-    a.mis = (int32_t)((reinterpret_cast<uintptr_t>(dst_dev) / esize) & (uintptr_t)(vec - 1));
-    const int64_t nvec = ((int64_t)w + a.mis + vec - 1) / vec;
-    a.tx = 1;
-    a.tx_log2 = 0;
-    while (a.tx < TX_MAX && a.tx < nvec) {
-        a.tx *= 2;
-        a.tx_log2 += 1;
-    }
-    const int ty = THREADS / a.tx;
-    const int64_t n_strips = (nvec + a.tx - 1) / a.tx;              // at most 512 ...
-    const int64_t n_segs = ((int64_t)h + ty - 1) / ty;              // ... times at most 4096: far below a launch's workgroups
-    a.n_strips = (int32_t)n_strips;
+    a.mis = dst.phase(vec);
+    StripGrid g;      // (at most 512 strips times at most 4096 segments: far below a launch's workgroups)
+    if (const int rc = strip_grid("sq_affine_tiles", ((int64_t)w + a.mis + vec - 1) / vec, TX_MAX, THREADS, 1, h, &g)) return rc;
+    a.tx = g.tx;
+    a.tx_log2 = g.tx_log2;
+    a.n_strips = g.n_strips;
     a.src_plane_stride = src_plane_stride;
     a.src_pitch = src_pitch;
     a.dst_plane_stride = dst_plane_stride;
     a.dst_pitch = dst_pitch;
-    constexpr int64_t PER_LAUNCH = (int64_t)65535 * WALK;      // gridDim.y runs of WALK planes
     // one grid per maximal run of consecutive equal tuples, the all-zero one included: the arguments stay scalar, no table goes
     // to the device
-    for (int32_t s0 = 0; s0 < n_params;) {
-        const int32_t *t = params_host + 6 * (int64_t)s0;
-        int32_t s1 = s0 + 1;
-        while (s1 < n_params && std::equal(t, t + 6, params_host + 6 * (int64_t)s1)) ++s1;
+    return for_each_run(params_host, n_params, 6, [&](const int32_t *t, int32_t s0, int32_t s1) {
         a.sy = t[0];
         a.sx = t[1];
         a.ayy = t[2];
@@ -400,21 +374,16 @@ extern "C" int sq_affine_tiles(const void *src_dev, void *dst_dev, int32_t n_ima
         a.axx = t[5];
         floor_divmod(32 * (int64_t)a.ayx, a.vq, a.vr);
         floor_divmod(32 * (int64_t)a.axx, a.uq, a.ur);
-        const int64_t first = (int64_t)s0 * images_per_param, last = (int64_t)s1 * images_per_param;
-        for (int64_t p0 = first; p0 < last; p0 += PER_LAUNCH) {
-            const int32_t m = (int32_t)std::min<int64_t>(PER_LAUNCH, last - p0);
-            const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)((m + WALK - 1) / WALK));
-            a.src = static_cast<const char *>(src_dev) + p0 * src_plane_stride * esize;
-            a.dst = static_cast<char *>(dst_dev) + p0 * dst_plane_stride * esize;
+        return for_each_launch("sq_affine_tiles", (int64_t)s0 * images_per_param, (int64_t)s1 * images_per_param, WALK,
+                               [&](int64_t p0, int32_t m, unsigned grid_y) {
+            const dim3 grid(g.x(), grid_y);      // gridDim.y runs of WALK planes
+            a.src = src.at(p0);
+            a.dst = dst.at(p0);
             a.n_planes = m;
             if (dtype == SQ_U16)
                 affine_kernel<uint16_t><<<grid, dim3(THREADS), 0, stream>>>(a);
             else
                 affine_kernel<uint8_t><<<grid, dim3(THREADS), 0, stream>>>(a);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_affine_tiles: launch failed: %s", hipGetErrorString(e));
-        }
-        s0 = s1;
-    }
-    return SQ_OK;
+        });
+    });
 }

@@ -39,10 +39,10 @@
 #include <vector>
 
 #include "common.h"
+#include "device_util.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define SQ_G1 __attribute__((address_space(1)))
 
 // The probe's write pattern: a G x G grid of tiles, every tile `rows` row segments of SEG bytes at `pitch`, one workgroup per

@@ -27,15 +27,12 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int RPT = 4;      // dst rows a thread walks down (K * RPT source rows)
@@ -201,25 +198,15 @@ extern "C" int sq_bin_tiles(const void *src_dev, void *dst_dev, int32_t n_images
     if (n_images == 0) return SQ_OK;
     if (!src_dev || !dst_dev) return fail(SQ_ERR_INVALID, "sq_bin_tiles: NULL buffer");
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    if (reinterpret_cast<uintptr_t>(src_dev) % esize || reinterpret_cast<uintptr_t>(dst_dev) % esize)
-        return fail(SQ_ERR_INVALID, "sq_bin_tiles: planes must be aligned to their element");
-    const int64_t src_plane = (int64_t)(h - 1) * src_pitch + w, dst_plane = (int64_t)(hb - 1) * dst_pitch + wb;
-    if (n_images > 1 && (src_plane_stride < src_plane || dst_plane_stride < dst_plane))
-        return fail(SQ_ERR_INVALID, "sq_bin_tiles: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (src_plane_stride > plane_limit || dst_plane_stride > plane_limit || src_plane > plane_limit || dst_plane > plane_limit)
-        return fail(SQ_ERR_INVALID, "sq_bin_tiles: extents beyond the address space");
-    {   // the extents (first to last element of all planes) must not overlap: a block is read after its neighbour's result is written
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), d0 = reinterpret_cast<uintptr_t>(dst_dev);
-        const uintptr_t s1 = s0 + (uintptr_t)(((int64_t)(n_images - 1) * src_plane_stride + src_plane) * esize);
-        const uintptr_t d1 = d0 + (uintptr_t)(((int64_t)(n_images - 1) * dst_plane_stride + dst_plane) * esize);
-        if (s0 < d1 && d0 < s1) return fail(SQ_ERR_INVALID, "sq_bin_tiles: src and dst overlap (the binning is out of place)");
-    }
+    const PlaneBatch src{src_dev, n_images, h, w, src_plane_stride, src_pitch, esize};
+    const PlaneBatch dst{dst_dev, n_images, hb, wb, dst_plane_stride, dst_pitch, esize};
+    if (const int rc = check_batches("sq_bin_tiles", "plane", {src, dst})) return rc;
+    // a block is read after its neighbour's result is written
+    if (overlap(src, dst)) return fail(SQ_ERR_INVALID, "sq_bin_tiles: src and dst overlap (the binning is out of place)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int vec = 16 / esize, outs = outs_of(factor, vec);      // a thread's run of dst columns (the kernel's OUTS)
-    const int src_phase = (int)((reinterpret_cast<uintptr_t>(src_dev) / esize) & (uintptr_t)(vec - 1));
-    const int dst_phase = (int)((reinterpret_cast<uintptr_t>(dst_dev) / esize) & (uintptr_t)(outs - 1));
+    const int src_phase = src.phase(vec), dst_phase = dst.phase(outs);
     BinArgs a{};
     a.hb = hb;
     a.wb = wb;
@@ -230,34 +217,22 @@ extern "C" int sq_bin_tiles(const void *src_dev, void *dst_dev, int32_t n_images
     for (int s = 0; s < outs; ++s)
         if ((factor * s - src_phase) % vec == 0 && (a.shift < 0 || s == dst_phase)) a.shift = s;
     if (a.shift < 0) a.shift = dst_phase;
-    const int64_t nvec = ((int64_t)wb + a.shift + outs - 1) / outs;
-    a.tx = 1;
-    a.tx_log2 = 0;
-    while (a.tx < THREADS && a.tx < nvec) {
-        a.tx *= 2;
-        a.tx_log2 += 1;
-    }
-    const int ty = THREADS / a.tx;
-    const int64_t n_strips = (nvec + a.tx - 1) / a.tx;
-    const int64_t n_segs = ((int64_t)hb + (int64_t)ty * RPT - 1) / ((int64_t)ty * RPT);
-    if (n_strips * n_segs > INT32_MAX)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_bin_tiles: a plane of %d x %d needs more workgroups than a launch has", h, w);
-    a.n_strips = (int32_t)n_strips;
+    StripGrid g;
+    if (const int rc = strip_grid("sq_bin_tiles", ((int64_t)wb + a.shift + outs - 1) / outs, THREADS, THREADS, RPT, hb, &g)) return rc;
+    a.tx = g.tx;
+    a.tx_log2 = g.tx_log2;
+    a.n_strips = g.n_strips;
     a.src_plane_stride = src_plane_stride;
     a.src_pitch = src_pitch;
     a.dst_plane_stride = dst_plane_stride;
     a.dst_pitch = dst_pitch;
-    for (int32_t p0 = 0; p0 < n_images; p0 += 65535) {
-        const int32_t m = std::min<int32_t>(65535, n_images - p0);
-        const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)m);
-        a.src = static_cast<const char *>(src_dev) + (int64_t)p0 * src_plane_stride * esize;
-        a.dst = static_cast<char *>(dst_dev) + (int64_t)p0 * dst_plane_stride * esize;
+    return for_each_launch("sq_bin_tiles", 0, n_images, 1, [&](int64_t p0, int32_t, unsigned grid_y) {
+        const dim3 grid(g.x(), grid_y);
+        a.src = src.at(p0);
+        a.dst = dst.at(p0);
         if (dtype == SQ_U16)
             launch<uint16_t>(factor, method, grid, stream, a);
         else
             launch<uint8_t>(factor, method, grid, stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_bin_tiles: launch failed: %s", hipGetErrorString(e));
-    }
-    return SQ_OK;
+    });
 }

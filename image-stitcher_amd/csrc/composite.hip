@@ -22,17 +22,15 @@
 #include <algorithm>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed)) U32x4U {
     u32x4 v;
 };
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;

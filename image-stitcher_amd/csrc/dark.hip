@@ -24,19 +24,16 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
-
 constexpr int THREADS = 256;
 constexpr int RPT = 8;      // rows a thread walks down
 constexpr int IPT = SQ_DARK_IMAGES_PER_THREAD;
-constexpr int32_t GRID_Y = 65535;
 
 struct DarkArgs {
     void *tiles;                // the run's first image
@@ -195,25 +192,15 @@ extern "C" int sq_dark_tiles(void *tiles_dev, int32_t n_images, int32_t h, int32
         any_frame = any_frame || k >= 0;
     }
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    const uintptr_t t0 = reinterpret_cast<uintptr_t>(tiles_dev), f0 = reinterpret_cast<uintptr_t>(frames_dev);
-    if (t0 % esize) return fail(SQ_ERR_INVALID, "sq_dark_tiles: planes must be aligned to their element");
-    const int64_t plane = (int64_t)(h - 1) * pitch + w;
-    if (n_images > 1 && plane_stride < plane) return fail(SQ_ERR_INVALID, "sq_dark_tiles: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (plane_stride > plane_limit || plane > plane_limit) return fail(SQ_ERR_INVALID, "sq_dark_tiles: extents beyond the address space");
+    const PlaneBatch tiles{tiles_dev, n_images, h, w, plane_stride, pitch, esize};
+    if (const int rc = check_batches("sq_dark_tiles", "plane", {tiles})) return rc;
     if (any_frame) {
         if (!frames_dev) return fail(SQ_ERR_INVALID, "sq_dark_tiles: NULL frames");
-        if (f0 % esize) return fail(SQ_ERR_INVALID, "sq_dark_tiles: frames must be aligned to their element");
         if (frame_pitch < w) return fail(SQ_ERR_INVALID, "sq_dark_tiles: frame pitch %lld below the width %d", (long long)frame_pitch, w);
-        const int64_t frame_plane = (int64_t)(h - 1) * frame_pitch + w;
-        if (n_frames > 1 && frame_stride < frame_plane) return fail(SQ_ERR_INVALID, "sq_dark_tiles: frame stride smaller than a frame");
-        const int64_t frame_limit = (INT64_MAX / 4) / n_frames;
-        if (frame_stride > frame_limit || frame_plane > frame_limit)
-            return fail(SQ_ERR_INVALID, "sq_dark_tiles: extents beyond the address space");
-        // the extents (first to last element of all planes) must not overlap: the call works in place on the tiles
-        const uintptr_t t1 = t0 + (uintptr_t)(((int64_t)(n_images - 1) * plane_stride + plane) * esize);
-        const uintptr_t f1 = f0 + (uintptr_t)(((int64_t)(n_frames - 1) * frame_stride + frame_plane) * esize);
-        if (t0 < f1 && f0 < t1) return fail(SQ_ERR_INVALID, "sq_dark_tiles: the frames overlap the tiles");
+        const PlaneBatch frames{frames_dev, n_frames, h, w, frame_stride, frame_pitch, esize};
+        if (const int rc = check_batches("sq_dark_tiles", "frame", {frames})) return rc;
+        // the call works in place on the tiles
+        if (overlap(tiles, frames)) return fail(SQ_ERR_INVALID, "sq_dark_tiles: the frames overlap the tiles");
     }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
@@ -228,38 +215,25 @@ extern "C" int sq_dark_tiles(void *tiles_dev, int32_t n_images, int32_t h, int32
     // vectors a row can touch: its phase is the base's in every row when pitch and plane stride are whole vectors, else any
     const bool stride_whole = n_images == 1 || plane_stride % vec == 0;
     const bool one_phase = pitch % vec == 0 && stride_whole;
-    const int64_t mis = one_phase ? (int64_t)((t0 / esize) & (uintptr_t)(vec - 1)) : vec - 1;
-    const int64_t nvec = ((int64_t)w + mis + vec - 1) / vec;
-    a.tx = 1;
-    a.tx_log2 = 0;
-    while (a.tx < THREADS && a.tx < nvec) {
-        a.tx *= 2;
-        a.tx_log2 += 1;
-    }
-    const int ty = THREADS / a.tx;
-    const int64_t n_strips = (nvec + a.tx - 1) / a.tx;
-    const int64_t n_segs = ((int64_t)h + (int64_t)ty * RPT - 1) / ((int64_t)ty * RPT);
-    if (n_strips * n_segs > INT32_MAX)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_dark_tiles: a plane of %d x %d needs more workgroups than a launch has", h, w);
-    a.n_strips = (int32_t)n_strips;
+    const int64_t mis = one_phase ? tiles.phase(vec) : vec - 1;
+    StripGrid g;
+    if (const int rc = strip_grid("sq_dark_tiles", ((int64_t)w + mis + vec - 1) / vec, THREADS, THREADS, RPT, h, &g)) return rc;
+    a.tx = g.tx;
+    a.tx_log2 = g.tx_log2;
+    a.n_strips = g.n_strips;
     // the images a thread walks with one frame vector: they must share the row's phase
     const int ipt = stride_whole ? IPT : 1;
     // one grid per maximal run of consecutive equal pairs, none for a run that is the identity: the arguments stay scalar, no
     // table goes to the device
-    for (int32_t s0 = 0; s0 < n_params;) {
-        int32_t s1 = s0 + 1;
-        while (s1 < n_params && params_host[2 * s1] == params_host[2 * s0] && params_host[2 * s1 + 1] == params_host[2 * s0 + 1]) ++s1;
-        const int32_t k = params_host[2 * s0], c = params_host[2 * s0 + 1];
-        const int64_t first = (int64_t)s0 * images_per_param, last = (int64_t)s1 * images_per_param;
-        s0 = s1;
-        if (k < 0 && c == pedestal) continue;      // the identity: nothing is issued, the planes stay untouched
+    return for_each_run(params_host, n_params, 2, [&](const int32_t *t, int32_t s0, int32_t s1) {
+        const int32_t k = t[0], c = t[1];
+        if (k < 0 && c == pedestal) return (int)SQ_OK;      // the identity: nothing is issued, the planes stay untouched
         a.k = pedestal - c;
         a.frame = k < 0 ? nullptr : static_cast<const char *>(frames_dev) + (int64_t)k * frame_stride * esize;
-        const int64_t per_grid = (int64_t)GRID_Y * ipt;
-        for (int64_t p0 = first; p0 < last; p0 += per_grid) {
-            const int32_t m = (int32_t)std::min<int64_t>(per_grid, last - p0);
-            const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)((m + ipt - 1) / ipt));
-            a.tiles = static_cast<char *>(tiles_dev) + p0 * plane_stride * esize;
+        return for_each_launch("sq_dark_tiles", (int64_t)s0 * images_per_param, (int64_t)s1 * images_per_param, ipt,
+                               [&](int64_t p0, int32_t m, unsigned grid_y) {
+            const dim3 grid(g.x(), grid_y);
+            a.tiles = tiles.at(p0);
             a.n_images = m;
             if (dtype == SQ_U16) {
                 if (ipt == 1) launch<uint16_t, 1>(a, k < 0, grid, stream);
@@ -268,9 +242,6 @@ extern "C" int sq_dark_tiles(void *tiles_dev, int32_t n_images, int32_t h, int32
                 if (ipt == 1) launch<uint8_t, 1>(a, k < 0, grid, stream);
                 else launch<uint8_t, IPT>(a, k < 0, grid, stream);
             }
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_dark_tiles: launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    return SQ_OK;
+        });
+    });
 }

@@ -29,14 +29,12 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int RPT = 32;     // rows a thread walks down (each run re-reads two halo rows: 6 % of the reads)
@@ -52,15 +50,6 @@ struct DespeckleArgs {
     int32_t tx, tx_log2;        // vectors across a workgroup
     int32_t n_strips;
 };
-
-// s_waitcnt lgkmcnt(0) by the wave that has just written LDS, in front of a barrier (the case tools/barrier_scan.py looks for;
-// encoding and history: lds_written() in fuse_device.h).
-__device__ __forceinline__ void lds_written() {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-}
 
 __device__ __forceinline__ uint32_t med3(uint32_t a, uint32_t b, uint32_t c) {
     return max(min(a, b), min(max(a, b), c));
@@ -197,22 +186,13 @@ extern "C" int sq_despeckle_tiles(const void *src_dev, void *dst_dev, int32_t n_
                     (long long)src_pitch, (long long)dst_pitch);
     if (n_images == 0) return SQ_OK;
     if (!src_dev || !dst_dev) return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: NULL buffer");
+    if (reinterpret_cast<uintptr_t>(counts_dev) % 8) return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: the counts must be aligned to 8 bytes");
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    if (reinterpret_cast<uintptr_t>(src_dev) % esize || reinterpret_cast<uintptr_t>(dst_dev) % esize ||
-        reinterpret_cast<uintptr_t>(counts_dev) % 8)
-        return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: planes must be aligned to their element, the counts to 8 bytes");
-    const int64_t src_plane = (int64_t)(h - 1) * src_pitch + w, dst_plane = (int64_t)(h - 1) * dst_pitch + w;
-    if (n_images > 1 && (src_plane_stride < src_plane || dst_plane_stride < dst_plane))
-        return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (src_plane_stride > plane_limit || dst_plane_stride > plane_limit || src_plane > plane_limit || dst_plane > plane_limit)
-        return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: extents beyond the address space");
-    {   // the extents (first to last element of all planes) must not overlap: the stencil reads what a neighbour writes
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), d0 = reinterpret_cast<uintptr_t>(dst_dev);
-        const uintptr_t s1 = s0 + (uintptr_t)(((int64_t)(n_images - 1) * src_plane_stride + src_plane) * esize);
-        const uintptr_t d1 = d0 + (uintptr_t)(((int64_t)(n_images - 1) * dst_plane_stride + dst_plane) * esize);
-        if (s0 < d1 && d0 < s1) return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: src and dst overlap (the filter is out of place)");
-    }
+    const PlaneBatch src{src_dev, n_images, h, w, src_plane_stride, src_pitch, esize};
+    const PlaneBatch dst{dst_dev, n_images, h, w, dst_plane_stride, dst_pitch, esize};
+    if (const int rc = check_batches("sq_despeckle_tiles", "plane", {src, dst})) return rc;
+    // the stencil reads what a neighbour writes
+    if (overlap(src, dst)) return fail(SQ_ERR_INVALID, "sq_despeckle_tiles: src and dst overlap (the filter is out of place)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int vec = 16 / esize;
@@ -220,29 +200,20 @@ extern "C" int sq_despeckle_tiles(const void *src_dev, void *dst_dev, int32_t n_
     a.h = h;
     a.w = w;
     a.threshold = threshold;
-    a.mis = (int32_t)((reinterpret_cast<uintptr_t>(dst_dev) / esize) & (uintptr_t)(vec - 1));
-    const int64_t nvec = ((int64_t)w + a.mis + vec - 1) / vec;
-    a.tx = 1;
-    a.tx_log2 = 0;
-    while (a.tx < THREADS && a.tx < nvec) {
-        a.tx *= 2;
-        a.tx_log2 += 1;
-    }
-    const int ty = THREADS / a.tx;
-    const int64_t n_strips = (nvec + a.tx - 1) / a.tx;
-    const int64_t n_segs = ((int64_t)h + (int64_t)ty * RPT - 1) / ((int64_t)ty * RPT);
-    if (n_strips * n_segs > INT32_MAX)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_despeckle_tiles: a plane of %d x %d needs more workgroups than a launch has", h, w);
-    a.n_strips = (int32_t)n_strips;
+    a.mis = dst.phase(vec);
+    StripGrid g;
+    if (const int rc = strip_grid("sq_despeckle_tiles", ((int64_t)w + a.mis + vec - 1) / vec, THREADS, THREADS, RPT, h, &g)) return rc;
+    a.tx = g.tx;
+    a.tx_log2 = g.tx_log2;
+    a.n_strips = g.n_strips;
     a.src_plane_stride = src_plane_stride;
     a.src_pitch = src_pitch;
     a.dst_plane_stride = dst_plane_stride;
     a.dst_pitch = dst_pitch;
-    for (int32_t p0 = 0; p0 < n_images; p0 += 65535) {
-        const int32_t m = std::min<int32_t>(65535, n_images - p0);
-        const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)m);
-        a.src = static_cast<const char *>(src_dev) + (int64_t)p0 * src_plane_stride * esize;
-        a.dst = static_cast<char *>(dst_dev) + (int64_t)p0 * dst_plane_stride * esize;
+    return for_each_launch("sq_despeckle_tiles", 0, n_images, 1, [&](int64_t p0, int32_t, unsigned grid_y) {
+        const dim3 grid(g.x(), grid_y);
+        a.src = src.at(p0);
+        a.dst = dst.at(p0);
         a.counts = counts_dev ? reinterpret_cast<unsigned long long *>(counts_dev) + p0 : nullptr;
         if (dtype == SQ_U16) {
             if (mode == SQ_DESPECKLE_BOTH)
@@ -255,8 +226,5 @@ extern "C" int sq_despeckle_tiles(const void *src_dev, void *dst_dev, int32_t n_
             else
                 despeckle_kernel<uint8_t, false><<<grid, dim3(THREADS), 0, stream>>>(a);
         }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_despeckle_tiles: launch failed: %s", hipGetErrorString(e));
-    }
-    return SQ_OK;
+    });
 }

@@ -22,14 +22,12 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int RPT = 8;      // rows a thread walks down
@@ -151,27 +149,15 @@ extern "C" int sq_dpc_tiles(const void *left_dev, const void *right_dev, void *o
     if (n_images == 0) return SQ_OK;
     if (!left_dev || !right_dev || !out_dev) return fail(SQ_ERR_INVALID, "sq_dpc_tiles: NULL buffer");
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    const uintptr_t l0 = reinterpret_cast<uintptr_t>(left_dev), r0 = reinterpret_cast<uintptr_t>(right_dev),
-                    o0 = reinterpret_cast<uintptr_t>(out_dev);
-    if (l0 % esize || r0 % esize || o0 % esize) return fail(SQ_ERR_INVALID, "sq_dpc_tiles: planes must be aligned to their element");
-    const int64_t left_plane = (int64_t)(h - 1) * left_pitch + w, right_plane = (int64_t)(h - 1) * right_pitch + w,
-                  out_plane = (int64_t)(h - 1) * out_pitch + w;
-    if (n_images > 1 && (left_plane_stride < left_plane || right_plane_stride < right_plane || out_plane_stride < out_plane))
-        return fail(SQ_ERR_INVALID, "sq_dpc_tiles: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (left_plane_stride > plane_limit || right_plane_stride > plane_limit || out_plane_stride > plane_limit ||
-        left_plane > plane_limit || right_plane > plane_limit || out_plane > plane_limit)
-        return fail(SQ_ERR_INVALID, "sq_dpc_tiles: extents beyond the address space");
-    {   // out is exactly left (in place), or its extent (first to last element of all planes) meets neither input's
-        const int64_t last = n_images - 1;      // (a single plane's stride is never used)
-        const uintptr_t l1 = l0 + (uintptr_t)((last * left_plane_stride + left_plane) * esize);
-        const uintptr_t r1 = r0 + (uintptr_t)((last * right_plane_stride + right_plane) * esize);
-        const uintptr_t o1 = o0 + (uintptr_t)((last * out_plane_stride + out_plane) * esize);
-        const bool in_place = o0 == l0 && out_pitch == left_pitch && (n_images == 1 || out_plane_stride == left_plane_stride);
-        if (!in_place && l0 < o1 && o0 < l1)
-            return fail(SQ_ERR_INVALID, "sq_dpc_tiles: out overlaps left without being exactly left (base, plane stride, pitch)");
-        if (r0 < o1 && o0 < r1) return fail(SQ_ERR_INVALID, "sq_dpc_tiles: out overlaps right");
-    }
+    const PlaneBatch left{left_dev, n_images, h, w, left_plane_stride, left_pitch, esize};
+    const PlaneBatch right{right_dev, n_images, h, w, right_plane_stride, right_pitch, esize};
+    const PlaneBatch out{out_dev, n_images, h, w, out_plane_stride, out_pitch, esize};
+    if (const int rc = check_batches("sq_dpc_tiles", "plane", {left, right, out})) return rc;
+    // out is exactly left (in place; a single plane's stride is never used), or its extent meets neither input's
+    const bool in_place = out_dev == left_dev && out_pitch == left_pitch && (n_images == 1 || out_plane_stride == left_plane_stride);
+    if (!in_place && overlap(left, out))
+        return fail(SQ_ERR_INVALID, "sq_dpc_tiles: out overlaps left without being exactly left (base, plane stride, pitch)");
+    if (overlap(right, out)) return fail(SQ_ERR_INVALID, "sq_dpc_tiles: out overlaps right");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int vec = 16 / esize;
@@ -181,38 +167,26 @@ extern "C" int sq_dpc_tiles(const void *left_dev, const void *right_dev, void *o
     a.gain2 = 2 * gain;
     // vectors a row can touch: its phase is the base's in every row when pitch and plane stride are whole vectors, else any
     const bool one_phase = out_pitch % vec == 0 && (n_images == 1 || out_plane_stride % vec == 0);
-    const int64_t mis = one_phase ? (int64_t)((o0 / esize) & (uintptr_t)(vec - 1)) : vec - 1;
-    const int64_t nvec = ((int64_t)w + mis + vec - 1) / vec;
-    a.tx = 1;
-    a.tx_log2 = 0;
-    while (a.tx < THREADS && a.tx < nvec) {
-        a.tx *= 2;
-        a.tx_log2 += 1;
-    }
-    const int ty = THREADS / a.tx;
-    const int64_t n_strips = (nvec + a.tx - 1) / a.tx;
-    const int64_t n_segs = ((int64_t)h + (int64_t)ty * RPT - 1) / ((int64_t)ty * RPT);
-    if (n_strips * n_segs > INT32_MAX)
-        return fail(SQ_ERR_UNSUPPORTED, "sq_dpc_tiles: a plane of %d x %d needs more workgroups than a launch has", h, w);
-    a.n_strips = (int32_t)n_strips;
+    const int64_t mis = one_phase ? out.phase(vec) : vec - 1;
+    StripGrid g;
+    if (const int rc = strip_grid("sq_dpc_tiles", ((int64_t)w + mis + vec - 1) / vec, THREADS, THREADS, RPT, h, &g)) return rc;
+    a.tx = g.tx;
+    a.tx_log2 = g.tx_log2;
+    a.n_strips = g.n_strips;
     a.left_plane_stride = left_plane_stride;
     a.left_pitch = left_pitch;
     a.right_plane_stride = right_plane_stride;
     a.right_pitch = right_pitch;
     a.out_plane_stride = out_plane_stride;
     a.out_pitch = out_pitch;
-    for (int32_t p0 = 0; p0 < n_images; p0 += 65535) {
-        const int32_t m = std::min<int32_t>(65535, n_images - p0);
-        const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)m);
-        a.left = static_cast<const char *>(left_dev) + (int64_t)p0 * left_plane_stride * esize;
-        a.right = static_cast<const char *>(right_dev) + (int64_t)p0 * right_plane_stride * esize;
-        a.out = static_cast<char *>(out_dev) + (int64_t)p0 * out_plane_stride * esize;
+    return for_each_launch("sq_dpc_tiles", 0, n_images, 1, [&](int64_t p0, int32_t, unsigned grid_y) {
+        const dim3 grid(g.x(), grid_y);
+        a.left = left.at(p0);
+        a.right = right.at(p0);
+        a.out = out.at(p0);
         if (dtype == SQ_U16)
             dpc_kernel<uint16_t><<<grid, dim3(THREADS), 0, stream>>>(a);
         else
             dpc_kernel<uint8_t><<<grid, dim3(THREADS), 0, stream>>>(a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_dpc_tiles: launch failed: %s", hipGetErrorString(e));
-    }
-    return SQ_OK;
+    });
 }

@@ -13,12 +13,12 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
@@ -28,7 +28,6 @@ struct __attribute__((packed)) U32x4U {  // 16 bytes at any alignment
 struct __attribute__((packed)) F32x4U {
     f32x4 v;
 };
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed)) U32x2U {  // 8 bytes at any alignment
     u32x2 v;
 };
@@ -36,7 +35,6 @@ struct __attribute__((packed)) F64x2U {
     f64x2 v;
 };
 
-#define SQ_GLOBAL __attribute__((address_space(1)))
 // Explicit global-address-space accessors: pointers that come out of a table are generic to the
 // compiler and would be lowered to flat_* instructions.
 template <typename V>
@@ -365,22 +363,8 @@ __device__ __forceinline__ void for_each_queued_item(const FuseParams &P, const 
             c = atomicAdd(&P.queue[queue_of(given_up) * QUEUE_STRIDE], 1u);
         }
     };
-    // lds_written(): s_waitcnt lgkmcnt(0) by the wave that has just written the NEXT chunk's (queue, index) into LDS.  The
-    // barrier at the top of the loop is what publishes them, and a barrier only orders what has completed: the compiler
-    // (ROCm 7.2) puts the wait in front of the barrier after the descriptor stores below but NOT in front of the one at the
-    // top of the loop, which it reaches round the back edge straight after thread 0's ds_write -- the other waves could
-    // then read the slot before the write landed, i.e. the (queue, index) of two chunks ago: they repeated an old chunk
-    // (harmless) and skipped their share of the new one.  Found in round 3 as 28 ... 508 unwritten voxels in 1-2 % of the
-    // launches of the per-plane feather kernel on a small plan (tools/queue_stress.py; the plane-group kernels never
-    // showed it in thousands of launches, but their code had the same gap).
-    // 0xc07f is the s_waitcnt immediate of the gfx9 family (vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8]): lgkmcnt(0) with
-    // vmcnt / expcnt at their maxima.  gfx10+ lay the fields out differently -- there the same bits would wait on something else
-    // and the race would be back, silently -- so a device pass for anything but gfx9 stops here (tools/barrier_scan.py,
-    // run by tests/test_isa_cpu.py, checks the listing of the build that ships).
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    auto lds_written = [] { __builtin_amdgcn_s_waitcnt(0xc07f); };
+    // lds_written() (device_util.h) after thread 0 has written the NEXT chunk's (queue, index) into LDS: the barrier at the top
+    // of the loop is what publishes them, and it is reached round the back edge straight after the ds_write.
     if (threadIdx.x == 0) {
         const Chunk first = settle(atomicAdd(&P.queue[queue_of(0) * QUEUE_STRIDE], 1u));
         s_q[0] = first.q;

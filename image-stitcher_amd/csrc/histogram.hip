@@ -27,13 +27,11 @@
 #include <algorithm>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 1024;
 constexpr int WAVES = THREADS / 64;
@@ -77,15 +75,6 @@ __device__ __forceinline__ void add<uint16_t>(uint32_t *lds, unsigned long long 
 template <>
 __device__ __forceinline__ void add<uint8_t>(uint32_t *lds, unsigned long long *, uint32_t v, uint32_t n) {
     atomicAdd(&lds[(threadIdx.x >> 6) * 1024 + v * 4 + (threadIdx.x & 3)], n);
-}
-
-// s_waitcnt lgkmcnt(0) by the wave that has just added into LDS: a no-return ds_add in front of a barrier was seen without the
-// wait that publishes it (the case tools/barrier_scan.py looks for; encoding and history: lds_written() in fuse_device.h).
-__device__ __forceinline__ void lds_written() {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    __builtin_amdgcn_s_waitcnt(0xc07f);
 }
 
 // LDS counters -> the global row, LDS zeroed.  All threads.

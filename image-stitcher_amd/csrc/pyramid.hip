@@ -20,17 +20,15 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed)) U32x4U {
     u32x4 v;
 };
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 template <typename T>
 struct OddSel;

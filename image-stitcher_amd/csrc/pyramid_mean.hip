@@ -27,17 +27,15 @@
 #include <algorithm>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed)) U32x4U {
     u32x4 v;
 };
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int MAX_LEVELS = SQ_PYRAMID_MEAN_MAX_LEVELS;   // levels per launch
 constexpr int STRIP_ROWS = 1 << MAX_LEVELS;              // source rows of a tile

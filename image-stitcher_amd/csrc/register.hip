@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
@@ -698,7 +699,6 @@ template <typename T>
 __global__ __launch_bounds__(256) void minmax_kernel(const void *const *tile_ptrs, const void *tile_base,
                                                      int64_t tile_stride, int tile_h, int tile_w, int pitch,
                                                      uint32_t *mm) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     constexpr int VEC = 16 / sizeof(T);
     const int t = blockIdx.y;
     const T *tile = tile_ptrs ? static_cast<const T *>(tile_ptrs[t]) : static_cast<const T *>(tile_base) + t * tile_stride;

@@ -38,6 +38,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace sq;
 
@@ -62,15 +63,6 @@ struct SeamArgs {
     unsigned long long *out;                       // [planes of this launch][n_pairs][words], the first pair of this launch
     int64_t out_plane_stride;                      // n_pairs * words
 };
-
-// s_waitcnt lgkmcnt(0) by the wave that has just written LDS, in front of a barrier (the case tools/barrier_scan.py looks for;
-// encoding and history: lds_written() in fuse_device.h).
-__device__ __forceinline__ void lds_written() {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-}
 
 __device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int m) {
     const uint32_t lo = __shfl_xor((uint32_t)v, m, WAVE), hi = __shfl_xor((uint32_t)(v >> 32), m, WAVE);

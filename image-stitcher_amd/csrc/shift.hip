@@ -34,17 +34,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// 16 bytes in one load at the alignment of an element: the compiler is told so and picks the instruction
-typedef u32x4 span_of_u16 __attribute__((aligned(2)));
-typedef u32x4 span_of_u8 __attribute__((aligned(1)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int RPT = SQ_SHIFT_ROWS_PER_THREAD;     // rows a thread walks down (each run reads one halo row: 3 % of the reads)
@@ -179,65 +174,42 @@ extern "C" int sq_shift_tiles(const void *src_dev, void *dst_dev, int32_t n_imag
             return fail(SQ_ERR_INVALID, "sq_shift_tiles: shift %d of pair %d outside -%d..%d (1/256 pixel)", shifts_host[i], i / 2,
                         SQ_SHIFT_MAX, SQ_SHIFT_MAX);
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    if (reinterpret_cast<uintptr_t>(src_dev) % esize || reinterpret_cast<uintptr_t>(dst_dev) % esize)
-        return fail(SQ_ERR_INVALID, "sq_shift_tiles: planes must be aligned to their element");
-    const int64_t src_plane = (int64_t)(h - 1) * src_pitch + w, dst_plane = (int64_t)(h - 1) * dst_pitch + w;
-    if (n_images > 1 && (src_plane_stride < src_plane || dst_plane_stride < dst_plane))
-        return fail(SQ_ERR_INVALID, "sq_shift_tiles: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (src_plane_stride > plane_limit || dst_plane_stride > plane_limit || src_plane > plane_limit || dst_plane > plane_limit)
-        return fail(SQ_ERR_INVALID, "sq_shift_tiles: extents beyond the address space");
-    {   // the extents (first to last element of all planes) must not overlap: a thread reads what a neighbour writes
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_dev), d0 = reinterpret_cast<uintptr_t>(dst_dev);
-        const uintptr_t s1 = s0 + (uintptr_t)(((int64_t)(n_images - 1) * src_plane_stride + src_plane) * esize);
-        const uintptr_t d1 = d0 + (uintptr_t)(((int64_t)(n_images - 1) * dst_plane_stride + dst_plane) * esize);
-        if (s0 < d1 && d0 < s1) return fail(SQ_ERR_INVALID, "sq_shift_tiles: src and dst overlap (the shift is out of place)");
-    }
+    const PlaneBatch src{src_dev, n_images, h, w, src_plane_stride, src_pitch, esize};
+    const PlaneBatch dst{dst_dev, n_images, h, w, dst_plane_stride, dst_pitch, esize};
+    if (const int rc = check_batches("sq_shift_tiles", "plane", {src, dst})) return rc;
+    // a thread reads what a neighbour writes
+    if (overlap(src, dst)) return fail(SQ_ERR_INVALID, "sq_shift_tiles: src and dst overlap (the shift is out of place)");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int vec = 16 / esize;
     ShiftArgs a{};
     a.h = h;
     a.w = w;
-    a.mis = (int32_t)((reinterpret_cast<uintptr_t>(dst_dev) / esize) & (uintptr_t)(vec - 1));
-    const int64_t nvec = ((int64_t)w + a.mis + vec - 1) / vec;
-    a.tx = 1;
-    a.tx_log2 = 0;
-    while (a.tx < THREADS && a.tx < nvec) {
-        a.tx *= 2;
-        a.tx_log2 += 1;
-    }
-    const int ty = THREADS / a.tx;
-    const int64_t n_strips = (nvec + a.tx - 1) / a.tx;
-    const int64_t n_segs = ((int64_t)h + (int64_t)ty * RPT - 1) / ((int64_t)ty * RPT);
-    a.n_strips = (int32_t)n_strips;      // (sides up to 65535: at most 512 strips and 2048 segments)
+    a.mis = dst.phase(vec);
+    StripGrid g;      // (sides up to 65535: at most 512 strips and 2048 segments)
+    if (const int rc = strip_grid("sq_shift_tiles", ((int64_t)w + a.mis + vec - 1) / vec, THREADS, THREADS, RPT, h, &g)) return rc;
+    a.tx = g.tx;
+    a.tx_log2 = g.tx_log2;
+    a.n_strips = g.n_strips;
     a.src_plane_stride = src_plane_stride;
     a.src_pitch = src_pitch;
     a.dst_plane_stride = dst_plane_stride;
     a.dst_pitch = dst_pitch;
     // one grid per maximal run of consecutive equal pairs, (0, 0) included: the arguments stay scalar, no table goes to the device
-    for (int32_t s0 = 0; s0 < n_shifts;) {
-        int32_t s1 = s0 + 1;
-        while (s1 < n_shifts && shifts_host[2 * s1] == shifts_host[2 * s0] && shifts_host[2 * s1 + 1] == shifts_host[2 * s0 + 1]) ++s1;
-        const int32_t sy = shifts_host[2 * s0], sx = shifts_host[2 * s0 + 1];
-        a.iy = sy >> 8;
-        a.ix = sx >> 8;
-        a.fy = (uint32_t)(sy & 255);
-        a.fx = (uint32_t)(sx & 255);
-        const int64_t first = (int64_t)s0 * images_per_shift, last = (int64_t)s1 * images_per_shift;
-        for (int64_t p0 = first; p0 < last; p0 += 65535) {
-            const int32_t m = (int32_t)std::min<int64_t>(65535, last - p0);
-            const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)m);
-            a.src = static_cast<const char *>(src_dev) + p0 * src_plane_stride * esize;
-            a.dst = static_cast<char *>(dst_dev) + p0 * dst_plane_stride * esize;
+    return for_each_run(shifts_host, n_shifts, 2, [&](const int32_t *t, int32_t s0, int32_t s1) {
+        a.iy = t[0] >> 8;
+        a.ix = t[1] >> 8;
+        a.fy = (uint32_t)(t[0] & 255);
+        a.fx = (uint32_t)(t[1] & 255);
+        return for_each_launch("sq_shift_tiles", (int64_t)s0 * images_per_shift, (int64_t)s1 * images_per_shift, 1,
+                               [&](int64_t p0, int32_t, unsigned grid_y) {
+            const dim3 grid(g.x(), grid_y);
+            a.src = src.at(p0);
+            a.dst = dst.at(p0);
             if (dtype == SQ_U16)
                 shift_kernel<uint16_t><<<grid, dim3(THREADS), 0, stream>>>(a);
             else
                 shift_kernel<uint8_t><<<grid, dim3(THREADS), 0, stream>>>(a);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_shift_tiles: launch failed: %s", hipGetErrorString(e));
-        }
-        s0 = s1;
-    }
-    return SQ_OK;
+        });
+    });
 }

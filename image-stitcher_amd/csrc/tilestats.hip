@@ -32,14 +32,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int WAVE = 64;
@@ -56,15 +54,6 @@ struct TileStatsArgs {
     int32_t tx_log2;               // vectors across a workgroup: 64, 128 or 256
     int32_t n_strips;
 };
-
-// s_waitcnt lgkmcnt(0) by the wave that has just written LDS, in front of a barrier (the case tools/barrier_scan.py looks for;
-// encoding and history: lds_written() in fuse_device.h).
-__device__ __forceinline__ void lds_written() {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-}
 
 // What a thread has seen of its plane.  A run is RPT rows of VEC columns: sums of values and counts fit 32 bits
 // (64 * 8 * 65535 < 2^25), sums of squares fit them for uint8 only (64 * 16 * 255^2 < 2^26).
@@ -248,13 +237,10 @@ extern "C" int sq_tile_stats(const void *src_dev, int32_t n_images, int32_t h, i
         return fail(SQ_ERR_UNSUPPORTED, "sq_tile_stats: a plane of %d x %d is beyond 2^31 pixels (or 2^30 a side): a word could wrap", h, w);
     if (n_images == 0) return SQ_OK;
     if (!src_dev || !out_dev) return fail(SQ_ERR_INVALID, "sq_tile_stats: NULL buffer");
+    if (reinterpret_cast<uintptr_t>(out_dev) % 8) return fail(SQ_ERR_INVALID, "sq_tile_stats: the words must be aligned to 8 bytes");
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    if (reinterpret_cast<uintptr_t>(src_dev) % esize || reinterpret_cast<uintptr_t>(out_dev) % 8)
-        return fail(SQ_ERR_INVALID, "sq_tile_stats: planes must be aligned to their element, the words to 8 bytes");
-    const int64_t plane = (int64_t)(h - 1) * pitch + w;
-    if (n_images > 1 && plane_stride < plane) return fail(SQ_ERR_INVALID, "sq_tile_stats: plane stride smaller than a plane");
-    const int64_t plane_limit = (INT64_MAX / 4) / n_images;
-    if (plane_stride > plane_limit || plane > plane_limit) return fail(SQ_ERR_INVALID, "sq_tile_stats: extents beyond the address space");
+    const PlaneBatch src{src_dev, n_images, h, w, plane_stride, pitch, esize};
+    if (const int rc = check_batches("sq_tile_stats", "plane", {src})) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
 
     const int vec = 16 / esize;
@@ -263,7 +249,7 @@ extern "C" int sq_tile_stats(const void *src_dev, int32_t n_images, int32_t h, i
     a.w = w;
     a.pitch = pitch;
     a.plane_stride = plane_stride;
-    a.mis = (int32_t)((reinterpret_cast<uintptr_t>(src_dev) / esize) & (uintptr_t)(vec - 1));
+    a.mis = src.phase(vec);
     const int64_t nvec = ((int64_t)w + a.mis + vec - 1) / vec;
     a.tx_log2 = nvec <= 64 ? 6 : (nvec <= 128 ? 7 : 8);
     const int tx = 1 << a.tx_log2, ty = THREADS / tx;
@@ -276,19 +262,15 @@ extern "C" int sq_tile_stats(const void *src_dev, int32_t n_images, int32_t h, i
     const int64_t n_words = (int64_t)n_images * WORDS;
     tile_stats_init_kernel<<<dim3((unsigned)((n_words + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream>>>(
         reinterpret_cast<unsigned long long *>(out_dev), n_words);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_tile_stats: launch failed: %s", hipGetErrorString(e));
-    for (int32_t p0 = 0; p0 < n_images; p0 += 65535) {
-        const int32_t m = std::min<int32_t>(65535, n_images - p0);
-        const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)m);
-        a.src = static_cast<const char *>(src_dev) + (int64_t)p0 * plane_stride * esize;
-        a.out = reinterpret_cast<unsigned long long *>(out_dev) + (int64_t)p0 * WORDS;
+    return for_each_launch("sq_tile_stats", 0, n_images, 1, [&](int64_t p0, int32_t, unsigned grid_y) {
+        const dim3 grid((unsigned)(n_strips * n_segs), grid_y);
+        a.src = src.at(p0);
+        a.out = reinterpret_cast<unsigned long long *>(out_dev) + p0 * WORDS;
         if (dtype == SQ_U16)
             tile_stats_kernel<uint16_t><<<grid, dim3(THREADS), 0, stream>>>(a);
         else
             tile_stats_kernel<uint8_t><<<grid, dim3(THREADS), 0, stream>>>(a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_tile_stats: launch failed: %s", hipGetErrorString(e));
-    }
-    return SQ_OK;
+    });
 }

@@ -30,14 +30,12 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "device_util.h"
+#include "plane_batch.h"
 
 using namespace sq;
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define SQ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int THREADS = 256;
 constexpr int MAX_RADIUS = 127;
@@ -55,15 +53,6 @@ struct MorphArgs {
     int32_t pitch;              // 16-bit values between two rows of F (and of B)
     int32_t n_strips, seg_h;    // blockIdx.x = row segment * n_strips + strip
 };
-
-// s_waitcnt lgkmcnt(0) by the wave that has just written LDS, in front of a barrier (the case tools/barrier_scan.py looks for;
-// encoding and history: lds_written() in fuse_device.h).
-__device__ __forceinline__ void lds_written() {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#error "lds_written(): the s_waitcnt immediate below is the gfx9 encoding; re-derive it for this target"
-#endif
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-}
 
 template <bool IS_MIN>
 __device__ __forceinline__ uint32_t op(uint32_t a, uint32_t b) {
@@ -249,11 +238,10 @@ extern "C" int sq_tophat_tiles(void *tiles_dev, int32_t n_images, int32_t h, int
     if (radius < 1 || radius > MAX_RADIUS) return fail(SQ_ERR_INVALID, "sq_tophat_tiles: radius %d outside 1..%d", radius, MAX_RADIUS);
     if (n_images == 0) return SQ_OK;
     if (!tiles_dev || !scratch_dev) return fail(SQ_ERR_INVALID, "sq_tophat_tiles: NULL buffer");
-    if (n_images > 1 && plane_stride < (int64_t)(h - 1) * pitch + w)
-        return fail(SQ_ERR_INVALID, "sq_tophat_tiles: plane stride smaller than a plane");
     const int esize = dtype == SQ_U16 ? 2 : 1;
-    if (reinterpret_cast<uintptr_t>(tiles_dev) % esize || reinterpret_cast<uintptr_t>(scratch_dev) % 16)
-        return fail(SQ_ERR_INVALID, "sq_tophat_tiles: tiles must be aligned to their element, the scratch to 16 bytes");
+    const PlaneBatch tiles{tiles_dev, n_images, h, w, plane_stride, pitch, esize};
+    if (const int rc = check_batches("sq_tophat_tiles", "plane", {tiles})) return rc;
+    if (reinterpret_cast<uintptr_t>(scratch_dev) % 16) return fail(SQ_ERR_INVALID, "sq_tophat_tiles: the scratch must be aligned to 16 bytes");
     const int64_t need = sq_tophat_scratch_bytes(n_images, h, w, dtype);
     if (scratch_bytes < need)
         return fail(SQ_ERR_WORKSPACE, "sq_tophat_tiles: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
@@ -280,13 +268,11 @@ extern "C" int sq_tophat_tiles(void *tiles_dev, int32_t n_images, int32_t h, int
     a.pitch = g.pitch;
     a.n_strips = n_strips;
     a.seg_h = seg_h;
-    for (int32_t p0 = 0; p0 < n_images; p0 += 65535) {
-        const int32_t m = std::min<int32_t>(65535, n_images - p0);
-        const dim3 grid((unsigned)(n_strips * n_segs), (unsigned)m);
-        char *tiles = static_cast<char *>(tiles_dev) + (int64_t)p0 * plane_stride * esize;
-        char *scratch = static_cast<char *>(scratch_dev) + (int64_t)p0 * h * w * esize;
+    return for_each_launch("sq_tophat_tiles", 0, n_images, 1, [&](int64_t p0, int32_t, unsigned grid_y) {
+        const dim3 grid((unsigned)(n_strips * n_segs), grid_y);
+        char *scratch = static_cast<char *>(scratch_dev) + p0 * h * w * esize;
         // erosion: tiles -> scratch (dense planes)
-        a.src = tiles;
+        a.src = tiles.at(p0);
         a.src_plane_stride = plane_stride;
         a.src_pitch = pitch;
         a.dst = scratch;
@@ -296,21 +282,16 @@ extern "C" int sq_tophat_tiles(void *tiles_dev, int32_t n_images, int32_t h, int
             launch<uint16_t, true>(a, g.lds, grid, stream);
         else
             launch<uint8_t, true>(a, g.lds, grid, stream);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_tophat_tiles: launch failed: %s", hipGetErrorString(e));
         // dilation of the scratch, subtracted from the tiles in place
         a.src = scratch;
         a.src_plane_stride = (int64_t)h * w;
         a.src_pitch = w;
-        a.dst = tiles;
+        a.dst = tiles.at(p0);
         a.dst_plane_stride = plane_stride;
         a.dst_pitch = pitch;
         if (dtype == SQ_U16)
             launch<uint16_t, false>(a, g.lds, grid, stream);
         else
             launch<uint8_t, false>(a, g.lds, grid, stream);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_tophat_tiles: launch failed: %s", hipGetErrorString(e));
-    }
-    return SQ_OK;
+    });
 }

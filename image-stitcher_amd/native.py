@@ -1150,19 +1150,14 @@ def tophat_tiles(tiles, radius: int, scratch=None, stream=None):
     """White top-hat of every H x W plane of ``tiles`` IN PLACE (sq_tophat_tiles; an extension, the reference has none): the plane
     minus its morphological opening with a square (2R+1) x (2R+1) window clipped to the plane -- ``tests/tophat_ref.tophat``.
 
-    tiles:   uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
-             uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    tiles:   a plane batch (``_plane_batch``).
     radius:  R, 1..127 (windows larger than the plane are fine).
     scratch: optional device uint8 tensor of at least ``tophat_scratch_bytes(n_planes, H, W, dtype)`` bytes (reuse it across
              calls); allocated here when None.
     Returns ``tiles``."""
     import torch
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    n_images, h, w, plane_stride, pitch = _plane_batch(tiles, 'tiles')
     radius = _int_in(radius, 1, SQ_TOPHAT_MAX_RADIUS, 'top-hat radius')
-    n_images, h, w, plane_stride, pitch = _plane_layout(tiles, 'tiles')
     np_dtype = np_dtype_of_torch(tiles.dtype)
     need = tophat_scratch_bytes(n_images, h, w, np_dtype)
     with _on_stream(stream):
@@ -1229,6 +1224,58 @@ def _overlap(a, b) -> bool:
     return a[0] < b[1] and b[0] < a[1]
 
 
+def _plane_batch(t, name, shape='[..., H, W]', dims=None):
+    """The plane batch every per-tile filter takes: ``t`` is a uint8 / uint16 device tensor [..., H, W] with unit-stride rows
+    (any row pitch, any base offset) whose leading dimensions are one uniform plane stride apart -- a contiguous stack, or a
+    view such as every other plane of one.  -> its ``_plane_layout``; ValueError otherwise."""
+    import torch
+    if not torch.is_tensor(t) or not t.is_cuda or (t.dim() < 2 if dims is None else t.dim() not in dims):
+        raise ValueError(f"{name} must be a {shape} device tensor")
+    if t.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"{name} must be uint8 or uint16, got {t.dtype}")
+    return _plane_layout(t, name)
+
+
+def _out_of_place(out, shape, tiles, src, noun, stream):
+    """The ``out`` of an out-of-place filter of the plane batch ``tiles`` (``src`` its layout), inside ``_on_stream(stream)``:
+    allocated contiguous when None, else a tensor of ``shape`` with the tiles' dtype and device that is a plane batch itself (its
+    columns beyond W stay as they are) and whose byte extent does not meet the tiles'.  -> (out, its layout)."""
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
+        if stream is not None:
+            out.record_stream(stream)
+    elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
+        raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
+    dst = _plane_layout(out, 'out')
+    assert dst[0] == src[0]
+    if src[0] and _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
+        raise ValueError(f"out shares memory with tiles: the {noun} is out of place")
+    return out, dst
+
+
+def _tuple_table(values, tiles, ranges, name, entry):
+    """``values`` is one tuple of integers for every plane of ``tiles``, or a sequence of one tuple per index of the leading
+    dimension (all planes under that index take it); position i of a tuple lies in ``ranges[i]`` = (lo, hi, noun).
+    -> (the flat int32 table for the library, the number of tuples); ``name`` and ``entry`` word the refusals."""
+    width = len(ranges)
+    try:
+        entries = list(values)
+    except TypeError:
+        raise ValueError(f"{name} must be {entry} or a sequence of them, got {values!r}")
+    if len(entries) == width and not any(isinstance(v, (list, tuple, np.ndarray)) for v in entries):
+        entries = [entries]      # one tuple for every plane
+    elif tiles.dim() < 3 or len(entries) != tiles.shape[0]:
+        raise ValueError(f"{name} must be {entry}, or one per index of the leading dimension "
+                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(entries)}")
+    table = []
+    for e in entries:
+        if isinstance(e, (str, bytes)) or not hasattr(e, '__len__') or len(e) != width:
+            raise ValueError(f"an entry of {name} is {entry}, got {e!r}")
+        table += [_int_in(v, lo, hi, noun) for v, (lo, hi, noun) in zip(e, ranges)]
+    return (C.c_int32 * len(table))(*table), len(entries)
+
+
 def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=None, stream=None):
     """Hot-pixel removal of every H x W plane of ``tiles`` into ``out`` (sq_despeckle_tiles; an extension, the reference has
     none): a pixel that differs from the median m of its edge-replicated 3 x 3 window by more than ``threshold`` -- mode 'hot':
@@ -1236,8 +1283,7 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
     ``tests/despeckle_ref.despeckle``.  The filter is out of place: ``tiles`` is left as it is and the caller goes on with the
     return value.
 
-    tiles:     uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
-               uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    tiles:     a plane batch (``_plane_batch``).
     threshold: T, an integer in 0..65535, in counts of the planes' dtype.
     out:       a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
                shares no memory with ``tiles``; allocated contiguous when None.
@@ -1245,34 +1291,19 @@ def despeckle_tiles(tiles, threshold: int, mode: str = 'hot', out=None, counts=N
                is ADDED to it.
     Returns ``out``."""
     import torch
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    src = _plane_batch(tiles, 'tiles')
+    n_images, h, w, src_plane_stride, src_pitch = src
     threshold = _int_in(threshold, 0, SQ_DESPECKLE_MAX_THRESHOLD, 'despeckle threshold')
     if not isinstance(mode, str) or mode not in DESPECKLE_MODES:
         raise ValueError(f"despeckle mode must be 'hot' or 'both', got {mode!r}")
-    src = _plane_layout(tiles, 'tiles')
-    n_images, h, w, src_plane_stride, src_pitch = src
     with _on_stream(stream):
-        if out is None:
-            out = torch.empty(tuple(tiles.shape), dtype=tiles.dtype, device=tiles.device)
-            if stream is not None:
-                out.record_stream(stream)
-        elif not torch.is_tensor(out) or tuple(out.shape) != tuple(tiles.shape) or out.dtype != tiles.dtype or \
-                out.device != tiles.device:
-            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {tuple(tiles.shape)} on the tiles' device")
-        dst = _plane_layout(out, 'out')
-        n_out, _, _, dst_plane_stride, dst_pitch = dst
-        assert n_out == n_images
+        out, (_, _, _, dst_plane_stride, dst_pitch) = _out_of_place(out, tuple(tiles.shape), tiles, src, 'filter', stream)
         if counts is not None:
             if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.device != tiles.device or \
                     counts.numel() != n_images or not counts.is_contiguous():
                 raise ValueError(f"counts must be a contiguous int64 tensor of {n_images} elements on the tiles' device")
         if n_images == 0:
             return out
-        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
-            raise ValueError("out shares memory with tiles: the filter is out of place")
         _check(lib().sq_despeckle_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                         dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
                                         DESPECKLE_MODES[mode], threshold,
@@ -1295,11 +1326,7 @@ def tile_stats(tiles, out=None, stream=None):
     out:   int64 device tensor [planes, 8]; its words are overwritten.  Allocated when None.
     Returns ``out``."""
     import torch
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() not in (3, 4):
-        raise ValueError("tiles must be a [n, H, W] or [b, n, H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    n_images, h, w, plane_stride, pitch = _plane_layout(tiles, 'tiles')
+    n_images, h, w, plane_stride, pitch = _plane_batch(tiles, 'tiles', '[n, H, W] or [b, n, H, W]', (3, 4))
     with _on_stream(stream):
         if out is None:
             out = torch.empty((n_images, SQ_TILE_STATS_WORDS), dtype=torch.int64, device=tiles.device)
@@ -1418,17 +1445,14 @@ def dpc_tiles(left, right, gain: int = 1, out=None, stream=None):
                  columns beyond W stay as they are) that is exactly ``left`` or shares no memory with either input.
     Returns ``out`` (``left`` when None)."""
     import torch
-    if not torch.is_tensor(left) or not left.is_cuda or left.dim() < 2:
-        raise ValueError("left must be a [..., H, W] device tensor")
-    if left.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"left must be uint8 or uint16, got {left.dtype}")
+    lay_l = _plane_batch(left, 'left')
     gain = _int_in(gain, 1, SQ_DPC_MAX_GAIN, 'dpc gain')
     if out is None:
         out = left
     for name, t in (('right', right), ('out', out)):
         if not torch.is_tensor(t) or tuple(t.shape) != tuple(left.shape) or t.dtype != left.dtype or t.device != left.device:
             raise ValueError(f"{name} must be a {left.dtype} tensor of shape {tuple(left.shape)} on left's device")
-    lay_l, lay_r, lay_o = _plane_layout(left, 'left'), _plane_layout(right, 'right'), _plane_layout(out, 'out')
+    lay_r, lay_o = _plane_layout(right, 'right'), _plane_layout(out, 'out')
     n_images, h, w, left_plane_stride, left_pitch = lay_l
     (right_plane_stride, right_pitch), (out_plane_stride, out_pitch) = lay_r[3:], lay_o[3:]
     if n_images == 0:
@@ -1455,8 +1479,7 @@ def bin_tiles(tiles, factor: int, method: str = 'mean', out=None, stream=None):
     a K x K block, 'mean' gives floor(S / K^2) and 'sum' gives min(S, M), M the dtype's maximum, exact in integers --
     ``tests/bin_ref.bin_image``.  The binning is out of place: ``tiles`` is left as it is.
 
-    tiles:  uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
-            uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    tiles:  a plane batch (``_plane_batch``).
     factor: K, an integer in 2..8 no larger than H or W.
     method: 'mean' or 'sum'.
     out:    a tensor [..., hb, wb] with the same leading dimensions, dtype and device under the same rules (its columns beyond
@@ -1466,30 +1489,15 @@ def bin_tiles(tiles, factor: int, method: str = 'mean', out=None, stream=None):
     factor = _int_in(factor, 2, SQ_BIN_MAX_FACTOR, 'binning factor')
     if not isinstance(method, str) or method not in BIN_METHODS:
         raise ValueError(f"binning method must be 'mean' or 'sum', got {method!r}")
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    src = _plane_layout(tiles, 'tiles')
+    src = _plane_batch(tiles, 'tiles')
     n_images, h, w, src_plane_stride, src_pitch = src
     hb, wb = h // factor, w // factor
     if hb < 1 or wb < 1:
         raise ValueError(f"planes of {h} x {w} have no {factor} x {factor} block")
-    shape = tuple(tiles.shape[:-2]) + (hb, wb)
     with _on_stream(stream):
-        if out is None:
-            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
-            if stream is not None:
-                out.record_stream(stream)
-        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
-            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
-        dst = _plane_layout(out, 'out')
-        n_out, _, _, dst_plane_stride, dst_pitch = dst
-        assert n_out == n_images
+        out, (_, _, _, dst_plane_stride, dst_pitch) = _out_of_place(out, tuple(tiles.shape[:-2]) + (hb, wb), tiles, src, 'binning', stream)
         if n_images == 0:
             return out
-        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
-            raise ValueError("out shares memory with tiles: the binning is out of place")
         _check(lib().sq_bin_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                   dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), factor,
                                   BIN_METHODS[method], _stream_ptr(stream)), 'sq_bin_tiles')
@@ -1507,39 +1515,21 @@ def warp_tiles(tiles, ppm: int, out=None, stream=None):
     diagonal, bilinearly with 8 fractional bits and replicated edges, exact in integers -- ``tests/warp_ref.warp_image``; the
     formula stands in include/squidstitch.h.  The correction is out of place: ``tiles`` is left as it is.
 
-    tiles:  uint8 / uint16 device tensor [..., H, W], H and W at most 65535, with unit-stride rows (any row pitch) whose
-            leading dimensions are one uniform plane stride apart: a contiguous stack, or a view such as every other plane of
-            one.
+    tiles:  a plane batch (``_plane_batch``), H and W at most 65535.
     ppm:    an integer in -50000..50000, the relative displacement at the plane's corner in parts per million; positive
             undoes pincushion, negative barrel distortion, 0 gives an exact copy.
-    out:    a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
-            shares no memory with ``tiles``; allocated contiguous when None.
+    out:    None, or the tensor to fill: ``_out_of_place``.
     Returns ``out``."""
     import torch
     ppm = _int_in(ppm, -SQ_WARP_MAX_PPM, SQ_WARP_MAX_PPM, 'distortion ppm')
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    src = _plane_layout(tiles, 'tiles')
+    src = _plane_batch(tiles, 'tiles')
     n_images, h, w, src_plane_stride, src_pitch = src
     if h > SQ_WARP_MAX_SIDE or w > SQ_WARP_MAX_SIDE:
         raise ValueError(f"planes of {h} x {w} have a side above {SQ_WARP_MAX_SIDE}")
-    shape = tuple(tiles.shape)
     with _on_stream(stream):
-        if out is None:
-            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
-            if stream is not None:
-                out.record_stream(stream)
-        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
-            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
-        dst = _plane_layout(out, 'out')
-        n_out, _, _, dst_plane_stride, dst_pitch = dst
-        assert n_out == n_images
+        out, (_, _, _, dst_plane_stride, dst_pitch) = _out_of_place(out, tuple(tiles.shape), tiles, src, 'correction', stream)
         if n_images == 0:
             return out
-        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
-            raise ValueError("out shares memory with tiles: the correction is out of place")
         _check(lib().sq_warp_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                    dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), ppm,
                                    _stream_ptr(stream)), 'sq_warp_tiles')
@@ -1557,57 +1547,24 @@ def shift_tiles(tiles, shifts, out=None, stream=None):
     fractional bits and replicated edges, exact in integers -- ``tests/shift_ref.shift_image``; the formula stands in
     include/squidstitch.h.  The shift is out of place: ``tiles`` is left as it is.
 
-    tiles:  uint8 / uint16 device tensor [..., H, W], H and W at most 65535, with unit-stride rows (any row pitch) whose
-            leading dimensions are one uniform plane stride apart: a contiguous stack, or a view such as every other plane of
-            one.
+    tiles:  a plane batch (``_plane_batch``), H and W at most 65535.
     shifts: one pair (Sy, Sx) of integers in 1/256 pixel, each in -16384..16384, for every plane, or a sequence of one pair per
             index of the leading dimension (all planes under that index take it).  (0, 0) gives an exact copy.
-    out:    a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
-            shares no memory with ``tiles``; allocated contiguous when None.
+    out:    None, or the tensor to fill: ``_out_of_place``.
     Returns ``out``."""
-    import torch
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    try:
-        pairs = list(shifts)
-    except TypeError:
-        raise ValueError(f"shifts must be a pair (Sy, Sx) or a sequence of pairs, got {shifts!r}")
-    if len(pairs) == 2 and not any(isinstance(v, (list, tuple, np.ndarray)) for v in pairs):
-        pairs = [pairs]      # one pair for every plane
-    elif tiles.dim() < 3 or len(pairs) != tiles.shape[0]:
-        raise ValueError(f"shifts must be one pair, or one pair per index of the leading dimension "
-                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(pairs)}")
-    table = []
-    for pair in pairs:
-        if len(pair) != 2:
-            raise ValueError(f"a shift is a pair (Sy, Sx), got {pair!r}")
-        table += [_int_in(pair[0], -SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)'),
-                  _int_in(pair[1], -SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)')]
-    src = _plane_layout(tiles, 'tiles')
+    src = _plane_batch(tiles, 'tiles')
     n_images, h, w, src_plane_stride, src_pitch = src
+    shift = (-SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)')
+    host, n_pairs = _tuple_table(shifts, tiles, (shift, shift), 'shifts', 'a pair (Sy, Sx)')
     if h > SQ_SHIFT_MAX_SIDE or w > SQ_SHIFT_MAX_SIDE:
         raise ValueError(f"planes of {h} x {w} have a side above {SQ_SHIFT_MAX_SIDE}")
-    shape = tuple(tiles.shape)
     with _on_stream(stream):
-        if out is None:
-            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
-            if stream is not None:
-                out.record_stream(stream)
-        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
-            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
-        dst = _plane_layout(out, 'out')
-        n_out, _, _, dst_plane_stride, dst_pitch = dst
-        assert n_out == n_images
+        out, (_, _, _, dst_plane_stride, dst_pitch) = _out_of_place(out, tuple(tiles.shape), tiles, src, 'shift', stream)
         if n_images == 0:
             return out
-        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
-            raise ValueError("out shares memory with tiles: the shift is out of place")
-        host = (C.c_int32 * len(table))(*table)
         _check(lib().sq_shift_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                     dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), host,
-                                    n_images // len(pairs), _stream_ptr(stream)), 'sq_shift_tiles')
+                                    n_images // n_pairs, _stream_ptr(stream)), 'sq_shift_tiles')
     return out
 
 
@@ -1623,58 +1580,27 @@ def affine_tiles(tiles, params, out=None, stream=None):
     ``tests/affine_ref.affine_image``; the formula stands in include/squidstitch.h.  With A = 0 it is ``shift_tiles``.  The map is
     out of place: ``tiles`` is left as it is.
 
-    tiles:  uint8 / uint16 device tensor [..., H, W], H and W at most 65535, with unit-stride rows (any row pitch) whose
-            leading dimensions are one uniform plane stride apart: a contiguous stack, or a view such as every other plane of
-            one.
+    tiles:  a plane batch (``_plane_batch``), H and W at most 65535.
     params: one six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx) of integers -- S in 1/256 pixel, each in -16384..16384, A in parts per
             million, each in -50000..50000 -- for every plane, or a sequence of one six-tuple per index of the leading dimension
             (all planes under that index take it).  All zero gives an exact copy.
-    out:    a tensor of the same shape, dtype and device under the same rules (its columns beyond W stay as they are) that
-            shares no memory with ``tiles``; allocated contiguous when None.
+    out:    None, or the tensor to fill: ``_out_of_place``.
     Returns ``out``."""
-    import torch
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
-    try:
-        tuples = list(params)
-    except TypeError:
-        raise ValueError(f"params must be a six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx) or a sequence of them, got {params!r}")
-    if len(tuples) == 6 and not any(isinstance(v, (list, tuple, np.ndarray)) for v in tuples):
-        tuples = [tuples]      # one tuple for every plane
-    elif tiles.dim() < 3 or len(tuples) != tiles.shape[0]:
-        raise ValueError(f"params must be one six-tuple, or one per index of the leading dimension "
-                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(tuples)}")
-    table = []
-    for entry in tuples:
-        if isinstance(entry, (str, bytes)) or not hasattr(entry, '__len__') or len(entry) != 6:
-            raise ValueError(f"a parameter set is a six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx), got {entry!r}")
-        table += [_int_in(v, -SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)') for v in entry[:2]]
-        table += [_int_in(v, -SQ_AFFINE_MAX_PPM, SQ_AFFINE_MAX_PPM, 'channel affine coefficient (ppm)') for v in entry[2:]]
-    src = _plane_layout(tiles, 'tiles')
+    src = _plane_batch(tiles, 'tiles')
     n_images, h, w, src_plane_stride, src_pitch = src
+    shift = (-SQ_SHIFT_MAX, SQ_SHIFT_MAX, 'channel shift (1/256 pixel)')
+    coeff = (-SQ_AFFINE_MAX_PPM, SQ_AFFINE_MAX_PPM, 'channel affine coefficient (ppm)')
+    host, n_tuples = _tuple_table(params, tiles, (shift, shift, coeff, coeff, coeff, coeff), 'params',
+                                  'a six-tuple (Sy, Sx, Ayy, Ayx, Axy, Axx)')
     if h > SQ_AFFINE_MAX_SIDE or w > SQ_AFFINE_MAX_SIDE:
         raise ValueError(f"planes of {h} x {w} have a side above {SQ_AFFINE_MAX_SIDE}")
-    shape = tuple(tiles.shape)
     with _on_stream(stream):
-        if out is None:
-            out = torch.empty(shape, dtype=tiles.dtype, device=tiles.device)
-            if stream is not None:
-                out.record_stream(stream)
-        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != tiles.dtype or out.device != tiles.device:
-            raise ValueError(f"out must be a {tiles.dtype} tensor of shape {shape} on the tiles' device")
-        dst = _plane_layout(out, 'out')
-        n_out, _, _, dst_plane_stride, dst_pitch = dst
-        assert n_out == n_images
+        out, (_, _, _, dst_plane_stride, dst_pitch) = _out_of_place(out, tuple(tiles.shape), tiles, src, 'map', stream)
         if n_images == 0:
             return out
-        if _overlap(_byte_extent(tiles, src), _byte_extent(out, dst)):
-            raise ValueError("out shares memory with tiles: the map is out of place")
-        host = (C.c_int32 * len(table))(*table)
         _check(lib().sq_affine_tiles(tiles.data_ptr(), out.data_ptr(), n_images, h, w, src_plane_stride, src_pitch,
                                      dst_plane_stride, dst_pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)), host,
-                                     n_images // len(tuples), _stream_ptr(stream)), 'sq_affine_tiles')
+                                     n_images // n_tuples, _stream_ptr(stream)), 'sq_affine_tiles')
     return out
 
 
@@ -1687,8 +1613,7 @@ def dark_tiles(tiles, params, frames=None, pedestal: int = 0, stream=None):
     clamp(I - D + P, 0, M) with M the dtype's maximum, exact in integers -- ``tests/dark_ref.dark_image``; the formula stands in
     include/squidstitch.h.
 
-    tiles:    uint8 / uint16 device tensor [..., H, W] with unit-stride rows (any row pitch) whose leading dimensions are one
-              uniform plane stride apart: a contiguous stack, or a view such as every other plane of one.
+    tiles:    a plane batch (``_plane_batch``).
     params:   one pair (k, c) of integers for every plane, or a sequence of one pair per index of the leading dimension (all
               planes under that index take it): k >= 0 names frame k of ``frames`` (with c == 0), k == -1 the constant c in 0..M.
               A run of pairs that is the identity (k == -1, c == pedestal) launches nothing.
@@ -1697,21 +1622,10 @@ def dark_tiles(tiles, params, frames=None, pedestal: int = 0, stream=None):
     pedestal: P, an integer in 0..M.
     Returns ``tiles``."""
     import torch
-    if not torch.is_tensor(tiles) or not tiles.is_cuda or tiles.dim() < 2:
-        raise ValueError("tiles must be a [..., H, W] device tensor")
-    if tiles.dtype not in (torch.uint8, torch.uint16):
-        raise ValueError(f"tiles must be uint8 or uint16, got {tiles.dtype}")
+    lay = _plane_batch(tiles, 'tiles')
+    n_images, h, w, plane_stride, pitch = lay
     top = 255 if tiles.dtype == torch.uint8 else 65535
     pedestal = _int_in(pedestal, 0, top, 'dark pedestal')
-    try:
-        pairs = list(params)
-    except TypeError:
-        raise ValueError(f"params must be a pair (k, c) or a sequence of pairs, got {params!r}")
-    if len(pairs) == 2 and not any(isinstance(v, (list, tuple, np.ndarray)) for v in pairs):
-        pairs = [pairs]      # one pair for every plane
-    elif tiles.dim() < 3 or len(pairs) != tiles.shape[0]:
-        raise ValueError(f"params must be one pair, or one pair per index of the leading dimension "
-                         f"({tiles.shape[0] if tiles.dim() > 2 else 1}), got {len(pairs)}")
     n_frames = 0
     lay_f = None
     if frames is not None:
@@ -1720,23 +1634,18 @@ def dark_tiles(tiles, params, frames=None, pedestal: int = 0, stream=None):
             raise ValueError(f"frames must be a {tiles.dtype} tensor [K, {tiles.shape[-2]}, {tiles.shape[-1]}] on the tiles' device")
         lay_f = _plane_layout(frames, 'frames')
         n_frames = lay_f[0]
-    table = []
-    for pair in pairs:
-        if len(pair) != 2:
-            raise ValueError(f"a dark param is a pair (k, c), got {pair!r}")
-        k = _int_in(pair[0], -1, n_frames - 1, 'dark frame index')
-        c = _int_in(pair[1], 0, 0 if k >= 0 else top, 'dark constant')
-        table += [k, c]
-    lay = _plane_layout(tiles, 'tiles')
-    n_images, h, w, plane_stride, pitch = lay
+    host, n_pairs = _tuple_table(params, tiles, ((-1, n_frames - 1, 'dark frame index'), (0, top, 'dark constant')), 'params',
+                                 'a pair (k, c)')
+    for k, c in zip(host[0::2], host[1::2]):
+        if k >= 0:
+            _int_in(c, 0, 0, 'dark constant')      # a frame takes no constant
     if n_images == 0:
         return tiles
     if lay_f is not None and n_frames and _overlap(_byte_extent(tiles, lay), _byte_extent(frames, lay_f)):
         raise ValueError("frames shares memory with tiles")
-    host = (C.c_int32 * len(table))(*table)
     _check(lib().sq_dark_tiles(tiles.data_ptr(), n_images, h, w, plane_stride, pitch, sq_dtype_of(np_dtype_of_torch(tiles.dtype)),
                                frames.data_ptr() if n_frames else None, n_frames, lay_f[3] if n_frames else 0,
-                               lay_f[4] if n_frames else 0, host, n_images // len(pairs), pedestal, _stream_ptr(stream)),
+                               lay_f[4] if n_frames else 0, host, n_images // n_pairs, pedestal, _stream_ptr(stream)),
            'sq_dark_tiles')
     return tiles
 

@@ -377,6 +377,22 @@ int sq_composite_render(const void *means_dev, int64_t plane_stride, int32_t h, 
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Plane batches: the convention of the nine per-tile filters below (sq_tophat_tiles, sq_despeckle_tiles, sq_tile_stats,
+ * sq_dpc_tiles, sq_bin_tiles, sq_warp_tiles, sq_shift_tiles, sq_affine_tiles, sq_dark_tiles; csrc/plane_batch.h is its one
+ * implementation).  A batch is n planes of h x w elements of one dtype (SQ_U8 / SQ_U16) behind a base pointer: plane p's row y
+ * starts at element p * plane_stride + y * pitch, both in elements, pitch >= w.  Every batch argument of a call has its own
+ * base, plane stride and pitch; n, h, w and the dtype are the call's.  No alignment is asked of a base, a pitch or a stride
+ * beyond the element's own; the columns between w and the pitch and whatever lies between two planes are neither read into a
+ * result nor written.  With one plane the stride is never used for an address.  A batch's extent is the byte range from its
+ * first element to its last, gaps included; "must not meet" and "overlap" speak of extents, so interleaved views count.
+ * n == 0 is SQ_OK and nothing is launched (after the checks of the call's own parameters, sizes and pitches).  Otherwise
+ * SQ_ERR_INVALID, and nothing is launched, for n < 0, h or w < 1, a pitch below the width, a NULL or element-misaligned base,
+ * n > 1 with a plane stride smaller than a plane ((h - 1) * pitch + w), and a stride or plane above (INT64_MAX / 4) / n
+ * elements ("extents beyond the address space": no offset the library forms can wrap).  A batch longer than a launch's 65535
+ * grid rows (times the planes a thread of the kernel walks over) is split into several launches.
+ * ---------------------------------------------------------------------------------------- */
+
+/* ------------------------------------------------------------------------------------------
  * Background removal (--background-subtract tophat; extension: the reference has none -- its BaSiC runs with
  * get_darkfield=False, so nothing there removes an additive term).  A white top-hat with a square window of radius R per plane
  * I [h, w] (SQ_U8 / SQ_U16), IN PLACE:
@@ -384,12 +400,12 @@ int sq_composite_render(const void *means_dev, int64_t plane_stride, int32_t h, 
  *     O(y, x) = max E over the same clipped window
  *     I      := I - O                       (O <= I, so nothing wraps)
  * The definition is the numpy restatement in tests/tophat_ref.py.  n_images planes plane_stride elements apart, rows pitch
- * elements apart (pitch >= w); no alignment asked of the base or the pitch beyond the element's own.  1 <= radius <= 127, any
+ * elements apart (pitch >= w): a plane batch (above).  1 <= radius <= 127, any
  * h, w >= 1 (windows larger than the plane included).  The caller owns the scratch (16-byte aligned, at least
  * sq_tophat_scratch_bytes(n_images, h, w, dtype) bytes: the erosion of the batch); the library allocates nothing.  Two launches
  * (erosion into the scratch; dilation, subtraction and store), the work per pixel independent of R (running extrema, csrc/tophat.hip);
  * integers only, no atomics, deterministic.  SQ_ERR_INVALID for a radius out of range, a pitch below w, a NULL or misaligned
- * buffer; SQ_ERR_WORKSPACE for scratch that is too small.
+ * buffer, extents beyond the address space; SQ_ERR_WORKSPACE for scratch that is too small.
  * ---------------------------------------------------------------------------------------- */
 #define SQ_TOPHAT_MAX_RADIUS 127
 int64_t sq_tophat_scratch_bytes(int32_t n_images, int32_t h, int32_t w, int32_t dtype);
@@ -422,9 +438,8 @@ int sq_despeckle_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int
 
 /* ------------------------------------------------------------------------------------------
  * Per-tile quality words (--tile-qc; extension: the reference has none).  For each of n_images planes I [h, w] (SQ_U8 / SQ_U16),
- * the planes a plane stride and the rows a pitch apart (elements, pitch >= w; no alignment asked of the base or the pitch
- * beyond the element's own -- the conventions of sq_despeckle_tiles), SQ_TILE_STATS_WORDS = 8 uint64 are written to
- * out_dev[n_images][8] (8-byte aligned).  The words are OVERWRITTEN, not added to:
+ * the planes a plane stride and the rows a pitch apart (elements, pitch >= w): a plane batch (above).  SQ_TILE_STATS_WORDS = 8
+ * uint64 are written to out_dev[n_images][8] (8-byte aligned).  The words are OVERWRITTEN, not added to:
  *     0  min I                4  number of pixels equal to the dtype's maximum (255 / 65535)
  *     1  max I                5  number of pixels equal to 0
  *     2  S = sum I            6  Bx = sum over y, x < w - 2 of (I(y, x + 2) - I(y, x))^2      (0 when w <= 2)
@@ -454,8 +469,8 @@ int sq_tile_stats(const void *src_dev, int32_t n_images, int32_t h, int32_t w, i
  *         = clamp(floor(M N / (2 S)), 0, M)   otherwise          (floor of the exact rational)
  * For g = 1 that is M (0.5 + (L - R) / (L + R)), truncated and clipped.  The definition is the numpy restatement in
  * tests/dpc_ref.py, and the result is bit for bit that on every input.  n_images planes, the planes a plane stride and the rows
- * a pitch apart (elements, pitch >= w), left, right and out each with their own -- the conventions of sq_despeckle_tiles: no
- * alignment asked of a base or a pitch beyond the element's own; any h, w >= 1.  out may be EXACTLY left (same base, plane
+ * a pitch apart (elements, pitch >= w), left, right and out each with their own: plane batches (above);
+ * any h, w >= 1.  out may be EXACTLY left (same base, plane
  * stride and pitch: in place); otherwise its extent (first to last element of all planes) must meet neither input's.  left and
  * right are read once and out is written once (csrc/dpc.hip); the columns between w and out_pitch and the rows between h and
  * the plane stride are never written, and nothing past w or h is read into a result.  No scratch, no allocation, no atomics;
@@ -479,7 +494,7 @@ int sq_dpc_tiles(const void *left_dev, const void *right_dev, void *out_dev, int
  *     SQ_BIN_SUM :  out(y, x) = min(S(y, x), M)          (what camera binning does: counts add, and the result saturates)
  * The definition is the numpy restatement in tests/bin_ref.py, and the result is bit for bit that on every input.  n_images
  * planes, the planes a plane stride and the rows a pitch apart (elements; src_pitch >= w, dst_pitch >= wb), src and dst each
- * with their own -- the conventions of sq_despeckle_tiles: no alignment asked of a base or a pitch beyond the element's own.
+ * with their own: plane batches (above).
  * dst [n_images][hb][wb] must not meet src.  Every source element inside the K hb x K wb area is read exactly once, nothing of
  * the dropped rows and columns reaches a result, and nothing outside hb x wb of a destination plane is written
  * (csrc/bin.hip).  No scratch, no allocation, no atomics; asynchronous on `stream`; deterministic.  SQ_ERR_INVALID, and
@@ -515,8 +530,8 @@ int sq_bin_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t h
  * samples farther out (it undoes pincushion distortion), D < 0 undoes barrel distortion, D = 0 is an exact copy.  The map fits
  * 64 bits and the blend unsigned 32 bits up to the largest side and |D|.  The definition is the numpy restatement in
  * tests/warp_ref.py, and the result is bit for bit that on every input.  n_images planes, the planes a plane stride and the
- * rows a pitch apart (elements; both pitches >= w), src and dst each with their own -- the conventions of sq_bin_tiles: no
- * alignment asked of a base or a pitch beyond the element's own.  dst [n_images][h][w] must not meet src.  Every output element
+ * rows a pitch apart (elements; both pitches >= w), src and dst each with their own: plane batches (above).
+ * dst [n_images][h][w] must not meet src.  Every output element
  * is written exactly once, nothing outside h x w of a destination plane is written, and every tap lies inside its source plane
  * (csrc/warp.hip: a thread works the map of its positions out once and walks over SQ_WARP_PLANES_PER_THREAD planes with it; a
  * launch takes 65535 such runs of planes, longer batches are split).  No scratch, no allocation, no atomics; asynchronous on
@@ -549,8 +564,8 @@ int sq_warp_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t 
  * [k * images_per_shift, (k + 1) * images_per_shift) take pair k, and n_images must be a multiple of images_per_shift >= 1.
  * One grid is issued per maximal run of consecutive equal pairs (a run of (0, 0) goes through the same kernel as a copy), each
  * split at 65535 planes, so no table goes to the device.  The planes a plane stride and the rows a pitch apart (elements; both
- * pitches >= w), src and dst each with their own -- the conventions of sq_despeckle_tiles: no alignment asked of a base or a
- * pitch beyond the element's own.  dst [n_images][h][w] must not meet src.  Every output element is written exactly once,
+ * pitches >= w), src and dst each with their own: plane batches (above).
+ * dst [n_images][h][w] must not meet src.  Every output element is written exactly once,
  * nothing outside h x w of a destination plane is written, and every tap lies inside its source plane (csrc/shift.hip: a
  * thread owns 16 bytes of dst columns and walks down SQ_SHIFT_ROWS_PER_THREAD rows, every source row is read once per run).
  * No scratch, no allocation, no atomics; asynchronous on `stream`; deterministic.  SQ_ERR_INVALID, and nothing is launched,
@@ -588,8 +603,8 @@ int sq_shift_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_t
  * returns: images [k * images_per_param, (k + 1) * images_per_param) take tuple k, and n_images must be a multiple of
  * images_per_param >= 1.  One grid is issued per maximal run of consecutive equal tuples (a run of zeros goes through the same
  * kernel as a copy), each split at 65535 * SQ_AFFINE_PLANES_PER_THREAD planes, so no table goes to the device.  Every other
- * convention is that of sq_shift_tiles: planes a plane stride and rows a pitch apart (elements; both pitches >= w), no alignment
- * asked of a base or a pitch beyond the element's own; dst must not meet src; every output element is written exactly once,
+ * convention is that of sq_shift_tiles: src and dst are plane batches (above; both pitches >= w); dst must not meet src; every
+ * output element is written exactly once,
  * nothing outside h x w of a destination plane is written, and every tap lies inside its source plane (csrc/affine.hip: a thread
  * owns 16 bytes of dst columns of one row, steps the map along them without a division per pixel and walks over
  * SQ_AFFINE_PLANES_PER_THREAD planes with it; the taps of a vector come as 16-byte loads of two or three source rows).  No
@@ -615,9 +630,8 @@ int sq_affine_tiles(const void *src_dev, void *dst_dev, int32_t n_images, int32_
  * must be a multiple of images_per_param >= 1.  k >= 0 selects frame k of frames_dev [n_frames] (the frames a frame stride and
  * their rows a frame pitch apart, in elements) and goes with c == 0; k == -1 means the constant c.  One grid is issued per maximal
  * run of consecutive equal pairs; a run that is the identity (k == -1 and c == pedestal) issues nothing and leaves its planes
- * untouched; longer runs are split at 65535 * SQ_DARK_IMAGES_PER_THREAD planes.  No table goes to the device.  The layout
- * conventions are those of sq_dpc_tiles: planes a plane stride and rows a pitch apart (elements; pitch >= w), no alignment asked
- * of a base or a pitch beyond the element's own; any h, w >= 1; the columns between w and the pitch and the rows beyond h are
+ * untouched; longer runs are split at 65535 * SQ_DARK_IMAGES_PER_THREAD planes.  No table goes to the device.  The tiles and
+ * the frames are plane batches (above); any h, w >= 1; the columns between w and the pitch and the rows beyond h are
  * never written, and nothing there is read into a result.  The frames must not meet the tiles.  csrc/dark.hip: a thread owns one
  * 16-byte vector of columns laid at the phase of the tile row, keeps P - D of its (row, columns) in registers and walks
  * SQ_DARK_IMAGES_PER_THREAD images of the run with it, so a frame is fetched once per that many tiles (image by image where the

@@ -63,6 +63,17 @@ def test_kernel_equals_the_definition(case, dtype):
 
 
 @pytest.mark.parametrize('dtype', affine_cases.DTYPES)
+def test_grid_edges(dtype):
+    """Two planes at the three edges of the strip / segment grid: narrower than one vector; one vector more than a workgroup is
+    wide (two strips); and, at that width, one row more than a workgroup's rows (two segments)."""
+    wide = affine_cases.STRIP[dtype] + affine_cases.VEC[dtype]
+    for h, w in ((3, 5), (3, wide), (affine_cases.ROWS + 1, wide)):
+        planes = affine_cases.planes(dtype, h, w, 2)
+        got = native.affine_tiles(_dev(planes), _six(*ROT02)).cpu().numpy()
+        np.testing.assert_array_equal(got, affine_cases.reference(dtype, h, w, *ROT02, 2), err_msg=f'{(h, w)}')
+
+
+@pytest.mark.parametrize('dtype', affine_cases.DTYPES)
 def test_a_table_of_tuples_with_several_runs(dtype):
     h, w, n = affine_cases.MANY
     assert h > affine_cases.ROWS and n == affine_cases.WALK + 1

@@ -53,6 +53,17 @@ def test_kernel_equals_the_definition(shift, dtype):
 
 
 @pytest.mark.parametrize('dtype', shift_cases.DTYPES)
+def test_grid_edges(dtype):
+    """Two planes at the three edges of the strip / segment grid: narrower than one vector; one vector more than a workgroup is
+    wide (two strips); and, at that width, one row more than a workgroup's rows (two segments)."""
+    wide = shift_cases.STRIP[dtype] + shift_cases.VEC[dtype]
+    for h, w in ((3, 5), (3, wide), (shift_cases.RPT + 1, wide)):
+        planes = shift_cases.planes(dtype, h, w, 2)
+        got = native.shift_tiles(_dev(planes), shift_cases.MIXED).cpu().numpy()
+        np.testing.assert_array_equal(got, shift_cases.reference(dtype, h, w, shift_cases.MIXED, 2), err_msg=f'{(h, w)}')
+
+
+@pytest.mark.parametrize('dtype', shift_cases.DTYPES)
 def test_a_table_of_shifts_with_several_runs(dtype):
     h, w, n = shift_cases.MANY
     assert h > shift_cases.RPT

@@ -56,6 +56,18 @@ def test_kernel_equals_the_definition(path, dtype):
 
 
 @pytest.mark.parametrize('dtype', dark_cases.DTYPES)
+def test_grid_edges(dtype):
+    """Two planes at the three edges of the strip / segment grid: narrower than one vector; one vector more than a workgroup is
+    wide (two strips); and, at that width, one row more than a workgroup's rows (two segments)."""
+    wide = dark_cases.STRIP[dtype] + dark_cases.VEC[dtype]
+    for h, w in ((3, 5), (3, wide), (dark_cases.RPT + 1, wide)):
+        planes, frames = dark_cases.planes(dtype, h, w, 2), dark_cases.frames(dtype, h, w)
+        got = native.dark_tiles(_dev(planes), [(2, 0), (-1, 4)], frames=_dev(frames), pedestal=9).cpu().numpy()
+        np.testing.assert_array_equal(got[0], dark_ref.dark_image(planes[0], frames[2], 9), err_msg=f'{(h, w)} frame')
+        np.testing.assert_array_equal(got[1], dark_ref.dark_image(planes[1], 4, 9), err_msg=f'{(h, w)} constant')
+
+
+@pytest.mark.parametrize('dtype', dark_cases.DTYPES)
 def test_a_table_with_several_runs_and_identity_runs_in_the_middle(dtype):
     """Planes a stride of two planes apart and rows a pitch of 32 apart in a buffer of guard bytes (the stride is a whole number of
     vectors: a thread walks IPT images): the planes of the identity runs, every gap between two planes and the columns behind w

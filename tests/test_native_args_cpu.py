@@ -149,3 +149,99 @@ def test_device_checks_sit_in_the_helpers():
             native._plane_stack(_t(), 'planes', integer_only)
     with pytest.raises(ValueError):
         native._check_plane('out', torch.zeros((8, 8)), (8, 8))
+
+
+SHIFT = (-16384, 16384, 'shift')
+COEFF = (-50000, 50000, 'coefficient')
+
+
+def _table(values, tiles, ranges=(SHIFT, SHIFT)):
+    table, n = native._tuple_table(values, tiles, ranges, 'params', 'a tuple')
+    return list(table), n
+
+
+def test_tuple_table_one_for_all_or_one_per_leading_index():
+    assert _table((3, -4), _t()) == ([3, -4], 1)
+    assert _table([np.int64(3), np.int32(-4)], torch.zeros((8, 8))) == ([3, -4], 1)      # one tuple suits a single plane too
+    assert _table([(1, 2), [3, 4], np.array([5, 6])], _t()) == ([1, 2, 3, 4, 5, 6], 3)
+    assert _table([(1, 2), (3, 4)], _b()) == ([1, 2, 3, 4], 2)                           # per index of the FIRST dimension
+    assert _table([(1, 2), (3, 4)], torch.zeros((2, 8, 8))) == ([1, 2, 3, 4], 2)         # two pairs, not one pair of pairs
+    six = (1, 2, 3, 4, 5, 6)
+    assert _table(six, _t(), (SHIFT, SHIFT) + (COEFF,) * 4) == (list(six), 1)
+    assert _table([six] * 3, _t(), (SHIFT, SHIFT) + (COEFF,) * 4) == (list(six) * 3, 3)
+    table, n = native._tuple_table((3, -4), _t(), (SHIFT, SHIFT), 'params', 'a tuple')
+    assert np.ctypeslib.as_array(table).dtype == np.int32 and n == 1
+
+
+@pytest.mark.parametrize('values,tiles', [
+    (5, _t),                                        # no sequence at all
+    ([(1, 2), (3, 4)], _t),                         # wrong count: two for three leading indices
+    ([(1, 2)] * 4, _t),
+    ([], _t),
+    ((1, 2, 3), _t),                                # wrong width: three integers are three entries, none a pair
+    ([(1, 2), (3, 4), (5, 6, 7)], _t),              # ... and an entry of another width
+    ([(1, 2), (3, 4), 5], _t),
+    ([(1, 2), (3, 4), 'ab'], _t),
+    ((1.0, 2), _t),                                 # a non-integer
+    ((True, 2), _t),
+    ([(1, 2), (3, 4), (5, 6.5)], _t),
+    ([(1, 2)], lambda: torch.zeros((8, 8))),        # a 2-d tensor has no leading index to give a sequence to
+    ([(1, 2), (3, 4)], lambda: torch.zeros((8, 8))),
+])
+def test_tuple_table_refuses(values, tiles):
+    with pytest.raises(ValueError):
+        _table(values, tiles())
+
+
+def test_tuple_table_holds_every_position_to_its_own_range():
+    ranges = ((-1, 1, 'frame index'), (0, 255, 'constant'))
+    for good in ((-1, 0), (1, 255)):
+        assert _table(good, _t(), ranges) == (list(good), 1)
+    for bad, noun in (((-2, 0), 'frame index'), ((2, 0), 'frame index'), ((0, -1), 'constant'), ((0, 256), 'constant')):
+        with pytest.raises(ValueError, match=noun):
+            _table(bad, _t(), ranges)
+        with pytest.raises(ValueError, match=noun):
+            _table([(0, 0), (0, 0), bad], _t(), ranges)
+
+
+def test_batch_and_output_checks_sit_in_the_helpers():
+    """Host tensors and no shared object: what can be refused without a device is refused by the helpers, by name."""
+    for bad in (_t(), np.zeros((3, 8, 8), np.uint16), None):
+        with pytest.raises(ValueError, match='left must be a .* device tensor'):
+            native._plane_batch(bad, 'left')
+    with pytest.raises(ValueError, match=r'\[n, H, W\] or \[b, n, H, W\] device tensor'):
+        native._plane_batch(_t(), 'tiles', '[n, H, W] or [b, n, H, W]', (3, 4))
+    t = _t()
+    src = native._plane_layout(t, 'tiles')
+    for bad in (torch.zeros((3, 8, 8), dtype=torch.float32),        # a float tensor
+                torch.zeros((3, 8, 9), dtype=torch.uint16),         # another shape
+                torch.zeros((3, 8, 8), dtype=torch.uint16).numpy()):
+        with pytest.raises(ValueError, match='out must be'):
+            native._out_of_place(bad, (3, 8, 8), t, src, 'filter', None)
+    with pytest.raises(ValueError):                                   # a permuted view: its rows are not contiguous
+        native._out_of_place(torch.zeros((3, 8, 8), dtype=torch.uint16).permute(0, 2, 1), (3, 8, 8), t, src, 'filter', None)
+    whole = torch.zeros((4, 8, 8), dtype=torch.uint16)
+    src = native._plane_layout(whole[:3], 'tiles')
+    for noun in ('filter', 'binning', 'correction', 'shift', 'map'):
+        with pytest.raises(ValueError, match=f'shares memory with tiles: the {noun} is out of place'):
+            native._out_of_place(whole[1:], (3, 8, 8), whole[:3], src, noun, None)
+    good = torch.zeros((3, 8, 12), dtype=torch.uint16)[:, :, :8]
+    out, dst = native._out_of_place(good, (3, 8, 8), t, native._plane_layout(t, 'tiles'), 'filter', None)
+    assert out is good and dst == (3, 8, 8, 96, 12)
+    made, dst = native._out_of_place(None, (3, 4, 4), t, native._plane_layout(t, 'tiles'), 'binning', None)
+    assert made.shape == (3, 4, 4) and made.dtype == t.dtype and dst == (3, 4, 4, 16, 4)
+    empty = torch.zeros((0, 8, 8), dtype=torch.uint16)               # no plane: nothing to overlap with
+    assert native._out_of_place(empty, (0, 8, 8), empty, native._plane_layout(empty, 'tiles'), 'filter', None)[0] is empty
+
+
+@pytest.mark.parametrize('call', [
+    lambda t: native.tophat_tiles(t, 3), lambda t: native.despeckle_tiles(t, 5), lambda t: native.tile_stats(t),
+    lambda t: native.dpc_tiles(t, t), lambda t: native.bin_tiles(t, 2), lambda t: native.warp_tiles(t, 100),
+    lambda t: native.shift_tiles(t, (1, 2)), lambda t: native.affine_tiles(t, (0,) * 6), lambda t: native.dark_tiles(t, (-1, 1)),
+])
+def test_every_per_tile_wrapper_refuses_a_host_tensor_by_the_batch_checker(monkeypatch, call):
+    def no_library():
+        raise AssertionError('lib() was reached before the batch was checked')
+    monkeypatch.setattr(native, 'lib', no_library)
+    with pytest.raises(ValueError, match='device tensor'):
+        call(_t())

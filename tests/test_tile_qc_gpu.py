@@ -73,6 +73,16 @@ def test_kernel_equals_the_definition(dtype):
 
 
 @pytest.mark.parametrize('dtype', ['uint8', 'uint16'])
+def test_grid_edges(dtype):
+    """Two planes at the edges of the strip / segment grid: narrower than one vector; a workgroup of 128 and of 256 vectors; one
+    vector more than the widest workgroup (two strips); and, at that width, one row more than a workgroup's run (two segments)."""
+    vec = 16 // np.dtype(dtype).itemsize
+    for h, w in ((3, 5), (3, 100 * vec), (3, 256 * vec), (3, 257 * vec), (RPT + 1, 257 * vec)):
+        got = native.tile_stats(_dev(_planes(dtype, h, w, 2)))
+        np.testing.assert_array_equal(got.cpu().numpy(), _reference(dtype, h, w, 2), err_msg=f'{h} x {w}')
+
+
+@pytest.mark.parametrize('dtype', ['uint8', 'uint16'])
 @pytest.mark.parametrize('n', [1, 3, 37])
 def test_plane_counts(n, dtype):
     for h, w in ((RPT + 1, 65), (3, 257), (2 * RPT + 1, 9)):

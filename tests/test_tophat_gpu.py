@@ -23,7 +23,8 @@ DEV = 'cuda:0'
 # wide), column segments of 2R+1, row segments of at least max(64, 4R) rows, blocks of up to 32 rows, three LDS sizes.
 BIG_R = (1, 2, 7, 63, 64, 65, 127)
 CASES = [((1, 1), 4), ((1, 300), 4), ((300, 1), 4), ((5, 7), 4), ((33, 31), 16), ((33, 31), 15)] + \
-        [((257, 255), r) for r in BIG_R] + [((130, 1301), r) for r in BIG_R] + [((512, 640), 50)]
+        [((257, 255), r) for r in BIG_R] + [((130, 1301), r) for r in BIG_R] + [((512, 640), 50)] + \
+        [((6, 5), 2), ((70, 257), 4), ((70, 129), 65)]      # narrower than a vector; one column past a strip of 256 and of 128
 
 
 def _dev(a):
